@@ -9,15 +9,21 @@ sharded over ranks, one RCCL all-gather of trajectory records per tick; `--agent
 BASELINE configs[3] (512 agents over 8 GPUs).
 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment starts the N ranks itself
-(re-executes under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`);
+(a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`);
 under a launcher it checks that WORLD_SIZE == N.  It refuses to run with fewer visible GPUs than ranks.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline`.
+A plain run sets up, warms up, times `--steps` ticks and prints ONE JSON line (rank 0): the driver's contract (`value`,
+`ms_per_step`, ...) and the run's configuration.  `--full` adds everything else measured after the timed region — roofline and
+per-stage figures, the dense-clear and sustained blocks, the labelled variants, the other BASELINE configurations, the CPU
+baseline — and prints the compact line that ends with `summary` (the full record goes to profiles/bench_last_detail.json).
+`--dump-outputs DIR` writes what the last timed tick computed (the swarm's trajectory records and the tick's ok flags) as
+DIR/<name>.npy; the scene is seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import importlib
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -47,16 +53,21 @@ def parse():
                     help="N > 1: seconds the sections after the headline may take before rank 0 prints the line without them (0 = off)")
     ap.add_argument("--no-variants", action="store_true", dest="no_variants",
                     help="skip the labelled variants (pre-stamped lock-step, sogm_flight_run) and the cfg1 / cfg4 blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything behind the headline (roofline, stage times, dense / sustained blocks, variants, "
+                         "other configs, CPU baseline); the options above that name those sections apply only with it")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="write what the last timed tick computed as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
 def launch_plan(gpus, env, device_count, argv, port=None):
     """How `bench.py --gpus N` gets its N ranks.  Returns None (run in this process) or the command line to
-    re-execute; raises SystemExit with a message when the request cannot be honoured — a bench that silently ran
+    run as a child; raises SystemExit with a message when the request cannot be honoured — a bench that silently ran
     one rank while claiming N would print a wrong n_gpus (missing #1).
       * launched by torch.distributed.run / the driver (RANK in env): WORLD_SIZE must equal --gpus;
       * not launched, N == 1: this process is the only rank;
-      * not launched, N > 1: re-execute under torch.distributed.run with N local ranks (127.0.0.1 rendezvous)."""
+      * not launched, N > 1: run torch.distributed.run with N local ranks (127.0.0.1 rendezvous) as a child."""
     if gpus < 1:
         raise SystemExit(f"bench.py: --gpus {gpus}: need at least one GPU")
     if "RANK" in env:
@@ -235,8 +246,21 @@ class PostHeadlineWatchdog:
         self.t.cancel()
 
 
+def headline_line(out):
+    """The contract's keys of the line and the run's configuration without its prose (what a plain run prints)."""
+    cfg = dict(out.get("config") or {})
+    for k in ("world", "tick_overlap"):  # prose: in the detail file
+        cfg.pop(k, None)
+    line = {k: out[k] for k in ("metric", "value", "value_ok", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in out}
+    line["config"] = cfg
+    if "multi_gpu" in out:
+        line["multi_gpu"] = out["multi_gpu"]
+    return line
+
+
 def compact_line(out):
-    """The ONE JSON line bench.py prints.  Everything measured goes to a file (profiles/bench_last_detail.json here, copied to
+    """The ONE JSON line bench.py --full prints.  Everything measured goes to a file (profiles/bench_last_detail.json here, copied to
     gpurun_out/ when that exists); the line keeps the contract's keys, the roofline and cpu_baseline objects without their
     prose, and ENDS with `summary` (< 1200 characters): a driver that keeps only the last 2000 characters of the line still
     holds every number DESIGN.md section 6 quotes."""
@@ -251,14 +275,8 @@ def compact_line(out):
             except OSError:
                 pass
     g = lambda o, *ks: (g(o.get(ks[0]), *ks[1:]) if len(ks) > 1 else o.get(ks[0])) if isinstance(o, dict) else None
-    ro, cb, cfg = out.get("roofline") or {}, out.get("cpu_baseline"), dict(out.get("config") or {})
-    for k in ("world", "tick_overlap"):  # prose: in the detail file
-        cfg.pop(k, None)
-    line = {k: out[k] for k in ("metric", "value", "value_ok", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-                                "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in out}
-    line["config"] = cfg
-    if "multi_gpu" in out:
-        line["multi_gpu"] = out["multi_gpu"]
+    ro, cb = out.get("roofline") or {}, out.get("cpu_baseline")
+    line = headline_line(out)
     if "watchdog" in out:
         line["watchdog"] = out["watchdog"]
     line["detail_file"] = detail_paths
@@ -300,6 +318,110 @@ def compact_line(out):
     return line
 
 
+def headline(sw, spec, args, world, dt, n_ok, outcomes, sparse_on, overlap_mode, world_note):
+    """The timed region's result: the contract's keys and the run's configuration (plain and --full runs alike)."""
+    exchange_kind = "abi" if sw.exchange.active else "torch" if sw.distributed else "local"
+    if world > 1 and exchange_kind != "abi":
+        raise SystemExit(f"bench.py: {world} ranks but the trajectory exchange is '{exchange_kind}' "
+                         f"({sw.exchange.fallback_reason}): the N > 1 line must measure the all-gather behind the C ABI")
+    return {
+        "metric": "replans/sec (SOGM update + QP: full replan = SOGM update + A* + corridors + QP + deconfliction), "
+                  f"{sw.A_loc}-agent batch per GPU, {spec.L}x{spec.W}x{spec.H}x{spec.T} voxel grid; aggregate over all agents",
+        "value": sw.A_tot * args.steps / dt,   # replan cycles executed per second (BASELINE.json's metric)
+        "value_ok": n_ok / dt,                  # of which replan() returned true
+        "unit": "replans/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("f16" if spec.storage & 1 else "f32") + " occupancy / f64 planning",
+        "data": "synthetic",
+        "config": {"workload": f"{sw.A_loc} agents/GPU x {world} GPU, {spec.L}x{spec.W}x{spec.H}x{spec.T} SOGM, "
+                               f"sim_fkpcp-style moving cylinders, batched ADMM QP (BASELINE {'configs[4]' if args.grid == 'cfg4' else 'configs[2]'} per GPU)",
+                   "agents_total": sw.A_tot, "grid": [spec.L, spec.W, spec.H, spec.T],
+                   "cloud_points": int(sw.scene["cloud"].shape[0]), "cylinders": int(len(sw.scene["cylinders"])),
+                   "world": world_note,
+                   # ticks between the sensor frame a tick's map is built from and the tick itself: 0 = the reference's
+                   # updateMap-from-the-latest-cloud; 1 = built by the previous replan's pre-stamp from ITS tick's frame
+                   "map_input_staleness_ticks": sw.map_input_staleness_ticks,
+                   "replans_ok_fraction": n_ok / float(sw.A_tot * args.steps),
+                   # where the timed replans ended + capacity limits hit (sogm_planner_counters)
+                   "outcomes": outcomes,
+                   "parallelism": f"agents sharded x{world}, 1 all-gather/tick",
+                   "tick_overlap": "lock-step (every agent's tick k ends before any agent's tick k + 1 starts; overlay and "
+                                   "isSafeAfterOpt read the neighbours' records of tick k - 1) — variants.flight: per-agent overlap "
+                                   "under the staleness rule (sogm_flight_run)",
+                   # which all-gather ran: "abi" = sogm_traj_allgather (RCCL behind the C ABI), "local" = one process
+                   "exchange": exchange_kind,
+                   "exchange_fallback_reason": sw.exchange.fallback_reason,
+                   "sogm_grids_per_agent": overlap_mode if overlap_mode >= 2 else 1,
+                   "sogm_reset": "sparse (logged 32-byte sectors)" if sparse_on else "dense clear",
+                   "sogm_cell_order": "2x2x2 tiles" if spec.storage & 16 else "x-fastest rows",
+                   # where the tick's map update runs: inside the previous replan, agent by agent as their records are
+                   # published (sogm_planner_set_prestamp), or at the start of the tick
+                   "map_update": ("pre-stamped by the previous replan" if sw.prestamp and sparse_on
+                                  else "at the start of the tick")},
+    }
+
+
+def multi_gpu_block(pop, sw, dist, world, dt_local, steps, exchange_ms):
+    """N > 1: the first N > 1 run verifies itself — what RCCL says, every rank's clock, the collective's own duration."""
+    import torch
+    info = sw.exchange.info()
+    mine = torch.tensor([dt_local / steps * 1e3, float(info["ranks"]),
+                         float(exchange_ms.mean()) if len(exchange_ms) else -1.0],
+                        dtype=torch.float64, device="cuda")
+    allr = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(allr, mine)
+    block = {"rccl_ranks": info["ranks"], "rccl_ranks_per_rank": [int(t[1].item()) for t in allr],
+             "rank_ms_per_step": [float(t[0].item()) for t in allr],
+             "allgather_ms_per_rank": [float(t[2].item()) for t in allr],
+             "allgather_launches_timed": int(len(exchange_ms)),
+             "allgather_bytes_per_rank": sw.A_loc * pop._abi.TRAJ_RECORD_BYTES,
+             "exchange": "abi" if sw.exchange.active else "torch" if sw.distributed else "local"}
+    if any(int(t[1].item()) != world for t in allr):
+        raise SystemExit(f"bench.py: ncclCommCount != {world} on some rank: {block}")
+    return block
+
+
+def timed_outputs(pop, sw, dist, world, ok_last):
+    """What the last timed tick hands its caller: the swarm's trajectory records as they stand after it (the table every
+    agent executes and the next tick reads, all ranks' agents in order) and the tick's replan() flags.  The records are
+    decoded field by field into float64; the pieces beyond a record's n_pieces are zeroed (no reader looks at them).
+    Collective on N > 1 (every rank calls it); synchronises."""
+    import numpy as np
+    import torch
+    P = pop._abi.SOGM_MAX_PIECES
+    rec_t = np.dtype([("drone_id", "<i4"), ("n_pieces", "<i4"), ("time_start", "<f8"), ("duration", "<f8", (P,)),
+                      ("cpts", "<f8", (P * 15,))])
+    assert rec_t.itemsize == pop._abi.TRAJ_RECORD_BYTES
+    ok = ok_last.to(torch.int32)
+    if dist is not None and world > 1:
+        parts = [torch.zeros_like(ok) for _ in range(world)]
+        dist.all_gather(parts, ok)
+        ok = torch.cat(parts)
+    raw = sw.records_all().contiguous().cpu().numpy()
+    rec = raw.view(rec_t).reshape(raw.shape[0])
+    n = np.clip(rec["n_pieces"], 0, P)
+    duration = np.where(np.arange(P)[None, :] < n[:, None], rec["duration"], 0.0)
+    cpts = np.where(np.arange(P * 15)[None, :] < 15 * n[:, None], rec["cpts"], 0.0).reshape(-1, P, 5, 3)
+    return {"replan_ok": ok.cpu().numpy().astype(np.float32),
+            "traj_drone_id": rec["drone_id"].astype(np.float64), "traj_n_pieces": rec["n_pieces"].astype(np.float64),
+            "traj_time_start": rec["time_start"].astype(np.float64), "traj_duration": duration.astype(np.float64),
+            "traj_cpts": cpts.astype(np.float64)}
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     args = parse()
     import torch
@@ -307,7 +429,8 @@ def main():
     if cmd is not None:
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         sys.stdout.flush()
-        os.execvpe(cmd[0], cmd, env)
+        # the ranks run in a child launcher: this process has initialised HIP (device_count), so it is not replaced in place
+        raise SystemExit(subprocess.call(cmd, env=env))
     pop = importlib.import_module("pred-occ-planner_amd")
     driver = importlib.import_module("pred-occ-planner_amd.driver")
     rank = int(os.environ.get("RANK", "0"))
@@ -327,7 +450,7 @@ def main():
     # processes NOW, before this process holds a hardware queue (they exit before the first tick here); their per-tick rows
     # are replayed in the configs block at the end
     share_rows, share_err = None, None
-    if world == 1 and not launched and not args.no_variants and args.grid == "cfg2" and args.agents is None:
+    if args.full and world == 1 and not launched and not args.no_variants and args.grid == "cfg2" and args.agents is None:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         rank_share = importlib.import_module("bench_rank_share")
         try:
@@ -346,8 +469,10 @@ def main():
                           grids=int(os.environ["SOGM_GRIDS"]) if os.environ.get("SOGM_GRIDS") else None,
                           moving_world=moving)
     spec = sw.spec
-    n_frames = args.warmup + args.steps + (3 + args.dense_ticks if args.dense_ticks > 0 else 0) + \
-        (3 + args.sustained if args.sustained > 0 else 0) + (3 + args.steps) + 8
+    n_frames = args.warmup + args.steps + 1
+    if args.full:  # (the frames of the blocks after the timed region as well)
+        n_frames = args.warmup + args.steps + (3 + args.dense_ticks if args.dense_ticks > 0 else 0) + \
+            (3 + args.sustained if args.sustained > 0 else 0) + (3 + args.steps) + 8
     t_up = time.perf_counter()
     sw.compute.prepare(0, n_frames)
     world_upload_s = time.perf_counter() - t_up
@@ -397,10 +522,30 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         n_ok = int(t[0].item())
         outcomes = dict(zip(sorted(outcomes), [int(v) for v in t[1:].tolist()]))
+    import numpy as np
+    if args.dump_outputs:
+        arrays = timed_outputs(pop, sw, dist, world, oks[-1])
+        if rank == 0:
+            write_outputs(args.dump_outputs, arrays)
+    world_note = (("moving: per-tick sensor frames (cylinders advance by v*dt, up to 1 m/s, their cloud points with "
+                   "them), cropped on the device around each agent's current map centre through 256-point blocks; "
+                   f"{n_frames} frames uploaded before the first tick in {world_upload_s:.1f} s") if moving
+                  else "static (SOGM_WORLD=static): one frame for every tick")
+    if not args.full:
+        out = headline(sw, spec, args, world, dt, n_ok, outcomes, sw.map.sparse_reset_state()["enabled"], sw.overlap_mode,
+                       world_note)
+        if world > 1:
+            out["multi_gpu"] = multi_gpu_block(pop, sw, dist, world, dt_local, args.steps,
+                                               np.array(sw.map.profile_read_all(pop._abi.PROF_EXCHANGE)))
+        if rank == 0:
+            print(json.dumps(headline_line(out)), flush=True)
+        sw.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # The rated kernel, launch by launch, INSIDE the timed region: the library records a HIP event pair around every
     # reset (and every all-gather) on the stream it is launched on and keeps one pair per launch, so nothing
     # synchronises between ticks (sogm_profile_read_all).
-    import numpy as np
     planner = importlib.import_module("pred-occ-planner_amd.planner")
     per_slot = {k: np.array(sw.map.profile_read_all(k)) for k in range(pop._abi.PROF_N)}
     moved = sw.map.map_traffic(reset=True)      # device-side counts of the timed region: what the resets and stamps moved
@@ -565,53 +710,7 @@ def main():
                     "timed_where": "HIP events on the clear's stream around the clear (both of its launches), every clear of the timed region",
                     "standalone": dict(k_dense["standalone"], kernel=k_dense["kernel"], bytes_per_launch=grid_bytes),
                     "kernels": [k_stamp, k_dense]}
-    exchange_kind = "abi" if sw.exchange.active else "torch" if sw.distributed else "local"
-    if world > 1 and exchange_kind != "abi":
-        raise SystemExit(f"bench.py: {world} ranks but the trajectory exchange is '{exchange_kind}' "
-                         f"({sw.exchange.fallback_reason}): the N > 1 line must measure the all-gather behind the C ABI")
-    out = {
-        "metric": "replans/sec (SOGM update + QP: full replan = SOGM update + A* + corridors + QP + deconfliction), "
-                  f"{sw.A_loc}-agent batch per GPU, {spec.L}x{spec.W}x{spec.H}x{spec.T} voxel grid; aggregate over all agents",
-        "value": sw.A_tot * args.steps / dt,   # replan cycles executed per second (BASELINE.json's metric)
-        "value_ok": n_ok / dt,                  # of which replan() returned true
-        "unit": "replans/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("f16" if spec.storage & 1 else "f32") + " occupancy / f64 planning",
-        "data": "synthetic",
-        "config": {"workload": f"{sw.A_loc} agents/GPU x {world} GPU, {spec.L}x{spec.W}x{spec.H}x{spec.T} SOGM, "
-                               f"sim_fkpcp-style moving cylinders, batched ADMM QP (BASELINE {'configs[4]' if args.grid == 'cfg4' else 'configs[2]'} per GPU)",
-                   "agents_total": sw.A_tot, "grid": [spec.L, spec.W, spec.H, spec.T],
-                   "cloud_points": int(sw.scene["cloud"].shape[0]), "cylinders": int(len(sw.scene["cylinders"])),
-                   "world": ("moving: per-tick sensor frames (cylinders advance by v*dt, up to 1 m/s, their cloud points with "
-                             "them), cropped on the device around each agent's current map centre through 256-point blocks; "
-                             f"{n_frames} frames uploaded before the first tick in {world_upload_s:.1f} s") if moving
-                            else "static (SOGM_WORLD=static): one frame for every tick",
-                   # ticks between the sensor frame a tick's map is built from and the tick itself: 0 = the reference's
-                   # updateMap-from-the-latest-cloud; 1 = built by the previous replan's pre-stamp from ITS tick's frame
-                   "map_input_staleness_ticks": sw.map_input_staleness_ticks,
-                   "replans_ok_fraction": n_ok / float(sw.A_tot * args.steps),
-                   # where the timed replans ended + capacity limits hit (sogm_planner_counters)
-                   "outcomes": outcomes,
-                   "parallelism": f"agents sharded x{world}, 1 all-gather/tick",
-                   "tick_overlap": "lock-step (every agent's tick k ends before any agent's tick k + 1 starts; overlay and "
-                                   "isSafeAfterOpt read the neighbours' records of tick k - 1) — variants.flight: per-agent overlap "
-                                   "under the staleness rule (sogm_flight_run)",
-                   # which all-gather ran: "abi" = sogm_traj_allgather (RCCL behind the C ABI), "local" = one process
-                   "exchange": exchange_kind,
-                   "exchange_fallback_reason": sw.exchange.fallback_reason,
-                   "sogm_grids_per_agent": overlap_mode if overlap_mode >= 2 else 1,
-                   "sogm_reset": "sparse (logged 32-byte sectors)" if sparse["enabled"] else "dense clear",
-                   "sogm_cell_order": "2x2x2 tiles" if spec.storage & 16 else "x-fastest rows",
-                   # where the tick's map update runs: inside the previous replan, agent by agent as their records are
-                   # published (sogm_planner_set_prestamp), or at the start of the tick
-                   "map_update": ("pre-stamped by the previous replan" if sw.prestamp and sparse["enabled"]
-                                  else "at the start of the tick")},
+    out = dict(headline(sw, spec, args, world, dt, n_ok, outcomes, sparse["enabled"], overlap_mode, world_note), **{
         "replans_per_s_per_agent": sw.A_tot * args.steps / dt / sw.A_tot,
         "stage_ms": {"clear": avg[0], "stamp": avg[1], "splat": avg[2], "astar": avg[3], "corridor": avg[4],
                      "qp": avg[5],
@@ -621,22 +720,9 @@ def main():
                              "(per agent, chained: chain_ms)"},
         "chain_ms": chain,
         "roofline": roofline,
-    }
-    if world > 1:  # the first N > 1 run verifies itself: what RCCL says, every rank's clock, the collective's own duration
-        info = sw.exchange.info()
-        mine = torch.tensor([dt_local / args.steps * 1e3, float(info["ranks"]),
-                             float(per_slot[pop._abi.PROF_EXCHANGE].mean()) if len(per_slot[pop._abi.PROF_EXCHANGE]) else -1.0],
-                            dtype=torch.float64, device="cuda")
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        out["multi_gpu"] = {"rccl_ranks": info["ranks"], "rccl_ranks_per_rank": [int(t[1].item()) for t in allr],
-                            "rank_ms_per_step": [float(t[0].item()) for t in allr],
-                            "allgather_ms_per_rank": [float(t[2].item()) for t in allr],
-                            "allgather_launches_timed": int(len(per_slot[pop._abi.PROF_EXCHANGE])),
-                            "allgather_bytes_per_rank": sw.A_loc * pop._abi.TRAJ_RECORD_BYTES,
-                            "exchange": exchange_kind}
-        if any(int(t[1].item()) != world for t in allr):
-            raise SystemExit(f"bench.py: ncclCommCount != {world} on some rank: {out['multi_gpu']}")
+    })
+    if world > 1:
+        out["multi_gpu"] = multi_gpu_block(pop, sw, dist, world, dt_local, args.steps, per_slot[pop._abi.PROF_EXCHANGE])
     dog = PostHeadlineWatchdog(out, rank, args.watchdog) if world > 1 and args.watchdog > 0 else None
     if dog:
         dog.section = "dense ticks"

@@ -137,3 +137,31 @@ print("NOT REACHED")
     code3 = code.replace("time.sleep(30)", "dog.cancel(); time.sleep(1)")
     r = subprocess.run([sys.executable, "-c", code3], capture_output=True, text=True, timeout=25)
     assert r.returncode == 0 and r.stdout.strip() == "NOT REACHED"
+
+
+def test_dumped_outputs_decode_the_trajectory_records(bench, pop, tmp_path):
+    """--dump-outputs: every record field lands in its own float64 array, the pieces beyond n_pieces are zeroed, the ok flags
+    are float32; the files are DIR/<name>.npy."""
+    import numpy as np
+    import torch
+
+    A, P = 3, pop._abi.SOGM_MAX_PIECES
+    recs = (pop._abi.SogmTrajRecord * A)()
+    for a in range(A):
+        recs[a].drone_id, recs[a].n_pieces, recs[a].time_start = 7 + a, a, 1.5 * a
+        for i in range(P):
+            recs[a].duration[i] = i + 0.25
+        for i in range(P * 15):
+            recs[a].cpts[i] = i * 0.5
+    raw = torch.from_numpy(np.frombuffer(bytes(recs), np.uint8).reshape(A, -1).copy())
+    sw = type("Swarm", (), {"records_all": lambda self: raw})()
+    out = bench.timed_outputs(pop, sw, None, 1, torch.tensor([1, 0, 1], dtype=torch.int32))
+    assert out["replan_ok"].dtype == np.float32 and out["replan_ok"].tolist() == [1, 0, 1]
+    assert out["traj_drone_id"].tolist() == [7, 8, 9] and out["traj_n_pieces"].tolist() == [0, 1, 2]
+    assert out["traj_time_start"].tolist() == [0.0, 1.5, 3.0]
+    assert out["traj_duration"].shape == (A, P) and out["traj_duration"][2].tolist() == [0.25, 1.25] + [0.0] * (P - 2)
+    assert out["traj_cpts"].shape == (A, P, 5, 3) and not out["traj_cpts"][0].any()
+    assert out["traj_cpts"][1, 0].ravel().tolist() == [i * 0.5 for i in range(15)] and not out["traj_cpts"][1, 1:].any()
+    bench.write_outputs(str(tmp_path / "d"), out)
+    for name, a in out.items():
+        assert np.array_equal(np.load(tmp_path / "d" / (name + ".npy")), a)

@@ -15,10 +15,10 @@ cd /tmp && export TMPDIR=/tmp
 db() { find "$1" -name "*.db" | head -1; }
 if [ "$PART" = core ]; then
   rocm-smi --showclocks --showpower --showtemp > $OUT/smi_before.txt 2>&1
-  timeout 900 python $REPO/bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+  timeout 900 python $REPO/bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
   cp $REPO/gpurun_out/bench_last_detail.json $OUT/bench_plain_detail.json
   rocm-smi --showclocks --showpower --showtemp > $OUT/smi_after.txt 2>&1
-  timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_trace -- python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --sustained 0 --dense-ticks 0 --no-variants > $OUT/bench_trace.json 2> $OUT/trace.err
+  timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_trace -- python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --sustained 0 --dense-ticks 0 --no-variants > $OUT/bench_trace.json 2> $OUT/trace.err
   cp $REPO/gpurun_out/bench_last_detail.json $OUT/bench_trace_detail.json
   # counter collection serialises kernels: the dataflow replan's persistent kernels cannot overlap then, so the map
   # kernels run by themselves (tools/diag_reset_pmc.py: reset + stamp + overlay per update, the reset in the variant the
@@ -42,12 +42,12 @@ if [ "$PART" = core ]; then
   tail -c 300 $OUT/bench_plain.json
 else
   cd $REPO
-  SOGM_LAYOUT=rows timeout 400 python bench.py --no-cpu-baseline --no-variants --sustained 100 --dense-ticks 0 > $OUT/bench_rows.json 2>/dev/null
+  SOGM_LAYOUT=rows timeout 400 python bench.py --full --no-cpu-baseline --no-variants --sustained 100 --dense-ticks 0 > $OUT/bench_rows.json 2>/dev/null
   cp $REPO/gpurun_out/bench_last_detail.json $OUT/bench_rows_detail.json
   SOGM_LAYOUT=rows timeout 300 python tools/bench_flight.py 20 "" > $OUT/flight_rows.txt 2>&1
-  SOGM_SPARSE_RESET=0 timeout 300 python bench.py --no-cpu-baseline --no-variants --sustained 100 --dense-ticks 0 > $OUT/bench_dense.json 2>/dev/null
+  SOGM_SPARSE_RESET=0 timeout 300 python bench.py --full --no-cpu-baseline --no-variants --sustained 100 --dense-ticks 0 > $OUT/bench_dense.json 2>/dev/null
   cp $REPO/gpurun_out/bench_last_detail.json $OUT/bench_dense_detail.json
-  SOGM_FLOW=0 timeout 300 python bench.py --no-cpu-baseline --no-variants --sustained 100 --dense-ticks 0 > $OUT/bench_flow0.json 2>/dev/null
+  SOGM_FLOW=0 timeout 300 python bench.py --full --no-cpu-baseline --no-variants --sustained 100 --dense-ticks 0 > $OUT/bench_flow0.json 2>/dev/null
   cp $REPO/gpurun_out/bench_last_detail.json $OUT/bench_flow0_detail.json
   timeout 900 python -m pytest tests/test_residency_gpu.py -q -s 2>&1 | grep -E "residency:|flight:" > $OUT/residency.txt
   ls $OUT | wc -l
