@@ -849,6 +849,82 @@ int sogm_replan(sogm_planner *p, const double *start_pva, const double *goal,
                 int32_t *out_ok, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* flight audit: what the swarm flies against the world that is there (the reference took these   */
+/*   numbers from its eval_helper submodule, absent from its tree)                                */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Semantics (one definition; tests/swarm_audit_reference.py restates it in numpy):
+ *   - What an agent flies (traj_server/src/bezier_traj_server.cpp): commands sampled every sample_dt (DELTA_T = 0.01 s,
+ *     :34); a new trajectory takes over at its start_time (bezierCallback :283-357); after its end the last point is held
+ *     (PubCallback :415+).
+ *   - Input: EXECUTED tables.  tables[k][a] is the record agent a executes after tick k (the latest-wins table).
+ *   - Samples: tick k of a call has the stamp t_k = t0 + (first_tick + k) * period (the tick driver's own expression) and the
+ *     samples t = t_k + j * sample_dt, j = 0 .. m - 1, m = period / sample_dt, which must be a whole number to 1e-9.  Times
+ *     are built from integers: auditing ticks in several calls gives the same samples as one call.
+ *   - Record: tables[k][a] is evaluated at t if it has n_pieces > 0 and time_start <= t; otherwise tables[k - 1][a] under the
+ *     same test (for k = 0 of a call: prev_table, or none if NULL); otherwise the agent is at fallback_pos[a] (where it hovers
+ *     before its first trajectory).  Evaluation is sogm_traj_eval's (clamped to [time_start, time_start + total]: the end
+ *     point is held).
+ *   - Body: an axis-aligned box of size body[] (0.4, 0.4, 0.45: plan_manager/config/sim_fake.yaml:85-87).
+ *   - Agent-agent collision at a sample: |dx| < bx && |dy| < by && |dz| < bz (two boxes overlap).  The separation is the
+ *     Euclidean distance of the two centres.
+ *   - Agent-obstacle collision (SogmCylinder type 3): diameter w, z extent [z - h/2, z + h/2], axis at time t at
+ *     (x + vx (t - t_obstacles), y + vy (t - t_obstacles)).  The z extents overlap if |pz - z| < (h + bz) / 2.  The gap is
+ *     the xy distance from the axis to the body's xy rectangle minus w / 2 (-w / 2 when the axis is inside the rectangle);
+ *     a collision is z overlap and gap < 0.  Only type 3 is audited: rings (type 2) and any other type are refused (below).
+ *   - Goal: the first sample with |p - goal| < goal_tolerance (1.0: fsm/goal_tolerance, sim_fake.yaml:5).
+ *   - Path length: sum of |p(t_i) - p(t_(i-1))| over consecutive samples, carried across calls (last_pos).
+ *   - Minima break ties by the earliest sample, then the lowest index.  Events: one per colliding (sample, agent, other or
+ *     obstacle), ordered by (tick, sample, agent, kind, other) within a call and appended in call order; when
+ *     event_capacity runs out the earliest are kept and *n_events still counts every one (a count -> exclusive scan ->
+ *     write, no order-dependent atomic: the output is bit-identical on repeated runs).
+ */
+typedef struct SogmAuditParams {
+  double  body[3];          /* box size, 0.4 0.4 0.45 */
+  double  sample_dt;        /* 0.01 */
+  double  goal_tolerance;   /* 1.0 */
+  double  t_obstacles;      /* the instant cylinders[] describes */
+  int32_t event_capacity;   /* entries of events[] (>= 0) */
+  int32_t reserved_;
+} SogmAuditParams;
+
+/* One audited agent's accumulator; sogm_audit_init_agents sets +inf minima, -1 times and indices, zero counts. */
+typedef struct SogmAuditAgent {
+  double  min_gap, min_gap_time;   /* smallest obstacle gap over samples with z overlap (+inf if none) */
+  double  min_sep, min_sep_time;   /* smallest centre distance to any other agent (+inf if none) */
+  double  goal_time;               /* first arrival, -1 never */
+  double  first_collision_time;    /* first sample in collision of either kind, -1 never */
+  double  path_length, last_pos[3];
+  int32_t min_gap_obstacle, min_sep_agent;
+  int32_t obstacle_samples, agent_samples;   /* samples in collision, per kind */
+  int32_t n_samples, has_last;
+} SogmAuditAgent;
+
+enum { SOGM_AUDIT_AGENT = 0, SOGM_AUDIT_OBSTACLE = 1 };
+typedef struct SogmAuditEvent {
+  double  t;
+  int32_t agent, other, kind, reserved_;   /* kind SOGM_AUDIT_AGENT (other = agent index) | SOGM_AUDIT_OBSTACLE (cylinder) */
+} SogmAuditEvent;
+
+/* dev acc [n_local]: the initial accumulator, stream-ordered. */
+int sogm_audit_init_agents(SogmAuditAgent *acc, int n_local, void *stream);
+/*
+ * Audits n_ticks executed tables (rows [agent0, agent0 + n_local) against all n_total rows and the cylinders) and adds the
+ * result to acc / events.  Stateless: the current device, the caller's stream, stream-ordered scratch; no streams, events or
+ * host synchronisation.
+ * dev tables [n_ticks][n_total], dev prev_table [n_total] or NULL (the table before tables[0]), dev fallback_pos [n_total][3],
+ * dev goals [n_local][3], dev cylinders [n_cyl] (NULL if n_cyl == 0), dev acc [n_local] in/out, dev events [event_capacity]
+ * (NULL if the capacity is 0), dev n_events [1] in/out: every colliding sample seen so far, kept or not.
+ * SOGM_ERR_INVALID_ARG (with sogm_last_error text) for null pointers, counts out of range, period / sample_dt not whole.
+ * The cylinders are device data the call does not read on the host: a cylinder whose type is not 3 makes the call add
+ * nothing and set *n_events = -1, which every later call keeps (the Python binding refuses such obstacles on the host).
+ */
+int sogm_swarm_audit(const SogmAuditParams *prm, const SogmTrajRecord *tables, int n_ticks, int n_total,
+                     const SogmTrajRecord *prev_table, double t0, int first_tick, double period, int agent0, int n_local,
+                     const double *fallback_pos, const double *goals, const SogmCylinder *cylinders, int n_cyl,
+                     SogmAuditAgent *acc, SogmAuditEvent *events, int32_t *n_events, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory exchange: the /broadcast_traj topic as ONE RCCL all-gather per replan tick          */
 /*   (plan_manager/src/plan_manager.cpp:364-399 publish, traj_coordinator/src/particles.cpp:131-191 receive)  */
 /* ------------------------------------------------------------------------------------------ */

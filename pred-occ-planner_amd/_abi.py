@@ -121,6 +121,28 @@ class SogmFlight(C.Structure):
                 ("log_ok", C.c_void_p), ("nccl_comm", C.c_void_p)]
 
 
+class SogmAuditParams(C.Structure):
+    _fields_ = [("body", C.c_double * 3), ("sample_dt", C.c_double), ("goal_tolerance", C.c_double),
+                ("t_obstacles", C.c_double), ("event_capacity", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SogmAuditAgent(C.Structure):
+    _fields_ = [("min_gap", C.c_double), ("min_gap_time", C.c_double), ("min_sep", C.c_double),
+                ("min_sep_time", C.c_double), ("goal_time", C.c_double), ("first_collision_time", C.c_double),
+                ("path_length", C.c_double), ("last_pos", C.c_double * 3), ("min_gap_obstacle", C.c_int32),
+                ("min_sep_agent", C.c_int32), ("obstacle_samples", C.c_int32), ("agent_samples", C.c_int32),
+                ("n_samples", C.c_int32), ("has_last", C.c_int32)]
+
+
+class SogmAuditEvent(C.Structure):
+    _fields_ = [("t", C.c_double), ("agent", C.c_int32), ("other", C.c_int32), ("kind", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+SOGM_AUDIT_AGENT, SOGM_AUDIT_OBSTACLE = 0, 1
+AUDIT_AGENT_BYTES = C.sizeof(SogmAuditAgent)  # 104
+AUDIT_EVENT_BYTES = C.sizeof(SogmAuditEvent)  # 24
+
 FLIGHT_MAX_TICKS = 64
 FLIGHT_HDR_ERR, FLIGHT_HDR_FINISHED, FLIGHT_HDR_LATE_WGS = 4, 5, 15  # sogm_flight_stats out_hdr indices
 FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "chain", "ticks")
@@ -200,6 +222,9 @@ PROTOTYPES = {
     "sogm_flight_prepare": (_i, [_vp, _i]),
     "sogm_flight_stats": (_i, [_vp, _vp, _vp]),
     "sogm_planner_set_swarm": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "sogm_audit_init_agents": (_i, [_vp, _i, _vp]),
+    "sogm_swarm_audit": (_i, [C.POINTER(SogmAuditParams), _vp, _i, _i, _vp, C.c_double, _i, C.c_double, _i, _i, _vp, _vp,
+                              _vp, _i, _vp, _vp, _vp, _vp]),
     "sogm_traj_allgather": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "sogm_exchange_wait": (_i, [_vp, _vp]),
     "sogm_comm_unique_id": (_i, [C.c_char_p]),

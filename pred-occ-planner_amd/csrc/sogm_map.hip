@@ -1305,51 +1305,6 @@ __global__ __launch_bounds__(256) void k_vt_to_slabs(const float *__restrict__ v
   for (int t = 0; t < g.T; ++t) cell_st(slabs, (size_t)t * g.V + p, vt[(size_t)v * g.T + t], g.half);
 }
 
-// Bezier pos / vel / acc of a trajectory record at an absolute time (bernstein.cpp:25-59)
-// returns false (and zeros) for an empty record
-__device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, double out[9]) {
-  if (r.n_pieces <= 0) {
-    for (int k = 0; k < 9; ++k) out[k] = 0.0;
-    return false;
-  }
-  double total = 0;
-  for (int k = 0; k < r.n_pieces; ++k) total += r.duration[k];
-  double tt = t_abs - r.time_start;
-  tt        = tt < 0 ? 0 : (tt > total ? total : tt);
-  // locatePiece (bernstein.hpp:164-172)
-  int    piece = r.n_pieces - 1;
-  double rem   = tt;
-  for (int k = 0; k < r.n_pieces; ++k) {
-    rem -= r.duration[k];
-    if (rem < 0) {
-      piece = k;
-      break;
-    }
-  }
-  double t0 = 0;
-  for (int k = 0; k < piece; ++k) t0 += r.duration[k];
-  const double tf = t0 + r.duration[piece], dur = tf - t0, s = (tt - t0) / dur;
-  const double A[5][5] = {{1, -4, 6, -4, 1}, {0, 4, -12, 12, -4}, {0, 0, 6, -12, 6},
-                          {0, 0, 0, 4, -4},  {0, 0, 0, 0, 1}};
-  const double S0[5] = {1, s, s * s, s * s * s, (s * s) * (s * s)};
-  const double S1[5] = {0, 1, 2 * s, 3 * (s * s), 4 * (s * s * s)};
-  const double S2[5] = {0, 0, 2, 6 * s, 12 * (s * s)};
-  const double *c    = r.cpts + piece * 15;
-  for (int d = 0; d < 3; ++d) {
-    double p = 0, v = 0, a = 0;
-    for (int j = 0; j < 5; ++j) {
-      double b = 0;
-      for (int q = 0; q < 5; ++q) b += c[q * 3 + d] * A[q][j];
-      p += b * S0[j];
-      v += b * S1[j];
-      a += b * S2[j];
-    }
-    out[d]     = p;
-    out[3 + d] = v / dur;
-    out[6 + d] = a / (dur * dur);
-  }
-  return true;
-}
 __global__ __launch_bounds__(64) void k_traj_eval(const SogmTrajRecord *__restrict__ rec, int n,
                                                   const double *__restrict__ t,
                                                   double *__restrict__ out, int32_t *__restrict__ ok) {

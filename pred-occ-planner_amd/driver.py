@@ -365,7 +365,7 @@ class SwarmTick:
     def __init__(self, grid="cfg2", agents_per_rank=None, rank=0, world=1, device=0, seed=0x5069,
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
-                 moving_world=None, neighbour_lag=1):
+                 moving_world=None, neighbour_lag=1, audit=False):
         self.rank, self.world, self.dist = rank, world, dist
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
@@ -437,6 +437,22 @@ class SwarmTick:
         # several ranks (or a process group of one): the swarm table is refreshed by the all-gather, not locally
         self.distributed = dist is not None and (world > 1 or dist.is_initialized())
         self.exchange = exchange if exchange is not None else RecordExchange(c.ctx, dist, rank, world, device)
+        # flight audit (audit.py): every tick's executed table, this rank's rows against all rows and the world's cylinders
+        self.auditor = None
+        if audit:
+            from .audit import SwarmAudit
+            tl = getattr(c, "timeline", None) or scene_mod.WorldTimeline(self.scene, TICK_PERIOD, moving=False)
+            self.auditor = SwarmAudit(self.A_tot, self.scene["goals"][lo:hi], self.scene["starts"], tl.cylinders(0),
+                                      self.t0, agent0=lo, n_local=self.A_loc, moving=tl.moving, device=d)
+
+    def _audit_tick(self, table):
+        """audit the table every agent executes after tick self.tick (stream-ordered)"""
+        if self.auditor is not None:
+            self.auditor.add(table, self.t0, self.tick, TICK_PERIOD)
+
+    def audit_report(self):
+        """the flight audit's report (synchronises); None when the SwarmTick was made without audit=True"""
+        return self.auditor.report() if self.auditor is not None else None
 
     def set_prestamp(self, on):
         """switch the pre-stamp on / off between two ticks of a flight (bench.py's labelled variant on the same swarm)"""
@@ -513,6 +529,8 @@ class SwarmTick:
         self.last_fsm = {"now": stamp, "ok": ok, "safe": safe, "reached": reached, "pub_new": pub_new,
                          "pub_hover": pub_hover, "hover_start": hover_start, "t_start": t_start, "pos": pva_now[:, :3]}
         self._exchange()
+        if self.auditor is not None:
+            self._audit_tick(self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all())
         self.tick += 1
         return ok.to(torch.int32)
 
@@ -552,9 +570,13 @@ class SwarmTick:
                                                           else torch.zeros_like(self.all))
             if self.deconflict:
                 c.set_swarm(self.all, self.A_tot, self.now)
+            if self.auditor is not None:
+                self._audit_tick(self.own)     # ver(k); self.all is the stale table the readers see
         else:
             c.replan(self.pva, self.goals, self.t_start, self.new, self.ok)
             self._publish()
+        if self.auditor is not None and self.neighbour_lag == 1:
+            self._audit_tick(self.records_all())
         self.tick += 1
         return self.ok.clone()  # self.ok is rewritten by the next tick
 
@@ -568,6 +590,9 @@ class SwarmTick:
         assert getattr(c, "use_world", False), "fly() needs world frames (moving_world=True / False)"
         assert not self.fsm
         if self.world > 1:
+            if self.auditor is not None:
+                # log_r holds this rank's rows only and the four-table ring does not keep the other ranks' versions
+                raise NotImplementedError("fly() with audit=True over several ranks: audit step() ticks instead")
             return self._fly_ranks(n_ticks)
         if not hasattr(self, "_fl_tables"):
             assert self.tick == 0, "a flight starts at tick 0 (or continues a flight)"
@@ -578,8 +603,15 @@ class SwarmTick:
         log_r = torch.zeros((n_ticks, self.A_loc, _abi.TRAJ_RECORD_BYTES), dtype=torch.uint8, device="cuda")
         log_ok = torch.zeros((n_ticks, self.A_loc), dtype=torch.int32, device="cuda")
         worlds = [c.world(self.tick + i) for i in range(n_ticks)]
+        executed = self.own.clone() if self.auditor is not None else None   # the table before the call
         self.planner.flight(worlds, self.tick, self.t0, TICK_PERIOD, REPLAN_START_TIME, self.goals, self.dev["ego_ids"],
                             self.hover, self.own, self._fl_tables, log_r, log_ok)
+        if self.auditor is not None:
+            # the flight's executed tables: latest-wins merges of its log, one launch per tick, then one audit call
+            tables = torch.empty((n_ticks, self.A_tot, _abi.TRAJ_RECORD_BYTES), dtype=torch.uint8, device="cuda")
+            for i in range(n_ticks):
+                c.merge_latest(log_r[i], log_ok[i], executed, tables[i])
+            self.auditor.add(tables, self.t0, self.tick, TICK_PERIOD)
         self.tick += n_ticks
         self._fl_next = self.tick
         self.all = self._fl_tables[(self.tick - 1) & 3]   # ver(last tick): what every agent executes now

@@ -378,4 +378,51 @@ class Planner {
   sogm_planner     *p_ = nullptr;
 };
 
+// Flight audit (sogm_abi.h "flight audit"): owns the accumulators of n_local agents and the event list on the device;
+// add() audits a batch of executed tables on the caller's stream (no synchronisation), agents() / events() read them back.
+class Audit {
+ public:
+  Audit(const SogmAuditParams &prm, int n_local, void *stream = nullptr)
+      : prm_(prm), n_(n_local), acc_((size_t)(n_local > 0 ? n_local : 1)),
+        ev_((size_t)(prm.event_capacity > 0 ? prm.event_capacity : 1)), n_ev_(1) {
+    check_abi();
+    check(sogm_audit_init_agents(acc_.data(), n_local, stream), "sogm_audit_init_agents");
+    (void)hipMemsetAsync(n_ev_.data(), 0, sizeof(int32_t), (hipStream_t)stream);
+  }
+  // dev tables [n_ticks][n_total], prev_table [n_total] or null, fallback_pos [n_total][3], goals [n_local][3], cylinders [n_cyl]
+  void add(const SogmTrajRecord *tables, int n_ticks, int n_total, const SogmTrajRecord *prev_table, double t0, int first_tick,
+           double period, int agent0, const double *fallback_pos, const double *goals, const SogmCylinder *cylinders,
+           int n_cyl, void *stream = nullptr) {
+    check(sogm_swarm_audit(&prm_, tables, n_ticks, n_total, prev_table, t0, first_tick, period, agent0, n_, fallback_pos,
+                           goals, cylinders, n_cyl, acc_.data(), prm_.event_capacity > 0 ? ev_.data() : nullptr,
+                           n_ev_.data(), stream),
+          "sogm_swarm_audit");
+  }
+  // synchronous read-backs
+  std::vector<SogmAuditAgent> agents() {
+    std::vector<SogmAuditAgent> out((size_t)n_);
+    (void)hipDeviceSynchronize();
+    acc_.get(out.data(), out.size());
+    return out;
+  }
+  // the kept events (earliest first) and, in *seen, every colliding sample counted (-1: an unsupported obstacle type)
+  std::vector<SogmAuditEvent> events(int32_t *seen = nullptr) {
+    int32_t n = 0;
+    (void)hipDeviceSynchronize();
+    n_ev_.get(&n, 1);
+    if (seen) *seen = n;
+    const int kept = n < 0 ? 0 : (n < prm_.event_capacity ? n : prm_.event_capacity);
+    std::vector<SogmAuditEvent> out((size_t)kept);
+    if (kept) ev_.get(out.data(), out.size());
+    return out;
+  }
+
+ private:
+  SogmAuditParams        prm_;
+  int                    n_;
+  DevBuf<SogmAuditAgent> acc_;
+  DevBuf<SogmAuditEvent> ev_;
+  DevBuf<int32_t>        n_ev_;
+};
+
 }  // namespace sogm_host

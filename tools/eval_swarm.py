@@ -1,0 +1,78 @@
+"""Fly a swarm with the flight audit on and print ONE JSON line: the audit's report (arrivals, collisions of each kind,
+minimum separation and gap) and its cost.
+
+    python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight [--frozen] [--events N]
+
+ms_per_tick: the same swarm flown twice back to back in this process, audit off then audit on (hip events around the
+whole run after a warm-up swarm); audit_ms_per_tick: device time of the audit's own launches in the audited run (hip
+events around each audit call)."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def run(driver, args, audit):
+    import torch
+    sw = driver.SwarmTick(args.grid, args.agents, moving_world=not args.frozen, prestamp=False if args.mode == "flight" else None,
+                          fsm=args.mode == "fsm", audit=audit)
+    sw.compute.prepare(0, args.ticks)
+    audit_ms = []
+    if audit:   # time every audit call with events of its own on the same stream
+        inner = sw.auditor.add
+
+        def timed(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            inner(*a, **k)
+            e1.record()
+            audit_ms.append((e0, e1))
+        sw.auditor.add = timed
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    if args.mode == "flight":
+        done = 0
+        while done < args.ticks:
+            n = min(60, args.ticks - done)
+            sw.fly(n)
+            done += n
+    else:
+        for _ in range(args.ticks):
+            sw.step()
+    end.record()
+    torch.cuda.synchronize()
+    ms = start.elapsed_time(end) / args.ticks
+    rep = sw.audit_report() if audit else None
+    a_ms = sum(e0.elapsed_time(e1) for e0, e1 in audit_ms) / args.ticks if audit else None
+    sw.close()
+    return ms, rep, a_ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("grid")
+    ap.add_argument("agents", type=int)
+    ap.add_argument("ticks", type=int)
+    ap.add_argument("mode", choices=("lockstep", "fsm", "flight"))
+    ap.add_argument("--frozen", action="store_true", help="a frozen world (moving_world=False)")
+    ap.add_argument("--events", type=int, default=20, help="events printed (the report counts all)")
+    args = ap.parse_args()
+    driver = importlib.import_module("pred-occ-planner_amd.driver")
+    run(driver, argparse.Namespace(**dict(vars(args), ticks=min(args.ticks, 5))), False)   # warm-up
+    ms_off, _, _ = run(driver, args, False)
+    ms_on, rep, audit_ms = run(driver, args, True)
+    ev = rep.pop("events")
+    out = {"grid": args.grid, "agents": args.agents, "ticks": args.ticks, "mode": args.mode, "moving_world": not args.frozen,
+           **rep, "first_events": ev[:args.events], "ms_per_tick_audit_off": round(ms_off, 4),
+           "ms_per_tick_audit_on": round(ms_on, 4), "audit_ms_per_tick": round(audit_ms, 4),
+           "timing": "same process, audit off then on, back to back; audit_ms_per_tick = hip events around each audit call"}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
