@@ -577,7 +577,11 @@ int sogm_corridor_generate(sogm_planner *p, const double *start_pva, const doubl
 /*
  * BezierOpt::setup + optimize (traj_opt/src/bezier_optimizer.cpp:27-285) for every agent.
  * dev out_cpts [n_agents*SOGM_MAX_PIECES*15] fp64, dev out_status [n_agents] int32 (OSQP status_val:
- * 1 solved, -2 max iter, -3 primal infeasible ...), dev out_iters [n_agents] int32.
+ * 1 solved, 2 solved inaccurate (max_iter, tolerances x 10), -2 max iter, -3 primal infeasible, 3 primal infeasible
+ * inaccurate, -7 KKT factorisation failed, -100 no pieces), dev out_iters [n_agents] int32.
+ * Contract on the unscaled rows, viol = ||max(Ax - u, l - Ax, 0)||_inf: status 1 means viol <= (eps_abs + eps_rel
+ * ||Ax||_inf) / (1 - eps_rel), 2 the same with both eps x 10; -3 / 3 only on an infeasible QP (tests/qp_contract.py).
+ * replan() accepts status 1 and 2 (as BezierOpt::optimize does): a status-2 trajectory is flown.
  */
 int sogm_bezier_qp_solve(sogm_planner *p, const double *start_pva, const double *goal_pv,
                          const double *polys, const int32_t *nfaces, const int32_t *npoly,
