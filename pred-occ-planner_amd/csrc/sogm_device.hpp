@@ -13,6 +13,7 @@
 
 #include "../../include/sogm_abi_debug.h"  // (includes sogm_abi.h: the library defines both headers' entry points)
 #include "../../include/sogm_detmath.h"
+#include "sogm_resources.hpp"
 
 namespace sogm {
 
@@ -554,6 +555,7 @@ enum {
 
 // ---- context (opaque in the C ABI) ----
 struct sogm_ctx {
+  sogm::Resources res;  // owns every buffer, stream and event below (sogm_resources.hpp)
   SogmSpec       spec;
   sogm::GridGeom geom;
   int            n_agents;
@@ -645,7 +647,7 @@ struct sogm_ctx {
   // set by a publishing sogm_replan: the event after which `records_final_ptr` (the host's own records) and every
   // reader of the swarm table inside that replan are done — the finishing kernel's end.  sogm_traj_allgather of exactly
   // those records starts from it instead of from the caller's stream position, i.e. under the pre-stamp's tail.
-  hipEvent_t            ev_records_final;
+  hipEvent_t            ev_records_final;  // an alias of the planner's ev_fdone[3]: not owned here
   const SogmTrajRecord *records_final_ptr;
   int                   records_final_valid;
   // set by a pre-stamping sogm_replan: the caller's stream is NOT joined to the pre-stamp's end inside that call — the
@@ -677,26 +679,21 @@ struct sogm_ctx {
   int            profiling;   // bit k: slot k is timed (sogm_set_profiling: all, sogm_set_profiling_slots: a choice)
   // per-slot ring of HIP event pairs: every launch of a profiled kernel since profiling was enabled keeps its own
   // pair, so a run can be timed launch by launch WITHOUT synchronising between launches (sogm_profile_read_all)
-  hipEvent_t    *ring[SOGM_PROF_N];    // [SOGM_PROF_RING][2], created lazily
+  std::vector<hipEvent_t> ring[SOGM_PROF_N];  // [SOGM_PROF_RING][2], created lazily
   long long      ring_n[SOGM_PROF_N];  // launches recorded since sogm_set_profiling(1)
 };
 #define SOGM_PROF_RING 1024
 
 namespace sogm {
-// Internal streams.  (CU-masked variants — the clear or the QP stage on CUs of their own — were measured in rounds 3
-// and 4 and lost: the latency-bound planner waves need the whole machine, profiles/EXPERIMENTS.md.)
-inline hipError_t create_stream_partitioned(hipStream_t *st, int /*role*/) {
-  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-}
-
-// RAII-free helper: record the begin/end events of profiling slot `slot` on `st`.
+// record the begin/end events of profiling slot `slot` on `st`.
 inline hipEvent_t *prof_pair(sogm_ctx *c, int slot, long long n) {
-  if (!c->ring[slot]) {
-    c->ring[slot] = new (std::nothrow) hipEvent_t[2 * SOGM_PROF_RING]();
-    if (!c->ring[slot]) return nullptr;
+  if (c->ring[slot].empty()) c->ring[slot].resize(2 * SOGM_PROF_RING, nullptr);
+  hipEvent_t *p = c->ring[slot].data() + 2 * (n % SOGM_PROF_RING);
+  if (!p[0]) {
+    Resources::Setup setup(c->res);
+    if (c->res.event(&p[0], hipEventDefault) != hipSuccess || c->res.event(&p[1], hipEventDefault) != hipSuccess) return nullptr;
+    setup.done();
   }
-  hipEvent_t *p = c->ring[slot] + 2 * (n % SOGM_PROF_RING);
-  if (!p[0] && (hipEventCreate(&p[0]) != hipSuccess || hipEventCreate(&p[1]) != hipSuccess)) return nullptr;
   return p;
 }
 inline void prof_begin(sogm_ctx *c, int slot, hipStream_t st) {

@@ -1540,25 +1540,14 @@ struct sogm_dsp {
   sogm_ctx          *map;
   DspDev             d;
   SogmDspParams      P;
-  std::vector<void *> allocs;
+  Resources          res;  // owns every buffer of `d`
 };
 
 namespace {
 template <typename T>
-int dmalloc(sogm_dsp *h, T **out, size_t n) {
-  void *p = nullptr;
-  if (hipMalloc(&p, n * sizeof(T) ? n * sizeof(T) : 16) != hipSuccess) return -1;
-  h->allocs.push_back(p);
-  *out = (T *)p;
-  return 0;
-}
-template <typename T>
 int dupload(sogm_dsp *h, const T **out, const T *src, size_t n) {
-  T *p;
-  if (dmalloc(h, &p, n)) return -1;
-  if (hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
-  *out = p;
-  return 0;
+  if (h->res.array(const_cast<T **>(out), n) != hipSuccess) return -1;
+  return hipMemcpy(const_cast<T *>(*out), src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ? -1 : 0;
 }
 }  // namespace
 
@@ -1567,7 +1556,7 @@ extern "C" {
 void sogm_dsp_destroy(sogm_dsp *h) {
   if (!h) return;
   (void)hipSetDevice(h->map->device);
-  for (void *p : h->allocs) (void)hipFree(p);
+  h->res.release_all();
   delete h;
 }
 
@@ -1596,12 +1585,11 @@ int sogm_dsp_create(sogm_ctx *map, const SogmDspParams *P, const float *p_gauss,
       return SOGM_ERR_CAPACITY;
     }
   }
-  sogm_dsp *h = new (std::nothrow) sogm_dsp;
+  sogm_dsp *h = new (std::nothrow) sogm_dsp();  // (value-initialised: `d` is zero)
   if (!h) return SOGM_ERR_HIP;
   h->map    = map;
   h->P      = *P;
   DspDev &d = h->d;
-  std::memset(&d, 0, sizeof(d));
   d.A   = map->n_agents;
   d.L   = sp.L;
   d.W   = sp.W;
@@ -1666,42 +1654,42 @@ int sogm_dsp_create(sogm_ctx *map, const SogmDspParams *P, const float *p_gauss,
   }
   const size_t A = d.A, V = d.V, VS = V * DSP_SLOTS, NP = d.NP, MP = d.max_pts, NB = d.nb, CC = d.cand_cap;
   int          bad = 0;
-  bad |= dmalloc(h, &d.ag, A);
-  bad |= dmalloc(h, &d.flag, A * VS);
-  for (int k = 0; k < 6; ++k) bad |= dmalloc(h, &d.f[k], A * VS);
-  bad |= dmalloc(h, &d.fut, A * d.T * V);
-  bad |= dmalloc(h, &d.occ, A * 4 * V);
-  bad |= dmalloc(h, &d.pc, A * NP * d.OM * 5);
-  bad |= dmalloc(h, &d.nobs, A * NP);
-  bad |= dmalloc(h, &d.maxlen, A * NP);
-  bad |= dmalloc(h, &d.obs_list, A * MP);
-  bad |= dmalloc(h, &d.bp_h, A * (d.nph + 1) * 3);
-  bad |= dmalloc(h, &d.bp_v, A * (d.npv + 1) * 3);
-  bad |= dmalloc(h, &d.born, A * MP * 7);
-  bad |= dmalloc(h, &d.vel_adj, A * MP * VEL_ADJ_CAP);
-  bad |= dmalloc(h, &d.vel_deg, A * MP);
-  bad |= dmalloc(h, &d.c_key, A * CC);
-  bad |= dmalloc(h, &d.c_dest, A * CC);
-  bad |= dmalloc(h, &d.c_pyr, A * CC);
-  bad |= dmalloc(h, &d.c_assign, A * CC);
-  bad |= dmalloc(h, &d.c_vnext, A * CC);
-  bad |= dmalloc(h, &d.c_pnext, A * CC);
-  bad |= dmalloc(h, &d.c_kill, A * CC);
-  bad |= dmalloc(h, &d.c_pay, A * CC * 6);
-  bad |= dmalloc(h, &d.vhead, A * V);
-  bad |= dmalloc(h, &d.phead, A * NP);
-  bad |= dmalloc(h, &d.pyr_list, A * NP * d.SP);
-  bad |= dmalloc(h, &d.pyr_n, A * NP);
-  bad |= dmalloc(h, &d.pyr_key, A * NP * d.SP);
-  bad |= dmalloc(h, &d.pyr_id, A * NP * d.SP);
-  bad |= dmalloc(h, &d.b_valid, A * MP);
-  bad |= dmalloc(h, &d.b_nstatic, A * MP);
-  bad |= dmalloc(h, &d.b_vi, A * MP);
-  bad |= dmalloc(h, &d.b_c, A * MP * 3);
-  bad |= dmalloc(h, &d.b_cls, A * MP * NB);
-  bad |= dmalloc(h, &d.b_dest, A * MP * NB);
-  bad |= dmalloc(h, &d.b_vnext, A * MP * NB);
-  bad |= dmalloc(h, &d.b_pay, A * MP * NB * 5);
+  bad |= h->res.array(&d.ag, A);
+  bad |= h->res.array(&d.flag, A * VS);
+  for (int k = 0; k < 6; ++k) bad |= h->res.array(&d.f[k], A * VS);
+  bad |= h->res.array(&d.fut, A * d.T * V);
+  bad |= h->res.array(&d.occ, A * 4 * V);
+  bad |= h->res.array(&d.pc, A * NP * d.OM * 5);
+  bad |= h->res.array(&d.nobs, A * NP);
+  bad |= h->res.array(&d.maxlen, A * NP);
+  bad |= h->res.array(&d.obs_list, A * MP);
+  bad |= h->res.array(&d.bp_h, A * (d.nph + 1) * 3);
+  bad |= h->res.array(&d.bp_v, A * (d.npv + 1) * 3);
+  bad |= h->res.array(&d.born, A * MP * 7);
+  bad |= h->res.array(&d.vel_adj, A * MP * VEL_ADJ_CAP);
+  bad |= h->res.array(&d.vel_deg, A * MP);
+  bad |= h->res.array(&d.c_key, A * CC);
+  bad |= h->res.array(&d.c_dest, A * CC);
+  bad |= h->res.array(&d.c_pyr, A * CC);
+  bad |= h->res.array(&d.c_assign, A * CC);
+  bad |= h->res.array(&d.c_vnext, A * CC);
+  bad |= h->res.array(&d.c_pnext, A * CC);
+  bad |= h->res.array(&d.c_kill, A * CC);
+  bad |= h->res.array(&d.c_pay, A * CC * 6);
+  bad |= h->res.array(&d.vhead, A * V);
+  bad |= h->res.array(&d.phead, A * NP);
+  bad |= h->res.array(&d.pyr_list, A * NP * d.SP);
+  bad |= h->res.array(&d.pyr_n, A * NP);
+  bad |= h->res.array(&d.pyr_key, A * NP * d.SP);
+  bad |= h->res.array(&d.pyr_id, A * NP * d.SP);
+  bad |= h->res.array(&d.b_valid, A * MP);
+  bad |= h->res.array(&d.b_nstatic, A * MP);
+  bad |= h->res.array(&d.b_vi, A * MP);
+  bad |= h->res.array(&d.b_c, A * MP * 3);
+  bad |= h->res.array(&d.b_cls, A * MP * NB);
+  bad |= h->res.array(&d.b_dest, A * MP * NB);
+  bad |= h->res.array(&d.b_vnext, A * MP * NB);
+  bad |= h->res.array(&d.b_pay, A * MP * NB * 5);
   bad |= dupload(h, &d.pg, p_gauss, (size_t)n_gauss);
   bad |= dupload(h, &d.vg, v_gauss, (size_t)n_gauss);
   bad |= dupload(h, &d.rnd, (const int *)rand_tab, (size_t)n_rand);

@@ -84,6 +84,7 @@ int rccl_fail(const char *what, ncclResult_t r) {
 namespace sogm {
 int exchange_stream(sogm_ctx *ctx, hipStream_t *out) {
   if (!ctx->xstream) {
+    Resources::Setup setup(ctx->res);
     // A stream with a compute-unit mask — here: every unit — gets a hardware queue of its OWN (plain streams share a pool of
     // GPU_MAX_HW_QUEUES queues).  The exchange stream carries kernels that WAIT (k_flight_xwait of a multi-rank flight: until a
     // tick is complete) and collectives that wait for their peers: whatever shared their queue would wait with them — with two
@@ -92,12 +93,13 @@ int exchange_stream(sogm_ctx *ctx, hipStream_t *out) {
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
     uint32_t mask[16];
     for (int i = 0; i < 16; ++i) mask[i] = 0xFFFFFFFFu;
-    if (hipExtStreamCreateWithCUMask(&ctx->xstream, (uint32_t)((n_cu + 31) / 32 < 16 ? (n_cu + 31) / 32 : 16), mask) != hipSuccess) {
+    if (ctx->res.stream_masked(&ctx->xstream, (uint32_t)((n_cu + 31) / 32 < 16 ? (n_cu + 31) / 32 : 16), mask) != hipSuccess) {
       (void)hipGetLastError();
-      SOGM_HIP_CHECK(hipStreamCreateWithFlags(&ctx->xstream, hipStreamNonBlocking));
+      SOGM_HIP_CHECK(ctx->res.stream(&ctx->xstream));
     }
-    SOGM_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_xin, hipEventDisableTiming));
-    SOGM_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_xdone, hipEventDisableTiming));
+    SOGM_HIP_CHECK(ctx->res.event(&ctx->ev_xin));
+    SOGM_HIP_CHECK(ctx->res.event(&ctx->ev_xdone));
+    setup.done();
   }
   if (out) *out = ctx->xstream;
   return SOGM_OK;

@@ -245,10 +245,12 @@ extern "C" int sogm_filter_point_cloud(sogm_ctx *c, const float *raw_xyz, const 
   if (!c->d_filter_cells) {
     const int    max_cells = c->filter_max_cells > 0 ? c->filter_max_cells : (1 << 20);
     const size_t nb        = (size_t)(max_cells + 1023) / 1024;
-    SOGM_HIP_CHECK(hipMalloc((void **)&c->d_filter_cells, (size_t)A * max_cells * 4 * sizeof(float)));
-    SOGM_HIP_CHECK(hipMalloc((void **)&c->d_filter_box, (size_t)A * sizeof(FilterBox)));
-    SOGM_HIP_CHECK(hipMalloc((void **)&c->d_filter_blocks, (size_t)A * nb * sizeof(int)));
+    sogm::Resources::Setup setup(c->res);
+    SOGM_HIP_CHECK(c->res.device(&c->d_filter_cells, (size_t)A * max_cells * 4 * sizeof(float)));
+    SOGM_HIP_CHECK(c->res.device(&c->d_filter_box, (size_t)A * sizeof(FilterBox)));
+    SOGM_HIP_CHECK(c->res.device(&c->d_filter_blocks, (size_t)A * nb * sizeof(int)));
     SOGM_HIP_CHECK(hipMemsetAsync(c->d_filter_cells, 0, (size_t)A * max_cells * 4 * sizeof(float), st));
+    setup.done();
     c->filter_max_cells = max_cells;
   }
   const int   max_cells = c->filter_max_cells;

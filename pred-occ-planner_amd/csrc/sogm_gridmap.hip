@@ -600,7 +600,7 @@ using namespace sogm;
 struct sogm_gridmap {
   GmDev               d;
   int                 device;
-  std::vector<void *> allocs;
+  Resources           res;  // owns every buffer of `d`
 };
 
 extern "C" {
@@ -609,7 +609,7 @@ void sogm_gridmap_destroy(sogm_gridmap *g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
   (void)hipDeviceSynchronize();
-  for (void *p : g->allocs) (void)hipFree(p);
+  g->res.release_all();
   delete g;
 }
 
@@ -620,11 +620,10 @@ int sogm_gridmap_create(const SogmGridMapParams *P, int n_agents, int device, so
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOGM_ERR_NO_DEVICE;
   SOGM_HIP_CHECK(hipSetDevice(device));
-  sogm_gridmap *g = new (std::nothrow) sogm_gridmap;
+  sogm_gridmap *g = new (std::nothrow) sogm_gridmap();  // (value-initialised: `d` is zero)
   if (!g) return SOGM_ERR_HIP;
   g->device = device;
   GmDev &d  = g->d;
-  std::memset(&d, 0, sizeof(d));
   SogmGridMapParams p = *P;
   if (p.virtual_ceil_height - p.ground_height > p.map_size[2]) p.virtual_ceil_height = p.ground_height + p.map_size[2];
   d.A       = n_agents;
@@ -673,27 +672,22 @@ int sogm_gridmap_create(const SogmGridMapParams *P, int n_agents, int device, so
   d.has_ceil = p.virtual_ceil_height > -0.5;
   d.ceil_id  = (int)floor((p.virtual_ceil_height - d.origin[2]) * d.res_inv) - 1;
   const size_t A = n_agents, N = d.N, NS = d.n_samples > 0 ? d.n_samples : 1;
-  auto alloc = [&](void **ptr, size_t bytes) {
-    if (hipMalloc(ptr, bytes ? bytes : 16) != hipSuccess) return -1;
-    g->allocs.push_back(*ptr);
-    return 0;
-  };
   int bad = 0;
-  bad |= alloc((void **)&d.ag, A * sizeof(GmAgent));
-  bad |= alloc((void **)&d.occ, A * N * sizeof(double));
-  bad |= alloc((void **)&d.inflate, A * N);
-  bad |= alloc((void **)&d.cnt_hm, A * N * sizeof(int));
-  bad |= alloc((void **)&d.cnt_hit, A * N * sizeof(int));
-  bad |= alloc((void **)&d.rayend, A * N * 8);
-  bad |= alloc((void **)&d.own[0], A * N * 8);
-  bad |= alloc((void **)&d.own[1], A * N * 8);
-  bad |= alloc((void **)&d.touched, A * N * sizeof(int));
-  bad |= alloc((void **)&d.first_trav, A * N * 8);
-  bad |= alloc((void **)&d.pt, A * NS * 3 * sizeof(double));
-  bad |= alloc((void **)&d.end_vox, A * NS * sizeof(int));
-  bad |= alloc((void **)&d.stop[0], A * NS * sizeof(int));
-  bad |= alloc((void **)&d.stop[1], A * NS * sizeof(int));
-  bad |= alloc((void **)&d.active, A * NS);
+  bad |= g->res.array(&d.ag, A);
+  bad |= g->res.array(&d.occ, A * N);
+  bad |= g->res.array(&d.inflate, A * N);
+  bad |= g->res.array(&d.cnt_hm, A * N);
+  bad |= g->res.array(&d.cnt_hit, A * N);
+  bad |= g->res.array(&d.rayend, A * N);
+  bad |= g->res.array(&d.own[0], A * N);
+  bad |= g->res.array(&d.own[1], A * N);
+  bad |= g->res.array(&d.touched, A * N);
+  bad |= g->res.array(&d.first_trav, A * N);
+  bad |= g->res.array(&d.pt, A * NS * 3);
+  bad |= g->res.array(&d.end_vox, A * NS);
+  bad |= g->res.array(&d.stop[0], A * NS);
+  bad |= g->res.array(&d.stop[1], A * NS);
+  bad |= g->res.array(&d.active, A * NS);
   d.act_cap  = (int)(NS / 4 > 4096 ? NS / 4 : 4096);  // rays left after the ray-end de-duplication
   d.path_max = 192;                                   // DDA steps of the longest ray (max_ray_length / resolution * 3)
   {
@@ -701,11 +695,11 @@ int sogm_gridmap_create(const SogmGridMapParams *P, int n_agents, int device, so
     if (steps > d.path_max) d.path_max = (int)steps;
   }
   const size_t AC = d.act_cap;
-  bad |= alloc((void **)&d.act_ray, A * AC * sizeof(int));
-  bad |= alloc((void **)&d.path, A * AC * (size_t)d.path_max * sizeof(int));
-  bad |= alloc((void **)&d.plen, A * AC * sizeof(int));
-  bad |= alloc((void **)&d.astop[0], A * AC * sizeof(int));
-  bad |= alloc((void **)&d.astop[1], A * AC * sizeof(int));
+  bad |= g->res.array(&d.act_ray, A * AC);
+  bad |= g->res.array(&d.path, A * AC * (size_t)d.path_max);
+  bad |= g->res.array(&d.plen, A * AC);
+  bad |= g->res.array(&d.astop[0], A * AC);
+  bad |= g->res.array(&d.astop[1], A * AC);
   if (bad) {
     set_error("sogm_gridmap_create: hipMalloc", hipGetLastError());
     sogm_gridmap_destroy(g);

@@ -1832,36 +1832,22 @@ MarkLog mark_log(sogm_ctx *c, int slot) {
   MarkLog none{nullptr, nullptr, 0, nullptr};
   if (!c->sparse || slot < 0 || slot > 2) return none;
   if (!c->d_log[slot]) {
-    unsigned *e = nullptr, *n = nullptr;
+    Resources::Setup setup(c->res);
     // (The counters' first zeroing is COMPLETE when this returns: the memset is a null-stream operation, which the
     //  library's non-blocking streams do not wait for — with a second context busy on the device it was seen to run
     //  after the first stamp had appended its entries, i.e. it threw them away, and the slot's first reset through
     //  its log left that stamp's marks in the grid.  Only the null stream is synchronised: persistent kernels of a
     //  replan in flight on other streams are not waited for.)
-    if (hipMalloc((void **)&e, sizeof(unsigned) * (size_t)c->log_cap * c->n_agents) != hipSuccess ||
-        hipMalloc((void **)&n, sizeof(unsigned) * (size_t)c->n_agents) != hipSuccess ||
-        hipMemset(n, 0, sizeof(unsigned) * (size_t)c->n_agents) != hipSuccess ||
+    if (c->res.device(&c->d_log[slot], sizeof(unsigned) * (size_t)c->log_cap * c->n_agents) != hipSuccess ||
+        c->res.device(&c->d_log_n[slot], sizeof(unsigned) * (size_t)c->n_agents, true) != hipSuccess ||
+        (!c->d_reset_stat && c->res.device(&c->d_reset_stat, 8 * sizeof(unsigned long long), true) != hipSuccess) ||
         hipStreamSynchronize(nullptr) != hipSuccess) {
       (void)hipGetLastError();
-      if (e) (void)hipFree(e);
-      if (n) (void)hipFree(n);
       c->sparse = 0;  // no room: dense clears from here on
       for (int i = 0; i < 3; ++i) c->tracked[i] = 0;
       return none;
     }
-    if (!c->d_reset_stat &&
-        (hipMalloc((void **)&c->d_reset_stat, 8 * sizeof(unsigned long long)) != hipSuccess ||
-         hipMemset(c->d_reset_stat, 0, 8 * sizeof(unsigned long long)) != hipSuccess ||
-         hipStreamSynchronize(nullptr) != hipSuccess)) {
-      (void)hipGetLastError();
-      (void)hipFree(e);
-      (void)hipFree(n);
-      c->sparse = 0;
-      for (int i = 0; i < 3; ++i) c->tracked[i] = 0;
-      return none;
-    }
-    c->d_log[slot]   = e;
-    c->d_log_n[slot] = n;
+    setup.done();
     c->tracked[slot] = 0;  // what the grid holds now was written without a log
   }
   return MarkLog{c->d_log[slot], c->d_log_n[slot], c->log_cap, c->d_reset_stat ? c->d_reset_stat + 4 : nullptr};
@@ -1895,23 +1881,23 @@ int reset_slot(sogm_ctx *c, hipStream_t st, int slot, float *grid, bool polite) 
 
 static int stamp_scratch(sogm_ctx *c, hipStream_t st, int *words_out) {
   const int A = c->n_agents;
-  if (!c->d_cand) {
-    SOGM_HIP_CHECK(hipMalloc(&c->d_cand, sizeof(CylCand) * SOGM_MAX_CYL_LDS * (size_t)A));
-    SOGM_HIP_CHECK(hipMalloc(&c->d_ncand, sizeof(int) * (size_t)A));
-  }
   const int words = (((c->geom.V + 31) / 32) + 255) & ~255;  // k_stamp_marks reads 256 words per trip
-  if (!c->d_stamp_bits) {
-    SOGM_HIP_CHECK(hipMalloc((void **)&c->d_stamp_bits, sizeof(unsigned) * (size_t)words * A));
-    SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * (size_t)words * A, st));
-  }
   *words_out = words;
-  return SOGM_OK;
+  if (c->d_cand) return SOGM_OK;
+  Resources::Setup setup(c->res);
+  SOGM_HIP_CHECK(c->res.device(&c->d_cand, sizeof(CylCand) * SOGM_MAX_CYL_LDS * (size_t)A));
+  SOGM_HIP_CHECK(c->res.device(&c->d_ncand, sizeof(int) * (size_t)A));
+  SOGM_HIP_CHECK(c->res.device(&c->d_stamp_bits, sizeof(unsigned) * (size_t)words * A));
+  SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * (size_t)words * A, st));
+  return setup.done();
 }
 int prestamp_buffers(sogm_ctx *c, PrestampDev *d) {
   SOGM_HIP_CHECK(hipSetDevice(c->device));
   if (!c->d_poses_next) {
-    SOGM_HIP_CHECK(hipMalloc(&c->d_poses_next, sizeof(float) * 3 * (size_t)c->n_agents));
-    SOGM_HIP_CHECK(hipMalloc(&c->d_stamps_next, sizeof(double) * (size_t)c->n_agents));
+    Resources::Setup setup(c->res);
+    SOGM_HIP_CHECK(c->res.device(&c->d_poses_next, sizeof(float) * 3 * (size_t)c->n_agents));
+    SOGM_HIP_CHECK(c->res.device(&c->d_stamps_next, sizeof(double) * (size_t)c->n_agents));
+    setup.done();
   }
   int words = 0;
   if (int rc = stamp_scratch(c, nullptr, &words)) return rc;
@@ -1933,11 +1919,13 @@ int world_blocks(sogm_ctx *c, const SogmWorld *w, CloudBlocks *out) {
     // (grown between ticks only: a frame with more blocks than any before; the old lists may still be read by a
     //  pre-stamp in flight, so everything drains first)
     SOGM_HIP_CHECK(hipDeviceSynchronize());
-    if (c->d_blk_list) (void)hipFree(c->d_blk_list);
-    c->d_blk_list = nullptr;
+    c->res.release(&c->d_blk_list);
+    c->blk_cap = 0;
+    Resources::Setup setup(c->res);
     const int cap = (w->n_blocks + 1023) & ~1023;
-    SOGM_HIP_CHECK(hipMalloc((void **)&c->d_blk_list, sizeof(int) * (size_t)cap * (size_t)c->n_agents));
-    if (!c->d_blk_n) SOGM_HIP_CHECK(hipMalloc((void **)&c->d_blk_n, sizeof(int) * (size_t)c->n_agents));
+    SOGM_HIP_CHECK(c->res.device(&c->d_blk_list, sizeof(int) * (size_t)cap * (size_t)c->n_agents));
+    if (!c->d_blk_n) SOGM_HIP_CHECK(c->res.device(&c->d_blk_n, sizeof(int) * (size_t)c->n_agents));
+    setup.done();
     c->blk_cap = cap;
   }
   // (rows of blk_cap entries whatever the frame holds: a row never exceeds n_blocks <= blk_cap)
@@ -2179,9 +2167,8 @@ int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) 
     return SOGM_ERR_NO_DEVICE;
   }
   if (hipSetDevice(device) != hipSuccess) return SOGM_ERR_NO_DEVICE;
-  sogm_ctx *c = new (std::nothrow) sogm_ctx();
+  sogm_ctx *c = new (std::nothrow) sogm_ctx();  // (value-initialised: every field is zero)
   if (!c) return SOGM_ERR_INVALID_ARG;
-  std::memset(c, 0, sizeof(*c));
   c->spec          = *spec;
   c->geom          = make_geom(*spec);
   c->n_agents      = n_agents;
@@ -2199,23 +2186,20 @@ int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) 
     c->log_cap    = (int)(dflt < (1 << 20) ? (1 << 20) : (dflt > (1 << 26) ? (1 << 26) : dflt));
   }
   const size_t n   = (size_t)n_agents * spec->T * (size_t)c->geom.V;
-  hipError_t   e   = hipMalloc(&c->d_grid, (n * c->cell_bytes() + 15) & ~(size_t)15);
-  if (e == hipSuccess) e = hipMalloc(&c->d_poses, sizeof(float) * 3 * n_agents);
-  if (e == hipSuccess) e = hipMalloc(&c->d_stamps, sizeof(double) * n_agents);
-  if (e == hipSuccess) e = hipMalloc(&c->d_scratch_vt, sizeof(float) * (size_t)c->geom.V * spec->T);
-  if (e == hipSuccess) e = hipMemset(c->d_poses, 0, sizeof(float) * 3 * n_agents);
-  if (e == hipSuccess) e = hipMemset(c->d_stamps, 0, sizeof(double) * n_agents);
-  if (e == hipSuccess) e = hipMalloc((void **)&c->clear_cursor, 2 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(c->clear_cursor, 0, 2 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = sogm::create_stream_partitioned(&c->side, 0);
-  if (e == hipSuccess) e = sogm::create_stream_partitioned(&c->side2, 0);
-  if (e == hipSuccess) e = sogm::create_stream_partitioned(&c->pstream, 0);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_side2_go, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_side2_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_grid_free, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_cleared, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_gate_open, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_gate_frac, hipEventDisableTiming);
+  hipError_t   e   = c->res.device(&c->d_grid, (n * c->cell_bytes() + 15) & ~(size_t)15);
+  if (e == hipSuccess) e = c->res.device(&c->d_poses, sizeof(float) * 3 * n_agents, true);
+  if (e == hipSuccess) e = c->res.device(&c->d_stamps, sizeof(double) * n_agents, true);
+  if (e == hipSuccess) e = c->res.device(&c->d_scratch_vt, sizeof(float) * (size_t)c->geom.V * spec->T);
+  if (e == hipSuccess) e = c->res.device(&c->clear_cursor, 2 * sizeof(unsigned long long), true);
+  if (e == hipSuccess) e = c->res.stream(&c->side);
+  if (e == hipSuccess) e = c->res.stream(&c->side2);
+  if (e == hipSuccess) e = c->res.stream(&c->pstream);
+  if (e == hipSuccess) e = c->res.event(&c->ev_side2_go);
+  if (e == hipSuccess) e = c->res.event(&c->ev_side2_done);
+  if (e == hipSuccess) e = c->res.event(&c->ev_grid_free);
+  if (e == hipSuccess) e = c->res.event(&c->ev_cleared);
+  if (e == hipSuccess) e = c->res.event(&c->ev_gate_open);
+  if (e == hipSuccess) e = c->res.event(&c->ev_gate_frac);
   // the memsets above are null-stream operations, which the non-blocking streams every later call uses do not wait for
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess) {
@@ -2229,73 +2213,8 @@ int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) 
 
 void sogm_destroy(sogm_ctx *c) {
   if (!c) return;
-  if (c->n_pool == 0 && c->d_grid) (void)hipFree(c->d_grid);
-  for (int i = 0; i < c->n_pool; ++i)
-    if (c->pool[i]) (void)hipFree(c->pool[i]);
-  for (int i = 0; i < 3; ++i)
-    if (c->pool_ev[i]) (void)hipEventDestroy(c->pool_ev[i]);
-  for (int i = 0; i < 3; ++i) {
-    if (c->d_log[i]) (void)hipFree(c->d_log[i]);
-    if (c->d_log_n[i]) (void)hipFree(c->d_log_n[i]);
-  }
-  if (c->d_reset_stat) (void)hipFree(c->d_reset_stat);
-  if (c->d_poses_next) (void)hipFree(c->d_poses_next);
-  if (c->d_stamps_next) (void)hipFree(c->d_stamps_next);
-  if (c->d_poses) (void)hipFree(c->d_poses);
-  if (c->d_stamps) (void)hipFree(c->d_stamps);
-  if (c->clear_cursor) (void)hipFree(c->clear_cursor);
-  if (c->d_body) (void)hipFree(c->d_body);
-  if (c->d_scratch_vt) (void)hipFree(c->d_scratch_vt);
-  if (c->d_cand) (void)hipFree(c->d_cand);
-  if (c->d_stamp_bits) (void)hipFree(c->d_stamp_bits);
-  if (c->d_ncand) (void)hipFree(c->d_ncand);
-  if (c->h_tick_clock) (void)hipHostFree(c->h_tick_clock);
-  if (c->d_blk_list) (void)hipFree(c->d_blk_list);
-  if (c->d_blk_n) (void)hipFree(c->d_blk_n);
-  if (c->d_filter_cells) (void)hipFree(c->d_filter_cells);
-  if (c->d_filter_box) (void)hipFree(c->d_filter_box);
-  if (c->d_filter_blocks) (void)hipFree(c->d_filter_blocks);
-  if (c->side) {
-    (void)hipStreamSynchronize(c->side);
-    (void)hipStreamDestroy(c->side);
-  }
-  if (c->side2) {
-    (void)hipStreamSynchronize(c->side2);
-    (void)hipStreamDestroy(c->side2);
-  }
-  if (c->pstream) {
-    (void)hipStreamSynchronize(c->pstream);
-    (void)hipStreamDestroy(c->pstream);
-  }
-  if (c->ustream) {
-    (void)hipStreamSynchronize(c->ustream);
-    (void)hipStreamDestroy(c->ustream);
-  }
-  if (c->ev_uin) (void)hipEventDestroy(c->ev_uin);
-  if (c->ev_udone) (void)hipEventDestroy(c->ev_udone);
-  if (c->d_map_ready) (void)hipFree(c->d_map_ready);
-  if (c->d_update_ctl) (void)hipFree(c->d_update_ctl);
-  if (c->d_update_order) (void)hipFree(c->d_update_order);
-  if (c->d_update_ts) (void)hipFree(c->d_update_ts);
-  if (c->ev_side2_go) (void)hipEventDestroy(c->ev_side2_go);
-  if (c->ev_side2_done) (void)hipEventDestroy(c->ev_side2_done);
-  if (c->ev_grid_free) (void)hipEventDestroy(c->ev_grid_free);
-  if (c->ev_cleared) (void)hipEventDestroy(c->ev_cleared);
-  if (c->ev_gate_open) (void)hipEventDestroy(c->ev_gate_open);
-  if (c->ev_gate_frac) (void)hipEventDestroy(c->ev_gate_frac);
-  if (c->xstream) {
-    (void)hipStreamSynchronize(c->xstream);
-    (void)hipStreamDestroy(c->xstream);
-  }
-  if (c->ev_xin) (void)hipEventDestroy(c->ev_xin);
-  if (c->ev_xdone) (void)hipEventDestroy(c->ev_xdone);
-  for (int k = 0; k < SOGM_PROF_N; ++k) {
-    if (c->ring[k]) {
-      for (int i = 0; i < 2 * SOGM_PROF_RING; ++i)
-        if (c->ring[k][i]) (void)hipEventDestroy(c->ring[k][i]);
-      delete[] c->ring[k];
-    }
-  }
+  (void)hipSetDevice(c->device);
+  c->res.release_all();
   delete c;
 }
 
@@ -2317,10 +2236,8 @@ int sogm_set_sparse_reset(sogm_ctx *c, int enable, int log_capacity) {
   SOGM_HIP_CHECK(hipSetDevice(c->device));
   SOGM_HIP_CHECK(hipDeviceSynchronize());  // resets / writers in flight use the logs
   for (int i = 0; i < 3; ++i) {
-    if (c->d_log[i]) (void)hipFree(c->d_log[i]);
-    if (c->d_log_n[i]) (void)hipFree(c->d_log_n[i]);
-    c->d_log[i]   = nullptr;
-    c->d_log_n[i] = nullptr;
+    c->res.release(&c->d_log[i]);
+    c->res.release(&c->d_log_n[i]);
     c->tracked[i] = 0;  // contents unknown to the (new) logs: each slot's next reset is dense
   }
   c->sparse = enable ? 1 : 0;
@@ -2658,46 +2575,28 @@ int sogm_set_overlap_clear(sogm_ctx *c, int mode) {
     std::swap(c->hist_dense[0], c->hist_dense[c->cur_idx]);
     c->cur_idx         = 0;
   }
-  while (c->n_pool > want) {
-    (void)hipFree(c->pool[--c->n_pool]);
-    c->pool[c->n_pool] = nullptr;
-  }
+  while (c->n_pool > want) c->res.release(&c->pool[--c->n_pool]);
   for (int i = 1; i < 3; ++i) c->tracked[i] = 0;  // spares hold garbage: their first reset is the dense clear
   for (int i = 1; i < 3; ++i) c->hist_sparse[i] = c->hist_dense[i] = 0;
   const size_t bytes = ((size_t)sogm_grid_bytes(c) + 15) & ~(size_t)15;
-  const int    had   = c->n_pool;
-  while (c->n_pool < want) {
-    float *g = nullptr;
-    if (hipMalloc(&g, bytes) != hipSuccess) {
+  {
+    sogm::Resources::Setup setup(c->res);  // all or nothing: the mode is unchanged when a spare or an event cannot be had
+    hipError_t e = hipSuccess;
+    bool       grid = false;
+    for (int i = c->n_pool; i < want && e == hipSuccess; ++i) grid = (e = c->res.device(&c->pool[i], bytes)) != hipSuccess;
+    for (int i = 0; i < want && e == hipSuccess; ++i)  // every slot takes the spare role in turn
+      if (!c->pool_ev[i]) e = c->res.event(&c->pool_ev[i]);
+    if (e != hipSuccess) {
       (void)hipGetLastError();
-      while (c->n_pool > had) {  // all or nothing: the mode is unchanged
-        (void)hipFree(c->pool[--c->n_pool]);
-        c->pool[c->n_pool] = nullptr;
-      }
-      sogm::set_error("sogm_set_overlap_clear: no room for the spare grid(s)", hipErrorOutOfMemory);
       c->n_ready = 0;
       c->n_dirty = 0;
-      for (int i = 1; i < c->n_pool; ++i) c->dirty[c->n_dirty++] = i;
-      return SOGM_ERR_CAPACITY;
+      for (int i = 1; i < c->n_pool; ++i) c->dirty[c->n_dirty++] = i;  // the lists describe the pool again
+      sogm::set_error(grid ? "sogm_set_overlap_clear: no room for the spare grid(s)" : "sogm_set_overlap_clear: event", e);
+      return grid ? SOGM_ERR_CAPACITY : SOGM_ERR_HIP;
     }
-    if (!c->pool_ev[c->n_pool] &&
-        hipEventCreateWithFlags(&c->pool_ev[c->n_pool], hipEventDisableTiming) != hipSuccess) {
-      // same roll-back as a failed allocation: the grids added by this call go, the lists describe the pool again
-      (void)hipFree(g);
-      while (c->n_pool > had) {
-        (void)hipFree(c->pool[--c->n_pool]);
-        c->pool[c->n_pool] = nullptr;
-      }
-      c->n_ready = 0;
-      c->n_dirty = 0;
-      for (int i = 1; i < c->n_pool; ++i) c->dirty[c->n_dirty++] = i;
-      sogm::set_error("sogm_set_overlap_clear: event", hipErrorUnknown);
-      return SOGM_ERR_HIP;
-    }
-    c->pool[c->n_pool++] = g;
+    setup.done();
+    c->n_pool = want;
   }
-  for (int i = 0; i < c->n_pool; ++i)  // every slot takes the spare role in turn
-    if (!c->pool_ev[i]) SOGM_HIP_CHECK(hipEventCreateWithFlags(&c->pool_ev[i], hipEventDisableTiming));
   c->n_ready = 0;
   c->n_dirty = 0;
   for (int i = 1; i < c->n_pool; ++i) c->dirty[c->n_dirty++] = i;  // spares hold garbage until a replan clears them
@@ -2722,8 +2621,8 @@ int sogm_profile_read(sogm_ctx *c, double *out_ms) {
   SOGM_HIP_CHECK(hipDeviceSynchronize());
   for (int k = 0; k < SOGM_PROF_N; ++k) {
     out_ms[k] = -1.0;
-    if (c->ring_n[k] <= 0 || !c->ring[k]) continue;
-    hipEvent_t *p  = c->ring[k] + 2 * ((c->ring_n[k] - 1) % SOGM_PROF_RING);
+    if (c->ring_n[k] <= 0 || c->ring[k].empty()) continue;
+    hipEvent_t *p  = c->ring[k].data() + 2 * ((c->ring_n[k] - 1) % SOGM_PROF_RING);
     float       ms = 0.f;
     if (hipEventElapsedTime(&ms, p[0], p[1]) == hipSuccess) out_ms[k] = (double)ms;
   }
@@ -2738,9 +2637,9 @@ int sogm_profile_read_all(sogm_ctx *c, int slot, double *out_ms, int cap, int *o
   if (n > SOGM_PROF_RING) n = SOGM_PROF_RING;
   if (n > cap) n = cap;
   *out_n = 0;
-  if (!c->ring[slot]) return SOGM_OK;
+  if (c->ring[slot].empty()) return SOGM_OK;
   for (long long i = c->ring_n[slot] - n; i < c->ring_n[slot]; ++i) {  // oldest kept launch first
-    hipEvent_t *p  = c->ring[slot] + 2 * (i % SOGM_PROF_RING);
+    hipEvent_t *p  = c->ring[slot].data() + 2 * (i % SOGM_PROF_RING);
     float       ms = 0.f;
     if (hipEventElapsedTime(&ms, p[0], p[1]) != hipSuccess) ms = -1.f;
     out_ms[(*out_n)++] = (double)ms;
@@ -2751,9 +2650,8 @@ int sogm_profile_read_all(sogm_ctx *c, int slot, double *out_ms, int cap, int *o
 int sogm_set_body_particles(sogm_ctx *c, const double *xyz, int n) {
   if (!c || !xyz || n <= 0) return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (c->d_body) (void)hipFree(c->d_body);
-  c->d_body = nullptr;
-  SOGM_HIP_CHECK(hipMalloc(&c->d_body, sizeof(double) * 3 * n));
+  c->res.release(&c->d_body);
+  SOGM_HIP_CHECK(c->res.device(&c->d_body, sizeof(double) * 3 * n));
   SOGM_HIP_CHECK(hipMemcpy(c->d_body, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
   c->n_body = n;
   for (int k = 0; k < 3; ++k) {
@@ -2860,20 +2758,19 @@ namespace sogm {
 // stream, events and words of the update flow (first use)
 static int update_flow_setup(sogm_ctx *c) {
   if (c->ustream) return SOGM_OK;
+  Resources::Setup setup(c->res);
   const int A = c->n_agents;
-  SOGM_HIP_CHECK(sogm::create_stream_partitioned(&c->ustream, 0));
-  SOGM_HIP_CHECK(hipEventCreateWithFlags(&c->ev_uin, hipEventDisableTiming));
-  SOGM_HIP_CHECK(hipEventCreateWithFlags(&c->ev_udone, hipEventDisableTiming));
-  SOGM_HIP_CHECK(hipMalloc((void **)&c->d_map_ready, sizeof(int) * A));
-  SOGM_HIP_CHECK(hipMalloc((void **)&c->d_update_ctl, sizeof(int) * (size_t)(UF_STAGE + UF_STAGE_STRIDE * A)));
-  SOGM_HIP_CHECK(hipMalloc((void **)&c->d_update_order, sizeof(int) * A));
-  SOGM_HIP_CHECK(hipMalloc((void **)&c->d_update_ts, sizeof(long long) * 4 * A));
-  SOGM_HIP_CHECK(hipMemset(c->d_update_ts, 0, sizeof(long long) * 4 * A));
-  SOGM_HIP_CHECK(hipMemset(c->d_map_ready, 0, sizeof(int) * A));
+  SOGM_HIP_CHECK(c->res.stream(&c->ustream));
+  SOGM_HIP_CHECK(c->res.event(&c->ev_uin));
+  SOGM_HIP_CHECK(c->res.event(&c->ev_udone));
+  SOGM_HIP_CHECK(c->res.device(&c->d_map_ready, sizeof(int) * A, true));
+  SOGM_HIP_CHECK(c->res.device(&c->d_update_ctl, sizeof(int) * (size_t)(UF_STAGE + UF_STAGE_STRIDE * A)));
+  SOGM_HIP_CHECK(c->res.device(&c->d_update_order, sizeof(int) * A));
+  SOGM_HIP_CHECK(c->res.device(&c->d_update_ts, sizeof(long long) * 4 * A, true));
   hipLaunchKernelGGL(k_iota, dim3((A + 255) / 256), dim3(256), 0, nullptr, c->d_update_order, A);
   SOGM_HIP_CHECK(hipGetLastError());
   SOGM_HIP_CHECK(hipStreamSynchronize(nullptr));  // (null-stream work is not ordered with the non-blocking streams)
-  return SOGM_OK;
+  return setup.done();
 }
 }  // namespace sogm
 
@@ -3048,7 +2945,7 @@ int sogm_device_clock(sogm_ctx *c, int64_t *out_ticks, void *stream) {
   if (!c || !out_ticks) return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(c->device));
   if (!c->h_tick_clock) {
-    SOGM_HIP_CHECK(hipHostMalloc((void **)&c->h_tick_clock, sizeof(long long) * 4, hipHostMallocMapped));
+    SOGM_HIP_CHECK(c->res.pinned(&c->h_tick_clock, sizeof(long long) * 4, hipHostMallocMapped));
     for (int i = 0; i < 4; ++i) c->h_tick_clock[i] = 0;
   }
   hipLaunchKernelGGL(k_device_clock, dim3(1), dim3(1), 0, (hipStream_t)stream, c->h_tick_clock + 2);

@@ -111,9 +111,8 @@ extern "C" {
 int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmPlannerParams *pp,
                         const SogmQpSettings *qp, sogm_planner **out) {
   if (!map || !astar || !pp || !qp || !out) return SOGM_ERR_INVALID_ARG;
-  sogm_planner *p = new (std::nothrow) sogm_planner();
+  sogm_planner *p = new (std::nothrow) sogm_planner();  // (value-initialised: every field without an initialiser is zero)
   if (!p) return SOGM_ERR_INVALID_ARG;
-  std::memset(p, 0, sizeof(*p));
   p->map = map;
   p->ap  = *astar;
   p->pp  = *pp;
@@ -139,15 +138,14 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
   p->aw.pool_stride = astar_node_bytes() * (size_t)astar->allocate_num;
   p->route_cap      = 64;
   // two pools / hash tables per agent: the replan's second search attempt runs speculatively beside the first
-  hipError_t e      = hipMalloc((void **)&p->aw.pool, p->aw.pool_stride * A * 2);
-  if (e == hipSuccess) e = hipMalloc(&p->aw.hkeys, 8 * (size_t)hc * A * 2);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->aw.verdict, sizeof(int) * A);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->aw.dbg, sizeof(long long) * 8 * A);
-  if (e == hipSuccess) e = hipMemset(p->aw.dbg, 0, sizeof(long long) * 8 * A);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_ret, sizeof(int32_t) * A);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_route_len, sizeof(int32_t) * A);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_stats, sizeof(int32_t) * 4 * A);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_route, sizeof(double) * 6 * p->route_cap * A);
+  hipError_t e      = p->res.device(&p->aw.pool, p->aw.pool_stride * A * 2);
+  if (e == hipSuccess) e = p->res.device(&p->aw.hkeys, 8 * (size_t)hc * A * 2);
+  if (e == hipSuccess) e = p->res.device(&p->aw.verdict, sizeof(int) * A);
+  if (e == hipSuccess) e = p->res.device(&p->aw.dbg, sizeof(long long) * 8 * A, true);
+  if (e == hipSuccess) e = p->res.device(&p->d_ret, sizeof(int32_t) * A);
+  if (e == hipSuccess) e = p->res.device(&p->d_route_len, sizeof(int32_t) * A);
+  if (e == hipSuccess) e = p->res.device(&p->d_stats, sizeof(int32_t) * 4 * A);
+  if (e == hipSuccess) e = p->res.device(&p->d_route, sizeof(double) * 6 * p->route_cap * A);
   {
     if (pp->max_faces < 6 || pp->max_faces > 64 || pp->pc_capacity < 1 || pp->pc_capacity > 16384 ||
         pp->firi_iterations < 1) {
@@ -155,35 +153,32 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
       return SOGM_ERR_INVALID_ARG;
     }
     const size_t slots = (size_t)A * SOGM_MAX_PIECES, cap = (size_t)pp->pc_capacity;
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.pc, sizeof(double) * slots * cap * 3);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.fpc, sizeof(double) * slots * cap * 3);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.tang, sizeof(double) * slots * cap * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.distr, sizeof(double) * slots * cap);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.polys, sizeof(double) * slots * pp->max_faces * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.seg_nfaces, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.seg_state, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.seg_npts, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.seg_dbg, sizeof(long long) * 16 * slots);
+    if (e == hipSuccess) e = p->res.device(&p->cw.pc, sizeof(double) * slots * cap * 3);
+    if (e == hipSuccess) e = p->res.device(&p->cw.fpc, sizeof(double) * slots * cap * 3);
+    if (e == hipSuccess) e = p->res.device(&p->cw.tang, sizeof(double) * slots * cap * 4);
+    if (e == hipSuccess) e = p->res.device(&p->cw.distr, sizeof(double) * slots * cap);
+    if (e == hipSuccess) e = p->res.device(&p->cw.polys, sizeof(double) * slots * pp->max_faces * 4);
+    if (e == hipSuccess) e = p->res.device(&p->cw.seg_nfaces, sizeof(int32_t) * slots);
+    if (e == hipSuccess) e = p->res.device(&p->cw.seg_state, sizeof(int32_t) * slots);
+    if (e == hipSuccess) e = p->res.device(&p->cw.seg_npts, sizeof(int32_t) * slots);
     // (slots no segment ever ran in are read by sogm_debug_corridor_stats as well: zero, not whatever the allocation held)
-    if (e == hipSuccess) e = hipMemset(p->cw.seg_dbg, 0, sizeof(long long) * 16 * slots);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cw.counters, sizeof(unsigned long long) * SOGM_CNT_N);
-    if (e == hipSuccess) e = hipMemset(p->cw.counters, 0, sizeof(unsigned long long) * SOGM_CNT_N);
+    if (e == hipSuccess) e = p->res.device(&p->cw.seg_dbg, sizeof(long long) * 16 * slots, true);
+    if (e == hipSuccess) e = p->res.device(&p->cw.counters, sizeof(unsigned long long) * SOGM_CNT_N, true);
     // QP row storage fallback (rows normally live in LDS)
     p->qw.scratch_stride = qp_scratch_bytes_per_agent(pp->max_faces);
     p->qw.dyn_lds_bytes  = qp_dynamic_lds_bytes();  // 160 KiB/CU minus k_qp's static LDS
-    if (e == hipSuccess) e = hipMalloc((void **)&p->qw.scratch, p->qw.scratch_stride * (size_t)A);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->qw.k1_scratch, qp_k1_scratch_bytes_per_agent() * (size_t)A);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->qw.dbg, sizeof(long long) * 16 * (size_t)A);
-    if (e == hipSuccess) e = hipMemset(p->qw.dbg, 0, sizeof(long long) * 16 * (size_t)A);
+    if (e == hipSuccess) e = p->res.device(&p->qw.scratch, p->qw.scratch_stride * (size_t)A);
+    if (e == hipSuccess) e = p->res.device(&p->qw.k1_scratch, qp_k1_scratch_bytes_per_agent() * (size_t)A);
+    if (e == hipSuccess) e = p->res.device(&p->qw.dbg, sizeof(long long) * 16 * (size_t)A, true);
     min_jerk_block(p->qc.QM);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_polys, sizeof(double) * slots * pp->max_faces * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_goal, sizeof(double) * 6 * A);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_cpts, sizeof(double) * slots * 15);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_nfaces, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_npoly, sizeof(int32_t) * A);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_status, sizeof(int32_t) * A);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_iters, sizeof(int32_t) * A);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_safe, sizeof(int32_t) * A);
+    if (e == hipSuccess) e = p->res.device(&p->d_polys, sizeof(double) * slots * pp->max_faces * 4);
+    if (e == hipSuccess) e = p->res.device(&p->d_goal, sizeof(double) * 6 * A);
+    if (e == hipSuccess) e = p->res.device(&p->d_cpts, sizeof(double) * slots * 15);
+    if (e == hipSuccess) e = p->res.device(&p->d_nfaces, sizeof(int32_t) * slots);
+    if (e == hipSuccess) e = p->res.device(&p->d_npoly, sizeof(int32_t) * A);
+    if (e == hipSuccess) e = p->res.device(&p->d_status, sizeof(int32_t) * A);
+    if (e == hipSuccess) e = p->res.device(&p->d_iters, sizeof(int32_t) * A);
+    if (e == hipSuccess) e = p->res.device(&p->d_safe, sizeof(int32_t) * A);
   }
   // Streams beyond the number of hardware queues (ROCm default GPU_MAX_HW_QUEUES = 4) share a queue
   // and serialise, so the default is 2 groups; the Python driver raises both (GPU_MAX_HW_QUEUES = 32 before HIP
@@ -205,18 +200,17 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
   // (the group streams themselves are created by the grouped path's first replan: the dataflow path never uses them,
   // and every stream is a hardware queue the process holds — INTEGRATION.md section 2 on sharing a GPU)
   for (int g = 0; g < p->n_groups && e == hipSuccess; ++g) {
-    e = hipEventCreateWithFlags(&p->ev_corr[g], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_pts[g], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_done[g], hipEventDisableTiming);
+    e = p->res.event(&p->ev_corr[g]);
+    if (e == hipSuccess) e = p->res.event(&p->ev_pts[g]);
+    if (e == hipSuccess) e = p->res.event(&p->ev_done[g]);
   }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_in, hipEventDisableTiming);
+  if (e == hipSuccess) e = p->res.event(&p->ev_in);
   // dataflow replan: control block + four streams (needs >= 5 hardware queues to overlap with the clear)
   {
     const char *ef = getenv("SOGM_FLOW");  // (one of the library's three environment switches)
     p->flow        = ef ? atoi(ef) != 0 : 1;
     // layout: header, seg_done[A], stage[A] (zeroed per replan), then the four ready lists (-1 per replan)
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_flow, sizeof(int) * (FLOW_HDR + 6 * (size_t)A + 1));  // (+ the reset's generation word)
-    if (e == hipSuccess) e = hipMemset(p->d_flow, 0, sizeof(int) * (FLOW_HDR + 6 * (size_t)A + 1));
+    if (e == hipSuccess) e = p->res.device(&p->d_flow, sizeof(int) * (FLOW_HDR + 6 * (size_t)A + 1), true);  // (+ the reset's generation word)
     p->fc.hdr      = p->d_flow;
     p->fc.seg_done = p->d_flow + FLOW_HDR;
     p->fc.stage    = p->fc.seg_done + A;
@@ -224,20 +218,18 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
     p->fc.q_ready  = p->fc.a_ready + A;
     p->fc.f_ready  = p->fc.q_ready + A;
     p->fc.p_ready  = p->fc.f_ready + A;
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_pdone, hipEventDisableTiming);
+    if (e == hipSuccess) e = p->res.event(&p->ev_pdone);
     // [A][8] chain stamps, then [A][4] pre-stamp stamps (record seen, cull done, bits done, marks done)
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_flow_ts, sizeof(long long) * 12 * (size_t)A);
-    if (e == hipSuccess) e = hipMemset(p->d_flow_ts, 0, sizeof(long long) * 12 * (size_t)A);
+    if (e == hipSuccess) e = p->res.device(&p->d_flow_ts, sizeof(long long) * 12 * (size_t)A, true);
     p->fc.ts = p->d_flow_ts;
 
     for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-      e = sogm::create_stream_partitioned(&p->fstream[k], k == 2 ? 2 : 1);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_fdone[k], hipEventDisableTiming);
+      e = p->res.stream(&p->fstream[k]);
+      if (e == hipSuccess) e = p->res.event(&p->ev_fdone[k]);
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_gate, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_epoch, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(p->d_epoch, 0, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_flow_fail, sizeof(int) * 2, hipHostMallocMapped);
+    if (e == hipSuccess) e = p->res.event(&p->ev_gate);
+    if (e == hipSuccess) e = p->res.device(&p->d_epoch, sizeof(int), true);
+    if (e == hipSuccess) e = p->res.pinned(&p->h_flow_fail, sizeof(int) * 2, hipHostMallocMapped);
     if (e == hipSuccess) p->h_flow_fail[0] = p->h_flow_fail[1] = 0;
   }
   // (the memsets above are null-stream operations: complete before any kernel on the planner's non-blocking streams)
@@ -274,50 +266,7 @@ void sogm_planner_destroy(sogm_planner *p) {
     (void)hipDeviceSynchronize();  // a gate kernel may still be polling this planner's words
     p->map->clear_gate = p->map->clear_gate_err = p->map->clear_epoch_word = nullptr;
   }
-  void *ptrs[] = {p->aw.pool, p->aw.hkeys, p->aw.dbg, p->aw.verdict,
-                  p->d_ret,   p->d_route_len, p->d_stats, p->d_route,
-                  p->cw.pc,   p->cw.fpc,  p->cw.tang, p->cw.distr, p->cw.polys,
-                  p->cw.seg_nfaces, p->cw.seg_state, p->cw.seg_npts, p->cw.seg_dbg, p->cw.counters,
-                  p->qw.scratch, p->qw.dbg, p->qw.k1_scratch,
-                  p->d_polys, p->d_goal, p->d_cpts, p->d_nfaces, p->d_npoly, p->d_status, p->d_iters,
-                  p->d_safe,  p->d_flow, p->d_flow_ts, p->d_epoch};
-  for (void *q : ptrs)
-    if (q) (void)hipFree(q);
-  for (int g = 0; g < SOGM_MAX_GROUPS; ++g) {
-    if (p->gstream[g]) {
-      (void)hipStreamSynchronize(p->gstream[g]);
-      (void)hipStreamDestroy(p->gstream[g]);
-    }
-    if (p->ev_corr[g]) (void)hipEventDestroy(p->ev_corr[g]);
-    if (p->ev_pts[g]) (void)hipEventDestroy(p->ev_pts[g]);
-    if (p->ev_done[g]) (void)hipEventDestroy(p->ev_done[g]);
-  }
-  if (p->ev_in) (void)hipEventDestroy(p->ev_in);
-  for (int k = 0; k < 4; ++k) {
-    if (p->fstream[k]) {
-      (void)hipStreamSynchronize(p->fstream[k]);
-      (void)hipStreamDestroy(p->fstream[k]);
-    }
-    if (p->ev_fdone[k]) (void)hipEventDestroy(p->ev_fdone[k]);
-  }
-  if (p->peek) (void)hipStreamDestroy(p->peek);
-  for (int k = 0; k < 4; ++k) {
-    if (p->fl_stream[k]) {
-      (void)hipStreamSynchronize(p->fl_stream[k]);
-      (void)hipStreamDestroy(p->fl_stream[k]);
-    }
-    if (p->fl_ev_done[k]) (void)hipEventDestroy(p->fl_ev_done[k]);
-  }
-  if (p->fl_ev_in) (void)hipEventDestroy(p->fl_ev_in);
-  if (p->h_fl_worlds) (void)hipHostFree(p->h_fl_worlds);
-  {
-    void *fp[] = {p->d_fl, p->d_fl_worlds, p->d_fl_pva, p->d_fl_tstart, p->d_fl_now, p->fl.ts, p->fl.acc, p->fl.prof, p->fl.ts_log};
-    for (void *q : fp)
-      if (q) (void)hipFree(q);
-  }
-  if (p->ev_gate) (void)hipEventDestroy(p->ev_gate);
-  if (p->ev_pdone) (void)hipEventDestroy(p->ev_pdone);
-  if (p->h_flow_fail) (void)hipHostFree(p->h_flow_fail);
+  p->res.release_all();
   delete p;
 }
 
@@ -485,7 +434,7 @@ int sogm_planner_set_search_mode(sogm_planner *p, int mode) {
 // diagnostics (tools/ only): the dataflow control block, copied on a private stream while the tick's kernels run
 int sogm_debug_flow_peek(sogm_planner *p, int *out_host, int n) {
   if (!p || !out_host || n < 0) return SOGM_ERR_INVALID_ARG;
-  if (!p->peek) SOGM_HIP_CHECK(hipStreamCreateWithFlags(&p->peek, hipStreamNonBlocking));
+  if (!p->peek) SOGM_HIP_CHECK(p->res.stream(&p->peek));
   hipStream_t peek = p->peek;
   const int nf = FLOW_HDR + 6 * p->map->n_agents;
   SOGM_HIP_CHECK(hipMemcpyAsync(out_host, p->d_flow, sizeof(int) * (size_t)(n < nf ? n : nf), hipMemcpyDeviceToHost, peek));
@@ -914,7 +863,7 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
   const MapView mv = view_of(c);
   if (int rc = sogm::join_update(c, main)) return rc;
   for (int g = 0; g < G; ++g)
-    if (!p->gstream[g]) SOGM_HIP_CHECK(sogm::create_stream_partitioned(&p->gstream[g], 1));
+    if (!p->gstream[g]) SOGM_HIP_CHECK(p->res.stream(&p->gstream[g]));
   // the swarm's records (deconfliction) may come from an all-gather still in flight on the exchange stream
   if (p->swarm)
     if (int rc = sogm::join_exchange(c, main)) return rc;
@@ -1156,13 +1105,13 @@ static int flight_setup(sogm_planner *p) {
   sogm_ctx *c = p->map;
   const int A = c->n_agents;
   if (p->d_fl) return SOGM_OK;
+  sogm::Resources::Setup setup(p->res);
   int ring = 1;
   while (ring < 2 * A) ring <<= 1;
   if (A >= (1 << 16)) return SOGM_ERR_INVALID_ARG;
   const size_t words = FL_HDR + 4 * (size_t)ring + 6 * (size_t)FL_WQ_SLOTS + 3 * FLIGHT_MAX_TICKS + 4 * (size_t)A +
                        (size_t)FLIGHT_MAX_TICKS * A + 2;
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->d_fl, sizeof(int) * words));
-  SOGM_HIP_CHECK(hipMemset(p->d_fl, 0, sizeof(int) * words));  // (once: the urgent / priority queues start empty at position 0)
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl, sizeof(int) * words, true));  // (once: the urgent / priority queues start empty at position 0)
   int *q          = p->d_fl;
   p->fl.hdr       = q;              q += FL_HDR;
   p->fl.s_ring    = q;              q += ring;
@@ -1184,19 +1133,16 @@ static int flight_setup(sogm_planner *p) {
   p->fl.uw        = reinterpret_cast<unsigned long long *>(q);  q += 2 * FL_WQ_SLOTS;
   p->fl.ring_mask = ring - 1;
   p->fl.n_agents  = A;
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->fl.ts, sizeof(long long) * FL_TS * (size_t)A));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->fl.acc, sizeof(long long) * 8 * (size_t)A));
-  SOGM_HIP_CHECK(hipMemset(p->fl.ts, 0, sizeof(long long) * FL_TS * (size_t)A));
-  SOGM_HIP_CHECK(hipMemset(p->fl.acc, 0, sizeof(long long) * 8 * (size_t)A));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->fl.ts_log, sizeof(long long) * FL_TS * (size_t)A * FLIGHT_MAX_TICKS));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->fl.wg_start, sizeof(long long) * 8 * FL_WG_LOG));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->fl.prof, sizeof(unsigned long long) * 16));
-  SOGM_HIP_CHECK(hipMemset(p->fl.prof, 0, sizeof(unsigned long long) * 16));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->d_fl_worlds, sizeof(FlightWorld) * FLIGHT_MAX_TICKS));
-  SOGM_HIP_CHECK(hipHostMalloc((void **)&p->h_fl_worlds, sizeof(FlightWorld) * FLIGHT_MAX_TICKS, hipHostMallocDefault));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->d_fl_pva, sizeof(double) * 9 * (size_t)A));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->d_fl_tstart, sizeof(double) * (size_t)A));
-  SOGM_HIP_CHECK(hipMalloc((void **)&p->d_fl_now, sizeof(double) * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->fl.ts, sizeof(long long) * FL_TS * (size_t)A, true));
+  SOGM_HIP_CHECK(p->res.device(&p->fl.acc, sizeof(long long) * 8 * (size_t)A, true));
+  SOGM_HIP_CHECK(p->res.device(&p->fl.ts_log, sizeof(long long) * FL_TS * (size_t)A * FLIGHT_MAX_TICKS));
+  SOGM_HIP_CHECK(p->res.device(&p->fl.wg_start, sizeof(long long) * 8 * FL_WG_LOG));
+  SOGM_HIP_CHECK(p->res.device(&p->fl.prof, sizeof(unsigned long long) * 16, true));
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_worlds, sizeof(FlightWorld) * FLIGHT_MAX_TICKS));
+  SOGM_HIP_CHECK(p->res.pinned(&p->h_fl_worlds, sizeof(FlightWorld) * FLIGHT_MAX_TICKS, hipHostMallocDefault));
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_pva, sizeof(double) * 9 * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_tstart, sizeof(double) * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_now, sizeof(double) * (size_t)A));
   // the four streams and their compute units: QP, search, map take flight_*_units units of 16 CUs, corridor + finish
   // the rest; workgroups = what the partition holds at once (every workgroup of a flight kernel is resident from the
   // start: nothing waits for a workgroup that is not running)
@@ -1229,18 +1175,18 @@ static int flight_setup(sogm_planner *p) {
     // the smallest engine share (flight_layout balances the shares; an unbalanced rest is cut here)
     p->fl_cus[k] = masks ? cus * L.resident_units[k] / (u[k] > 0 ? u[k] : 1) : cus;
     if (masks)
-      SOGM_HIP_CHECK(hipExtStreamCreateWithCUMask(&p->fl_stream[k], (uint32_t)((n_cu + 31) / 32), mask));
+      SOGM_HIP_CHECK(p->res.stream_masked(&p->fl_stream[k], (uint32_t)((n_cu + 31) / 32), mask));
     else
-      SOGM_HIP_CHECK(hipStreamCreateWithFlags(&p->fl_stream[k], hipStreamNonBlocking));
-    SOGM_HIP_CHECK(hipEventCreateWithFlags(&p->fl_ev_done[k], hipEventDisableTiming));
+      SOGM_HIP_CHECK(p->res.stream(&p->fl_stream[k]));
+    SOGM_HIP_CHECK(p->res.event(&p->fl_ev_done[k]));
   }
-  SOGM_HIP_CHECK(hipEventCreateWithFlags(&p->fl_ev_in, hipEventDisableTiming));
+  SOGM_HIP_CHECK(p->res.event(&p->fl_ev_in));
   p->fl_wgs[0] = p->fl_cus[0];      // one QP workgroup per CU (a whole CU's LDS and registers)
   p->fl_wgs[1] = p->fl_cus[1];      // one search workgroup per CU (124 KB of LDS)
   p->fl_wgs[2] = c->tune_i(SOGM_TUNE_FLIGHT_LIGHT_PER_CU) * p->fl_cus[2];  // corridor / finish waves: 39.8 KB of LDS, one per SIMD
   p->fl_wgs[3] = c->tune_i(SOGM_TUNE_FLIGHT_MAP_PER_CU) * p->fl_cus[3];    // map waves: two per SIMD
   SOGM_HIP_CHECK(hipStreamSynchronize(nullptr));
-  return SOGM_OK;
+  return setup.done();
 }
 
 #ifdef SOGM_FLIGHT_TRACE

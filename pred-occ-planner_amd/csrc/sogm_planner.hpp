@@ -110,7 +110,7 @@ __device__ inline int flow_ticket(int *counter) {  // one ticket per wave, unifo
 // fixed by a staleness rule — agent a's tick k reads its own record of tick k - 1 and the neighbours' records as of
 // their tick k - 2 (table ver(k - 2)), and may start once every agent has finished tick k - 2 — and the SCHEDULE is free:
 // an agent whose chain is done goes straight on to its next tick while a straggler still solves its QP.
-// Four persistent kernels, each on a stream with its own compute units (hipExtStreamCreateWithCUMask; every mask balanced over
+// Four persistent kernels, each on a stream with its own compute units (a CU-masked stream; every mask balanced over
 // the shader engines it touches and every launch exactly as large as its mask holds — flight_layout in sogm_planner.hip: all
 // workgroups resident from the first microsecond, which is also what lets a flight survive the hardware scheduler's queue
 // save / restore; no residency gates, no dispatch-order assumptions, four hardware queues):
@@ -602,6 +602,7 @@ int    launch_astar(const MapView &m, const SogmAstarParams &ap, double corridor
 #define SOGM_MAX_GROUPS 64
 
 struct sogm_planner {
+  sogm::Resources      res;  // owns every buffer, stream and event below (sogm_resources.hpp)
   sogm_ctx            *map;
   SogmAstarParams      ap;
   SogmPlannerParams    pp;
