@@ -13,9 +13,11 @@
 
 #include "../../include/sogm_abi_debug.h"  // (includes sogm_abi.h: the library defines both headers' entry points)
 #include "../../include/sogm_detmath.h"
+#include "sogm_gridpool.hpp"
 #include "sogm_resources.hpp"
 
 namespace sogm {
+typedef float vfloat4 __attribute__((ext_vector_type(4)));  // one 16-byte store
 
 // Geometry of one agent's SOGM.  Device layout is time-major slabs:
 //     grid[agent][t][z][y][x]      (fp32)
@@ -560,7 +562,7 @@ struct sogm_ctx {
   sogm::GridGeom geom;
   int            n_agents;
   int            device;
-  float         *d_grid;    // [A][T][V] cells (fp32, or __half when geom.half)
+  float         *d_grid;    // = pool.grid(), cached for the launch sites (sogm::sync_grid is its one assignment)
   size_t         cell_bytes() const { return geom.half ? 2 : 4; }
   float         *d_poses;   // [A][3]
   double        *d_stamps;  // [A]
@@ -569,15 +571,7 @@ struct sogm_ctx {
   int            updated;
   float         *d_scratch_vt;  // [V][T] staging for download / upload
   int            overlap;     // tick pipelining: 0 off, 1 pre-clear in place, 2 / 3 pre-clear of spare grids
-  // modes 2 and 3: d_grid rotates through a pool of 2 / 3 grids.  `ready` = spares whose clear has been queued on
-  // the side stream (FIFO; the next update adopts the front one after waiting for its event), `dirty` = spares
-  // that still hold an old map (the next sogm_replan queues their clear).  Mode 1 uses ev_cleared only.
-  float         *pool[3];
-  hipEvent_t     pool_ev[3];
-  int            n_pool, cur_idx;
-  int            ready[2], n_ready;
-  int            dirty[2], n_dirty;
-  int            precleared;  // the next update finds a (being-)cleared grid: mode 1 in place, modes 2 / 3 n_ready > 0
+  sogm::GridPool pool;      // the 1 to 3 grids d_grid rotates through, their logs and histories (sogm_gridpool.hpp)
   hipStream_t    side;
   hipStream_t    pstream;     // the pre-stamp's stream (tuning key prestamp_stream; the resets stay on `side`)
   hipEvent_t     ev_gate_frac;  // (the same for prestamp_gate_frac < 1: recorded behind a gate kernel with that share of the agents as its target)
@@ -608,33 +602,17 @@ struct sogm_ctx {
   int           *d_filter_blocks;
   int            filter_max_cells;
   unsigned      *d_stamp_bits;     // [A][ceil(V / 32)] occupancy bits of slice 0 between k_stamp_bits and k_stamp_marks (lazy)
-  // Sparse reset.  The reference rebuilds the map from zero at every update (fake_particle_risk_voxel.cpp:107-108:
-  // a fill over all V x T cells); here every mark written into a grid since its last reset is logged as the index
-  // of its 32-byte sector (per agent), and the reset zeroes exactly those sectors — the cells of the rebuilt map
-  // are the same, the 640 MB per agent of zero stores are not issued.  tracked[s] = every non-zero cell of slot s
-  // is covered by its log (false after dense writers — sogm_set_future_risk, sogm_dsp_publish, sogm_grid_ptr —
-  // and for a fresh allocation: the next reset of that slot is the dense clear).  A log that overflows makes the
-  // reset kernel zero that agent's whole grid.
-  // pre-stamp (sogm_planner_set_prestamp): the replan builds the next tick's map into pool slot prestamp_slot (-1:
-  // none) with the next map centres / stamps in d_poses_next / d_stamps_next; sogm_update_prestamped adopts both
+  // pre-stamp (sogm_planner_set_prestamp): the replan builds the next tick's map into the pool's next grid with the
+  // next map centres / stamps in d_poses_next / d_stamps_next; sogm_update_prestamped adopts both
   float         *d_poses_next;
   double        *d_stamps_next;
-  int            prestamp_slot;
   int            sparse;           // feature switch (sogm_set_sparse_reset; default on, SOGM_SPARSE_RESET=0 turns it off)
-  int            log_cap;          // entries per agent
-  unsigned      *d_log[3];         // [A][log_cap] per pool slot (slot 0 = the only grid without a pool), lazy
-  unsigned      *d_log_n[3];       // [A] entries appended since the slot's last reset (beyond log_cap: overflow)
-  int            tracked[3];
+  int            log_cap;          // entries per agent of a slot's mark log
   unsigned long long *d_reset_stat;  // [8]: {entries read, launches, bytes zeroed, -} of k_reset_sectors since the last
                                      // state query; {marks written, entries logged, -, -} of the stamp (sogm_map_traffic)
   long long      n_stamps;           // stamps launched since the last sogm_map_traffic reset (host count)
   long long     *h_tick_clock;       // pinned, device-visible [4]: wall_clock64 (100 MHz) of {the last update's first kernel,
                                      // the last replan's report, the last sogm_device_clock kernel, -} (sogm_tick_clock)
-  // history of each pool slot since the pool was (re)built: resets through its log, dense clears (host-side launch
-  // counts), and whether the CURRENT grid was built by a replan's pre-stamp (sogm_grid_history: lets a parity test
-  // assert that the grid it compares went through k_reset_sectors and k_prestamp_flow)
-  int            hist_sparse[3], hist_dense[3];
-  int            cur_prestamped;
   void          *d_cand;           // [A][1024] candidate cylinders of the stamp (k_cull_cylinders)
   int           *d_ncand;          // [A]
   int           *d_blk_list;       // [A][blk_cap] block ids of each agent's crop of a SogmWorld cloud (lazy)
@@ -758,6 +736,7 @@ int  retire_wide_clear(sogm_ctx *c, hipStream_t st);
 int  announce_clear_epoch(sogm_ctx *c, hipStream_t st);
 int  next_clear_epoch(sogm_ctx *c);  // the epoch a replan writes itself (k_flow_reset) instead of a launch of its own
 int  queue_spare_clears(sogm_ctx *c, hipEvent_t after);
+int  queue_spare_clears_ahead(sogm_ctx *c, hipStream_t st);
 // device view of a SogmWorld cloud (blocks of consecutive points with xy bounds) + the per-agent crop lists the stamp builds
 struct CloudBlocks {
   const float *bounds;  // [n_blocks][4] {xmin, xmax, ymin, ymax}; null = the caller's per-agent {begin, end} ranges are used
@@ -770,15 +749,16 @@ struct CloudBlocks {
 };
 // the context's crop lists sized for `w` (grown on demand; stream-ordered)
 int world_blocks(sogm_ctx *c, const SogmWorld *w, CloudBlocks *out);
-// sparse reset (sogm_map.hip): the mark log of a pool slot as the writers see it (null entries = not logging)
+// sparse reset (sogm_clear.hip): the mark log of a pool slot as the writers see it (null entries = not logging)
 struct MarkLog {
   unsigned *entries;  // [A][cap]
   unsigned *n;        // [A]
   int       cap;
   unsigned long long *stat;  // {marks written by the stamp, entries it logged} (sogm_map_traffic), or null
 };
-inline int cur_slot(const sogm_ctx *c) { return c->n_pool ? c->cur_idx : 0; }
+// the log of a slot, allocated on first use
 MarkLog    mark_log(sogm_ctx *c, int slot);
+inline void sync_grid(sogm_ctx *c) { c->d_grid = c->pool.grid(); }
 // zero slot `slot`'s grid on `st`: the logged sectors when the slot is tracked, the dense clear otherwise
 int  reset_slot(sogm_ctx *c, hipStream_t st, int slot, float *grid, bool polite);
 struct PrestampDev;

@@ -1788,11 +1788,11 @@ int sogm_dsp_publish(sogm_dsp *h, int32_t *out_n_occupied, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   SOGM_HIP_CHECK(hipSetDevice(c->device));
   if (int rc = sogm::join_update(c, st)) return rc;
-  if (c->precleared) {  // a pending side-stream clear must not race the copy
+  if (c->pool.precleared()) {  // a pending side-stream clear must not race the copy
     int rc = sogm::adopt_preclear(c, st);
     if (rc) return rc;
   }
-  c->tracked[sogm::cur_slot(c)] = 0;  // every cell is written: the next reset of this grid is the dense clear
+  c->pool.dense_write_current();  // every cell is written: the next reset of this grid is the dense clear
   hipLaunchKernelGGL(k_dsp_publish, dim3((unsigned)((d.V + 255) / 256), (unsigned)d.A), dim3(256), 0, st, d,
                      (void *)c->d_grid, c->geom, c->geom.risk_threshold, c->d_poses, c->d_stamps);
   hipLaunchKernelGGL(k_dsp_publish_ego, dim3((unsigned)d.A), dim3(128), 0, st, d, (void *)c->d_grid, c->geom, c->geom.inf_step,

@@ -1,8 +1,7 @@
 // sogm_map.hip — batched SOGM build + queries for gfx950 (MI355X), behind include/sogm_abi.h.
 //
 // Kernels (all HBM-bound integer / fp32 work — no MFMA anywhere on this path):
-//   k_clear_slabs        zero sogm[A][T][V]: 16-B coalesced streaming stores, grid-stride.
-//                        This IS the voxel-update roofline kernel: B = V*T*4 bytes per agent-update.
+//   (the kernels that zero a grid, the mark logs and the pool of grids: sogm_clear.hip)
 //   k_stamp_cloud        per (agent, cloud point): crop, slice-0 mark, GT-velocity lookup (cylinders
 //                        staged in LDS), T-1 advected marks.   fake_particle_risk_voxel.cpp:88-161
 //   k_splat_neighbours   per (agent, record, slice): Bezier sample (fp64) + body particles,
@@ -31,195 +30,6 @@ void set_error(const char *what, hipError_t e) {
   std::snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
 }
 void set_error_text(const char *text) { std::snprintf(g_err, sizeof(g_err), "%s", text); }
-
-// ------------------------------------------------------------------------------------------------
-// clear
-// ------------------------------------------------------------------------------------------------
-// Pure streaming store.  One float4 (16 B) per lane per iteration -> 1 KiB per wave-instruction,
-// fully coalesced; 4 independent stores in flight per lane per trip.  The grid is sized to
-// ~8 workgroups per CU and strides over the buffer.
-typedef float vfloat4 __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ inline void clear_store(vfloat4 *p) {
-  const vfloat4 z = {0.f, 0.f, 0.f, 0.f};
-  if (NT)
-    __builtin_nontemporal_store(z, p);
-  else
-    *p = z;
-}
-template <bool NT>
-__global__ __launch_bounds__(256) void k_clear_slabs(vfloat4 *__restrict__ p, size_t n_vec4,
-                                                     float *__restrict__ tail, int n_tail, int throttle) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  size_t       i      = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + 3 * stride < n_vec4; i += 4 * stride) {
-    clear_store<NT>(p + i);
-    clear_store<NT>(p + i + stride);
-    clear_store<NT>(p + i + 2 * stride);
-    clear_store<NT>(p + i + 3 * stride);
-    // tuning aid: bound the stores a wave keeps in flight (vmcnt <= 4 / 8 / 12)
-    if (throttle == 4) __builtin_amdgcn_s_waitcnt(0x0F74);
-    else if (throttle == 8) __builtin_amdgcn_s_waitcnt(0x0F78);
-    else if (throttle == 12) __builtin_amdgcn_s_waitcnt(0x0F7C);
-    else if (throttle == 1) __builtin_amdgcn_s_waitcnt(0x0F70);
-  }
-  for (; i < n_vec4; i += stride) clear_store<NT>(p + i);
-  if (blockIdx.x == 0 && (int)threadIdx.x < n_tail) tail[threadIdx.x] = 0.f;
-}
-
-// The same stream of stores with a width that follows the tick (side-stream clear of the dataflow replan).  The
-// grid is cut into 4 MiB chunks handed out by an atomic cursor shared by TWO launches: a narrow one (64 workgroups,
-// <= 4 stores in flight per wave: what the latency-bound planner kernels tolerate beside them) that starts with the
-// tick, and a wide, unbounded one on a second stream behind k_clear_gate, which returns once *gate >= gate_target —
-// every agent's corridors are final, what is left of the tick iterates in LDS (QP) — or the tick failed, or no
-// chunk is left.  (Gating at launch granularity matters: workgroups that merely SLEEP on a CU hold a wave slot per
-// SIMD, and a QP workgroup — 2 x 256 registers per SIMD — cannot be placed beside them.)  A workgroup asks for its
-// next chunk before it stores the current one, so the cursor's round trip hides under the stores.
-#define CLEAR_CHUNK_V4 (size_t)(4u << 20 >> 4)  // 16-byte elements per chunk
-__global__ void k_clear_gate(const unsigned long long *__restrict__ cursor, size_t nchunks,
-                             const int *__restrict__ gate, const int *__restrict__ gate_err, int gate_target,
-                             const int *__restrict__ epoch_word, int epoch) {
-  if (threadIdx.x != 0) return;
-  // bounded like every device-side wait of the tick (0.5 s of the 100 MHz clock): opening the wide launch early is
-  // harmless, a gate that never returns is not (e.g. under a profiler that serialises kernels and runs this one
-  // before the narrow launch it watches)
-  const long long t0 = wall_clock64();
-  for (;;) {
-    if (wall_clock64() - t0 > 50000000LL) break;
-    if (__hip_atomic_load(cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nchunks) break;
-    // the replan this clear runs under writes `epoch` after resetting its counters; a later epoch = it is over
-    const int e = __hip_atomic_load(epoch_word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    if (e != 0 && e - epoch > 0) break;
-    if (e == epoch && (__hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= gate_target ||
-                       __hip_atomic_load(gate_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
-      break;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_s_sleep(127);  // ~14 us between polls
-  }
-}
-__global__ void k_set_word(int *p, int v) { *p = v; }
-// (the mark log's counters are zeroed by a kernel, not a memset node: measured with four hardware queues, a 24-byte
-//  hipMemsetAsync ran AFTER work another stream had ordered behind an event recorded after it)
-__global__ void k_zero_words(unsigned *p, int n) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (i < n) p[i] = 0u;
-}
-
-// Sparse reset: zero the 32-byte sectors named by an agent's mark log (duplicates and ~0 place-holders included; the
-// sector of a logged cell holds nothing but marks of the same log or zeros).  An overflowed log (n > cap) makes the
-// agent's workgroups zero its whole grid instead.  Launched (blocks, A); the counts are reset by a kernel behind it.
-// LANES adjacent lanes zero one entry with one 16-byte store each, so an entry is ONE write request of 16*LANES bytes
-// at the L2 instead of two of 16; LANES = 4 zeroes the aligned 64-byte pair of sectors (everything
-// non-zero in a tracked grid is in the log, so the neighbour sector holds marks of the same log or zeros as well).  An
-// entry equal to the one before it in the wave is skipped: neighbouring marks of a stamp row log the same sector.
-// Measured alone on 80.6 M entries (cfg2, 128 agents): one lane per entry with two stores 1.10 ms; 2 lanes 0.91;
-// 4 lanes 0.87; 4 lanes x 8 entries per trip 0.745; 8 lanes (128-byte lines) 1.08-1.2.  reset_slot picks per use.
-template <int LANES, int UNROLL>
-__global__ __launch_bounds__(256) void k_reset_sectors(char *__restrict__ grid, size_t agent_bytes,
-                                                       const unsigned *__restrict__ entries,
-                                                       const unsigned *__restrict__ counts, int cap,
-                                                       unsigned long long *__restrict__ stat) {
-  const int      agent = blockIdx.y;
-  const unsigned n     = counts[agent];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // statistics for sogm_sparse_reset_state: entries read, launches
-    atomicAdd(stat, (unsigned long long)(n > (unsigned)cap ? (unsigned)cap : n));
-    if (agent == 0) atomicAdd(stat + 1, 1ull);
-  }
-  char          *base  = grid + (size_t)agent * agent_bytes;
-  const vfloat4  z     = {0.f, 0.f, 0.f, 0.f};
-  const size_t   tid   = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
-  if (n > (unsigned)cap) {
-    // dense fall-back for this agent: 16-byte stores over the aligned body, bytes at the two ends
-    char  *lo = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 15) & ~(uintptr_t)15);
-    char  *hi = reinterpret_cast<char *>(reinterpret_cast<uintptr_t>(base + agent_bytes) & ~(uintptr_t)15);
-    if (hi < lo) hi = lo = base + agent_bytes;
-    const size_t nv = (size_t)(hi - lo) / 16;
-    for (size_t i = tid; i < nv; i += nthr) __builtin_nontemporal_store(z, reinterpret_cast<vfloat4 *>(lo) + i);
-    if (tid == 0) {
-      for (char *q = base; q < lo && q < base + agent_bytes; ++q) *q = 0;
-      for (char *q = hi; q < base + agent_bytes; ++q) *q = 0;
-    }
-    return;
-  }
-  const unsigned *e       = entries + (size_t)agent * cap;
-  unsigned        n_lines = 0;  // lines this lane group zeroed (counted on the group's first lane)
-  const int       part    = (int)(threadIdx.x % LANES);
-  const bool      first   = (threadIdx.x & 63) < LANES;  // the wave's first entry has no predecessor to compare with
-  const bool      aligned = (reinterpret_cast<uintptr_t>(base) & (16 * LANES - 1)) == 0;
-  // UNROLL entries per trip, their loads issued together (a trip is otherwise one dependent load -> store pair)
-  const size_t  stride = nthr / LANES;
-  for (size_t i0 = tid / LANES; i0 < n; i0 += UNROLL * stride) {
-    unsigned sct[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) sct[u] = i0 + u * stride < n ? e[i0 + u * stride] : 0xFFFFFFFFu;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const unsigned id   = LANES == 4 ? sct[u] >> 1 : sct[u];  // the 16*LANES-byte line this entry zeroes
-      const unsigned prev = __shfl_up(id, LANES);               // (lanes below an active lane are active: smaller i0)
-      if (sct[u] == 0xFFFFFFFFu || (!first && prev == id)) continue;
-      if (part == 0) ++n_lines;
-      const size_t off = (size_t)id * (16 * LANES) + 16 * part;
-      if (aligned) {
-        if (off + 16 <= agent_bytes) *reinterpret_cast<vfloat4 *>(base + off) = z;
-        else if (off < agent_bytes)  // a short last sector
-          for (size_t b = off; b + 2 <= agent_bytes; b += 2) *reinterpret_cast<unsigned short *>(base + b) = 0;
-      } else if (part == 0) {  // odd grid sizes: the agent's base is only cell-aligned
-        const size_t o32 = (size_t)sct[u] * 32;
-        const size_t end = o32 + 32 <= agent_bytes ? o32 + 32 : agent_bytes;
-        for (size_t b = o32; b + 2 <= end; b += 2) *reinterpret_cast<unsigned short *>(base + b) = 0;
-      }
-    }
-  }
-  // statistics: the 16 * LANES-byte lines zeroed (what the launch wrote), one atomic per wave
-  for (int d = 32; d >= 1; d >>= 1) n_lines += (unsigned)__shfl_xor((int)n_lines, d, 64);
-  if ((threadIdx.x & 63) == 0 && n_lines) atomicAdd(stat + 2, (unsigned long long)n_lines * (unsigned)(16 * LANES));
-}
-template <bool POLITE>
-__global__ __launch_bounds__(256) void k_clear_chunks(vfloat4 *__restrict__ p, size_t n_vec4,
-                                                      float *__restrict__ tail, int n_tail,
-                                                      unsigned long long *__restrict__ cursor,
-                                                      unsigned long long *__restrict__ next_cursor,
-                                                      const int *__restrict__ epoch_word, int epoch, int bound) {
-  __shared__ unsigned long long s_next;
-  // two cursors take turns: the narrow launch of a clear zeroes the one the NEXT clear will use (the clear that used
-  // it last is complete — both of its launches are ordered before this one on the side stream); no memset node
-  if (POLITE && blockIdx.x == 0 && threadIdx.x == 0) *next_cursor = 0ull;
-  const size_t nchunks = (n_vec4 + CLEAR_CHUNK_V4 - 1) / CLEAR_CHUNK_V4;
-  // the wide launch only streams while the replan it was opened for is in flight (*epoch_word == epoch): once the
-  // next update starts (word reset) its workgroups take no further chunk and the narrow launch finishes alone
-  auto take = [&]() -> unsigned long long {
-    if (!POLITE && __hip_atomic_load(epoch_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) return ~0ull;
-    return atomicAdd(cursor, 1ull);
-  };
-  if (threadIdx.x == 0) s_next = take();
-  __syncthreads();
-  unsigned long long cur = s_next;
-  while (cur < nchunks) {
-    __syncthreads();  // everybody holds `cur`
-    unsigned long long nxt = 0;
-    if (threadIdx.x == 0) nxt = take();  // in flight under the stores below
-    const size_t b = (size_t)cur * CLEAR_CHUNK_V4;
-    const size_t e = b + CLEAR_CHUNK_V4 < n_vec4 ? b + CLEAR_CHUNK_V4 : n_vec4;
-    size_t       i = b + threadIdx.x;
-    for (; i + 768 < e; i += 1024) {
-      clear_store<true>(p + i);
-      clear_store<true>(p + i + 256);
-      clear_store<true>(p + i + 512);
-      clear_store<true>(p + i + 768);
-      if (POLITE) __builtin_amdgcn_s_waitcnt(0x0F75);  // vmcnt <= 5: four stores (+ the cursor's atomic on lane 0)
-      else if (bound == 8) __builtin_amdgcn_s_waitcnt(0x0F78);
-      else if (bound == 12) __builtin_amdgcn_s_waitcnt(0x0F7C);
-      else if (bound == 16) __builtin_amdgcn_s_waitcnt(0x4F70);
-      else if (bound == 24) __builtin_amdgcn_s_waitcnt(0x4F78);
-      else if (bound == 32) __builtin_amdgcn_s_waitcnt(0x8F70);
-    }
-    for (; i < e; i += 256) clear_store<true>(p + i);
-    if (threadIdx.x == 0) s_next = nxt;
-    __syncthreads();
-    cur = s_next;
-  }
-  if (POLITE && blockIdx.x == 0 && (int)threadIdx.x < n_tail) tail[threadIdx.x] = 0.f;
-}
 
 // ------------------------------------------------------------------------------------------------
 // stamp: cloud -> slice 0, GT velocity -> slices 1..T-1
@@ -1818,70 +1628,11 @@ __global__ __launch_bounds__(64) void k_traj_safe(MapView m, const SogmTrajRecor
   out[a] = safe;
 }
 
-static int launch_clear_impl(sogm_ctx *c, hipStream_t st, float *grid, bool polite, int part, size_t split);
-// ---- sparse reset: logs per pool slot --------------------------------------------------------------------
-static int slot_of_grid(const sogm_ctx *c, const float *grid) {
-  if (c->n_pool == 0) return 0;
-  for (int i = 0; i < c->n_pool; ++i)
-    if (c->pool[i] == grid) return i;
-  return -1;
-}
-// the log of a slot, allocated on first use; {nullptr, ...} when the feature is off or there is no room for it (the
-// slot then stays untracked and is cleared densely)
-MarkLog mark_log(sogm_ctx *c, int slot) {
-  MarkLog none{nullptr, nullptr, 0, nullptr};
-  if (!c->sparse || slot < 0 || slot > 2) return none;
-  if (!c->d_log[slot]) {
-    Resources::Setup setup(c->res);
-    // (The counters' first zeroing is COMPLETE when this returns: the memset is a null-stream operation, which the
-    //  library's non-blocking streams do not wait for — with a second context busy on the device it was seen to run
-    //  after the first stamp had appended its entries, i.e. it threw them away, and the slot's first reset through
-    //  its log left that stamp's marks in the grid.  Only the null stream is synchronised: persistent kernels of a
-    //  replan in flight on other streams are not waited for.)
-    if (c->res.device(&c->d_log[slot], sizeof(unsigned) * (size_t)c->log_cap * c->n_agents) != hipSuccess ||
-        c->res.device(&c->d_log_n[slot], sizeof(unsigned) * (size_t)c->n_agents, true) != hipSuccess ||
-        (!c->d_reset_stat && c->res.device(&c->d_reset_stat, 8 * sizeof(unsigned long long), true) != hipSuccess) ||
-        hipStreamSynchronize(nullptr) != hipSuccess) {
-      (void)hipGetLastError();
-      c->sparse = 0;  // no room: dense clears from here on
-      for (int i = 0; i < 3; ++i) c->tracked[i] = 0;
-      return none;
-    }
-    setup.done();
-    c->tracked[slot] = 0;  // what the grid holds now was written without a log
-  }
-  return MarkLog{c->d_log[slot], c->d_log_n[slot], c->log_cap, c->d_reset_stat ? c->d_reset_stat + 4 : nullptr};
-}
-static size_t agent_grid_bytes(const sogm_ctx *c) { return (size_t)c->spec.T * (size_t)c->geom.V * c->cell_bytes(); }
-
-int reset_slot(sogm_ctx *c, hipStream_t st, int slot, float *grid, bool polite) {
-  const MarkLog lg = mark_log(c, slot);
-  if (lg.entries && c->tracked[slot]) {
-    const int wgs = c->tune_i(SOGM_TUNE_RESET_WGS) > 0 ? c->tune_i(SOGM_TUNE_RESET_WGS) : 32;  // workgroups per agent
-    // under the replan (polite: beside the QP stage, few CUs free) two lanes and 32-byte lines are faster - 1.05 ms
-    // against 1.17 for the 64-byte lines, half the write traffic; with the machine to itself (reset in the update's
-    // own stream) four lanes x eight entries per trip - 0.75 ms against 0.91.  Both switches are tuning aids.
-    const int lanes_env = c->tune_i(SOGM_TUNE_RESET_LANES), unroll_env = c->tune_i(SOGM_TUNE_RESET_UNROLL);
-    const int lanes  = lanes_env == 2 || lanes_env == 4 ? lanes_env : polite ? 2 : 4;
-    const int unroll = unroll_env == 1 || unroll_env == 8 ? unroll_env : polite ? 1 : 8;
-    prof_begin(c, SOGM_PROF_CLEAR, st);
-    auto *kern = lanes == 4 ? (unroll == 1 ? k_reset_sectors<4, 1> : k_reset_sectors<4, 8>)
-                            : (unroll == 1 ? k_reset_sectors<2, 1> : k_reset_sectors<2, 8>);
-    hipLaunchKernelGGL(kern, dim3(wgs, c->n_agents), dim3(256), 0, st, reinterpret_cast<char *>(grid),
-                       agent_grid_bytes(c), lg.entries, lg.n, lg.cap, c->d_reset_stat);
-    prof_end(c, SOGM_PROF_CLEAR, st);
-    SOGM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_zero_words, dim3((c->n_agents + 255) / 256), dim3(256), 0, st, lg.n, c->n_agents);
-    SOGM_HIP_CHECK(hipGetLastError());
-    c->hist_sparse[slot]++;
-    return SOGM_OK;
-  }
-  return launch_clear(c, st, grid, polite);  // (a complete dense clear restarts the slot's log, see launch_clear)
-}
-
+// row length of the stamp's occupancy bitmask (one row per agent): k_stamp_marks reads 256 words per trip
+static int stamp_bits_words(const GridGeom &g) { return (((g.V + 31) / 32) + 255) & ~255; }
 static int stamp_scratch(sogm_ctx *c, hipStream_t st, int *words_out) {
   const int A = c->n_agents;
-  const int words = (((c->geom.V + 31) / 32) + 255) & ~255;  // k_stamp_marks reads 256 words per trip
+  const int words = stamp_bits_words(c->geom);
   *words_out = words;
   if (c->d_cand) return SOGM_OK;
   Resources::Setup setup(c->res);
@@ -1933,201 +1684,6 @@ int world_blocks(sogm_ctx *c, const SogmWorld *w, CloudBlocks *out) {
   return SOGM_OK;
 }
 
-// a new tick: wide clear workgroups opened for the replan that just ended retire (the stamp, the searches and the
-// corridor stage want the memory pipeline responsive), the narrow launch goes on.  (Only when a dense clear was
-// queued since the last update: sparse resets have no wide launch.)  Behind the side stream's work of that replan: its
-// gate kernels compare the word with their epoch.
-int retire_wide_clear(sogm_ctx *c, hipStream_t st) {
-  if (c->overlap >= 2 && c->clear_gate && c->wide_clear_pending) {
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, c->clear_epoch_word, 0);
-    SOGM_HIP_CHECK(hipGetLastError());
-    c->wide_clear_pending = 0;
-  }
-  return SOGM_OK;
-}
-
-int adopt_preclear(sogm_ctx *c, hipStream_t st, bool join) {
-  if (join)  // (sogm_update_prestamped joins behind its overlay instead, and retires the wide clear there)
-    if (int rc = join_prestamp(c, st)) return rc;
-  if (!c->precleared) return SOGM_OK;
-  if (c->overlap >= 2) {
-    // rotate: the front of the ready queue becomes the current grid, the old current grid is dirty
-    const int nxt = c->ready[0];
-    for (int i = 1; i < c->n_ready; ++i) c->ready[i - 1] = c->ready[i];
-    c->n_ready--;
-    c->dirty[c->n_dirty++] = c->cur_idx;
-    c->cur_idx             = nxt;
-    c->d_grid              = c->pool[nxt];
-    SOGM_HIP_CHECK(hipStreamWaitEvent(st, c->pool_ev[nxt], 0));
-    c->precleared = c->n_ready > 0;
-    const int early = c->tune_i(SOGM_TUNE_CLEAR_EARLY);
-    if (join)
-      if (int rc = retire_wide_clear(c, st)) return rc;
-    if (c->clear_gate && early) {
-      // tuning aid (clear_early = 1): queue the clear of the swapped-out grid NOW, under the stamp — its readers,
-      // the previous replan's kernels, are complete on `st` in stream order — for the replan that will announce
-      // epoch clear_epoch + 1.  Measured: the stamp beside it takes twice as long (1.4 -> 3.1 ms) and the first
-      // ticks of a flight lose 5 %; later ticks gain 3 %.  Off by default.
-      c->clear_epoch_ahead = 1;
-      SOGM_HIP_CHECK(hipEventRecord(c->ev_grid_free, st));
-      const int rc         = queue_spare_clears(c, c->ev_grid_free);
-      c->clear_epoch_ahead = 0;
-      return rc;
-    }
-    return SOGM_OK;
-  }
-  SOGM_HIP_CHECK(hipStreamWaitEvent(st, c->ev_cleared, 0));
-  c->precleared = 0;
-  return SOGM_OK;
-}
-
-// modes 2 / 3: queue the clear of every dirty spare grid on the side stream once `after` has fired (every reader
-// of those grids is ordered before it); sogm_replan calls this right after its fan-out event
-int queue_spare_clears(sogm_ctx *c, hipEvent_t after) {
-  if (c->overlap < 2 || c->n_dirty == 0) return SOGM_OK;
-  SOGM_HIP_CHECK(hipStreamWaitEvent(c->side, after, 0));
-  // The clear shares the machine with the whole replan, as ONE narrow launch by default.  clear_head_gb (a
-  // tuning aid) splits it into a narrow head of that many GB and a full-width rest: measured with the dataflow
-  // replan (profiles/r02_*), a wide rest shortens the clear (15.9 -> 14.3 ms) but costs the planner kernels more
-  // than it saves (tick 18.2 -> 19.3 ms), because per-agent chaining spreads the global-memory phases (searches,
-  // point scans, FIRI set-up of late agents) over the whole tick.
-  const double head_gb = c->tune[SOGM_TUNE_CLEAR_HEAD_GB] >= 0 ? c->tune[SOGM_TUNE_CLEAR_HEAD_GB] : 1.0e9;
-  const size_t total = clear_vec4_total(c);
-  size_t       head  = (size_t)(head_gb * 1e9 / 16.0);
-  if (head > total) head = total;
-  for (int i = 0; i < c->n_dirty; ++i) {
-    const int g  = c->dirty[i];
-    int       rc = SOGM_OK;
-    if (c->sparse && c->tracked[g] && mark_log(c, g).entries) {
-      // The reset is held back until every agent's corridors are final (the gate the dense clear's wide launch
-      // uses): beside the searches and the corridor stage's point scans its 3 GB of scattered stores cost the
-      // chain 0.8 ms (tick 13.8 -> 12.9 ms); under the QP stage, which lives in LDS, they cost nothing and the
-      // reset itself takes 1.3 instead of 2.4 ms.  reset_late = 0: start it with the replan.
-      const int late = c->tune_i(SOGM_TUNE_RESET_LATE);
-      if (late && c->clear_gate) {
-        if (c->gate_frac_agents > 0 && c->gate_frac_agents < c->clear_gate_target && !c->gate_frac_valid) {
-          // the pre-stamp may start when this share of the agents' corridors is final (tuning key prestamp_gate_frac):
-          // the same gate kernel with a lower target, on THIS stream (which spins for the full gate anyway), and an
-          // event for the pre-stamp's stream — no spinning kernel at the head of a second stream
-          hipLaunchKernelGGL(k_clear_gate, dim3(1), dim3(64), 0, c->side, c->clear_cursor, ~(size_t)0, c->clear_gate,
-                             c->clear_gate_err, c->gate_frac_agents, c->clear_epoch_word, c->clear_epoch);
-          SOGM_HIP_CHECK(hipGetLastError());
-          SOGM_HIP_CHECK(hipEventRecord(c->ev_gate_frac, c->side));
-          c->gate_frac_valid = 1;
-        }
-        hipLaunchKernelGGL(k_clear_gate, dim3(1), dim3(64), 0, c->side, c->clear_cursor, ~(size_t)0, c->clear_gate,
-                           c->clear_gate_err, c->clear_gate_target, c->clear_epoch_word, c->clear_epoch);
-        SOGM_HIP_CHECK(hipGetLastError());
-        // "every agent's corridors are final" as an EVENT for the pre-stamp's stream (sogm_replan): no second gate kernel
-        // spinning at the head of a stream (with shared or oversubscribed hardware queues every spinner is a hazard)
-        SOGM_HIP_CHECK(hipEventRecord(c->ev_gate_open, c->side));
-        c->gate_open_valid = 1;
-      }
-      rc = reset_slot(c, c->side, g, c->pool[g], true);  // the logged sectors only: a fraction of a millisecond
-    } else if (head == 0) {
-      rc = launch_clear(c, c->side, c->pool[g], false);
-    } else if (head >= total) {
-      rc = launch_clear(c, c->side, c->pool[g], true);
-    } else {
-      rc = launch_clear(c, c->side, c->pool[g], true, 1, head);
-      if (!rc) rc = launch_clear(c, c->side, c->pool[g], false, 2, head);
-    }
-    if (rc) return rc;
-    SOGM_HIP_CHECK(hipEventRecord(c->pool_ev[g], c->side));
-    c->ready[c->n_ready++] = g;
-  }
-  c->n_dirty    = 0;
-  c->precleared = 1;
-  return SOGM_OK;
-}
-
-// polite = the clear shares the machine with latency-bound kernels that read global memory (double-buffered
-// mode): a full-width clear (2048 persistent workgroups, unbounded stores in flight) starves every other
-// kernel's loads for its whole duration; 64 workgroups with <= 4 stores in flight per wave still stream at
-// ~5.7 TB/s and leave the memory pipeline responsive.  SOGM_CLEAR_WGS / SOGM_CLEAR_THROTTLE / SOGM_CLEAR_NT
-// override the choice (tuning aids: clear_wgs / clear_throttle / clear_nt).
-size_t clear_vec4_total(const sogm_ctx *c) {
-  return (size_t)c->n_agents * c->spec.T * (size_t)c->geom.V * c->cell_bytes() / 4 / 4;
-}
-// part: 0 = the whole grid, 1 = the first `split` 16-byte elements, 2 = everything from `split` on
-int launch_clear(sogm_ctx *c, hipStream_t st, float *grid, bool polite, int part, size_t split) {
-  if (!grid) grid = c->d_grid;
-  const int rc = launch_clear_impl(c, st, grid, polite, part, split);
-  if (rc == SOGM_OK && part != 1) {
-    // this launch completes a dense clear of the slot: behind it (stream order) the slot's mark log starts empty and
-    // covers every non-zero cell again
-    const int     slot = slot_of_grid(c, grid);
-    const MarkLog lg   = mark_log(c, slot);
-    if (slot >= 0 && slot < 3) c->hist_dense[slot]++;
-    if (lg.entries)
-    {
-      hipLaunchKernelGGL(k_zero_words, dim3((c->n_agents + 255) / 256), dim3(256), 0, st, lg.n, c->n_agents);
-      c->tracked[slot] = hipGetLastError() == hipSuccess ? 1 : 0;
-    }
-  }
-  return rc;
-}
-static int launch_clear_impl(sogm_ctx *c, hipStream_t st, float *grid, bool polite, int part, size_t split) {
-  // the clear is a byte stream: n = number of 4-byte words of the grid (fp16 grids: 2 cells per word)
-  // (rounded up: an odd number of fp16 cells ends in half a word; allocations are padded to 16 B)
-  const size_t n     = ((size_t)c->n_agents * c->spec.T * (size_t)c->geom.V * c->cell_bytes() + 3) / 4;
-  const size_t nall  = n / 4;
-  const size_t first = part == 2 ? split : 0;
-  const size_t nv4   = part == 1 ? split : nall - first;
-  const int    tail  = part == 1 ? 0 : (int)(n - nall * 4);
-  const int    slot  = part == 1 ? SOGM_PROF_CLEAR_HEAD : SOGM_PROF_CLEAR;
-  size_t       want  = (nv4 + 255) / 256;
-  const int env_wgs = c->tune_i(SOGM_TUNE_CLEAR_WGS) > 0 ? c->tune_i(SOGM_TUNE_CLEAR_WGS) : 0;
-  const int env_throttle = c->tune_i(SOGM_TUNE_CLEAR_THROTTLE), nt = c->tune_i(SOGM_TUNE_CLEAR_NT) != 0;
-  const size_t max_wgs  = env_wgs ? (size_t)env_wgs : (polite ? (c->clear_gate && part == 0 ? 80 : 64) : 2048);
-  const int    throttle = env_wgs ? env_throttle : (polite ? 4 : 0);
-  const int    nblk     = (int)(want < 1 ? 1 : (want > max_wgs ? max_wgs : want));
-  // clear_wide_wgs = 0 switches the adaptive width off; clear_wide_bound: stores in flight per wave of the wide launch
-  const int wide_wgs = c->tune_i(SOGM_TUNE_CLEAR_WIDE_WGS), wide_bound = c->tune_i(SOGM_TUNE_CLEAR_WIDE_BOUND);
-  if (polite && part == 0 && c->clear_gate && c->clear_cursor && c->side2 && wide_wgs > 0 && nt) {
-    const size_t        nchunks = (nall + CLEAR_CHUNK_V4 - 1) / CLEAR_CHUNK_V4;
-    unsigned long long *cur = c->clear_cursor + (c->clear_seq & 1), *nxt = c->clear_cursor + ((c->clear_seq + 1) & 1);
-    ++c->clear_seq;
-    SOGM_HIP_CHECK(hipEventRecord(c->ev_side2_go, st));
-    SOGM_HIP_CHECK(hipStreamWaitEvent(c->side2, c->ev_side2_go, 0));
-    prof_begin(c, slot, st);
-    const int epoch = c->clear_epoch + c->clear_epoch_ahead;
-    c->wide_clear_pending = 1;
-    hipLaunchKernelGGL(k_clear_chunks<true>, dim3(nblk), dim3(256), 0, st, (vfloat4 *)grid, nall, grid + nall * 4,
-                       tail, cur, nxt, c->clear_epoch_word, epoch, 0);
-    hipLaunchKernelGGL(k_clear_gate, dim3(1), dim3(64), 0, c->side2, cur, nchunks, c->clear_gate,
-                       c->clear_gate_err, c->clear_gate_target, c->clear_epoch_word, epoch);
-    hipLaunchKernelGGL(k_clear_chunks<false>, dim3(wide_wgs), dim3(256), 0, c->side2, (vfloat4 *)grid, nall,
-                       grid + nall * 4, 0, cur, nxt, c->clear_epoch_word, epoch, wide_bound);
-    SOGM_HIP_CHECK(hipEventRecord(c->ev_side2_done, c->side2));
-    SOGM_HIP_CHECK(hipStreamWaitEvent(st, c->ev_side2_done, 0));  // the clear is complete when both launches are
-    prof_end(c, slot, st);
-    SOGM_HIP_CHECK(hipGetLastError());
-    return SOGM_OK;
-  }
-  prof_begin(c, slot, st);
-  if (nt)
-    hipLaunchKernelGGL(k_clear_slabs<true>, dim3(nblk), dim3(256), 0, st, (vfloat4 *)grid + first, nv4,
-                       grid + nall * 4, tail, throttle);
-  else
-    hipLaunchKernelGGL(k_clear_slabs<false>, dim3(nblk), dim3(256), 0, st, (vfloat4 *)grid + first, nv4,
-                       grid + nall * 4, tail, throttle);
-  prof_end(c, slot, st);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
-int next_clear_epoch(sogm_ctx *c) {
-  if (++c->clear_epoch <= 0) c->clear_epoch = 1;  // 0 = "no replan in flight"
-  return c->clear_epoch;
-}
-int announce_clear_epoch(sogm_ctx *c, hipStream_t st) {
-  next_clear_epoch(c);
-  hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, c->clear_epoch_word, c->clear_epoch);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
 }  // namespace sogm
 
 using namespace sogm;
@@ -2173,7 +1729,6 @@ int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) 
   c->geom          = make_geom(*spec);
   c->n_agents      = n_agents;
   c->device        = device;
-  c->prestamp_slot = -1;
   {
 #define X(id, name, dflt, lo, hi) c->tune[SOGM_TUNE_##id] = (double)(dflt);
     SOGM_TUNING_TABLE(X)
@@ -2186,7 +1741,8 @@ int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) 
     c->log_cap    = (int)(dflt < (1 << 20) ? (1 << 20) : (dflt > (1 << 26) ? (1 << 26) : dflt));
   }
   const size_t n   = (size_t)n_agents * spec->T * (size_t)c->geom.V;
-  hipError_t   e   = c->res.device(&c->d_grid, (n * c->cell_bytes() + 15) & ~(size_t)15);
+  hipError_t   e   = c->res.device(&c->pool.slot[0].grid, (n * c->cell_bytes() + 15) & ~(size_t)15);
+  sogm::sync_grid(c);
   if (e == hipSuccess) e = c->res.device(&c->d_poses, sizeof(float) * 3 * n_agents, true);
   if (e == hipSuccess) e = c->res.device(&c->d_stamps, sizeof(double) * n_agents, true);
   if (e == hipSuccess) e = c->res.device(&c->d_scratch_vt, sizeof(float) * (size_t)c->geom.V * spec->T);
@@ -2227,58 +1783,8 @@ float *sogm_grid_ptr(sogm_ctx *c) {
     (void)hipStreamSynchronize(c->ustream);
     c->update_pending = 0;
   }
-  c->tracked[sogm::cur_slot(c)] = 0;  // the caller may write cells the mark log does not see
+  c->pool.dense_write_current();  // the caller may write cells the mark log does not see
   return c->d_grid;
-}
-
-int sogm_set_sparse_reset(sogm_ctx *c, int enable, int log_capacity) {
-  if (!c || log_capacity < 0) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());  // resets / writers in flight use the logs
-  for (int i = 0; i < 3; ++i) {
-    c->res.release(&c->d_log[i]);
-    c->res.release(&c->d_log_n[i]);
-    c->tracked[i] = 0;  // contents unknown to the (new) logs: each slot's next reset is dense
-  }
-  c->sparse = enable ? 1 : 0;
-  if (log_capacity > 0) c->log_cap = log_capacity;
-  return SOGM_OK;
-}
-
-int sogm_sparse_reset_state(sogm_ctx *c, int32_t *out) {
-  if (!c || !out) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  const int slot = sogm::cur_slot(c);
-  out[0] = c->sparse;
-  out[1] = c->log_cap;
-  out[2] = c->tracked[slot];
-  out[3] = 0;  // largest per-agent entry count of the current grid's log
-  out[4] = 0;  // entries of all agents (what the grid's next reset reads; capped at the capacity per agent)
-  if (c->sparse && c->d_log_n[slot]) {
-    std::vector<unsigned> n((size_t)c->n_agents);
-    SOGM_HIP_CHECK(hipMemcpy(n.data(), c->d_log_n[slot], sizeof(unsigned) * n.size(), hipMemcpyDeviceToHost));
-    unsigned           mx  = 0;
-    unsigned long long tot = 0;
-    for (unsigned v : n) {
-      mx = v > mx ? v : mx;
-      tot += v > (unsigned)c->log_cap ? (unsigned)c->log_cap : v;
-    }
-    out[3] = (int32_t)(mx > 0x7FFFFFFFu ? 0x7FFFFFFFu : mx);
-    out[4] = (int32_t)(tot > 0x7FFFFFFFull ? 0x7FFFFFFFull : tot);
-  }
-  out[5] = out[6] = out[7] = 0;  // sparse resets since the previous call: launches, entries read and KiB zeroed per launch (means)
-  if (c->d_reset_stat) {
-    unsigned long long st[4] = {0, 0, 0, 0};
-    SOGM_HIP_CHECK(hipMemcpy(st, c->d_reset_stat, sizeof(st), hipMemcpyDeviceToHost));
-    SOGM_HIP_CHECK(hipMemset(c->d_reset_stat, 0, sizeof(st)));  // (the reset's counters only: the stamp's stay)
-    out[5] = (int32_t)(st[1] > 0x7FFFFFFFull ? 0x7FFFFFFFull : st[1]);
-    const unsigned long long mean = st[1] ? st[0] / st[1] : 0;
-    out[6] = (int32_t)(mean > 0x7FFFFFFFull ? 0x7FFFFFFFull : mean);
-    const unsigned long long kib = st[1] ? st[2] / st[1] / 1024 : 0;
-    out[7] = (int32_t)(kib > 0x7FFFFFFFull ? 0x7FFFFFFFull : kib);
-  }
-  return SOGM_OK;
 }
 
 static const char *const k_tune_names[SOGM_TUNE_N] = {
@@ -2347,25 +1853,6 @@ int sogm_set_resample(sogm_ctx *c, float replan_risk_rate, int num_resample, con
   return SOGM_OK;
 }
 
-int sogm_map_traffic(sogm_ctx *c, int64_t *out, int reset) {
-  if (!c || !out) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (c->d_reset_stat) SOGM_HIP_CHECK(hipMemcpy(st, c->d_reset_stat, sizeof(st), hipMemcpyDeviceToHost));
-  out[0] = (int64_t)st[1];  // resets through the mark logs
-  out[1] = (int64_t)st[0];  // log entries they read
-  out[2] = (int64_t)st[2];  // bytes they zeroed
-  out[3] = (int64_t)c->n_stamps;
-  out[4] = (int64_t)st[4];  // marks (cells set to 1) the stamps wrote
-  out[5] = (int64_t)st[5];  // log entries the stamps appended
-  if (reset) {
-    if (c->d_reset_stat) SOGM_HIP_CHECK(hipMemset(c->d_reset_stat, 0, sizeof(st)));
-    c->n_stamps = 0;
-  }
-  return SOGM_OK;
-}
-
 // diagnostics (tools/ only): one agent's CURRENT grid ([T][V] cells, device layout) copied to a device buffer in stream
 // order — no device synchronisation, no effect on the mark logs (unlike sogm_grid_ptr)
 int sogm_debug_copy_grid(sogm_ctx *c, int agent, void *dst_dev, void *stream) {
@@ -2399,89 +1886,6 @@ __global__ __launch_bounds__(256) void k_div_check(sogm::GridGeom g, unsigned bi
   if (blockIdx.x == 0 && threadIdx.x == 0) out[2] = (unsigned long long)g.fast_div;
 }
 extern "C" {
-// diagnostics (bench.py, tools/): how many DISTINCT 32-byte sectors the current grid's mark log names.  The log holds one entry
-// per mark the wave-local lookback could not merge (sogm_map.hip, stamp_marks_trips) — marks of different waves in one sector
-// are logged once each, the reset zeroes such a sector more than once and the stores merge in the L2 — so "4 B x entries +
-// 32 B x entries" over-counts what HBM moves; 4 B x entries + 32 B x DISTINCT sectors is the honest denominator.  A
-// test-and-set over a throw-away bitmap (one bit per sector and agent), outside any timed region: a returning atomic per
-// entry at 25-30 G/s would cost the stamp more than the duplicates cost the reset.
-}  // extern "C"
-__global__ __launch_bounds__(256) void k_log_distinct(sogm::MarkLog lg, int n_agents, unsigned *bitmap, size_t words_per_agent,
-                                                      unsigned long long *out) {
-  const int agent = blockIdx.y;
-  if (agent >= n_agents) return;
-  const unsigned  n = lg.n[agent] > (unsigned)lg.cap ? (unsigned)lg.cap : lg.n[agent];
-  const unsigned *e = lg.entries + (size_t)agent * lg.cap;
-  unsigned       *bm = bitmap + (size_t)agent * words_per_agent;
-  unsigned long long ent = 0, dis = 0, near8 = 0, near63 = 0, near1k = 0;
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const unsigned sec = e[i];
-    if (sec == 0xFFFFFFFFu || (size_t)(sec >> 5) >= words_per_agent) continue;
-    ++ent;
-    const unsigned bit = 1u << (sec & 31);
-    if (!(atomicOr(bm + (sec >> 5), bit) & bit)) ++dis;
-    // where the duplicates sit: an equal entry among the previous 8 / 63 / 1023 positions of the log (a wave appends its
-    // entries as one block: "within 63" ~ what a wave-wide de-duplication could remove, "within 1023" a workgroup-wide one)
-    bool d8 = false, d63 = false, d1k = false;
-    for (unsigned b = 1; b <= 1023 && b <= i; ++b)
-      if (e[i - b] == sec) {
-        d1k = true;
-        if (b <= 63) d63 = true;
-        if (b <= 8) d8 = true;
-        break;
-      }
-    near8 += d8, near63 += d63, near1k += d1k;
-  }
-  for (int d = 32; d >= 1; d >>= 1) {
-    ent += __shfl_xor(ent, d, 64);
-    dis += __shfl_xor(dis, d, 64);
-    near8 += __shfl_xor(near8, d, 64);
-    near63 += __shfl_xor(near63, d, 64);
-    near1k += __shfl_xor(near1k, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0 && ent) {
-    atomicAdd(out, ent);
-    atomicAdd(out + 1, dis);
-    atomicAdd(out + 3, near8);
-    atomicAdd(out + 4, near63);
-    atomicAdd(out + 5, near1k);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && lg.n[agent] > (unsigned)lg.cap) atomicAdd(out + 2, 1ull);
-}
-extern "C" {
-// host out[6] = {valid entries of the current grid's mark logs (all agents), distinct sectors among them, agents whose log
-// overflowed (their reset is dense: not counted), entries with an equal entry among the previous 8 / 63 / 1023 log positions}.
-// Synchronises; allocates and frees V T / 64 bytes per agent.
-int sogm_debug_log_distinct(sogm_ctx *c, unsigned long long *out3_host) {
-  if (!c || !out3_host) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  const int     slot = sogm::cur_slot(c);
-  sogm::MarkLog lg   = c->sparse ? sogm::mark_log(c, slot) : sogm::MarkLog{nullptr, nullptr, 0, nullptr};
-  for (int i = 0; i < 6; ++i) out3_host[i] = 0;
-  if (!lg.entries || !c->tracked[slot]) return SOGM_ERR_STATE;
-  const size_t cells_per_sector = 32 / c->cell_bytes();
-  const size_t sectors = ((size_t)c->spec.T * (size_t)c->geom.V + cells_per_sector - 1) / cells_per_sector;
-  const size_t words   = (sectors + 31) / 32;
-  unsigned           *bm = nullptr;
-  unsigned long long *d  = nullptr;
-  SOGM_HIP_CHECK(hipMalloc((void **)&bm, sizeof(unsigned) * words * (size_t)c->n_agents));
-  hipError_t e = hipMalloc((void **)&d, 6 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(bm, 0, sizeof(unsigned) * words * (size_t)c->n_agents);
-  if (e == hipSuccess) e = hipMemset(d, 0, 6 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_log_distinct, dim3(64, c->n_agents), dim3(256), 0, nullptr, lg, c->n_agents, bm, words, d);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out3_host, d, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  (void)hipFree(bm);
-  if (d) (void)hipFree(d);
-  SOGM_HIP_CHECK(e);
-  return SOGM_OK;
-}
-
 // diagnostics (tests/ only): GridGeom::div_res — the three-instruction fp32 division the stamp and the search use — against
 // the IEEE division, on the device, for EVERY float in [lo, hi) and its negative.  out3_host = {mismatches, bit pattern of the
 // first one (2^64 - 1 if none), whether the context uses the fast sequence at all (its resolution is 0.15f)}
@@ -2534,76 +1938,6 @@ int sogm_debug_update_flow_times(sogm_ctx *c, int64_t *out_ts, int32_t *out_orde
   SOGM_HIP_CHECK(hipMemcpy(out_order, c->d_update_order, sizeof(int) * c->n_agents, hipMemcpyDeviceToHost));
   return SOGM_OK;
 }
-int sogm_grid_history(sogm_ctx *c, int32_t *out) {
-  if (!c || !out) return SOGM_ERR_INVALID_ARG;
-  const int slot = sogm::cur_slot(c);
-  out[0] = slot;
-  out[1] = c->hist_sparse[slot];
-  out[2] = c->hist_dense[slot];
-  out[3] = c->cur_prestamped;
-  return SOGM_OK;
-}
-
-int sogm_set_overlap_clear(sogm_ctx *c, int mode) {
-  if (!c || mode < 0 || mode > 3) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (c->update_pending) {
-    (void)hipDeviceSynchronize();
-    c->update_pending = 0;
-  }
-  if (c->precleared || c->n_ready || c->n_dirty) {
-    // pre-clears may be in flight: let them finish and forget them (the next update clears its grid itself)
-    (void)hipDeviceSynchronize();
-    c->precleared = 0;
-  }
-  c->prestamp_slot = -1;  // (a pre-stamped spare is dirty like the others: reset below)
-  const int want = mode >= 2 ? mode : 1;  // grids in the pool
-  // the current grid stays where it is (slot cur_idx); spares are added / released around it
-  if (c->n_pool == 0) {
-    c->pool[0] = c->d_grid;
-    c->n_pool  = 1;
-    c->cur_idx = 0;
-  }
-  if (c->cur_idx != 0) {  // keep the current grid in slot 0 so that spares are slots 1..n_pool-1
-    float *t           = c->pool[0];
-    c->pool[0]         = c->pool[c->cur_idx];
-    c->pool[c->cur_idx] = t;
-    std::swap(c->d_log[0], c->d_log[c->cur_idx]);  // the mark logs follow their grids
-    std::swap(c->d_log_n[0], c->d_log_n[c->cur_idx]);
-    std::swap(c->tracked[0], c->tracked[c->cur_idx]);
-    std::swap(c->hist_sparse[0], c->hist_sparse[c->cur_idx]);
-    std::swap(c->hist_dense[0], c->hist_dense[c->cur_idx]);
-    c->cur_idx         = 0;
-  }
-  while (c->n_pool > want) c->res.release(&c->pool[--c->n_pool]);
-  for (int i = 1; i < 3; ++i) c->tracked[i] = 0;  // spares hold garbage: their first reset is the dense clear
-  for (int i = 1; i < 3; ++i) c->hist_sparse[i] = c->hist_dense[i] = 0;
-  const size_t bytes = ((size_t)sogm_grid_bytes(c) + 15) & ~(size_t)15;
-  {
-    sogm::Resources::Setup setup(c->res);  // all or nothing: the mode is unchanged when a spare or an event cannot be had
-    hipError_t e = hipSuccess;
-    bool       grid = false;
-    for (int i = c->n_pool; i < want && e == hipSuccess; ++i) grid = (e = c->res.device(&c->pool[i], bytes)) != hipSuccess;
-    for (int i = 0; i < want && e == hipSuccess; ++i)  // every slot takes the spare role in turn
-      if (!c->pool_ev[i]) e = c->res.event(&c->pool_ev[i]);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      c->n_ready = 0;
-      c->n_dirty = 0;
-      for (int i = 1; i < c->n_pool; ++i) c->dirty[c->n_dirty++] = i;  // the lists describe the pool again
-      sogm::set_error(grid ? "sogm_set_overlap_clear: no room for the spare grid(s)" : "sogm_set_overlap_clear: event", e);
-      return grid ? SOGM_ERR_CAPACITY : SOGM_ERR_HIP;
-    }
-    setup.done();
-    c->n_pool = want;
-  }
-  c->n_ready = 0;
-  c->n_dirty = 0;
-  for (int i = 1; i < c->n_pool; ++i) c->dirty[c->n_dirty++] = i;  // spares hold garbage until a replan clears them
-  c->overlap = mode;
-  return SOGM_OK;
-}
-
 int sogm_set_profiling(sogm_ctx *c, int enable) {
   return sogm_set_profiling_slots(c, enable ? (1 << SOGM_PROF_N) - 1 : 0);
 }
@@ -2662,7 +1996,7 @@ int sogm_set_body_particles(sogm_ctx *c, const double *xyz, int n) {
   return SOGM_OK;
 }
 
-static int clear_grid(sogm_ctx *c, hipStream_t st) { return sogm::reset_slot(c, st, sogm::cur_slot(c), c->d_grid, false); }
+static int clear_grid(sogm_ctx *c, hipStream_t st) { return sogm::reset_slot(c, st, c->pool.current(), c->d_grid, false); }
 
 // ---- update flow (tuning key update_flow): the maps of a lock-step tick agent by agent ----
 // One persistent launch of one-wave workgroups over tickets; an agent's tickets are consecutive (bits, marks, overlay) and
@@ -2791,34 +2125,29 @@ static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cl
   // (poses / stamps are filed into the context by k_cull_cylinders below)
   // A grid the previous replan pre-stamped is not what this call builds (other inputs): it is the front of the ready
   // queue, i.e. the grid adopted below — its marks are in its log, so it is reset again before the stamp.
-  const int stale = c->prestamp_slot;
-  c->prestamp_slot = -1;
-  c->cur_prestamped = 0;
+  const int stale = c->pool.discard_prestamp();
   c->records_final_valid = 0;
-  if (c->precleared) {
+  if (c->pool.precleared()) {
     // the grid was already cleared on the side stream during the previous tick
     int rc = sogm::adopt_preclear(c, st);
     if (rc) return rc;
-    if (stale >= 0 && sogm::cur_slot(c) == stale) {
+    if (stale >= 0 && c->pool.current() == stale) {
       rc = sogm::reset_slot(c, st, stale, c->d_grid, false);
       if (rc) return rc;
     }
     if (stale >= 0 && c->d_stamp_bits) {
       // a pre-stamp that was cut short (a failed tick) may have left occupancy bits behind — only consumed words are
       // zeroed — and they are relative to ITS map centres: start this stamp from a clean mask
-      const int words = (((c->geom.V + 31) / 32) + 255) & ~255;
+      const int words = sogm::stamp_bits_words(c->geom);
       SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * (size_t)words * A, st));
     }
   } else {
     int rc = clear_grid(c, st);
     if (rc) return rc;
-    if (c->overlap >= 2 && c->n_dirty > 0 && c->clear_gate && c->tune_i(SOGM_TUNE_CLEAR_EARLY)) {
+    if (c->overlap >= 2 && c->pool.first_dirty() >= 0 && c->clear_gate && c->tune_i(SOGM_TUNE_CLEAR_EARLY)) {
       // tuning-aid mode: the pool's spare grids (dirty at the start, no readers) are cleared from here on as well,
       // so that a run of updates alone exercises the pooled clear (tools/diag_clear_pmc.py)
-      c->clear_epoch_ahead = 1;
-      SOGM_HIP_CHECK(hipEventRecord(c->ev_grid_free, st));
-      rc                   = sogm::queue_spare_clears(c, c->ev_grid_free);
-      c->clear_epoch_ahead = 0;
+      rc = sogm::queue_spare_clears_ahead(c, st);
       if (rc) return rc;
     }
   }
@@ -2844,7 +2173,7 @@ static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cl
     u.n_cyl   = n_cyl;
     u.cand    = c->d_cand;
     u.n_cand  = c->d_ncand;
-    u.lg      = sogm::mark_log(c, sogm::cur_slot(c));
+    u.lg      = sogm::mark_log(c, c->pool.current());
     u.poses   = c->d_poses;
     u.stamps  = c->d_stamps;
     u.rec     = records;
@@ -2888,7 +2217,7 @@ static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cl
   else
     hipLaunchKernelGGL(k_stamp_bits, dim3(bits_wgs, A), dim3(64), 0, st, c->geom, cloud_xyz, cloud_range, c->d_poses,
                        c->d_stamp_bits, words, 0);
-  const sogm::MarkLog lg = sogm::mark_log(c, sogm::cur_slot(c));
+  const sogm::MarkLog lg = sogm::mark_log(c, c->pool.current());
   // (dynamic LDS the kernel does not use bounds its waves per CU: the marks' scattered stores merge worse in L2 the more
   //  waves interleave theirs — tuning key stamp_lds_kb, 160 / kb workgroups per CU)
   const size_t marks_lds = (size_t)c->tune_i(SOGM_TUNE_STAMP_LDS_KB) * 1024;
@@ -2985,7 +2314,7 @@ int sogm_update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const
 int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
                            void *stream) {
   if (!c || n_records < 0 || (n_records > 0 && (!records || !ego_ids))) return SOGM_ERR_INVALID_ARG;
-  if (c->prestamp_slot < 0 || c->n_ready <= 0 || c->ready[0] != c->prestamp_slot || !c->precleared) {
+  if (!c->pool.front_is_prestamped()) {
     sogm::set_error_text("sogm_update_prestamped: the previous sogm_replan did not pre-stamp the next grid");
     return SOGM_ERR_STATE;
   }
@@ -3004,8 +2333,7 @@ int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_rec
   c->records_final_valid = 0;
   std::swap(c->d_poses, c->d_poses_next);                // its map centres and stamps with it
   std::swap(c->d_stamps, c->d_stamps_next);
-  c->prestamp_slot = -1;
-  c->cur_prestamped = 1;
+  c->pool.adopted_prestamped();
   if (n_records > 0) {
     // The replan that pre-stamped this grid left the caller's stream behind its fan-in, not behind the pre-stamp's
     // end: the overlay is launched now, narrow, and waits per agent for the stamp's completion word — it runs under the
@@ -3023,7 +2351,7 @@ int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_rec
     prof_begin(c, SOGM_PROF_SPLAT, st);
     hipLaunchKernelGGL(k_splat_neighbours, dim3((unsigned)nblk), dim3(256), 0, st, c->geom, (void *)c->d_grid, records,
                        n_records, ego_ids, c->d_poses, c->d_stamps, c->d_body, c->n_body, c->n_agents, 0,
-                       sogm::mark_log(c, sogm::cur_slot(c)), stage, c->ps_err);
+                       sogm::mark_log(c, c->pool.current()), stage, c->ps_err);
     prof_end(c, SOGM_PROF_SPLAT, st);
     SOGM_HIP_CHECK(hipGetLastError());
   }
@@ -3033,7 +2361,7 @@ int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_rec
   return SOGM_OK;
 }
 
-int sogm_prestamp_pending(const sogm_ctx *c) { return c && c->prestamp_slot >= 0 ? 1 : 0; }
+int sogm_prestamp_pending(const sogm_ctx *c) { return c && c->pool.prestamp_pending() ? 1 : 0; }
 int sogm_prestamp_join(sogm_ctx *c, void *stream) {
   if (!c) return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(c->device));
@@ -3054,7 +2382,7 @@ int sogm_project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_re
   prof_begin(c, SOGM_PROF_SPLAT, (hipStream_t)stream);
   hipLaunchKernelGGL(k_splat_neighbours, dim3(nblk), dim3(256), 0, (hipStream_t)stream, c->geom,
                      (void *)c->d_grid, records, n_records, ego_ids, c->d_poses, c->d_stamps, c->d_body,
-                     c->n_body, c->n_agents, 0, sogm::mark_log(c, sogm::cur_slot(c)), nullptr, nullptr);
+                     c->n_body, c->n_agents, 0, sogm::mark_log(c, c->pool.current()), nullptr, nullptr);
   prof_end(c, SOGM_PROF_SPLAT, (hipStream_t)stream);
   SOGM_HIP_CHECK(hipGetLastError());
   return SOGM_OK;
@@ -3070,14 +2398,13 @@ int sogm_set_future_risk(sogm_ctx *c, const float *grid_vt, const float *poses,
                                 hipMemcpyDeviceToDevice, st));
   SOGM_HIP_CHECK(hipMemcpyAsync(c->d_stamps, stamps, sizeof(double) * c->n_agents,
                                 hipMemcpyDeviceToDevice, st));
-  if (c->precleared) {
+  if (c->pool.precleared()) {
     int rc = sogm::adopt_preclear(c, st);
     if (rc) return rc;
   }
   const int    V = c->geom.V, T = c->spec.T;
   const size_t per = (size_t)V * T;
-  c->tracked[sogm::cur_slot(c)] = 0;  // every cell is written: the next reset of this grid is the dense clear
-  c->cur_prestamped = 0;
+  c->pool.dense_write_current();  // every cell is written: the next reset of this grid is the dense clear
   for (int a = 0; a < c->n_agents; ++a) {
     hipLaunchKernelGGL(k_vt_to_slabs, dim3((V + 255) / 256), dim3(256), 0, st, grid_vt + a * per, c->geom,
                        (void *)((char *)c->d_grid + a * per * c->cell_bytes()));

@@ -628,7 +628,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   // pre-stamping variant, behind the pre-stamp's end; the waiting kernels of THIS replan follow it on the same stream or
   // behind ev_gate.  The readers of the swarm table on those streams wait for an all-gather in flight themselves.
   SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_pdone, 0));  // (never recorded, or long complete, without a pre-stamp: no wait)
-  if (c->cur_prestamped) {
+  if (c->pool.current_prestamped()) {
     // a grid adopted by sogm_update_prestamped: its overlay (on the caller's stream) waits per agent on the control
     // block's stage words — the reset must not run under it.  An event on the caller's stream, as before (this variant pays
     // the marker in front of its searches)
@@ -718,7 +718,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   //  after a dense writer — queue_spare_clears above has queued dense clears even in sparse mode: the pre-stamp, the
   //  report and ev_pdone then sit behind them, the next sogm_update_prestamped overlay waits per agent for as long
   //  (tests/test_pipelining_gpu.py::test_overlay_under_the_prestamp_tail_at_full_size flies exactly that).)
-  const bool prestamp = p->ps_on && c->sparse && c->overlap >= 2 && c->n_ready > 0 && p->pub_own && c->clear_gate;
+  const bool prestamp = p->ps_on && c->sparse && c->overlap >= 2 && c->pool.front_ready() >= 0 && p->pub_own && c->clear_gate;
   if (!prestamp) fcf.p_ready = nullptr;
   if (sogm::launch_finish_flow(fcf, A, wg_f, p->pp.corridor_tau, p->d_ret, p->d_npoly, p->d_status, p->d_cpts,
                                p->swarm, p->n_swarm, p->swarm_ego, p->swarm_now, t_start, drone_ids, out_records,
@@ -729,11 +729,11 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   // pre-stamp (sogm_planner_set_prestamp): the next tick's map, agent by agent as their records are published, into
   // the pool's next grid — behind the gate that keeps store streams away from the searches and point scans, and
   // behind that grid's reset
-  c->prestamp_slot = -1;
+  c->pool.clear_prestamp_target();
   if (prestamp) {
-    const int nxt = c->ready[0];
+    const int nxt = c->pool.front_ready();
     sogm::PrestampDev d = p->ps;
-    d.grid     = (void *)c->pool[nxt];
+    d.grid     = (void *)c->pool.grid_of(nxt);
     d.lg       = sogm::mark_log(c, nxt);
     d.own      = p->pub_own;
     d.poses    = c->d_poses_next;
@@ -775,7 +775,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     hipStream_t pst        = own_stream ? c->pstream : c->side;
     SOGM_HIP_CHECK(hipStreamWaitEvent(pst, p->ev_in, 0));
     if (own_stream) {
-      SOGM_HIP_CHECK(hipStreamWaitEvent(pst, c->pool_ev[nxt], 0));
+      SOGM_HIP_CHECK(hipStreamWaitEvent(pst, c->pool.cleared_event(nxt), 0));
       if (c->gate_frac_valid && d.gate_agents < A)
         SOGM_HIP_CHECK(hipStreamWaitEvent(pst, c->ev_gate_frac, 0));
       else if (c->gate_open_valid && d.gate_agents >= A)
@@ -787,14 +787,14 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
       sogm::set_error("sogm_replan: k_prestamp_flow", hipGetLastError());
       return SOGM_ERR_HIP;
     }
-    c->prestamp_slot = nxt;
+    c->pool.set_prestamp_target(nxt);
     c->n_stamps++;
     c->ps_fail_host = p->h_flow_fail;  // sogm_update_prestamped refuses the grid if this replan turns out to have failed
     c->ps_fail_seen = p->h_flow_fail ? p->h_flow_fail[1] : 0;
   }
   // fan-in.  Without a pre-stamp the tick's report runs on the corridor stream behind the QP and finishing kernels, so that
   // the NEXT replan's reset — same stream — is ordered behind it without an event on the caller's stream
-  const bool report_on_sc = !(c->prestamp_slot >= 0);
+  const bool report_on_sc = !c->pool.prestamp_pending();
   for (int k = 0; k < 4; ++k)
     if (k != 1) SOGM_HIP_CHECK(hipEventRecord(p->ev_fdone[k], p->fstream[k]));
   if (report_on_sc) {
@@ -815,7 +815,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     SOGM_HIP_CHECK(hipGetLastError());
   }
   bool reported = report_on_sc;
-  if (c->prestamp_slot >= 0) {
+  if (c->pool.prestamp_pending()) {
     // the tick's report behind the pre-stamp on ITS stream (the last kernel of the tick to end), so that the caller's
     // stream goes from the fan-in straight to the next tick's first kernel instead of through one more launch
     const int retire_p = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);
@@ -901,8 +901,8 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
     size_t       head  = (size_t)28e9 / 16;
     if (head > total / 2) head = total / 2;
     for (int g = 0; g < G; ++g) SOGM_HIP_CHECK(hipStreamWaitEvent(c->side, p->ev_pts[g], 0));
-    const int slot = sogm::cur_slot(c);
-    if (c->sparse && c->tracked[slot] && sogm::mark_log(c, slot).entries) {
+    const int slot = c->pool.current();
+    if (c->pool.loggable(slot)) {
       // sparse reset: the logged sectors only, as soon as the SOGM's last readers are done
       int rc = sogm::reset_slot(c, c->side, slot, c->d_grid, true);
       if (rc) return rc;
@@ -914,8 +914,8 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
       if (rc) return rc;
     }
     SOGM_HIP_CHECK(hipEventRecord(c->ev_cleared, c->side));
-    c->precleared = 1;
-    c->updated    = 0;
+    c->pool.cleared_in_place();
+    c->updated = 0;
   }
   for (int g = 0; g < G; ++g) {
     const int a0 = (int)((long long)A * g / G), a1 = (int)((long long)A * (g + 1) / G), n = a1 - a0;
@@ -1249,12 +1249,11 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
     md.cb.n_blocks = max_blocks;  // (per frame in the kernel; the lists' row length is md.cb.row = the context's capacity)
   }
   // the agent's single grid of the flight is the context's current one; it must be covered by its mark log
-  const int slot = sogm::cur_slot(c);
-  if (c->precleared && c->overlap >= 2) {  // (a pooled tick path left a spare grid queued: nothing to adopt here)
-  }
-  if (!c->tracked[slot] || !sogm::mark_log(c, slot).entries) {
+  // (a pooled tick path may have left a spare grid queued: nothing to adopt here)
+  const int slot = c->pool.current();
+  if (!c->pool.loggable(slot)) {
     if (int rc = sogm::launch_clear(c, main, c->d_grid, false)) return rc;  // dense, once; restarts the log
-    if (!c->tracked[slot]) {
+    if (!c->pool.loggable(slot)) {
       sogm::set_error_text("sogm_flight_run: the current grid has no mark log (sogm_set_sparse_reset)");
       return SOGM_ERR_STATE;
     }
@@ -1413,7 +1412,7 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
   hipLaunchKernelGGL(k_flight_report, dim3(1), dim3(1), 0, main, (const int *)p->fl.hdr, p->h_flow_fail);
   SOGM_HIP_CHECK(hipGetLastError());
   c->updated             = 1;
-  c->cur_prestamped      = 0;
+  c->pool.current_rebuilt();
   c->records_final_valid = 0;
   c->n_stamps += f->n_ticks;
   return SOGM_OK;
@@ -1448,9 +1447,8 @@ int sogm_flight_prepare(sogm_planner *p, int max_cloud_points) {
       // the current grid's mark log (its creation ends with a null-stream memset and synchronisation, which waits for every
       // BLOCKING stream of the process — masked streams are — i.e. for another planner's flight) and the one dense clear that
       // puts the grid under its log
-      sogm_ctx *c    = p->map;
-      const int slot = sogm::cur_slot(c);
-      if (!c->tracked[slot] || !sogm::mark_log(c, slot).entries)
+      sogm_ctx *c = p->map;
+      if (!c->pool.loggable(c->pool.current()))
         if (int rc = sogm::launch_clear(c, nullptr, c->d_grid, false)) return rc;
     }
   }
@@ -1594,8 +1592,8 @@ int sogm_replan(sogm_planner *p, const double *start_pva, const double *goal,
     // a pre-clear may or may not have been issued.  Drain everything and forget the pre-clear (the next update
     // clears its grid itself); an in-place clear (mode 1) may already have eaten part of the map.
     (void)hipDeviceSynchronize();
-    if (c->precleared && c->overlap == 1) c->updated = 0;
-    if (c->overlap < 2) c->precleared = 0;  // modes 2 / 3: clears already queued stay valid (events recorded)
+    if (c->pool.precleared() && c->overlap == 1) c->updated = 0;
+    if (c->overlap < 2) c->pool.forget_preclear();  // modes 2 / 3: clears already queued stay valid (events recorded)
   }
   return rc;
 }
