@@ -832,7 +832,22 @@ int sogm_planner_counters(sogm_planner *p, int64_t *out_host, int reset);
 /* sogm_replan() chains its kernels per agent through device-side ready lists ("dataflow replan");
  * a wait that exceeds 3 s marks the tick as failed instead of hanging the GPU: agents whose chain did not complete
  * report ok = 0 and an empty record (n_pieces = 0) for that tick.  Synchronises the device and returns 0 if the
- * last sogm_replan() completed normally, a positive code if one of its waits timed out, negative = sogm_status. */
+ * last sogm_replan() completed normally, a positive code if one of its waits timed out, negative = sogm_status.
+ * The codes — which kernel waited for what (the same values in sogm_flight_stats out_hdr[4] for a flight, and, as 100 + code,
+ * in sogm_planner_flow_failures after a failed flight; enum FlowCode of csrc/sogm_handover.hpp):
+ *    1  k_flow_gate: every search workgroup of the replan resident
+ *    2  k_corridor_flow / k_finish_flow / k_prestamp_flow: its entry of the ready list (searches done / QPs done / records published)
+ *    3  k_qp_flow: its entry of the list of agents whose corridors are final
+ *    4  the second search attempt (k_astar, k_flight_search): the first attempt's verdict
+ *    6  k_prestamp_flow, k_update_flow, the heads of k_flight_map: a stage counter (the lower tickets of the agent's stamp; the
+ *       admission window)
+ *    7  k_prestamp_gate: corridors final, QP workgroups and finishing waves resident
+ *    8  k_splat_neighbours behind a pre-stamp: the agent's pre-stamp complete
+ *   12  k_flight_search / k_flight_qp: its position of the map-ready / corridors-final ring
+ *   15  three waiters for a work-queue descriptor: k_flight_light, the workers of k_flight_map on the plain and on the urgent queue
+ *   16  two waiters, in different error words: k_astar beside an update flow (replan): the agent's map of this tick; a plain head of
+ *       k_flight_map (flight): its turn in the admission order
+ *   17  a plain head of k_flight_map: its position of the ring of finished agents */
 int sogm_planner_flow_error(sogm_planner *p);
 /* The same without synchronising anything: out[0] = code of the most recent failed tick (0 = none ever),
  * out[1] = number of sogm_replan() calls that failed so far, as of the ticks that have COMPLETED on the device

@@ -910,18 +910,12 @@ __device__ __forceinline__ bool astar_search_wg(
     } else {
       if (dropped) return false;
       if (tid == ASTAR_MASTER) {
-        const long long t0 = wall_clock64();
-        int             v;
-        for (;;) {
-          v = __hip_atomic_load(&wsp.verdict[agent], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - vbase;
-          if (v == 1 || v == 2) break;
-          flow_pause();
-          if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-            if (flow_err) atomicExch(flow_err, 4);
-            v = 0;
-            break;
-          }
-        }
+        int v = 0;
+        if (bounded_wait<WaitVerdict, false>(flow_err, [&] {
+              v = flow_peek<false>(&wsp.verdict[agent]) - vbase;
+              return v == 1 || v == 2;
+            }))
+          v = 0;
         s_ret = v;
       }
       __syncthreads();
@@ -1011,14 +1005,8 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
   if (fc.reset_gen) {
     // dataflow replan: the control block's reset runs on another stream (under the map update, normally long done): wait
     // for its generation word before touching the block; then this agent's outputs back to "failed, empty record"
-    if (tid == 0) {
-      const long long t0 = wall_clock64();
-      while (__hip_atomic_load(fc.reset_gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != fc.reset_epoch) {
-        if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) break;  // (the finishing kernel's own timeout fails the tick)
-        __builtin_amdgcn_s_sleep(32);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
+    // (silent, and the error word — a word of that block — is not looked at: the finishing kernel's own limit fails the tick)
+    if (tid == 0) bounded_wait<WaitResetGeneration, false>(nullptr, [&] { return flow_peek<false>(fc.reset_gen) == fc.reset_epoch; });
     __syncthreads();
     if (!second) {
       if (tid == 0) fc.out_ok[agent] = 0;
@@ -1037,23 +1025,9 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
     // update flow: this tick's maps are being built beside this launch, agent by agent — wait for this agent's (bounded
     // like every wait of the tick: a flow that does not deliver fails the tick, code 16)
     __shared__ int s_map_ok;
-    if (tid == 0) {
-      const long long t0 = wall_clock64();
-      int             ok = 0;
-      for (;;) {
-        if (__hip_atomic_load(fc.map_ready + agent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == fc.map_epoch) {
-          ok = 1;
-          break;
-        }
-        if (__hip_atomic_load(&fc.hdr[FLOW_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-        if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-          atomicExch(&fc.hdr[FLOW_ERR], 16);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(32);  // ~1 us: the wait is on the tick's critical path
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      s_map_ok = ok;
+    if (tid == 0) {  // (naps of ~1 us: the wait is on the tick's critical path)
+      s_map_ok = bounded_wait<WaitMapReady, false>(&fc.hdr[FLOW_ERR],
+                                               [&] { return flow_peek<false>(fc.map_ready + agent) == fc.map_epoch; }) == 0;
       if (!second) fc.ts[agent * 8 + 0] = wall_clock64();  // the search starts now
     }
     __syncthreads();
@@ -1064,9 +1038,7 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
                                     fc.hdr ? &fc.hdr[FLOW_ERR] : nullptr, search_mode);
   if (mine && fc.hdr && tid == ASTAR_MASTER) {  // publish the agent, in completion order, to the corridor kernel
     fc.ts[agent * 8 + 1] = wall_clock64();
-    __threadfence();
-    const int r = atomicAdd(&fc.hdr[FLOW_A_READY_N], 1);
-    __hip_atomic_store(fc.a_ready + r, agent, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    publish_next(fc.a_ready, &fc.hdr[FLOW_A_READY_N], agent);
   }
 }
 
@@ -1100,7 +1072,7 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_flight_search(
                                       &fl.hdr[FL_ERR], 0);
     if (mine && tid == ASTAR_MASTER) {
       fl.ts[agent * FL_TS + 1] = wall_clock64();
-      wq_push(fl.lw, &fl.hdr[FL_LW_TAIL], ((unsigned)WK_CORRIDOR << 28) | (unsigned)agent, SOGM_MAX_PIECES);
+      wq_push(fl.lw, &fl.hdr[FL_LW_TAIL], wk_pack(WK_CORRIDOR, 0, agent), SOGM_MAX_PIECES);
     }
   }
 }

@@ -1867,10 +1867,7 @@ __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerPara
       __syncthreads();
       if (lane == 0) fc.ts[agent * 8 + 3] = wall_clock64();
       __threadfence();
-      if (lane == 0) {
-        const int r = atomicAdd(&fc.hdr[FLOW_Q_READY_N], 1);
-        __hip_atomic_store(fc.q_ready + r, agent, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (lane == 0) publish_next(fc.q_ready, &fc.hdr[FLOW_Q_READY_N], agent);
     }
     __syncthreads();
   }
@@ -2239,10 +2236,7 @@ __global__ __launch_bounds__(64) void k_finish_flow(FlowCtl fc, FinishArgs f, in
     const bool safe = (code & 1) != 0;
     if (fc.p_ready) {  // the agent's record is final: hand it to the pre-stamp
       __threadfence();
-      if (lane == 0) {
-        const int r = atomicAdd(&fc.hdr[FLOW_P_READY_N], 1);
-        __hip_atomic_store(fc.p_ready + r, a, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (lane == 0) publish_next(fc.p_ready, &fc.hdr[FLOW_P_READY_N], a);
     }
     if (lane == 0) {
       fc.ts[a * 8 + 6] = wall_clock64();
@@ -2289,7 +2283,7 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       }
       atomicAdd(&fl.prof[6], (unsigned long long)(c1 - c0));
     }
-    const int kind = desc >> 28, a = desc & 0xFFFF;
+    const int kind = wk_kind(desc), a = wk_agent(desc);
     c1_prev   = c1;
     kind_prev = kind;
     if (kind == WK_FINISH) {
@@ -2348,7 +2342,7 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       continue;
     }
     // ---- WK_CORRIDOR: segment slot `seg` of agent a ----
-    const int seg = (desc >> 16) & 0xFFF;
+    const int seg = wk_sub(desc);
     if (seg == 0 && lane == 0) fl.ts[a * FL_TS + 2] = wall_clock64();
     // diagnostics (sogm_debug_corridor_stats, tools/soak_flight.py): when this slot's descriptor was taken, its obstacle points
     // were out, its segment was done, and on which compute unit (HW_ID | XCC_ID << 32)
@@ -2392,17 +2386,8 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
 // residency gate of the dataflow replan: returns when every A* workgroup has started (see k_astar)
 __global__ void k_flow_gate(FlowCtl fc, int expected) {
   if (threadIdx.x != 0) return;
-  const long long t0 = wall_clock64();
-  while (__hip_atomic_load(&fc.hdr[FLOW_A_RESIDENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < expected) {
-    __builtin_amdgcn_s_sleep(8);
-    if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-      atomicExch(&fc.hdr[FLOW_ERR], 1);
-      break;
-    }
-  }
+  wait_at_least<WaitResidencyGate, false>(&fc.hdr[FLOW_ERR], &fc.hdr[FLOW_A_RESIDENT], expected);
 }
-
-
 
 // sdlp::linprog<d> for a batch of independent LPs: one wave per problem (sogm_linprog_batched)
 template <int D>

@@ -953,23 +953,9 @@ __global__ __launch_bounds__(256) void k_splat_neighbours(
       // order.  The launch is narrow (the waiting lanes must leave room for the pre-stamp's own waves: a full-size
       // grid of pollers starved a pre-stamp that was not resident yet until the timeouts fired).  Bounded: a
       // pre-stamp that failed has set the error word (the tick is reported as failed); nothing is written then, and an
-      // overlay whose own wait runs out sets it (code 8).
-      const long long t0 = wall_clock64();
-      bool            ok = false;
-      for (;;) {
-        if (__hip_atomic_load(wait_stage + agent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= FLOW_PS_DONE) {
-          ok = true;
-          break;
-        }
-        if (__hip_atomic_load(wait_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-        if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-          atomicExch(wait_err, 8);  // the tick is reported as failed (the report runs behind the pre-stamp), not
-          break;                    // silently left without its overlay
-        }
-        flow_pause();
-      }
-      if (!ok) return;
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      // overlay whose own wait runs out sets it: the tick is reported as failed (the report runs behind the pre-stamp), not
+      // silently left without its overlay.  Every lane waits for the word of its own item's agent.
+      if (!lane_wait_at_least(wait_stage + agent, FLOW_PS_DONE, wait_err, FLOW_CODE_OVERLAY_STAMP)) return;
     }
     splat_item(g, grid, rec[r], agent, t, ego_ids, poses, stamps, body, n_body, lg);
   }
@@ -1181,23 +1167,6 @@ __global__ __launch_bounds__(64) void k_tick_inputs(const SogmTrajRecord *__rest
 // any number of resident waves makes progress).  The next update then only adopts the grid and adds the overlay
 // (sogm_update_prestamped).  Same kernels' code, same cells.
 // ------------------------------------------------------------------------------------------------
-__device__ inline int flow_wait_count(int *p, int target, int *err) {
-  const long long t0 = wall_clock64();
-  for (;;) {
-    const int v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    if (v >= target) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      return 0;
-    }
-    flow_pause();
-    if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)
-      return -1;
-    if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-      if ((threadIdx.x & 63) == 0) atomicExch(err, 6);
-      return -1;
-    }
-  }
-}
 // Launch gate of the pre-stamp (one lane, on its stream in front of it): every agent's corridors final — store streams
 // stay away from the searches and point scans — AND every QP workgroup and finishing wave of this replan resident:
 // the pre-stamp's waves wait for what those produce, and a QP workgroup that is not placed yet (its launch can sit
@@ -1205,19 +1174,10 @@ __device__ inline int flow_wait_count(int *p, int target, int *err) {
 // waves would never leave it.  Bounded like every wait of the tick: on a timeout the tick fails, the waves drain.
 __global__ void k_prestamp_gate(int *hdr, int n_agents, int n_qp, int n_finish) {
   if (threadIdx.x != 0) return;
-  const long long t0 = wall_clock64();
-  for (;;) {
-    if (__hip_atomic_load(&hdr[FLOW_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
-    if (__hip_atomic_load(&hdr[FLOW_Q_READY_N], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_agents &&
-        __hip_atomic_load(&hdr[FLOW_Q_RESIDENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_qp &&
-        __hip_atomic_load(&hdr[FLOW_F_TICKET], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_finish)
-      return;
-    if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-      atomicExch(&hdr[FLOW_ERR], 7);
-      return;
-    }
-    flow_pause();
-  }
+  bounded_wait<WaitPrestampGate, false>(&hdr[FLOW_ERR], [&] {
+    return flow_peek<false>(&hdr[FLOW_Q_READY_N]) >= n_agents && flow_peek<false>(&hdr[FLOW_Q_RESIDENT]) >= n_qp &&
+           flow_peek<false>(&hdr[FLOW_F_TICKET]) >= n_finish;
+  });
 }
 __global__ __launch_bounds__(64) void k_prestamp_flow(GridGeom g, FlowCtl fc, PrestampDev ps) {
   __shared__ __attribute__((aligned(16))) SogmTrajRecord s_rec;
@@ -1408,21 +1368,8 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
       // — agents then leave the map stage (and reach every later stage) at a steady rate instead of in a burst, which is
       // what lets kernels with FIXED compute units all be busy at once: a swarm that moves in step serves one stage at a
       // time and the tick becomes the SUM of the stages' times (measured: 12.9 ms = 5.6 map + 3.7 corridors + 3.4 QP).
-      if (!urgent) {  // my turn: a tight poll — a handful of waves wait here, and the hand-over from head to head is the admission rate
-        const long long w0 = wall_clock64();
-        bool            bad = false;
-        while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&fl.hdr[FL_ADMITTED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < t) {
-          __builtin_amdgcn_s_sleep(8);
-          if (wall_clock64() - w0 > FLOW_TIMEOUT_TICKS ||
-              __builtin_amdgcn_readfirstlane(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) {
-            if (lane == 0) atomicCAS(err, 0, 16);
-            bad = true;
-            break;
-          }
-        }
-        if (bad) break;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
+      // my turn: a tight poll — a handful of waves wait here, and the hand-over from head to head is the admission rate
+      if (!urgent && wait_at_least<WaitAdmission, true>(err, &fl.hdr[FL_ADMITTED], t) < 0) break;
       if (!urgent && flow_wait_count(&fl.hdr[FL_MAPS_DONE], t - d.n_admit + 1, err)) break;
       if (!urgent && lane == 0) {
         long long *pc = reinterpret_cast<long long *>(&fl.hdr[FL_PACE_CLOCK]);
@@ -1451,8 +1398,8 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
       if (lane == 0) {  // the agent's grid may be reset and its occupancy bits set (neither touches what the other writes)
         ts[12] = wall_clock64();
         atomicExch(&fl.stage[agent], 1);  // (the agent's previous map is complete: nobody else touches the counter now)
-        wq_push(wq, wq_tail, ((unsigned)WK_MAP_RESET << 28) | (unsigned)agent, n_r);
-        wq_push(wq, wq_tail, ((unsigned)WK_MAP_BITS << 28) | (unsigned)agent, n_b);
+        wq_push(wq, wq_tail, wk_pack(WK_MAP_RESET, 0, agent), n_r);
+        wq_push(wq, wq_tail, wk_pack(WK_MAP_BITS, 0, agent), n_b);
       }
       __syncthreads();
     }
@@ -1488,7 +1435,7 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
       atomicAdd(&fl.prof[8 + kind_prev], 1ull);
     }
     if (lane == 0) atomicAdd(&fl.prof[0], (unsigned long long)(c1 - c0));
-    const int          kind = desc >> 28, sub = (desc >> 16) & 0xFFF, agent = desc & 0xFFFF;
+    const int          kind = wk_kind(desc), sub = wk_sub(desc), agent = wk_agent(desc);
     c1_prev   = c1;
     kind_prev = kind;
     const int          k = fl.tick_of[agent], kl = k - fl.first_tick;
@@ -1499,7 +1446,6 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
     cb.block_points = w.block_points;
     cb.n_points     = w.n_points;
     long long     *ts  = fl.ts + (size_t)agent * FL_TS;
-    const unsigned adr = (unsigned)agent;
     if (kind == WK_MAP_RESET || kind == WK_MAP_BITS) {
       if (kind == WK_MAP_RESET) {
         const unsigned n = d.lg.n[agent];
@@ -1519,7 +1465,7 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         d.lg.n[agent] = 0u;
         ts[13]        = wall_clock64();
-        wq_push(wq, wq_tail, ((unsigned)WK_MAP_MARKS << 28) | adr, n_m);
+        wq_push(wq, wq_tail, wk_pack(WK_MAP_MARKS, 0, agent), n_m);
       }
     } else if (kind == WK_MAP_MARKS) {
       stamp_marks_trips<true>(g, d.grid, d.bits, d.words, w.cyl, w.n_cyl, d.poses, (const CylCand *)d.cand, d.n_cand, agent, d.lg,
@@ -1535,7 +1481,7 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
         const bool open = fl_gate_open(fl, kl);
         if (open) {
           ts[14] = now;
-          wq_push(wq, wq_tail, ((unsigned)WK_MAP_SPLAT << 28) | adr, n_s);
+          wq_push(wq, wq_tail, wk_pack(WK_MAP_SPLAT, 0, agent), n_s);
         } else {
           int      *lst  = fl.parked + (size_t)kl * A;
           const int slot = atomicAdd(&fl.parked_n[kl], 1);
@@ -1544,7 +1490,7 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
           // (the releaser may have scanned the list before this slot was written)
           if (fl_gate_open(fl, kl) && atomicCAS(&lst[slot], agent, -2) == agent) {
             ts[14] = wall_clock64();
-            wq_push(wq, wq_tail, ((unsigned)WK_MAP_SPLAT << 28) | adr, n_s);
+            wq_push(wq, wq_tail, wk_pack(WK_MAP_SPLAT, 0, agent), n_s);
           }
         }
       }

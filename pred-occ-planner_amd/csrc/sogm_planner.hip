@@ -973,7 +973,7 @@ __global__ __launch_bounds__(256) void k_flight_seed(FlightCtl fl) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a < fl.n_agents) {
     fl.tick_of[a] = fl.first_tick;
-    fl.m_ring[a]  = (1 << 16) | a;               // position a, generation 1: every agent's first head, in agent order
+    fl.m_ring[a]  = ring_encode(a, fl.ring_mask + 1, a);               // position a, generation 1: every agent's first head, in agent order
     fl.ts[(size_t)a * FL_TS + 7] = wall_clock64();  // the head's publication
   }
   if (a == 0) fl.hdr[FL_M_READY] = fl.n_agents;
@@ -983,13 +983,9 @@ __global__ __launch_bounds__(256) void k_flight_seed(FlightCtl fl) {
 // call: k_flight_xwait -> ncclAllGather(rows of ver(first_tick + i)) -> k_flight_xsignal
 __global__ void k_flight_xwait(FlightCtl fl, int i) {  // every local agent has finished tick i: its rows of the version are final
   if (threadIdx.x != 0) return;
-  while (__hip_atomic_load(&fl.tick_done[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < fl.n_agents) {
-    // (no limit of its own: every wait INSIDE the flight is bounded and sets the error word, which ends this one — the
-    //  collective behind it still runs, its peers are waiting in theirs)
-    if (__hip_atomic_load(&fl.hdr[FL_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-    flow_pause();
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  // (no limit of its own: every wait INSIDE the flight is bounded and sets the error word, which ends this one — the
+  //  collective behind it still runs, its peers are waiting in theirs)
+  wait_at_least<WaitUntimed, false>(&fl.hdr[FL_ERR], &fl.tick_done[i], fl.n_agents);
 }
 __global__ void k_flight_xsignal(FlightCtl fl, int i) {  // every rank's rows of ver(first_tick + i) are here
   if (threadIdx.x != 0) return;

@@ -1830,17 +1830,8 @@ __global__ __launch_bounds__(QP_NT) void k_qp_flow(SogmPlannerParams pp, SogmQpS
     if (threadIdx.x == 0) {
       int       a = -1;
       const int k = atomicAdd(&fc.hdr[FLOW_Q_TICKET], 1);
-      if (k < n_agents) {
-        const long long t0 = wall_clock64();
-        while ((a = __hip_atomic_load(fc.q_ready + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < 0) {
-          flow_pause();
-          if (__hip_atomic_load(&fc.hdr[FLOW_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-          if (wall_clock64() - t0 > FLOW_TIMEOUT_TICKS) {
-            atomicExch(&fc.hdr[FLOW_ERR], 3);
-            break;
-          }
-        }
-      }
+      // (one lane polls and broadcasts through LDS)
+      if (k < n_agents) a = wait_at_least<WaitQpItem, false>(&fc.hdr[FLOW_ERR], fc.q_ready + k, 0);
       s_agent = a;
     }
     __syncthreads();
@@ -1853,10 +1844,7 @@ __global__ __launch_bounds__(QP_NT) void k_qp_flow(SogmPlannerParams pp, SogmQpS
     __syncthreads();
     if (threadIdx.x == 0) fc.ts[agent * 8 + 5] = wall_clock64();
     __threadfence();
-    if (threadIdx.x == 0) {
-      const int r = atomicAdd(&fc.hdr[FLOW_F_READY_N], 1);
-      __hip_atomic_store(fc.f_ready + r, agent, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (threadIdx.x == 0) publish_next(fc.f_ready, &fc.hdr[FLOW_F_READY_N], agent);
     __syncthreads();
   }
 }
@@ -1886,7 +1874,7 @@ __global__ __launch_bounds__(QP_NT) void k_flight_qp(SogmPlannerParams pp, SogmQ
     __syncthreads();
     if (threadIdx.x == 0) {
       fl.ts[agent * FL_TS + 5] = wall_clock64();
-      wq_push(fl.lw, &fl.hdr[FL_LW_TAIL], ((unsigned)WK_FINISH << 28) | (unsigned)agent, 1);
+      wq_push(fl.lw, &fl.hdr[FL_LW_TAIL], wk_pack(WK_FINISH, 0, agent), 1);
     }
     __syncthreads();
   }
