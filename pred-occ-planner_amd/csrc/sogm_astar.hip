@@ -316,12 +316,9 @@ __device__ inline void pos_to_index(const double *p, const double *center, doubl
 // the word is never reset).  Returns true (uniformly) when THIS workgroup wrote the agent's search outputs — the caller
 // publishes the agent — and false when it leaves them to the other attempt.
 __device__ __forceinline__ bool astar_search_wg(
-    const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
-    const double *__restrict__ start_pva, const double *__restrict__ goal,
-    const double *__restrict__ t_start, int32_t *__restrict__ out_ret,
-    double *__restrict__ out_route, int32_t *__restrict__ out_route_len, int route_cap,
-    int32_t *__restrict__ out_stats, int32_t *__restrict__ out_trace, int trace_cap, int agent, int second, bool spec,
-    int vbase, int *flow_err, int search_mode) {
+    const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp, const SearchIO &io,
+    int32_t *__restrict__ out_trace, int trace_cap, int agent, int second, bool spec, int vbase, int *flow_err,
+    int search_mode) {
   const int  tid    = threadIdx.x;
 
   __shared__ double             s_f[ASTAR_POOL_MAX];     // f-score mirror of every allocated node
@@ -363,11 +360,11 @@ __device__ __forceinline__ bool astar_search_wg(
   unsigned long long *htab = (unsigned long long *)wsp.hkeys + slot * wsp.hash_cap;
   const int           hcap = wsp.hash_cap;
 
-  const double *pva = start_pva + agent * 9;
+  const double *pva = io.start_pva + agent * 9;
   double        start_pt[3] = {pva[0], pva[1], pva[2]};
   double        start_v[3]  = {pva[3], pva[4], pva[5]};
   double        start_a[3]  = {pva[6], pva[7], pva[8]};
-  double        end_state[6] = {goal[agent * 3], goal[agent * 3 + 1], goal[agent * 3 + 2], 0, 0, 0};
+  double        end_state[6] = {io.goal[agent * 3], io.goal[agent * 3 + 1], io.goal[agent * 3 + 2], 0, 0, 0};
   const float  *pose      = m.poses + agent * 3;
   const double  center[3] = {(double)pose[0], (double)pose[1], (double)pose[2]};
   const double  inv_res   = 1.0 / ap.resolution;
@@ -379,7 +376,7 @@ __device__ __forceinline__ bool astar_search_wg(
   // in oracle/astar_oracle.cpp, with every node's time and time index ZERO, under which the 4-D table, the prune and
   // the same-voxel test coincide with the branch's 3-D ones and the SOGM is sampled over [0, tau]
   const bool   static_time = (search_mode & 16) != 0;
-  const double time_start  = static_time ? 0.0 : (search_mode & 4) ? t_start[agent] : t_start[agent] - m.stamps[agent];
+  const double time_start  = static_time ? 0.0 : (search_mode & 4) ? io.t_start[agent] : io.t_start[agent] - m.stamps[agent];
   const double time_origin = time_start;
   const double tau         = ap.time_resolution;
 
@@ -928,7 +925,7 @@ __device__ __forceinline__ bool astar_search_wg(
   if (tid == ASTAR_MASTER) {
     int n = 0;
     if (ret != NO_PATH && ret != SEARCH_ERR && terminal >= 0) {
-      double *route = out_route + (size_t)agent * route_cap * 6;
+      double *route = io.out_route + (size_t)agent * io.route_cap * 6;
       // walk back from the terminal node; points are produced last-to-first, then reversed
       int    node     = terminal;
       double t_node   = 0, t_sample = corridor_tau;
@@ -948,13 +945,13 @@ __device__ __forceinline__ bool astar_search_wg(
           t_node -= t_sample;
           double xt[6];
           state_transit(par.state, xt, nd.input, t_node);
-          if (n < route_cap)
+          if (n < io.route_cap)
             for (int q = 0; q < 6; ++q) route[n * 6 + q] = xt[q];
           ++n;
           t_sample = corridor_tau;
         }
       }
-      const int kept = n < route_cap ? n : route_cap;
+      const int kept = n < io.route_cap ? n : io.route_cap;
       for (int i = 0; i < kept / 2; ++i)
         for (int q = 0; q < 6; ++q) {
           const double tmp              = route[i * 6 + q];
@@ -972,12 +969,12 @@ __device__ __forceinline__ bool astar_search_wg(
         ++n_path;
       }
     }
-    out_ret[agent]           = ret;
-    out_route_len[agent]     = n;
-    out_stats[agent * 4 + 0] = use_node_num;
-    out_stats[agent * 4 + 1] = iter_num;
-    out_stats[agent * 4 + 2] = n_path;
-    out_stats[agent * 4 + 3] = searches;
+    io.out_ret[agent]           = ret;
+    io.out_route_len[agent]     = n;
+    io.out_stats[agent * 4 + 0] = use_node_num;
+    io.out_stats[agent * 4 + 1] = iter_num;
+    io.out_stats[agent * 4 + 2] = n_path;
+    io.out_stats[agent * 4 + 3] = searches;
     if (wsp.dbg)
       for (int k = 0; k < 6; ++k) wsp.dbg[(size_t)agent * 8 + k] = tk[k];
     if (out_trace && n_trace < trace_cap) out_trace[(size_t)agent * trace_cap + n_trace] = -1;
@@ -993,6 +990,9 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
     double *__restrict__ out_route, int32_t *__restrict__ out_route_len, int route_cap,
     int32_t *__restrict__ out_stats, int32_t *__restrict__ out_trace, int trace_cap, int agent0, FlowCtl fc,
     int search_mode) {
+  const SearchIO io{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = out_ret,
+                    .out_route = out_route, .out_route_len = out_route_len, .route_cap = route_cap,
+                    .out_stats = out_stats};
   // search_mode bit 3 (dataflow replan): the launch has 2 x n workgroups; workgroup b >= n runs the SECOND attempt of
   // agent b - n speculatively beside the first
   const bool spec   = (search_mode & 8) != 0;
@@ -1033,8 +1033,7 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
     __syncthreads();
     if (!s_map_ok) return;
   }
-  const bool mine = astar_search_wg(m, ap, corridor_tau, wsp, start_pva, goal, t_start, out_ret, out_route, out_route_len,
-                                    route_cap, out_stats, out_trace, trace_cap, agent, second, spec, 0,
+  const bool mine = astar_search_wg(m, ap, corridor_tau, wsp, io, out_trace, trace_cap, agent, second, spec, 0,
                                     fc.hdr ? &fc.hdr[FLOW_ERR] : nullptr, search_mode);
   if (mine && fc.hdr && tid == ASTAR_MASTER) {  // publish the agent, in completion order, to the corridor kernel
     fc.ts[agent * 8 + 1] = wall_clock64();
@@ -1051,6 +1050,9 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_flight_search(
     const double *__restrict__ start_pva, const double *__restrict__ goal, const double *__restrict__ t_start,
     int32_t *__restrict__ out_ret, double *__restrict__ out_route, int32_t *__restrict__ out_route_len, int route_cap,
     int32_t *__restrict__ out_stats, int spec) {
+  const SearchIO io{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = out_ret,
+                    .out_route = out_route, .out_route_len = out_route_len, .route_cap = route_cap,
+                    .out_stats = out_stats};
   __shared__ int s_item;
   const int tid   = threadIdx.x;
   const int per   = spec ? 2 : 1;
@@ -1067,8 +1069,7 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_flight_search(
     const int second = spec ? (t & 1) : 0;
     const int k      = fl.tick_of[agent];
     if (tid == 0 && !second) fl.ts[agent * FL_TS + 0] = wall_clock64();
-    const bool mine = astar_search_wg(m, ap, corridor_tau, wsp, start_pva, goal, t_start, out_ret, out_route, out_route_len,
-                                      route_cap, out_stats, nullptr, 0, agent, second, spec != 0, 4 * (k + 1),
+    const bool mine = astar_search_wg(m, ap, corridor_tau, wsp, io, nullptr, 0, agent, second, spec != 0, 4 * (k + 1),
                                       &fl.hdr[FL_ERR], 0);
     if (mine && tid == ASTAR_MASTER) {
       fl.ts[agent * FL_TS + 1] = wall_clock64();
@@ -1077,30 +1078,27 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_flight_search(
   }
 }
 
-int launch_flight_search(const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
-                         const FlightCtl &fl, int n_workgroups, const double *start_pva, const double *goal,
-                         const double *t_start, int32_t *out_ret, double *out_route, int32_t *out_route_len, int route_cap,
-                         int32_t *out_stats, int spec, hipStream_t st) {
-  hipLaunchKernelGGL(k_flight_search, dim3(n_workgroups), dim3(ASTAR_THREADS), 0, st, m, ap, corridor_tau, wsp, fl, start_pva,
-                     goal, t_start, out_ret, out_route, out_route_len, route_cap, out_stats, spec);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+hipError_t launch_flight_search(const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
+                                const FlightCtl &fl, int n_workgroups, const SearchIO &io, int spec, hipStream_t st) {
+  hipLaunchKernelGGL(k_flight_search, dim3(n_workgroups), dim3(ASTAR_THREADS), 0, st, m, ap, corridor_tau, wsp, fl,
+                     io.start_pva, io.goal, io.t_start, io.out_ret, io.out_route, io.out_route_len, io.route_cap,
+                     io.out_stats, spec);
+  return hipGetLastError();
 }
 
 size_t astar_node_bytes() { return sizeof(Node); }
 int    astar_pool_max() { return ASTAR_POOL_MAX; }
 
-int launch_astar(const MapView &m, const SogmAstarParams &ap, double corridor_tau,
-                 const AstarWorkspace &wsp, int n_agents, const double *start_pva,
-                 const double *goal, const double *t_start, int32_t *out_ret, double *out_route,
-                 int32_t *out_route_len, int route_cap, int32_t *out_stats, int32_t *out_trace,
-                 int trace_cap, hipStream_t st, int agent0, const FlowCtl *fc, int search_mode) {
+hipError_t launch_astar(const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
+                        int n_agents, const SearchIO &io, int32_t *out_trace, int trace_cap, hipStream_t st, int agent0,
+                        const FlowCtl *fc, int search_mode) {
   const FlowCtl none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const bool spec = (search_mode & 8) != 0 && wsp.verdict && fc && !out_trace;
   if (!spec) search_mode &= ~8;
   hipLaunchKernelGGL(k_astar, dim3(spec ? 2 * n_agents : n_agents), dim3(ASTAR_THREADS), 0, st, m, ap, corridor_tau, wsp,
-                     start_pva, goal, t_start, out_ret, out_route, out_route_len, route_cap,
-                     out_stats, out_trace, trace_cap, agent0, fc ? *fc : none, search_mode);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+                     io.start_pva, io.goal, io.t_start, io.out_ret, io.out_route, io.out_route_len, io.route_cap,
+                     io.out_stats, out_trace, trace_cap, agent0, fc ? *fc : none, search_mode);
+  return hipGetLastError();
 }
 
 // How many k_astar workgroups the device holds at once.  The speculative second attempts (workgroups A .. 2A - 1)

@@ -1205,11 +1205,10 @@ __device__ inline void segment_box(const SogmPlannerParams &pp, const double *sp
 // extracts its points).  Same cells, same order, same output for either.
 template <int NW>
 __device__ __forceinline__ void corridor_points_body(const MapView &m, const SogmPlannerParams &pp,
-                                                     const CorridorWorkspace &ws, const double *start_pva,
-                                                     const double *t_start, const double *route,
-                                                     const int32_t *route_len, int route_cap, int agent, int seg) {
+                                                     const CorridorWorkspace &ws, const CorridorIO &io, int agent,
+                                                     int seg) {
   const int tid   = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rl    = route_len[agent];
+  const int rl    = io.route_len[agent];
   const int slot  = agent * SOGM_MAX_PIECES + seg;
   if (seg >= rl - 1 || seg >= SOGM_MAX_PIECES) return;
   __shared__ double s_box[6], s_w[6];
@@ -1218,14 +1217,14 @@ __device__ __forceinline__ void corridor_points_body(const MapView &m, const Sog
   const float    *pose = m.poses + agent * 3;
   const int       cap  = pp.pc_capacity;
   double         *pc   = ws.pc + (size_t)slot * cap * 3;
-  if (tid == 0) segment_box(pp, start_pva + agent * 9, route + (size_t)agent * route_cap * 6, seg, s_box, s_w);
+  if (tid == 0) segment_box(pp, io.start_pva + agent * 9, io.route + (size_t)agent * io.route_cap * 6, seg, s_box, s_w);
   __syncthreads();
   int N = 0;
   {
     const double stamp = m.stamps[agent];
     const double tr    = (double)g.dt;
-    const double t1    = t_start[agent] + seg * pp.corridor_tau;
-    const double t2    = t_start[agent] + (seg + 1) * pp.corridor_tau;
+    const double t1    = io.t_start[agent] + seg * pp.corridor_tau;
+    const double t2    = io.t_start[agent] + (seg + 1) * pp.corridor_tau;
     int          js    = (int)floor((t1 - stamp) / tr);
     int          je    = (int)ceil((t2 - stamp) / tr);
     js                 = js < 0 ? 0 : js;
@@ -1321,8 +1320,9 @@ __global__ __launch_bounds__(256) void k_corridor_points(MapView m, SogmPlannerP
                                                         const double *__restrict__ route,
                                                         const int32_t *__restrict__ route_len, int route_cap,
                                                         int agent0) {
-  corridor_points_body<4>(m, pp, ws, start_pva, t_start, route, route_len, route_cap, blockIdx.y + agent0,
-                          blockIdx.x);
+  const CorridorIO io{.start_pva = start_pva, .t_start = t_start, .route = route, .route_len = route_len,
+                      .route_cap = route_cap};
+  corridor_points_body<4>(m, pp, ws, io, blockIdx.y + agent0, blockIdx.x);
 }
 
 namespace {
@@ -1355,14 +1355,12 @@ __host__ __device__ constexpr int firi_small_doubles() { return 34 + 9 * MB; }
 
 template <int MB, bool DIRECT>
 __device__ __forceinline__ void corridor_segment_body(const MapView &m, const SogmPlannerParams &pp,
-                                                      const CorridorWorkspace &ws, const double *start_pva,
-                                                      const double *t_start, const double *route,
-                                                      const int32_t *route_len, int route_cap, int agent, int seg,
-                                                      char *smem, const FiriDirect &fd) {
+                                                      const CorridorWorkspace &ws, const CorridorIO &io, int agent,
+                                                      int seg, char *smem, const FiriDirect &fd) {
   const int lane  = threadIdx.x;
   const int slot  = DIRECT ? agent : agent * SOGM_MAX_PIECES + seg;
   if constexpr (!DIRECT) {
-    const int rl = route_len[agent];
+    const int rl = io.route_len[agent];
     if (seg >= rl - 1 || seg >= SOGM_MAX_PIECES) {
       if (lane == 0) ws.seg_state[slot] = -2;  // no such segment
       return;
@@ -1395,8 +1393,8 @@ __device__ __forceinline__ void corridor_segment_body(const MapView &m, const So
   double *s_box  = s_dD + MB;               // 6  llc, lhc
   double *s_w    = s_box + 6;               // 6  w0, w1 (a, b)
 
-  const double   *rt    = DIRECT ? nullptr : route + (size_t)agent * route_cap * 6;
-  const double   *sp    = DIRECT ? nullptr : start_pva + agent * 9;
+  const double   *rt    = DIRECT ? nullptr : io.route + (size_t)agent * io.route_cap * 6;
+  const double   *sp    = DIRECT ? nullptr : io.start_pva + agent * 9;
   const int       cap   = pp.pc_capacity;
   const int       prob  = DIRECT ? fd.first + slot : 0;
   const double   *pc    = DIRECT ? fd.pc + (size_t)fd.pc_range[prob * 2] * 3 : ws.pc + (size_t)slot * cap * 3;
@@ -1707,26 +1705,23 @@ __global__ __launch_bounds__(64) void k_corridor_segment(
     const double *__restrict__ t_start, const double *__restrict__ route,
     const int32_t *__restrict__ route_len, int route_cap, int agent0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  corridor_segment_body<6, false>(m, pp, ws, start_pva, t_start, route, route_len, route_cap, blockIdx.y + agent0,
-                                  blockIdx.x, smem, FiriDirect{});
+  const CorridorIO io{.start_pva = start_pva, .t_start = t_start, .route = route, .route_len = route_len,
+                      .route_cap = route_cap};
+  corridor_segment_body<6, false>(m, pp, ws, io, blockIdx.y + agent0, blockIdx.x, smem, FiriDirect{});
 }
 
 #define FIRI_DIRECT_BD_MAX 32
 __global__ __launch_bounds__(64) void k_firi_direct(MapView m, SogmPlannerParams pp, CorridorWorkspace ws,
                                                     FiriDirect fd) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  corridor_segment_body<FIRI_DIRECT_BD_MAX, true>(m, pp, ws, nullptr, nullptr, nullptr, nullptr, 0, blockIdx.x, 0, smem,
-                                                  fd);
+  corridor_segment_body<FIRI_DIRECT_BD_MAX, true>(m, pp, ws, CorridorIO{}, blockIdx.x, 0, smem, fd);
 }
 
 // =================================================================================================
 // Kernel B: per agent bookkeeping (baseline_fake.cpp:364-414 / baseline.cpp:362-403)
 // =================================================================================================
 __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                                                       const double *start_pva, const double *route,
-                                                       const int32_t *route_len, int route_cap, double *out_polys,
-                                                       int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
-                                                       int agent, const SolverScratch &sc) {
+                                                       const CorridorIO &io, int agent, const SolverScratch &sc) {
   // The sequential bookkeeping below is executed by all 64 lanes with identical data (uniform control flow);
   // the LPs inside are solved by the whole wave, outputs are written by lane 0 / copied lane-parallel.
   const bool    w0    = threadIdx.x == 0;
@@ -1734,14 +1729,14 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
   const double *polys = ws.polys + (size_t)agent * SOGM_MAX_PIECES * MF * 4;
   const int    *nfs   = ws.seg_nfaces + agent * SOGM_MAX_PIECES;
   const int    *state = ws.seg_state + agent * SOGM_MAX_PIECES;
-  const double *rt    = route + (size_t)agent * route_cap * 6;
-  const double *sp    = start_pva + agent * 9;
-  const int     rl    = route_len[agent];
+  const double *rt    = io.route + (size_t)agent * io.route_cap * 6;
+  const double *sp    = io.start_pva + agent * 9;
+  const int     rl    = io.route_len[agent];
   int           npoly = 0;
   if (w0) {
-    for (int i = 0; i < SOGM_MAX_PIECES; ++i) out_nfaces[agent * SOGM_MAX_PIECES + i] = 0;
-    for (int i = 0; i < 6; ++i) out_goal[agent * 6 + i] = 0;
-    out_npoly[agent] = 0;
+    for (int i = 0; i < SOGM_MAX_PIECES; ++i) io.out_nfaces[agent * SOGM_MAX_PIECES + i] = 0;
+    for (int i = 0; i < 6; ++i) io.out_goal[agent * 6 + i] = 0;
+    io.out_npoly[agent] = 0;
   }
   if (!pp.fake_planner && rl < 2) return;
   if (rl < 1) return;
@@ -1790,17 +1785,17 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
     }
   }
   for (int i = 0; i < npoly; ++i) {
-    if (w0) out_nfaces[agent * SOGM_MAX_PIECES + i] = nfs[i];
+    if (w0) io.out_nfaces[agent * SOGM_MAX_PIECES + i] = nfs[i];
     const double *src = polys + (size_t)i * MF * 4;
-    double       *dst = out_polys + ((size_t)agent * SOGM_MAX_PIECES + i) * MF * 4;
+    double       *dst = io.out_polys + ((size_t)agent * SOGM_MAX_PIECES + i) * MF * 4;
     for (int k = threadIdx.x; k < nfs[i] * 4; k += 64) dst[k] = src[k];
   }
   if (w0) {
     for (int k = 0; k < 3; ++k) {
-      out_goal[agent * 6 + k]     = gpos[k];
-      out_goal[agent * 6 + 3 + k] = gvel[k];
+      io.out_goal[agent * 6 + k]     = gpos[k];
+      io.out_goal[agent * 6 + 3 + k] = gvel[k];
     }
-    out_npoly[agent] = npoly;
+    io.out_npoly[agent] = npoly;
   }
 }
 
@@ -1809,13 +1804,14 @@ __global__ __launch_bounds__(64) void k_corridor_finalize(
     const double *__restrict__ route, const int32_t *__restrict__ route_len, int route_cap,
     double *__restrict__ out_polys, int32_t *__restrict__ out_nfaces,
     int32_t *__restrict__ out_npoly, double *__restrict__ out_goal, int agent0) {
+  const CorridorIO io{.start_pva = start_pva, .route = route, .route_len = route_len, .route_cap = route_cap,
+                      .out_polys = out_polys, .out_nfaces = out_nfaces, .out_npoly = out_npoly, .out_goal = out_goal};
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double       *s_lp   = (double *)smem;
   double       *s_rows = s_lp + LP_WORK_DOUBLES;
   int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
   SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
-  corridor_finalize_body(pp, ws, start_pva, route, route_len, route_cap, out_polys, out_nfaces, out_npoly, out_goal,
-                         blockIdx.x + agent0, sc);
+  corridor_finalize_body(pp, ws, io, blockIdx.x + agent0, sc);
 }
 
 // =================================================================================================
@@ -1831,10 +1827,7 @@ __global__ __launch_bounds__(64) void k_corridor_finalize(
 // Called by ALL lanes of a wave (uniform control flow; every value that steers a branch goes through
 // readfirstlane so that the compiler sees a scalar condition): returns the published value, or -1 on failure.
 __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerParams pp, CorridorWorkspace ws,
-                                                      FlowCtl fc, const double *start_pva, const double *t_start,
-                                                      const double *route, const int32_t *route_len,
-                                                      int route_cap, double *out_polys, int32_t *out_nfaces,
-                                                      int32_t *out_npoly, double *out_goal, int n_agents) {
+                                                      FlowCtl fc, CorridorIO io, int n_agents) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane  = threadIdx.x;
   const int total = n_agents * SOGM_MAX_PIECES;
@@ -1846,13 +1839,12 @@ __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerPara
     __threadfence();        // the search's outputs (route, route_len) were published before the ready slot
     const int seg = k % SOGM_MAX_PIECES;
     if (seg == 0 && lane == 0) fc.ts[agent * 8 + 2] = wall_clock64();
-    if (seg < route_len[agent] - 1) {
-      corridor_points_body<1>(m, pp, ws, start_pva, t_start, route, route_len, route_cap, agent, seg);
+    if (seg < io.route_len[agent] - 1) {
+      corridor_points_body<1>(m, pp, ws, io, agent, seg);
       __threadfence_block();
       __syncthreads();
     }
-    corridor_segment_body<6, false>(m, pp, ws, start_pva, t_start, route, route_len, route_cap, agent, seg, smem,
-                                    FiriDirect{});
+    corridor_segment_body<6, false>(m, pp, ws, io, agent, seg, smem, FiriDirect{});
     __syncthreads();
     __threadfence();  // this segment's polytope is visible before its completion is counted
     const int last = flow_ticket(&fc.seg_done[agent]) == SOGM_MAX_PIECES - 1;
@@ -1862,8 +1854,7 @@ __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerPara
       double       *s_rows = s_lp + LP_WORK_DOUBLES;
       int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);  // the head of s_lm: free between segments
       SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
-      corridor_finalize_body(pp, ws, start_pva, route, route_len, route_cap, out_polys, out_nfaces, out_npoly,
-                             out_goal, agent, sc);
+      corridor_finalize_body(pp, ws, io, agent, sc);
       __syncthreads();
       if (lane == 0) fc.ts[agent * 8 + 3] = wall_clock64();
       __threadfence();
@@ -1873,6 +1864,10 @@ __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerPara
   }
 }
 
+// LDS of a wave that only solves LPs (validity / reachability / separation): sdlp work area, rows, permutation
+constexpr size_t lp_wave_lds() {
+  return sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5) + sizeof(int) * LP_MAX_ROWS;
+}
 size_t corridor_segment_lds(int pc_capacity) {
   return sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5 + 2 * 18 * 9 + 16 + 36 + 2 * FIRI_MAX_H * 4 + 96) +
          sizeof(int) * (LP_MAX_ROWS + 16) + 8 * (((size_t)pc_capacity + 63) / 64);
@@ -2353,14 +2348,13 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       sdbg[14] = 0;
       sdbg[15] = (long long)(unsigned)__builtin_amdgcn_s_getreg(63492) | ((long long)(unsigned)__builtin_amdgcn_s_getreg(63508) << 32);
     }
-    if (seg < d.route_len[a] - 1) {
-      corridor_points_body<1>(m, pp, ws, d.start_pva, d.t_start, d.route, d.route_len, d.route_cap, a, seg);
+    if (seg < d.cor.route_len[a] - 1) {
+      corridor_points_body<1>(m, pp, ws, d.cor, a, seg);
       __threadfence_block();
       __syncthreads();
     }
     if (lane == 0) sdbg[13] = wall_clock64();
-    corridor_segment_body<6, false>(m, pp, ws, d.start_pva, d.t_start, d.route, d.route_len, d.route_cap, a, seg, smem,
-                                    FiriDirect{});
+    corridor_segment_body<6, false>(m, pp, ws, d.cor, a, seg, smem, FiriDirect{});
     __syncthreads();
     if (lane == 0) sdbg[14] = wall_clock64();
     __threadfence();
@@ -2371,8 +2365,7 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       double       *s_rows = s_lp + LP_WORK_DOUBLES;
       int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
       SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
-      corridor_finalize_body(pp, ws, d.start_pva, d.route, d.route_len, d.route_cap, d.out_polys, d.out_nfaces, d.out_npoly,
-                             d.out_goal, a, sc);
+      corridor_finalize_body(pp, ws, d.cor, a, sc);
       __syncthreads();
       if (lane == 0) {
         fl.ts[a * FL_TS + 3] = wall_clock64();
@@ -2428,71 +2421,54 @@ __global__ void k_fill_i32(int32_t *p, int n, int32_t v, int agent0) {
   if (i < n) p[agent0 + i] = v;
 }
 
-int launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
-                      int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
-                      hipStream_t st, int agent0, unsigned long long *counters) {
+hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
+                             int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
+                             hipStream_t st, int agent0, unsigned long long *counters) {
   hipLaunchKernelGGL(k_fill_i32, dim3((n_agents + 63) / 64), dim3(64), 0, st, out_safe, n_agents, 1, agent0);
-  if (n_rec > 0) {
-    const size_t lds = sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5) + sizeof(int) * LP_MAX_ROWS;
-    hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), lds, st, cpts, npoly, rec, n_rec,
+  if (n_rec > 0)
+    hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), lp_wave_lds(), st, cpts, npoly, rec, n_rec,
                        ego_ids, t_now, out_safe, agent0, counters);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return hipGetLastError();
 }
 
-int launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st) {
+hipError_t launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st) {
   hipLaunchKernelGGL(k_flow_gate, dim3(1), dim3(64), 0, st, fc, expected);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return hipGetLastError();
 }
 
-int launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                         const FlowCtl &fc, int n_agents, int n_workgroups, const double *start_pva,
-                         const double *t_start, const double *route, const int32_t *route_len, int route_cap,
-                         double *out_polys, int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
-                         hipStream_t st) {
+hipError_t launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
+                                const FlowCtl &fc, int n_agents, int n_workgroups, const CorridorIO &io, hipStream_t st) {
   hipLaunchKernelGGL(k_corridor_flow, dim3(n_workgroups), dim3(64), corridor_segment_lds(pp.pc_capacity), st, m, pp,
-                     ws, fc, start_pva, t_start, route, route_len, route_cap, out_polys, out_nfaces, out_npoly,
-                     out_goal, n_agents);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+                     ws, fc, io, n_agents);
+  return hipGetLastError();
 }
 
-int launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, double corridor_tau, const int32_t *ret,
-                       const int32_t *npoly, const int32_t *status, const double *cpts, const SogmTrajRecord *swarm,
-                       int n_swarm, const int32_t *swarm_ego, const double *swarm_now, const double *t_start,
-                       const int32_t *drone_ids, SogmTrajRecord *out, int32_t *out_ok, int32_t *out_safe,
-                       unsigned long long *counters, hipStream_t st, SogmTrajRecord *pub_own,
-                       SogmTrajRecord *pub_table) {
-  const size_t lds = sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5) + sizeof(int) * LP_MAX_ROWS;
-  const FinishArgs f{corridor_tau, ret, npoly, status, cpts, swarm, n_swarm, swarm_ego, swarm_now, t_start, drone_ids,
-                     out, out_ok, out_safe, counters, pub_own, pub_table};
-  hipLaunchKernelGGL(k_finish_flow, dim3(n_workgroups), dim3(64), lds, st, fc, f, n_agents);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st) {
+  hipLaunchKernelGGL(k_finish_flow, dim3(n_workgroups), dim3(64), lp_wave_lds(), st, fc, f, n_agents);
+  return hipGetLastError();
 }
 
-int launch_flight_light(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlightCtl &fl,
-                        const FlightLightDev &d, int n_workgroups, hipStream_t st) {
+hipError_t launch_flight_light(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlightCtl &fl,
+                               const FlightLightDev &d, int n_workgroups, hipStream_t st) {
   hipLaunchKernelGGL(k_flight_light, dim3(n_workgroups), dim3(64), corridor_segment_lds(pp.pc_capacity), st, m, pp, ws, fl, d);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return hipGetLastError();
 }
 
-int launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                    int n_agents, const double *start_pva, const double *t_start,
-                    const double *route, const int32_t *route_len, int route_cap,
-                    double *out_polys, int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
-                    hipStream_t st, int agent0, hipEvent_t ev_map_read) {
-  hipLaunchKernelGGL(k_corridor_points, dim3(SOGM_MAX_PIECES, n_agents), dim3(256), 0, st, m, pp, ws, start_pva,
-                     t_start, route, route_len, route_cap, agent0);
-  if (hipGetLastError() != hipSuccess) return -1;
+hipError_t launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, int n_agents,
+                           const CorridorIO &io, hipStream_t st, int agent0, hipEvent_t ev_map_read) {
+  hipLaunchKernelGGL(k_corridor_points, dim3(SOGM_MAX_PIECES, n_agents), dim3(256), 0, st, m, pp, ws, io.start_pva,
+                     io.t_start, io.route, io.route_len, io.route_cap, agent0);
+  hipError_t e = hipGetLastError();
   // nothing after this point reads the SOGM
-  if (ev_map_read && hipEventRecord(ev_map_read, st) != hipSuccess) return -1;
-  const size_t ldsA = corridor_segment_lds(pp.pc_capacity);
-  hipLaunchKernelGGL(k_corridor_segment, dim3(SOGM_MAX_PIECES, n_agents), dim3(64), ldsA, st, m,
-                     pp, ws, start_pva, t_start, route, route_len, route_cap, agent0);
-  if (hipGetLastError() != hipSuccess) return -1;
-  const size_t ldsB = sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5) + sizeof(int) * LP_MAX_ROWS;
-  hipLaunchKernelGGL(k_corridor_finalize, dim3(n_agents), dim3(64), ldsB, st, pp, ws, start_pva,
-                     route, route_len, route_cap, out_polys, out_nfaces, out_npoly, out_goal, agent0);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  if (e == hipSuccess && ev_map_read) e = hipEventRecord(ev_map_read, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_corridor_segment, dim3(SOGM_MAX_PIECES, n_agents), dim3(64),
+                     corridor_segment_lds(pp.pc_capacity), st, m, pp, ws, io.start_pva, io.t_start, io.route,
+                     io.route_len, io.route_cap, agent0);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_corridor_finalize, dim3(n_agents), dim3(64), lp_wave_lds(), st, pp, ws, io.start_pva, io.route,
+                     io.route_len, io.route_cap, io.out_polys, io.out_nfaces, io.out_npoly, io.out_goal, agent0);
+  return hipGetLastError();
 }
 
 }  // namespace sogm
@@ -2503,7 +2479,7 @@ extern "C" int sogm_linprog_batched(int d, const double *c, const double *A, con
   if ((d != 3 && d != 4) || n < 0 || (n > 0 && (!c || !row_range || !out_x || !out_min)))
     return SOGM_ERR_INVALID_ARG;
   if (n == 0) return SOGM_OK;
-  const size_t lds = sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5) + sizeof(int) * LP_MAX_ROWS;
+  const size_t lds = sogm::lp_wave_lds();
   hipStream_t  st  = (hipStream_t)stream;
   if (d == 3)
     hipLaunchKernelGGL(sogm::k_linprog<3>, dim3(n), dim3(64), lds, st, c, A, b, row_range, out_x, out_min);

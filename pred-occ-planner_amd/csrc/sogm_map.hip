@@ -1509,16 +1509,16 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
     }
   }
 }
-int launch_flight_map(const GridGeom &g, const FlightCtl &fl, const FlightMapDev &d, int n_workgroups, hipStream_t st) {
+hipError_t launch_flight_map(const GridGeom &g, const FlightCtl &fl, const FlightMapDev &d, int n_workgroups, hipStream_t st) {
   hipLaunchKernelGGL(k_flight_map, dim3(n_workgroups), dim3(64), 0, st, g, fl, d, d.reset_stat);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return hipGetLastError();
 }
 
-int launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const PrestampDev &ps, int n_workgroups, int n_qp,
-                         int n_finish, hipStream_t st) {
+hipError_t launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const PrestampDev &ps, int n_workgroups, int n_qp,
+                                int n_finish, hipStream_t st) {
   hipLaunchKernelGGL(k_prestamp_gate, dim3(1), dim3(64), 0, st, fc.hdr, ps.gate_agents, n_qp, n_finish);
   hipLaunchKernelGGL(k_prestamp_flow, dim3(n_workgroups), dim3(64), 0, st, g, fc, ps);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return hipGetLastError();
 }
 // End of a tick: latest-wins per drone (particles.cpp:179-190) — a successful replan replaces the agent's record,
 // a failed one keeps the trajectory being executed (plan_manager.cpp:176-196); `all` (optional) is the swarm table of

@@ -57,14 +57,12 @@ static void min_jerk_block(double *QM /*15x15*/) {
 
 // BezierTraj record of a successful replan (plan_manager/src/plan_manager.cpp:364-399 publishes
 // duration[] and cpts[]); n_pieces = 0 marks "replan() returned false".
-__global__ void k_pack_records(int A, double corridor_tau, const int32_t *ret, const int32_t *npoly,
-                               const int32_t *status, const int32_t *safe, const double *cpts,
-                               const double *t_start, const int32_t *drone_ids, SogmTrajRecord *out,
-                               int32_t *ok, int agent0, unsigned long long *counters, SogmTrajRecord *pub_own,
-                               SogmTrajRecord *pub_table) {
+__global__ void k_pack_records(int A, FinishArgs f, int agent0) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x + agent0;
   if (a >= A) return;
-  if (counters) {  // where this replan ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe)
+  const int32_t *ret = f.ret, *npoly = f.npoly, *status = f.status;
+  const int32_t *safe = f.swarm ? f.out_safe : nullptr;  // (launch_deconflict ran in front of this kernel only with a swarm)
+  if (unsigned long long *counters = f.counters) {  // where this replan ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe)
     int k = SOGM_CNT_REPLAN_OK;
     if (ret[a] == 0) k = SOGM_CNT_FAIL_SEARCH;
     else if (npoly[a] <= 0) k = SOGM_CNT_FAIL_CORRIDOR;
@@ -72,20 +70,20 @@ __global__ void k_pack_records(int A, double corridor_tau, const int32_t *ret, c
     else if (safe != nullptr && safe[a] == 0) k = SOGM_CNT_FAIL_UNSAFE;
     atomicAdd(&counters[k], 1ull);
   }
-  SogmTrajRecord &r = out[a];
+  SogmTrajRecord &r = f.out[a];
   // isSafeAfterOpt false -> replan() returns false (baseline_fake.cpp:455-460)
   const bool good = ret[a] != 0 && npoly[a] > 0 && (status[a] == 1 || status[a] == 2) &&
                     (safe == nullptr || safe[a] != 0);
-  r.drone_id        = drone_ids[a];
-  r.time_start      = t_start[a];
+  r.drone_id        = f.drone_ids[a];
+  r.time_start      = f.t_start[a];
   r.n_pieces        = good ? npoly[a] : 0;
-  for (int i = 0; i < SOGM_MAX_PIECES; ++i) r.duration[i] = (good && i < npoly[a]) ? corridor_tau : 0.0;
+  for (int i = 0; i < SOGM_MAX_PIECES; ++i) r.duration[i] = (good && i < npoly[a]) ? f.corridor_tau : 0.0;
   for (int i = 0; i < SOGM_MAX_PIECES * 15; ++i)
-    r.cpts[i] = (good && i < npoly[a] * 15) ? cpts[(size_t)a * SOGM_MAX_PIECES * 15 + i] : 0.0;
-  ok[a] = good ? 1 : 0;
-  if (pub_own) {  // publication, as k_finish_flow does it (sogm_planner_set_publish)
-    if (good) pub_own[a] = r;
-    if (pub_table) pub_table[a] = pub_own[a];
+    r.cpts[i] = (good && i < npoly[a] * 15) ? f.cpts[(size_t)a * SOGM_MAX_PIECES * 15 + i] : 0.0;
+  f.out_ok[a] = good ? 1 : 0;
+  if (f.pub_own) {  // publication, as k_finish_flow does it (sogm_planner_set_publish)
+    if (good) f.pub_own[a] = r;
+    if (f.pub_table) f.pub_table[a] = f.pub_own[a];
   }
 }
 
@@ -111,6 +109,7 @@ extern "C" {
 int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmPlannerParams *pp,
                         const SogmQpSettings *qp, sogm_planner **out) {
   if (!map || !astar || !pp || !qp || !out) return SOGM_ERR_INVALID_ARG;
+  SOGM_HIP_CHECK(hipSetDevice(map->device));
   sogm_planner *p = new (std::nothrow) sogm_planner();  // (value-initialised: every field without an initialiser is zero)
   if (!p) return SOGM_ERR_INVALID_ARG;
   p->map = map;
@@ -166,7 +165,7 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
     if (e == hipSuccess) e = p->res.device(&p->cw.counters, sizeof(unsigned long long) * SOGM_CNT_N, true);
     // QP row storage fallback (rows normally live in LDS)
     p->qw.scratch_stride = qp_scratch_bytes_per_agent(pp->max_faces);
-    p->qw.dyn_lds_bytes  = qp_dynamic_lds_bytes();  // 160 KiB/CU minus k_qp's static LDS
+    p->qw.dyn_lds_bytes  = qp_kernel_setup();  // 160 KiB/CU minus the QP kernels' static LDS, granted on this device
     if (e == hipSuccess) e = p->res.device(&p->qw.scratch, p->qw.scratch_stride * (size_t)A);
     if (e == hipSuccess) e = p->res.device(&p->qw.k1_scratch, qp_k1_scratch_bytes_per_agent() * (size_t)A);
     if (e == hipSuccess) e = p->res.device(&p->qw.dbg, sizeof(long long) * 16 * (size_t)A, true);
@@ -278,6 +277,39 @@ static sogm::AstarWorkspace astar_ws(const sogm_planner *p) {
   return w;
 }
 
+// A launcher's error under the caller's label.  The launchers hand over what hipGetLastError() gave them: it clears the
+// error as it reads it, so a second call here would report "no error".
+static int launched(const char *what, hipError_t e) {
+  if (e == hipSuccess) return SOGM_OK;
+  sogm::set_error(what, e);
+  return SOGM_ERR_HIP;
+}
+
+// The stages' buffers of a replan or a flight: the planner's own between the stages, the caller's at both ends.
+static sogm::SearchIO search_io(const sogm_planner *p, const double *start_pva, const double *goal, const double *t_start) {
+  return sogm::SearchIO{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = p->d_ret,
+                        .out_route = p->d_route, .out_route_len = p->d_route_len, .route_cap = p->route_cap,
+                        .out_stats = p->d_stats};
+}
+static sogm::CorridorIO corridor_io(const sogm_planner *p, const double *start_pva, const double *t_start) {
+  return sogm::CorridorIO{.start_pva = start_pva, .t_start = t_start, .route = p->d_route,
+                          .route_len = p->d_route_len, .route_cap = p->route_cap, .out_polys = p->d_polys,
+                          .out_nfaces = p->d_nfaces, .out_npoly = p->d_npoly, .out_goal = p->d_goal};
+}
+static sogm::QpIO qp_io(const sogm_planner *p, const double *start_pva) {
+  return sogm::QpIO{.start_pva = start_pva, .goal_pv = p->d_goal, .polys = p->d_polys, .nfaces = p->d_nfaces,
+                    .npoly = p->d_npoly, .out_cpts = p->d_cpts, .out_status = p->d_status, .out_iters = p->d_iters};
+}
+// a replan's: swarm and publication as sogm_planner_set_swarm / _set_publish left them (the flight fills its own)
+static sogm::FinishArgs finish_args(const sogm_planner *p, const double *t_start, const int32_t *drone_ids,
+                                    SogmTrajRecord *out, int32_t *out_ok) {
+  return sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
+                          .status = p->d_status, .cpts = p->d_cpts, .swarm = p->swarm, .n_swarm = p->n_swarm,
+                          .swarm_ego = p->swarm_ego, .swarm_now = p->swarm_now, .t_start = t_start,
+                          .drone_ids = drone_ids, .out = out, .out_ok = out_ok, .out_safe = p->d_safe,
+                          .counters = p->cw.counters, .pub_own = p->pub_own, .pub_table = p->pub_table};
+}
+
 int sogm_astar_search(sogm_planner *p, const double *start_pva, const double *goal,
                       const double *t_start, int32_t *out_ret, double *out_route,
                       int32_t *out_route_len, int route_cap, int32_t *out_stats,
@@ -289,16 +321,14 @@ int sogm_astar_search(sogm_planner *p, const double *start_pva, const double *go
   SOGM_HIP_CHECK(hipSetDevice(p->map->device));
   hipStream_t st = (hipStream_t)stream;
   if (int rc0 = sogm::join_update(p->map, st)) return rc0;
+  const sogm::SearchIO io{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = out_ret,
+                          .out_route = out_route, .out_route_len = out_route_len, .route_cap = route_cap,
+                          .out_stats = out_stats};
   prof_begin(p->map, SOGM_PROF_ASTAR, st);
-  int rc = launch_astar(view_of(p->map), p->ap, p->pp.corridor_tau, astar_ws(p), p->sel_count,
-                        start_pva, goal, t_start, out_ret, out_route, out_route_len, route_cap,
-                        out_stats, out_trace, out_trace ? trace_cap : 0, st, p->sel_first, nullptr, p->search_mode);
+  const hipError_t e = launch_astar(view_of(p->map), p->ap, p->pp.corridor_tau, astar_ws(p), p->sel_count, io, out_trace,
+                                    out_trace ? trace_cap : 0, st, p->sel_first, nullptr, p->search_mode);
   prof_end(p->map, SOGM_PROF_ASTAR, st);
-  if (rc) {
-    sogm::set_error("k_astar", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
-  return SOGM_OK;
+  return launched("k_astar", e);
 }
 int sogm_corridor_generate(sogm_planner *p, const double *start_pva, const double *t_start,
                            const double *route, const int32_t *route_len, int route_cap,
@@ -311,16 +341,13 @@ int sogm_corridor_generate(sogm_planner *p, const double *start_pva, const doubl
   SOGM_HIP_CHECK(hipSetDevice(p->map->device));
   hipStream_t st = (hipStream_t)stream;
   if (int rc0 = sogm::join_update(p->map, st)) return rc0;
+  const sogm::CorridorIO io{.start_pva = start_pva, .t_start = t_start, .route = route, .route_len = route_len,
+                            .route_cap = route_cap, .out_polys = out_polys, .out_nfaces = out_nfaces,
+                            .out_npoly = out_npoly, .out_goal = out_goal};
   prof_begin(p->map, SOGM_PROF_CORRIDOR, st);
-  int rc = launch_corridor(view_of(p->map), p->pp, p->cw, p->sel_count, start_pva, t_start,
-                           route, route_len, route_cap, out_polys, out_nfaces, out_npoly, out_goal,
-                           st, p->sel_first);
+  const hipError_t e = launch_corridor(view_of(p->map), p->pp, p->cw, p->sel_count, io, st, p->sel_first);
   prof_end(p->map, SOGM_PROF_CORRIDOR, st);
-  if (rc) {
-    sogm::set_error("k_corridor", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
-  return SOGM_OK;
+  return launched("k_corridor", e);
 }
 // diagnostics (tools/ only): per-agent A* phase ticks
 int sogm_debug_astar_stats(sogm_planner *p, long long *out_host) {
@@ -367,17 +394,14 @@ int sogm_bezier_qp_solve(sogm_planner *p, const double *start_pva, const double 
     return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(p->map->device));
   hipStream_t st = (hipStream_t)stream;
+  const sogm::QpIO io{.start_pva = start_pva, .goal_pv = goal_pv, .polys = polys, .nfaces = nfaces, .npoly = npoly,
+                      .out_cpts = out_cpts, .out_status = out_status, .out_iters = out_iters};
   prof_begin(p->map, SOGM_PROF_QP, st);
   sogm::QpWorkspace qw0 = p->qw;
   qw0.ablate            = p->map->tune_i(SOGM_TUNE_QP_ABLATE);
-  int rc = launch_qp(p->pp, p->qs, qw0, p->qc, p->sel_count, start_pva, goal_pv, polys,
-                     nfaces, npoly, out_cpts, out_status, out_iters, st, p->sel_first);
+  const hipError_t e    = launch_qp(p->pp, p->qs, qw0, p->qc, p->sel_count, io, st, p->sel_first);
   prof_end(p->map, SOGM_PROF_QP, st);
-  if (rc) {
-    sogm::set_error("k_qp", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
-  return SOGM_OK;
+  return launched("k_qp", e);
 }
 int sogm_bezier_qp_solve_timed(sogm_planner *p, const double *start_pva, const double *end_pva,
                                const double *time_alloc, double max_vel, double max_acc, const double *polys,
@@ -394,15 +418,12 @@ int sogm_bezier_qp_solve_timed(sogm_planner *p, const double *start_pva, const d
   sogm::QpWorkspace qw = p->qw;
   qw.t_alloc           = time_alloc;
   qw.goal_stride       = 9;
+  const sogm::QpIO io{.start_pva = start_pva, .goal_pv = end_pva, .polys = polys, .nfaces = nfaces, .npoly = npoly,
+                      .out_cpts = out_cpts, .out_status = out_status, .out_iters = out_iters};
   prof_begin(p->map, SOGM_PROF_QP, st);
-  int rc = launch_qp(pp, p->qs, qw, p->qc, p->sel_count, start_pva, end_pva, polys, nfaces, npoly, out_cpts,
-                     out_status, out_iters, st, p->sel_first);
+  const hipError_t e = launch_qp(pp, p->qs, qw, p->qc, p->sel_count, io, st, p->sel_first);
   prof_end(p->map, SOGM_PROF_QP, st);
-  if (rc) {
-    sogm::set_error("k_qp", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
-  return SOGM_OK;
+  return launched("k_qp", e);
 }
 int sogm_safe_after_opt(sogm_planner *p, const double *cpts, const int32_t *npoly,
                         const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
@@ -411,12 +432,8 @@ int sogm_safe_after_opt(sogm_planner *p, const double *cpts, const int32_t *npol
     return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(p->map->device));
   if (int rc = sogm::join_exchange(p->map, (hipStream_t)stream)) return rc;
-  if (sogm::launch_deconflict(p->sel_count, cpts, npoly, records, n_records, ego_ids, t_now, out_safe,
-                              (hipStream_t)stream, p->sel_first) != 0) {
-    sogm::set_error("sogm_safe_after_opt", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
-  return SOGM_OK;
+  return launched("sogm_safe_after_opt", sogm::launch_deconflict(p->sel_count, cpts, npoly, records, n_records, ego_ids,
+                                                                t_now, out_safe, (hipStream_t)stream, p->sel_first));
 }
 
 int sogm_planner_select_agents(sogm_planner *p, int first, int count) {
@@ -655,16 +672,15 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   fca.out_ok      = out_ok;
   fca.out_records = reinterpret_cast<int *>(out_records);
   fca.rec_words   = (int)(sizeof(SogmTrajRecord) / sizeof(int));
-  if (launch_astar(mv, p->ap, p->pp.corridor_tau, astar_ws(p), A, start_pva, goal, t_start, p->d_ret, p->d_route,
-                   p->d_route_len, p->route_cap, p->d_stats, nullptr, 0, sA, 0, &fca, spec ? 8 : 0)) {
-    sogm::set_error("sogm_replan: k_astar", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
+  if (int rc = launched("sogm_replan: k_astar",
+                        launch_astar(mv, p->ap, p->pp.corridor_tau, astar_ws(p), A, search_io(p, start_pva, goal, t_start),
+                                     nullptr, 0, sA, 0, &fca, spec ? 8 : 0)))
+    return rc;
   prof_end(c, SOGM_PROF_ASTAR, sA);
   // "the searches are launched" for the side-stream work that starts from here (spare grids' clears, the pre-stamp):
   // recorded BEHIND k_astar — in front of it the record's marker held the searches back by 55 us
   SOGM_HIP_CHECK(hipEventRecord(p->ev_in, main));
-  if (sogm::launch_flow_gate(p->fc, spec ? 2 * A : A, sC)) return SOGM_ERR_HIP;
+  if (int rc = launched("sogm_replan: k_flow_gate", sogm::launch_flow_gate(p->fc, spec ? 2 * A : A, sC))) return rc;
   SOGM_HIP_CHECK(hipEventRecord(p->ev_gate, sC));
   SOGM_HIP_CHECK(hipStreamWaitEvent(sQ, p->ev_gate, 0));
   SOGM_HIP_CHECK(hipStreamWaitEvent(sF, p->ev_gate, 0));
@@ -681,21 +697,17 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   if (wg_q < 1) wg_q = 1;
   int wg_f = A < 64 ? A : 64;
   prof_begin(c, SOGM_PROF_CORRIDOR, sC);
-  if (sogm::launch_corridor_flow(mv, p->pp, p->cw, p->fc, A, wg_c, start_pva, t_start, p->d_route, p->d_route_len,
-                                 p->route_cap, p->d_polys, p->d_nfaces, p->d_npoly, p->d_goal, sC)) {
-    sogm::set_error("sogm_replan: k_corridor_flow", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
+  if (int rc = launched("sogm_replan: k_corridor_flow",
+                        sogm::launch_corridor_flow(mv, p->pp, p->cw, p->fc, A, wg_c, corridor_io(p, start_pva, t_start), sC)))
+    return rc;
   prof_end(c, SOGM_PROF_CORRIDOR, sC);
   // (a QP workgroup takes a whole CU — registers and LDS — from the moment it is resident, and the first corridors are
   //  final long after an update flow has ended: the QP kernel is dispatched behind the flow's end, not beside it)
   if (c->update_pending) SOGM_HIP_CHECK(hipStreamWaitEvent(sQ, c->ev_udone, 0));
   prof_begin(c, SOGM_PROF_QP, sQ);
-  if (sogm::launch_qp_flow(p->pp, p->qs, p->qw, p->qc, p->fc, A, wg_q, start_pva, p->d_goal, p->d_polys, p->d_nfaces,
-                           p->d_npoly, p->d_cpts, p->d_status, p->d_iters, sQ)) {
-    sogm::set_error("sogm_replan: k_qp_flow", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
+  if (int rc = launched("sogm_replan: k_qp_flow",
+                        sogm::launch_qp_flow(p->pp, p->qs, p->qw, p->qc, p->fc, A, wg_q, qp_io(p, start_pva), sQ)))
+    return rc;
   prof_end(c, SOGM_PROF_QP, sQ);
   // (queued AFTER the searches / corridor / QP launches: its gate waits for the corridor stage, and when streams share a
   //  hardware queue a launch behind a waiting gate waits with it — a QP kernel started 5 ms late costs the tick 5 ms)
@@ -720,16 +732,22 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   //  (tests/test_pipelining_gpu.py::test_overlay_under_the_prestamp_tail_at_full_size flies exactly that).)
   const bool prestamp = p->ps_on && c->sparse && c->overlap >= 2 && c->pool.front_ready() >= 0 && p->pub_own && c->clear_gate;
   if (!prestamp) fcf.p_ready = nullptr;
-  if (sogm::launch_finish_flow(fcf, A, wg_f, p->pp.corridor_tau, p->d_ret, p->d_npoly, p->d_status, p->d_cpts,
-                               p->swarm, p->n_swarm, p->swarm_ego, p->swarm_now, t_start, drone_ids, out_records,
-                               out_ok, p->d_safe, p->cw.counters, sF, p->pub_own, p->pub_table)) {
-    sogm::set_error("sogm_replan: k_finish_flow", hipGetLastError());
-    return SOGM_ERR_HIP;
-  }
+  if (int rc = launched("sogm_replan: k_finish_flow",
+                        sogm::launch_finish_flow(fcf, A, wg_f, finish_args(p, t_start, drone_ids, out_records, out_ok), sF)))
+    return rc;
   // pre-stamp (sogm_planner_set_prestamp): the next tick's map, agent by agent as their records are published, into
   // the pool's next grid — behind the gate that keeps store streams away from the searches and point scans, and
   // behind that grid's reset
   c->pool.clear_prestamp_target();
+  // the pre-stamp's stream (why it has one of its own: below); the tick's report follows it there
+  const bool        own_stream = c->tune_i(SOGM_TUNE_PRESTAMP_STREAM) != 0 && c->pstream != nullptr;
+  const hipStream_t pst        = own_stream ? c->pstream : c->side;
+  const int         retire     = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);  // measured: tick -2 %, but the clear 14.5 -> 15.5 ms; off
+  auto report = [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_flow_report, dim3(1), dim3(1), 0, st, (const int *)p->d_flow, p->h_flow_fail,
+                       retire ? p->d_epoch : (int *)nullptr, c->h_tick_clock);
+    return hipGetLastError();
+  };
   if (prestamp) {
     const int nxt = c->pool.front_ready();
     sogm::PrestampDev d = p->ps;
@@ -771,8 +789,6 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     // with the lower target is a kernel on the resets' stream — which spins for the full gate anyway — followed by an
     // event; a first version put a spinning gate at the head of THIS stream, one more spinner for shared or
     // oversubscribed hardware queues to stall on.  (prestamp_stream = 0: round 3's placement on the resets' stream.)
-    const bool  own_stream = c->tune_i(SOGM_TUNE_PRESTAMP_STREAM) != 0 && c->pstream != nullptr;
-    hipStream_t pst        = own_stream ? c->pstream : c->side;
     SOGM_HIP_CHECK(hipStreamWaitEvent(pst, p->ev_in, 0));
     if (own_stream) {
       SOGM_HIP_CHECK(hipStreamWaitEvent(pst, c->pool.cleared_event(nxt), 0));
@@ -783,10 +799,9 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     }
     int wg_p = 8 * n_cu;  // one-wave workgroups (512 / 1024 / 2048+: 14.0 / 12.3 / 12.1 ms per tick)
     if (c->tune_i(SOGM_TUNE_PRESTAMP_WGS) > 0) wg_p = c->tune_i(SOGM_TUNE_PRESTAMP_WGS);
-    if (sogm::launch_prestamp_flow(c->geom, p->fc, d, wg_p, wg_q, wg_f < A ? wg_f : A, pst)) {
-      sogm::set_error("sogm_replan: k_prestamp_flow", hipGetLastError());
-      return SOGM_ERR_HIP;
-    }
+    if (int rc = launched("sogm_replan: k_prestamp_flow",
+                          sogm::launch_prestamp_flow(c->geom, p->fc, d, wg_p, wg_q, wg_f < A ? wg_f : A, pst)))
+      return rc;
     c->pool.set_prestamp_target(nxt);
     c->n_stamps++;
     c->ps_fail_host = p->h_flow_fail;  // sogm_update_prestamped refuses the grid if this replan turns out to have failed
@@ -800,10 +815,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   if (report_on_sc) {
     SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_fdone[2], 0));
     SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_fdone[3], 0));
-    const int retire_c = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);
-    hipLaunchKernelGGL(k_flow_report, dim3(1), dim3(1), 0, sC, (const int *)p->d_flow, p->h_flow_fail,
-                       retire_c ? p->d_epoch : (int *)nullptr, c->h_tick_clock);
-    SOGM_HIP_CHECK(hipGetLastError());
+    SOGM_HIP_CHECK(report(sC));
   }
   SOGM_HIP_CHECK(hipEventRecord(p->ev_fdone[1], sC));
   for (int k = 0; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->ev_fdone[k], 0));
@@ -818,13 +830,9 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   if (c->pool.prestamp_pending()) {
     // the tick's report behind the pre-stamp on ITS stream (the last kernel of the tick to end), so that the caller's
     // stream goes from the fan-in straight to the next tick's first kernel instead of through one more launch
-    const int retire_p = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);
-    hipStream_t rst = c->tune_i(SOGM_TUNE_PRESTAMP_STREAM) != 0 && c->pstream ? c->pstream : c->side;  // = pst above
-    for (int k = 1; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(rst, p->ev_fdone[k], 0));
-    hipLaunchKernelGGL(k_flow_report, dim3(1), dim3(1), 0, rst, (const int *)p->d_flow, p->h_flow_fail,
-                       retire_p ? p->d_epoch : (int *)nullptr, c->h_tick_clock);
-    SOGM_HIP_CHECK(hipGetLastError());
-    SOGM_HIP_CHECK(hipEventRecord(p->ev_pdone, rst));
+    for (int k = 1; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(pst, p->ev_fdone[k], 0));
+    SOGM_HIP_CHECK(report(pst));
+    SOGM_HIP_CHECK(hipEventRecord(p->ev_pdone, pst));
     const int defer = c->tune_i(SOGM_TUNE_SPLAT_OVERLAP) != 0;  // 0: the caller's stream waits for the pre-stamp's end here
     if (defer) {
       // the caller's stream goes on behind the fan-in: the next update's overlay waits per agent (sogm_update_prestamped),
@@ -845,12 +853,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     c->records_final_ptr   = p->pub_own;
     c->records_final_valid = 1;
   }
-  const int retire = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);  // measured: tick -2 %, but the clear 14.5 -> 15.5 ms; off
-  if (!reported) {
-    hipLaunchKernelGGL(k_flow_report, dim3(1), dim3(1), 0, main, (const int *)p->d_flow, p->h_flow_fail,
-                       retire ? p->d_epoch : (int *)nullptr, c->h_tick_clock);
-    SOGM_HIP_CHECK(hipGetLastError());
-  }
+  if (!reported) SOGM_HIP_CHECK(report(main));
   return SOGM_OK;
 }
 
@@ -882,13 +885,10 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
     if (n <= 0) continue;
     hipStream_t st = p->gstream[g];
     SOGM_HIP_CHECK(hipStreamWaitEvent(st, p->ev_in, 0));
-    if (launch_astar(mv, p->ap, p->pp.corridor_tau, astar_ws(p), n, start_pva, goal, t_start, p->d_ret,
-                     p->d_route, p->d_route_len, p->route_cap, p->d_stats, nullptr, 0, st, a0) ||
-        launch_corridor(mv, p->pp, p->cw, n, start_pva, t_start, p->d_route, p->d_route_len,
-                        p->route_cap, p->d_polys, p->d_nfaces, p->d_npoly, p->d_goal, st, a0, p->ev_pts[g])) {
-      sogm::set_error("sogm_replan launch", hipGetLastError());
-      return SOGM_ERR_HIP;
-    }
+    hipError_t e = launch_astar(mv, p->ap, p->pp.corridor_tau, astar_ws(p), n, search_io(p, start_pva, goal, t_start),
+                                nullptr, 0, st, a0);
+    if (e == hipSuccess) e = launch_corridor(mv, p->pp, p->cw, n, corridor_io(p, start_pva, t_start), st, a0, p->ev_pts[g]);
+    if (int rc = launched("sogm_replan launch", e)) return rc;
     SOGM_HIP_CHECK(hipEventRecord(p->ev_corr[g], st));
   }
   if (c->overlap == 1) {
@@ -921,21 +921,15 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
     const int a0 = (int)((long long)A * g / G), a1 = (int)((long long)A * (g + 1) / G), n = a1 - a0;
     if (n <= 0) continue;
     hipStream_t st = p->gstream[g];
-    if (launch_qp(p->pp, p->qs, p->qw, p->qc, n, start_pva, p->d_goal, p->d_polys, p->d_nfaces,
-                  p->d_npoly, p->d_cpts, p->d_status, p->d_iters, st, a0)) {
-      sogm::set_error("sogm_replan launch_qp", hipGetLastError());
-      return SOGM_ERR_HIP;
-    }
-    if (p->swarm) {
-      if (sogm::launch_deconflict(n, p->d_cpts, p->d_npoly, p->swarm, p->n_swarm, p->swarm_ego, p->swarm_now,
-                                  p->d_safe, st, a0, p->cw.counters) != 0) {
-        sogm::set_error("sogm_replan launch_deconflict", hipGetLastError());
-        return SOGM_ERR_HIP;
-      }
-    }
-    hipLaunchKernelGGL(k_pack_records, dim3((n + 63) / 64), dim3(64), 0, st, a1, p->pp.corridor_tau,
-                       p->d_ret, p->d_npoly, p->d_status, p->swarm ? p->d_safe : nullptr, p->d_cpts, t_start,
-                       drone_ids, out_records, out_ok, a0, p->cw.counters, p->pub_own, p->pub_table);
+    if (int rc = launched("sogm_replan launch_qp", launch_qp(p->pp, p->qs, p->qw, p->qc, n, qp_io(p, start_pva), st, a0)))
+      return rc;
+    if (p->swarm)
+      if (int rc = launched("sogm_replan launch_deconflict",
+                            sogm::launch_deconflict(n, p->d_cpts, p->d_npoly, p->swarm, p->n_swarm, p->swarm_ego,
+                                                    p->swarm_now, p->d_safe, st, a0, p->cw.counters)))
+        return rc;
+    hipLaunchKernelGGL(k_pack_records, dim3((n + 63) / 64), dim3(64), 0, st, a1,
+                       finish_args(p, t_start, drone_ids, out_records, out_ok), a0);
     SOGM_HIP_CHECK(hipGetLastError());
     SOGM_HIP_CHECK(hipEventRecord(p->ev_done[g], st));
     SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->ev_done[g], 0));  // fan in
@@ -1339,39 +1333,32 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
   FL_TRACE("waits queued");
   // QP first, then search (each wants whole CUs), then the one-wave kernels: with masks the order is immaterial
   const int spec = c->tune_i(SOGM_TUNE_FLIGHT_SPEC) != 0 ? 1 : 0;
-  if (sogm::launch_flight_qp(p->pp, p->qs, p->qw, p->qc, fl, p->fl_wgs[0], p->d_fl_pva, p->d_goal, p->d_polys, p->d_nfaces,
-                             p->d_npoly, p->d_cpts, p->d_status, p->d_iters, p->fl_stream[0]) ||
-      sogm::launch_flight_search(mv, p->ap, p->pp.corridor_tau, astar_ws(p), fl, p->fl_wgs[1], p->d_fl_pva, f->goals,
-                                 p->d_fl_tstart, p->d_ret, p->d_route, p->d_route_len, p->route_cap, p->d_stats, spec,
-                                 p->fl_stream[1])) {
-    sogm::set_error("sogm_flight_run: launch", hipGetLastError());
+  hipError_t e = sogm::launch_flight_qp(p->pp, p->qs, p->qw, p->qc, fl, p->fl_wgs[0], qp_io(p, p->d_fl_pva), p->fl_stream[0]);
+  if (e == hipSuccess)
+    e = sogm::launch_flight_search(mv, p->ap, p->pp.corridor_tau, astar_ws(p), fl, p->fl_wgs[1],
+                                   search_io(p, p->d_fl_pva, f->goals, p->d_fl_tstart), spec, p->fl_stream[1]);
+  if (int rc = launched("sogm_flight_run: launch", e)) {
     (void)hipDeviceSynchronize();
-    return SOGM_ERR_HIP;
+    return rc;
   }
   FL_TRACE("qp + search launched");
   sogm::FlightLightDev ld{};
-  ld.start_pva   = p->d_fl_pva;
-  ld.t_start     = p->d_fl_tstart;
-  ld.route       = p->d_route;
-  ld.route_len   = p->d_route_len;
-  ld.route_cap   = p->route_cap;
-  ld.out_polys   = p->d_polys;
-  ld.out_nfaces  = p->d_nfaces;
-  ld.out_npoly   = p->d_npoly;
-  ld.out_goal    = p->d_goal;
-  ld.fin         = sogm::FinishArgs{p->pp.corridor_tau, p->d_ret, p->d_npoly, p->d_status, p->d_cpts, nullptr, f->n_total,
-                                    f->drone_ids, p->d_fl_now, p->d_fl_tstart, f->drone_ids, nullptr, nullptr, p->d_safe,
-                                    p->cw.counters, f->own_inout, nullptr};
+  ld.cor = corridor_io(p, p->d_fl_pva, p->d_fl_tstart);
+  // (the flight's swarm is its ring of tables: the kernel sets swarm / pub_table / out / out_ok per tick, null here)
+  ld.fin = sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
+                            .status = p->d_status, .cpts = p->d_cpts, .n_swarm = f->n_total, .swarm_ego = f->drone_ids,
+                            .swarm_now = p->d_fl_now, .t_start = p->d_fl_tstart, .drone_ids = f->drone_ids,
+                            .out_safe = p->d_safe, .counters = p->cw.counters, .pub_own = f->own_inout};
   ld.tables      = f->tables;
   ld.n_total     = f->n_total;
   ld.agent0      = f->agent0;
   ld.log_records = f->log_records;
   ld.log_ok      = f->log_ok;
-  if (sogm::launch_flight_light(mv, p->pp, p->cw, fl, ld, p->fl_wgs[2], p->fl_stream[2]) ||
-      sogm::launch_flight_map(c->geom, fl, md, p->fl_wgs[3], p->fl_stream[3])) {
-    sogm::set_error("sogm_flight_run: launch", hipGetLastError());
+  e = sogm::launch_flight_light(mv, p->pp, p->cw, fl, ld, p->fl_wgs[2], p->fl_stream[2]);
+  if (e == hipSuccess) e = sogm::launch_flight_map(c->geom, fl, md, p->fl_wgs[3], p->fl_stream[3]);
+  if (int rc = launched("sogm_flight_run: launch", e)) {
     (void)hipDeviceSynchronize();
-    return SOGM_ERR_HIP;
+    return rc;
   }
   FL_TRACE("light + map launched");
   if (xchg) {

@@ -83,7 +83,36 @@ struct FlightMapDev {
   size_t                agent_bytes;
   unsigned long long   *reset_stat;    // the context's reset statistics (sogm_sparse_reset_state / sogm_map_traffic), or null
 };
-int launch_flight_map(const GridGeom &g, const FlightCtl &fl, const FlightMapDev &d, int n_workgroups, hipStream_t st);
+hipError_t launch_flight_map(const GridGeom &g, const FlightCtl &fl, const FlightMapDev &d, int n_workgroups, hipStream_t st);
+
+// A stage's device buffers, one struct per stage: the grouped, dataflow and flight variants of a stage take the same
+// struct from the launcher down to the device body.  Field order = the kernels' argument order.  Every launch_* returns
+// the first error it saw: hipGetLastError() clears the error as it reads it, the caller cannot ask again.
+struct SearchIO {  // search: start state, goal and start time in, return code / route / statistics out
+  const double *start_pva, *goal, *t_start;
+  int32_t      *out_ret;
+  double       *out_route;
+  int32_t      *out_route_len;
+  int           route_cap;
+  int32_t      *out_stats;
+};
+struct CorridorIO {  // corridors: the search's route in, polytopes and the local goal out
+  const double  *start_pva, *t_start, *route;
+  const int32_t *route_len;
+  int            route_cap;
+  double        *out_polys;
+  int32_t       *out_nfaces, *out_npoly;
+  double        *out_goal;
+};
+struct QpIO {  // QP: the corridors' polytopes and goal in, control points / status / iterations out
+  const double  *start_pva, *goal_pv, *polys;
+  const int32_t *nfaces, *npoly;
+  double        *out_cpts;
+  int32_t       *out_status, *out_iters;
+};
+// `__restrict__` lives on the `__global__` parameters of the per-stage entries' kernels (k_astar, k_flight_search,
+// k_qp, k_corridor_points / _segment / _finalize), which fill the struct in their first lines: a struct member cannot
+// carry it.
 // what finish_agent (csrc/sogm_corridor.hip) reads and writes for one agent
 struct FinishArgs {
   double                corridor_tau;
@@ -101,12 +130,7 @@ struct FinishArgs {
 };
 // the light roles' arguments (k_flight_light): corridor stage buffers + the finishing role's
 struct FlightLightDev {
-  const double   *start_pva, *t_start, *route;
-  const int32_t  *route_len;
-  int             route_cap;
-  double         *out_polys;
-  int32_t        *out_nfaces, *out_npoly;
-  double         *out_goal;
+  CorridorIO      cor;
   FinishArgs      fin;          // swarm / pub_table / out / out_ok are set per tick from the fields below
   SogmTrajRecord *tables;       // [4][n_total] ring of swarm tables (null: no deconfliction, no table)
   int             n_total, agent0;
@@ -114,19 +138,15 @@ struct FlightLightDev {
   int32_t        *log_ok;       // [n_ticks][A]
 };
 struct CorridorWorkspace;
-int launch_flight_light(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlightCtl &fl,
-                        const FlightLightDev &d, int n_workgroups, hipStream_t st);
+hipError_t launch_flight_light(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlightCtl &fl,
+                               const FlightLightDev &d, int n_workgroups, hipStream_t st);
 struct AstarWorkspace;
-int launch_flight_search(const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
-                         const FlightCtl &fl, int n_workgroups, const double *start_pva, const double *goal,
-                         const double *t_start, int32_t *out_ret, double *out_route, int32_t *out_route_len, int route_cap,
-                         int32_t *out_stats, int spec, hipStream_t st);
+hipError_t launch_flight_search(const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
+                                const FlightCtl &fl, int n_workgroups, const SearchIO &io, int spec, hipStream_t st);
 struct QpWorkspace;
 struct QpConst;
-int launch_flight_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
-                     const FlightCtl &fl, int n_workgroups, const double *start_pva, const double *goal_pv,
-                     const double *polys, const int32_t *nfaces, const int32_t *npoly, double *out_cpts,
-                     int32_t *out_status, int32_t *out_iters, hipStream_t st);
+hipError_t launch_flight_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
+                            const FlightCtl &fl, int n_workgroups, const QpIO &io, hipStream_t st);
 
 // Arguments of the pre-stamp kernel (csrc/sogm_map.hip, k_prestamp_flow): the next tick's update inputs, the grid and
 // mark log it builds into, and where the next tick's start states go.
@@ -155,32 +175,21 @@ struct PrestampDev {
 };
 // n_qp / n_finish: the QP workgroups and finishing waves of this replan — the pre-stamp's waves are not dispatched before
 // all of them are resident (they wait for what those produce, and a QP workgroup needs a whole CU)
-int launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const PrestampDev &ps, int n_workgroups, int n_qp,
-                         int n_finish, hipStream_t st);
+hipError_t launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const PrestampDev &ps, int n_workgroups, int n_qp,
+                                int n_finish, hipStream_t st);
 
 // ParticleATC::isSafeAfterOpt for agents [agent0, agent0 + n_agents): out_safe[a] = 1 / 0
-int launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
-                      int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
-                      hipStream_t st, int agent0, unsigned long long *counters = nullptr);
-int launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                    int n_agents, const double *start_pva, const double *t_start,
-                    const double *route, const int32_t *route_len, int route_cap,
-                    double *out_polys, int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
-                    hipStream_t st, int agent0 = 0, hipEvent_t ev_map_read = nullptr);
+hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
+                             int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
+                             hipStream_t st, int agent0, unsigned long long *counters = nullptr);
+hipError_t launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, int n_agents,
+                           const CorridorIO &io, hipStream_t st, int agent0 = 0, hipEvent_t ev_map_read = nullptr);
 
 // dataflow replan launchers (persistent kernels; see k_corridor_flow / k_qp_flow / k_finish_flow)
-int launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st);
-int launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                         const FlowCtl &fc, int n_agents, int n_workgroups, const double *start_pva,
-                         const double *t_start, const double *route, const int32_t *route_len, int route_cap,
-                         double *out_polys, int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
-                         hipStream_t st);
-int launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, double corridor_tau, const int32_t *ret,
-                       const int32_t *npoly, const int32_t *status, const double *cpts, const SogmTrajRecord *swarm,
-                       int n_swarm, const int32_t *swarm_ego, const double *swarm_now, const double *t_start,
-                       const int32_t *drone_ids, SogmTrajRecord *out, int32_t *out_ok, int32_t *out_safe,
-                       unsigned long long *counters, hipStream_t st, SogmTrajRecord *pub_own = nullptr,
-                       SogmTrajRecord *pub_table = nullptr);
+hipError_t launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st);
+hipError_t launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
+                                const FlowCtl &fc, int n_agents, int n_workgroups, const CorridorIO &io, hipStream_t st);
+hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st);
 
 // Per-agent QP row storage in HBM, used only when a problem's rows do not fit in LDS.
 struct QpWorkspace {
@@ -201,28 +210,23 @@ struct QpWorkspace {
 };
 size_t qp_scratch_bytes_per_agent(int max_faces);
 size_t qp_k1_scratch_bytes_per_agent();
-int    qp_dynamic_lds_bytes();
+// Lets the three QP kernels use the CU's LDS beyond the default limit on the current device and returns the dynamic
+// LDS a workgroup of them may ask for (QpWorkspace::dyn_lds_bytes): once per planner, before its first launch.
+int    qp_kernel_setup();
 struct QpConst {
   double QM[225];  // per-piece min-jerk cost block (bezier_optimizer.cpp:96-111)
 };
 int astar_resident_workgroups(int device);
-int launch_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws,
-              const QpConst &qc, int n_agents, const double *start_pva, const double *goal_pv,
-              const double *polys, const int32_t *nfaces, const int32_t *npoly, double *out_cpts,
-              int32_t *out_status, int32_t *out_iters, hipStream_t st, int agent0 = 0);
-
-int launch_qp_flow(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws,
-                   const QpConst &qc, const FlowCtl &fc, int n_agents, int n_workgroups, const double *start_pva,
-                   const double *goal_pv, const double *polys, const int32_t *nfaces, const int32_t *npoly,
-                   double *out_cpts, int32_t *out_status, int32_t *out_iters, hipStream_t st);
+hipError_t launch_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
+                     int n_agents, const QpIO &io, hipStream_t st, int agent0 = 0);
+hipError_t launch_qp_flow(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
+                          const FlowCtl &fc, int n_agents, int n_workgroups, const QpIO &io, hipStream_t st);
 
 size_t astar_node_bytes();
-int    launch_astar(const MapView &m, const SogmAstarParams &ap, double corridor_tau,
-                    const AstarWorkspace &wsp, int n_agents, const double *start_pva,
-                    const double *goal, const double *t_start, int32_t *out_ret,
-                    double *out_route, int32_t *out_route_len, int route_cap, int32_t *out_stats,
-                    int32_t *out_trace, int trace_cap, hipStream_t st, int agent0 = 0, const FlowCtl *fc = nullptr,
-                 int search_mode = 0);
+// out_trace / trace_cap: the expansion trace of sogm_astar_search (null / 0 everywhere else)
+hipError_t launch_astar(const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp,
+                        int n_agents, const SearchIO &io, int32_t *out_trace, int trace_cap, hipStream_t st,
+                        int agent0 = 0, const FlowCtl *fc = nullptr, int search_mode = 0);
 
 }  // namespace sogm
 

@@ -202,10 +202,8 @@ size_t qp_scratch_bytes_per_agent(int max_faces) {
 // One agent's QP, executed by the whole workgroup (QP_NT lanes); called by k_qp (one workgroup per agent) and by
 // the dataflow kernel k_qp_flow (a workgroup solves agents one after the other as their corridors become final).
 __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, const SogmQpSettings &qs,
-                                               const QpWorkspace &ws, const QpConst &qc, const double *start_pva,
-                                               const double *goal_pv, const double *polys, const int32_t *nfaces,
-                                               const int32_t *npoly, double *out_cpts, int32_t *out_status,
-                                               int32_t *out_iters, int ablate_arg, int agent) {
+                                               const QpWorkspace &ws, const QpConst &qc, const QpIO &io,
+                                               int ablate_arg, int agent) {
   // phase ablation is a profiling aid: compiled in only with -DSOGM_QP_ABLATE_BUILD (tools/qp_ablate.py)
 #ifdef SOGM_QP_ABLATE_BUILD
   const int ablate = ablate_arg;
@@ -217,11 +215,11 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
   const long long dbg_t0 = wall_clock64(), dbg_clk0 = clock64();
   long long       dbg_refac = 0, dbg_check = 0, dbg_f1 = 0, dbg_f2 = 0, dbg_f3 = 0, dbg_k1 = 0, dbg_k2 = 0;
   int             dbg_nrefac = 0, dbg_ncheck = 0;
-  const int M = npoly[agent];
+  const int M = io.npoly[agent];
   if (M <= 0 || M > SOGM_MAX_PIECES) {
     if (tid == 0) {
-      out_status[agent] = -100;  // nothing to solve (an earlier stage failed)
-      out_iters[agent]  = 0;
+      io.out_status[agent] = -100;  // nothing to solve (an earlier stage failed)
+      io.out_iters[agent]  = 0;
     }
     return;
   }
@@ -253,7 +251,7 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
   if (tid == 0) {
     int acc = 0;
     for (int i = 0; i < M; ++i) {
-      const int f = nfaces[agent * SOGM_MAX_PIECES + i];
+      const int f = io.nfaces[agent * SOGM_MAX_PIECES + i];
       s_off[i]    = acc;
       s_nf[i]     = f;
       acc += 5 * f;
@@ -286,9 +284,9 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
   // the HBM-scratch fallback.
   auto body = [&](const Rows &R, auto fast_tag) __attribute__((always_inline)) {
   constexpr bool FAST = decltype(fast_tag)::value;  // compile-time: the two iterations never share a loop
-  const double *sp   = start_pva + agent * 9;
+  const double *sp   = io.start_pva + agent * 9;
   const int     gstr = ws.goal_stride == 9 ? 9 : 6;
-  const double *gp   = goal_pv + agent * gstr;
+  const double *gp   = io.goal_pv + agent * gstr;
   // time allocation t_[i] (bezier_optimizer.cpp:135,164-165,191-192,220,231): replan() gives every piece
   // corridor_tau (baseline.cpp:411); the general entry passes its own vector
   const double *tal  = ws.t_alloc ? ws.t_alloc + (size_t)agent * SOGM_MAX_PIECES : nullptr;
@@ -404,7 +402,7 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
     int i = 0;
     while (i + 1 < M && s >= s_off[i + 1]) ++i;
     const int     q = s - s_off[i], face = q / 5;
-    const double *h = polys + (((size_t)agent * SOGM_MAX_PIECES + i) * MF + face) * 4;
+    const double *h = io.polys + (((size_t)agent * SOGM_MAX_PIECES + i) * MF + face) * 4;
     R.sval[(size_t)s * 3 + 0] = h[0];
     R.sval[(size_t)s * 3 + 1] = h[1];
     R.sval[(size_t)s * 3 + 2] = h[2];
@@ -1742,11 +1740,11 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
     }
   }
   __syncthreads();
-  double *out = out_cpts + (size_t)agent * SOGM_MAX_PIECES * 15;
+  double *out = io.out_cpts + (size_t)agent * SOGM_MAX_PIECES * 15;
   for (int j = tid; j < SOGM_MAX_PIECES * 15; j += QP_NT) out[j] = j < n ? s_D[j] * s_x[j] : 0.0;
   if (tid == 0) {
-    out_status[agent] = status;
-    out_iters[agent]  = iter;
+    io.out_status[agent] = status;
+    io.out_iters[agent]  = iter;
     if (ws.dbg) {
       long long *o = ws.dbg + (size_t)agent * 16;
       o[8]  = dbg_f1;  // factor(): block assembly | forward sweep | backward rows + K^-1 registers (all factorisations)
@@ -1811,19 +1809,16 @@ __global__ __launch_bounds__(QP_NT) void k_qp(SogmPlannerParams pp, SogmQpSettin
                                             double *__restrict__ out_cpts,
                                             int32_t *__restrict__ out_status,
                                             int32_t *__restrict__ out_iters, int ablate_arg, int agent0) {
-  qp_solve_agent(pp, qs, ws, qc, start_pva, goal_pv, polys, nfaces, npoly, out_cpts, out_status, out_iters,
-                 ablate_arg, blockIdx.x + agent0);
+  const QpIO io{.start_pva = start_pva, .goal_pv = goal_pv, .polys = polys, .nfaces = nfaces, .npoly = npoly,
+                .out_cpts = out_cpts, .out_status = out_status, .out_iters = out_iters};
+  qp_solve_agent(pp, qs, ws, qc, io, ablate_arg, blockIdx.x + agent0);
 }
 
 // Dataflow kernel Q (sogm_replan): ONE persistent launch; a workgroup takes tickets and solves the agent whose
 // corridors became final ticket-th (k_corridor_flow publishes agents in completion order), so a 4000-iteration QP
 // only delays its own agent.  The solved agent is handed to the finishing kernel (deconfliction + record packing).
 __global__ __launch_bounds__(QP_NT) void k_qp_flow(SogmPlannerParams pp, SogmQpSettings qs, QpWorkspace ws,
-                                                 QpConst qc, FlowCtl fc, const double *start_pva,
-                                                 const double *goal_pv, const double *polys,
-                                                 const int32_t *nfaces, const int32_t *npoly, double *out_cpts,
-                                                 int32_t *out_status, int32_t *out_iters, int ablate_arg,
-                                                 int n_agents) {
+                                                 QpConst qc, FlowCtl fc, QpIO io, int ablate_arg, int n_agents) {
   __shared__ int s_agent;
   if (threadIdx.x == 0) atomicAdd(&fc.hdr[FLOW_Q_RESIDENT], 1);  // this workgroup holds its CU (pre-stamp gate)
   for (;;) {
@@ -1839,8 +1834,7 @@ __global__ __launch_bounds__(QP_NT) void k_qp_flow(SogmPlannerParams pp, SogmQpS
     if (agent < 0) break;  // no tickets left, or the tick failed
     __threadfence();       // corridor outputs were published before the ready slot
     if (threadIdx.x == 0) fc.ts[agent * 8 + 4] = wall_clock64();
-    qp_solve_agent(pp, qs, ws, qc, start_pva, goal_pv, polys, nfaces, npoly, out_cpts, out_status, out_iters,
-                   ablate_arg, agent);
+    qp_solve_agent(pp, qs, ws, qc, io, ablate_arg, agent);
     __syncthreads();
     if (threadIdx.x == 0) fc.ts[agent * 8 + 5] = wall_clock64();
     __threadfence();
@@ -1852,9 +1846,7 @@ __global__ __launch_bounds__(QP_NT) void k_qp_flow(SogmPlannerParams pp, SogmQpS
 // Flight kernel Q (sogm_flight_run): as k_qp_flow, over the flight's rings — tickets run over every (agent, tick) of the
 // flight, the solved agent goes to the finish queue.
 __global__ __launch_bounds__(QP_NT) void k_flight_qp(SogmPlannerParams pp, SogmQpSettings qs, QpWorkspace ws, QpConst qc,
-                                                   FlightCtl fl, const double *start_pva, const double *goal_pv,
-                                                   const double *polys, const int32_t *nfaces, const int32_t *npoly,
-                                                   double *out_cpts, int32_t *out_status, int32_t *out_iters) {
+                                                   FlightCtl fl, QpIO io) {
   __shared__ int s_agent;
   const int total = fl.n_agents * fl.n_ticks;
   fl_wg_started(fl, 0);
@@ -1870,7 +1862,7 @@ __global__ __launch_bounds__(QP_NT) void k_flight_qp(SogmPlannerParams pp, SogmQ
     if (agent < 0) break;  // no tickets left, or the flight failed
     __threadfence();
     if (threadIdx.x == 0) fl.ts[agent * FL_TS + 4] = wall_clock64();
-    qp_solve_agent(pp, qs, ws, qc, start_pva, goal_pv, polys, nfaces, npoly, out_cpts, out_status, out_iters, 0, agent);
+    qp_solve_agent(pp, qs, ws, qc, io, 0, agent);
     __syncthreads();
     if (threadIdx.x == 0) {
       fl.ts[agent * FL_TS + 5] = wall_clock64();
@@ -1880,61 +1872,40 @@ __global__ __launch_bounds__(QP_NT) void k_flight_qp(SogmPlannerParams pp, SogmQ
   }
 }
 
-// Dynamic LDS k_qp may ask for: the CU's 160 KiB minus the kernel's static LDS (queried, not assumed).
-int qp_dynamic_lds_bytes() {
-  hipFuncAttributes a, b;
-  if (hipFuncGetAttributes(&a, (const void *)k_qp) != hipSuccess) return 128 * 1024;
-  if (hipFuncGetAttributes(&b, (const void *)k_qp_flow) != hipSuccess) return 128 * 1024;
-  long stat = (long)(a.sharedSizeBytes > b.sharedSizeBytes ? a.sharedSizeBytes : b.sharedSizeBytes);
-  if (hipFuncGetAttributes(&b, (const void *)k_flight_qp) == hipSuccess && (long)b.sharedSizeBytes > stat) stat = (long)b.sharedSizeBytes;
-  const long dyn  = 160L * 1024 - stat;
-  return (int)(dyn & ~255L);
+// Dynamic LDS the QP kernels may ask for: the CU's 160 KiB minus the largest static LDS of the three (queried, not
+// assumed), granted to each of them on the current device.
+int qp_kernel_setup() {
+  const void *kernels[3] = {(const void *)k_qp, (const void *)k_qp_flow, (const void *)k_flight_qp};
+  long        stat       = 0;
+  bool        known      = true;
+  for (const void *k : kernels) {
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, k) != hipSuccess) known = false;
+    else if ((long)a.sharedSizeBytes > stat) stat = (long)a.sharedSizeBytes;
+  }
+  const int dyn = known ? (int)((160L * 1024 - stat) & ~255L) : 128 * 1024;
+  for (const void *k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+  return dyn;
 }
 
-int launch_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws,
-              const QpConst &qc, int n_agents, const double *start_pva, const double *goal_pv,
-              const double *polys, const int32_t *nfaces, const int32_t *npoly, double *out_cpts,
-              int32_t *out_status, int32_t *out_iters, hipStream_t st, int agent0) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_qp, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ws.dyn_lds_bytes);
-    attr_set = true;
-  }
+hipError_t launch_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
+                     int n_agents, const QpIO &io, hipStream_t st, int agent0) {
   // ws.ablate (profiling aid only, tuning key qp_ablate): bit0 skip A^T w, bit1 skip the solve, bit2/3 skip row updates
-  const int ablate = ws.ablate;
-  hipLaunchKernelGGL(k_qp, dim3(n_agents), dim3(QP_NT), ws.dyn_lds_bytes, st, pp, qs, ws, qc, start_pva,
-                     goal_pv, polys, nfaces, npoly, out_cpts, out_status, out_iters, ablate, agent0);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  hipLaunchKernelGGL(k_qp, dim3(n_agents), dim3(QP_NT), ws.dyn_lds_bytes, st, pp, qs, ws, qc, io.start_pva, io.goal_pv,
+                     io.polys, io.nfaces, io.npoly, io.out_cpts, io.out_status, io.out_iters, ws.ablate, agent0);
+  return hipGetLastError();
 }
 
-int launch_qp_flow(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws,
-                   const QpConst &qc, const FlowCtl &fc, int n_agents, int n_workgroups, const double *start_pva,
-                   const double *goal_pv, const double *polys, const int32_t *nfaces, const int32_t *npoly,
-                   double *out_cpts, int32_t *out_status, int32_t *out_iters, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_qp_flow, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ws.dyn_lds_bytes);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_qp_flow, dim3(n_workgroups), dim3(QP_NT), ws.dyn_lds_bytes, st, pp, qs, ws, qc, fc,
-                     start_pva, goal_pv, polys, nfaces, npoly, out_cpts, out_status, out_iters, 0, n_agents);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+hipError_t launch_qp_flow(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
+                          const FlowCtl &fc, int n_agents, int n_workgroups, const QpIO &io, hipStream_t st) {
+  hipLaunchKernelGGL(k_qp_flow, dim3(n_workgroups), dim3(QP_NT), ws.dyn_lds_bytes, st, pp, qs, ws, qc, fc, io, 0, n_agents);
+  return hipGetLastError();
 }
 
-int launch_flight_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
-                     const FlightCtl &fl, int n_workgroups, const double *start_pva, const double *goal_pv,
-                     const double *polys, const int32_t *nfaces, const int32_t *npoly, double *out_cpts,
-                     int32_t *out_status, int32_t *out_iters, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_flight_qp, hipFuncAttributeMaxDynamicSharedMemorySize, ws.dyn_lds_bytes);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_flight_qp, dim3(n_workgroups), dim3(QP_NT), ws.dyn_lds_bytes, st, pp, qs, ws, qc, fl, start_pva,
-                     goal_pv, polys, nfaces, npoly, out_cpts, out_status, out_iters);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+hipError_t launch_flight_qp(const SogmPlannerParams &pp, const SogmQpSettings &qs, const QpWorkspace &ws, const QpConst &qc,
+                            const FlightCtl &fl, int n_workgroups, const QpIO &io, hipStream_t st) {
+  hipLaunchKernelGGL(k_flight_qp, dim3(n_workgroups), dim3(QP_NT), ws.dyn_lds_bytes, st, pp, qs, ws, qc, fl, io);
+  return hipGetLastError();
 }
 
 }  // namespace sogm
