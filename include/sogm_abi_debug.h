@@ -137,6 +137,25 @@ int sogm_gridmap_download(sogm_gridmap *g, int agent, double *occupancy_host, in
 /* Test hook: sets raycast_num_ (the de-duplication flags are chars and stop matching after frame 127). */
 int sogm_gridmap_force_frame(sogm_gridmap *g, int raycast_num);
 
+/* Test hook: the corridor rules around FIRI (the per-segment box, ShrinkCorridor, checkCorridorValidity and the `break`,
+ * the adjacent-intersection scan, the goal scan; baseline.cpp:300-403 / baseline_fake.cpp:300-414) for n independent
+ * problems whose polytopes the caller injects where FIRI's would be — the replan's own device code, one wave per
+ * problem.  pp_host[n] is HOST memory (fake_planner, shrink_size, init_range and max_faces are read; every max_faces
+ * must equal `max_faces` <= 64, the stride of all polytope arrays); every other pointer is device memory:
+ * start_pva [n][9], route [n][route_cap][6] with route_cap > SOGM_MAX_PIECES, route_len [n], polys
+ * [n][SOGM_MAX_PIECES][max_faces][4] un-shrunk rows h.x + h3 <= 0, nfaces [n][SOGM_MAX_PIECES], seg_state
+ * [n][SOGM_MAX_PIECES] or NULL (-3 marks a segment "capacity exceeded", anything else leaves the verdict to the rules).
+ * Outputs: out_box [n][SOGM_MAX_PIECES][6] (llc, lhc), out_shrunk (as polys), out_seg_nfaces, out_seg_state
+ * [n][SOGM_MAX_PIECES] (1 valid, 0 invalid, -2 no such segment, -3 capacity) and sogm_corridor_generate's out_polys
+ * [n][SOGM_MAX_PIECES][max_faces][4], out_nfaces [n][SOGM_MAX_PIECES], out_npoly [n], out_goal [n][6].
+ * counters_of (may be NULL): the planner whose corridor_capacity / pieces_capacity counters the bookkeeping raises.
+ * Asynchronous on `stream` but for the copy of pp_host. */
+int sogm_corridor_rules_batched(sogm_planner *counters_of, const SogmPlannerParams *pp_host, const double *start_pva,
+                                const double *route, const int32_t *route_len, int route_cap, const double *polys,
+                                const int32_t *nfaces, const int32_t *seg_state, int n, int max_faces, double *out_box,
+                                double *out_shrunk, int32_t *out_seg_nfaces, int32_t *out_seg_state, double *out_polys,
+                                int32_t *out_nfaces, int32_t *out_npoly, double *out_goal, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,28 @@ def corridor_generate(spec, pp, grid, pose, stamp, start_pva, t_start, route):
     return {"npoly": n, "polys": polys, "nfaces": nf, "goal": goal}
 
 
+def corridor_rules(pp, start_pva, route, polys, nfaces, seg_state=None):
+    """The corridor rules around FIRI for injected polytopes: polys [16, max_faces, 4] un-shrunk, nfaces [16],
+    seg_state [16] or None (-3 marks a segment as over capacity)."""
+    s = np.ascontiguousarray(start_pva, np.float64).reshape(9)
+    route = np.ascontiguousarray(route, np.float64).reshape(-1, 6)
+    MP, MF = _abi.SOGM_MAX_PIECES, pp.max_faces
+    polys = np.ascontiguousarray(polys, np.float64).reshape(MP, MF, 4)
+    nfaces = np.ascontiguousarray(nfaces, np.int32).reshape(MP)
+    st = None if seg_state is None else np.ascontiguousarray(seg_state, np.int32).reshape(MP)
+    iptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    out = {"box": np.zeros((MP, 6)), "shrunk": np.zeros((MP, MF, 4)), "seg_nfaces": np.zeros(MP, np.int32),
+           "seg_state": np.zeros(MP, np.int32), "polys": np.zeros((MP, MF, 4)), "nfaces": np.zeros(MP, np.int32),
+           "goal": np.zeros(6)}
+    cap = np.zeros(2, np.int32)
+    out["npoly"] = int(lib().orc_corridor_rules(
+        C.byref(pp), dptr(s), dptr(route), route.shape[0], dptr(polys), iptr(nfaces), None if st is None else iptr(st),
+        dptr(out["box"]), dptr(out["shrunk"]), iptr(out["seg_nfaces"]), iptr(out["seg_state"]), dptr(out["polys"]),
+        iptr(out["nfaces"]), dptr(out["goal"]), iptr(cap)))
+    out["corridor_capacity"], out["pieces_capacity"] = int(cap[0]), int(cap[1])
+    return out
+
+
 # ---------------------------------------------------------------- QP
 def qp_assemble(start, goal, t_alloc, polys, nfaces, max_faces, vmax, amax, m_cap=8192):
     s = np.ascontiguousarray(start, np.float64).reshape(9)

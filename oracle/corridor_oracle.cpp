@@ -582,91 +582,46 @@ bool goalReachable(const double *poly, int m, const double start[3], double goal
   return false;
 }
 
-}  // namespace
-
-extern "C" {
-
-int orc_firi(const double *bd, int n_bd, const double *pc, int n_pc, const double a[3],
-             const double b[3], int iterations, double *hpoly, int max_faces, double r[3]) {
-  return firi(bd, n_bd, pc, n_pc, a, b, iterations, hpoly, max_faces, r);
-}
-
-void orc_lbfgs_set_max_iterations(int k) { g_lbfgs_max_iterations = k > 0 ? k : 0; }
-
-int orc_mvie(const double *hpoly, int m, double Rio[9], double p[3], double r[3]) {
-  M3 R;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = Rio[i * 3 + j];
-  const bool ok = maxVolInsEllipsoid(hpoly, m, R, p, r);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) Rio[i * 3 + j] = R[i][j];
-  return ok ? 1 : 0;
-}
-
-// Corridor stage.  out_polys: [SOGM_MAX_PIECES][max_faces][4]; out_nfaces [SOGM_MAX_PIECES];
-// returns the number of polytopes kept (0 = replan() returns false at this stage).
-int orc_corridor_generate(const SogmSpec *s, const SogmPlannerParams *pp, const float *grid,
-                          const float pose[3], double stamp, const double start_pva[9],
-                          double t_start, const double *route, int route_len, double *out_polys,
-                          int *out_nfaces, double out_goal[6]) {
-  const int MF = pp->max_faces;
-  for (int i = 0; i < SOGM_MAX_PIECES; ++i) out_nfaces[i] = 0;
-  for (int i = 0; i < 6; ++i) out_goal[i] = 0;
-  if (!pp->fake_planner && route_len < 2) return 0;  // baseline.cpp:304-307
-  if (route_len < 1) return 0;
-  const double *start_pos = start_pva;
-  std::vector<double> wpts((size_t)route_len * 3);
-  for (int i = 0; i < route_len; ++i) {
-    for (int k = 0; k < 3; ++k) wpts[(size_t)i * 3 + k] = route[(size_t)i * 6 + k];
-    if (wpts[(size_t)i * 3 + 2] < 0) wpts[(size_t)i * 3 + 2] = 0.1;
+// The local box of segment i (baseline.cpp:300-324): the two way-points (z < 0 lifted to 0.1) and llc / lhc
+void segmentBox(const SogmPlannerParams *pp, const double *start_pos, const double *route, int i, double w0[3],
+                double w1[3], double llc[3], double lhc[3]) {
+  for (int k = 0; k < 3; ++k) {
+    w0[k] = route[(size_t)i * 6 + k];
+    w1[k] = route[(size_t)(i + 1) * 6 + k];
   }
-  double lower[3] = {-4 + start_pos[0], -4 + start_pos[1], -1 + start_pos[2]};
+  if (w0[2] < 0) w0[2] = 0.1;
+  if (w1[2] < 0) w1[2] = 0.1;
+  double lower[3]  = {-4 + start_pos[0], -4 + start_pos[1], -1 + start_pos[2]};
   double higher[3] = {4 + start_pos[0], 4 + start_pos[1], 1 + start_pos[2]};
   if (lower[2] < 0) lower[2] = 0;
   if (higher[2] > 4) higher[2] = 4;
-  // getInitCorridor (baseline.cpp:127-141)
-  double bd[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 0};
-  std::vector<std::vector<double>> hPolys;
-  std::vector<double>              pc((size_t)pp->pc_capacity * 3);
-  for (int i = 0; i < route_len - 1 && (int)hPolys.size() < SOGM_MAX_PIECES; ++i) {
-    const double *w0 = &wpts[(size_t)i * 3], *w1 = &wpts[(size_t)(i + 1) * 3];
-    double        lhc[3], llc[3];
-    for (int k = 0; k < 3; ++k) {
-      lhc[k] = std::min(std::max(w0[k], w1[k]) + pp->init_range, higher[k]);
-      llc[k] = std::max(std::min(w0[k], w1[k]) - pp->init_range, lower[k]);
-    }
-    for (int k = 0; k < 3; ++k) {
-      bd[k * 4 + 3]       = -lhc[k];
-      bd[(k + 3) * 4 + 3] = llc[k];
-    }
-    const double t1 = t_start + i * pp->corridor_tau;
-    const double t2 = t_start + (i + 1) * pp->corridor_tau;
-    int n = orc_obstacle_points(s, grid, pose, stamp, t1, t2, llc, lhc, pc.data(), pp->pc_capacity);
-    // capacity limits (not in the reference, which grows its vectors): a corridor whose point list
-    // or face list would be truncated is unsafe, so it is treated as invalid (loop breaks)
-    if (n > pp->pc_capacity) break;
-    std::vector<double> hp((size_t)MF * 4, 0.0);
-    double              r[3] = {1, 1, 1};
-    int nf = firi(bd, 6, pc.data(), n, w0, w1, pp->firi_iterations, hp.data(), MF, r);
-    if (nf == -2 || nf > MF) break;  // capacity exceeded -> invalid
-    if (nf < 0) nf = 0;  // seed outside bd: hPoly stays empty (firi's return value is ignored)
-    // ShrinkCorridor(hPoly, path)
-    const double path[3] = {w1[0] - w0[0], w1[1] - w0[1], w1[2] - w0[2]};
-    for (int f = 0; f < nf; ++f) {
-      double      *h    = &hp[(size_t)f * 4];
-      const double nrm  = std::sqrt(dot3(h, h));
-      if (pp->fake_planner) {
-        // baseline_fake.cpp:211-223
-        const double pn = std::sqrt(dot3(path, path));
-        if (dot3(h, path) / nrm / pn > 0.8) continue;
-        if (std::fabs(h[2]) / nrm > 0.8) continue;
-      }
-      h[3] += nrm * pp->shrink_size;
-    }
-    if (!corridorValid(hp.data(), nf)) break;
-    hp.resize((size_t)nf * 4);
-    hPolys.push_back(hp);
+  for (int k = 0; k < 3; ++k) {
+    lhc[k] = std::min(std::max(w0[k], w1[k]) + pp->init_range, higher[k]);
+    llc[k] = std::max(std::min(w0[k], w1[k]) - pp->init_range, lower[k]);
   }
+}
+
+// ShrinkCorridor(hPoly, path)
+void shrinkCorridor(const SogmPlannerParams *pp, double *hp, int nf, const double w0[3], const double w1[3]) {
+  const double path[3] = {w1[0] - w0[0], w1[1] - w0[1], w1[2] - w0[2]};
+  for (int f = 0; f < nf; ++f) {
+    double      *h   = &hp[(size_t)f * 4];
+    const double nrm = std::sqrt(dot3(h, h));
+    if (pp->fake_planner) {
+      // baseline_fake.cpp:211-223
+      const double pn = std::sqrt(dot3(path, path));
+      if (dot3(h, path) / nrm / pn > 0.8) continue;
+      if (std::fabs(h[2]) / nrm > 0.8) continue;
+    }
+    h[3] += nrm * pp->shrink_size;
+  }
+}
+
+// What replan() does with the corridors kept up to the first invalid one: adjacent intersections, truncation, goal.
+int corridorBookkeeping(const SogmPlannerParams *pp, const double *start_pos, const double *route,
+                        std::vector<std::vector<double>> &hPolys, double *out_polys, int *out_nfaces,
+                        double out_goal[6]) {
+  const int MF = pp->max_faces;
   if (hPolys.empty()) return 0;  // the reference would index hPolys[0] (size_t underflow)
   // adjacent intersection (baseline.cpp:366-377 / baseline_fake.cpp:375-386)
   for (size_t i = 0; i + 1 < hPolys.size(); ++i) {
@@ -714,6 +669,111 @@ int orc_corridor_generate(const SogmSpec *s, const SogmPlannerParams *pp, const 
     out_goal[3 + k] = gvel[k];
   }
   return (int)hPolys.size();
+}
+
+}  // namespace
+
+extern "C" {
+
+int orc_firi(const double *bd, int n_bd, const double *pc, int n_pc, const double a[3],
+             const double b[3], int iterations, double *hpoly, int max_faces, double r[3]) {
+  return firi(bd, n_bd, pc, n_pc, a, b, iterations, hpoly, max_faces, r);
+}
+
+void orc_lbfgs_set_max_iterations(int k) { g_lbfgs_max_iterations = k > 0 ? k : 0; }
+
+int orc_mvie(const double *hpoly, int m, double Rio[9], double p[3], double r[3]) {
+  M3 R;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[i][j] = Rio[i * 3 + j];
+  const bool ok = maxVolInsEllipsoid(hpoly, m, R, p, r);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) Rio[i * 3 + j] = R[i][j];
+  return ok ? 1 : 0;
+}
+
+// Corridor stage.  out_polys: [SOGM_MAX_PIECES][max_faces][4]; out_nfaces [SOGM_MAX_PIECES];
+// returns the number of polytopes kept (0 = replan() returns false at this stage).
+int orc_corridor_generate(const SogmSpec *s, const SogmPlannerParams *pp, const float *grid,
+                          const float pose[3], double stamp, const double start_pva[9],
+                          double t_start, const double *route, int route_len, double *out_polys,
+                          int *out_nfaces, double out_goal[6]) {
+  const int MF = pp->max_faces;
+  for (int i = 0; i < SOGM_MAX_PIECES; ++i) out_nfaces[i] = 0;
+  for (int i = 0; i < 6; ++i) out_goal[i] = 0;
+  if (!pp->fake_planner && route_len < 2) return 0;  // baseline.cpp:304-307
+  if (route_len < 1) return 0;
+  // getInitCorridor (baseline.cpp:127-141)
+  double bd[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 0};
+  std::vector<std::vector<double>> hPolys;
+  std::vector<double>              pc((size_t)pp->pc_capacity * 3);
+  for (int i = 0; i < route_len - 1 && (int)hPolys.size() < SOGM_MAX_PIECES; ++i) {
+    double w0[3], w1[3], lhc[3], llc[3];
+    segmentBox(pp, start_pva, route, i, w0, w1, llc, lhc);
+    for (int k = 0; k < 3; ++k) {
+      bd[k * 4 + 3]       = -lhc[k];
+      bd[(k + 3) * 4 + 3] = llc[k];
+    }
+    const double t1 = t_start + i * pp->corridor_tau;
+    const double t2 = t_start + (i + 1) * pp->corridor_tau;
+    int n = orc_obstacle_points(s, grid, pose, stamp, t1, t2, llc, lhc, pc.data(), pp->pc_capacity);
+    // capacity limits (not in the reference, which grows its vectors): a corridor whose point list
+    // or face list would be truncated is unsafe, so it is treated as invalid (loop breaks)
+    if (n > pp->pc_capacity) break;
+    std::vector<double> hp((size_t)MF * 4, 0.0);
+    double              r[3] = {1, 1, 1};
+    int nf = firi(bd, 6, pc.data(), n, w0, w1, pp->firi_iterations, hp.data(), MF, r);
+    if (nf == -2 || nf > MF) break;  // capacity exceeded -> invalid
+    if (nf < 0) nf = 0;  // seed outside bd: hPoly stays empty (firi's return value is ignored)
+    shrinkCorridor(pp, hp.data(), nf, w0, w1);
+    if (!corridorValid(hp.data(), nf)) break;
+    hp.resize((size_t)nf * 4);
+    hPolys.push_back(hp);
+  }
+  return corridorBookkeeping(pp, start_pva, route, hPolys, out_polys, out_nfaces, out_goal);
+}
+
+// The same rules for polytopes the caller injects where FIRI's would be (test hook, the contract of the HIP side's
+// sogm_corridor_rules_batched).  polys [SOGM_MAX_PIECES][max_faces][4] un-shrunk, nfaces [SOGM_MAX_PIECES], seg_state
+// [SOGM_MAX_PIECES] or null (-3: "capacity exceeded" in that segment).  Per segment (every segment of the route, also
+// those past the `break`): out_box [..][6] = llc, lhc, out_shrunk, out_seg_nfaces, out_seg_state (1 valid, 0 invalid,
+// -2 no such segment, -3 capacity).  out_capacity[2] = {chain cut at a capacity segment, route longer than
+// SOGM_MAX_PIECES segments}.  Returns the number of polytopes kept.
+int orc_corridor_rules(const SogmPlannerParams *pp, const double start_pva[9], const double *route, int route_len,
+                       const double *polys, const int *nfaces, const int *seg_state, double *out_box,
+                       double *out_shrunk, int *out_seg_nfaces, int *out_seg_state, double *out_polys,
+                       int *out_nfaces, double out_goal[6], int out_capacity[2]) {
+  const int MF = pp->max_faces;
+  for (int i = 0; i < SOGM_MAX_PIECES; ++i) {
+    out_nfaces[i] = out_seg_nfaces[i] = 0;
+    out_seg_state[i]                  = -2;
+    for (int k = 0; k < 6; ++k) out_box[i * 6 + k] = 0;
+  }
+  for (int i = 0; i < 6; ++i) out_goal[i] = 0;
+  out_capacity[0] = out_capacity[1] = 0;
+  for (int i = 0; i < route_len - 1 && i < SOGM_MAX_PIECES; ++i) {
+    double w0[3], w1[3];
+    segmentBox(pp, start_pva, route, i, w0, w1, out_box + i * 6, out_box + i * 6 + 3);
+    const int nf = std::max(0, std::min(nfaces[i], MF));
+    double   *hp = out_shrunk + (size_t)i * MF * 4;
+    std::memcpy(hp, polys + (size_t)i * MF * 4, sizeof(double) * 4 * nf);
+    shrinkCorridor(pp, hp, nf, w0, w1);
+    out_seg_nfaces[i] = nf;
+    out_seg_state[i]  = seg_state && seg_state[i] == -3 ? -3 : (corridorValid(hp, nf) ? 1 : 0);
+  }
+  if (!pp->fake_planner && route_len < 2) return 0;  // baseline.cpp:304-307
+  if (route_len < 1) return 0;
+  std::vector<std::vector<double>> hPolys;
+  for (int i = 0; i < route_len - 1 && (int)hPolys.size() < SOGM_MAX_PIECES; ++i) {
+    if (out_seg_state[i] != 1) {
+      if (out_seg_state[i] == -3) out_capacity[0] = 1;
+      break;
+    }
+    const double *hp = out_shrunk + (size_t)i * MF * 4;
+    hPolys.emplace_back(hp, hp + (size_t)out_seg_nfaces[i] * 4);
+  }
+  if ((int)hPolys.size() == SOGM_MAX_PIECES && route_len - 1 > SOGM_MAX_PIECES) out_capacity[1] = 1;
+  return corridorBookkeeping(pp, start_pva, route, hPolys, out_polys, out_nfaces, out_goal);
 }
 
 }  // extern "C"

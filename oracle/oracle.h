@@ -127,6 +127,13 @@ int orc_osqp_dense(const double *P, const double *q, const double *A, const doub
                    int *iters_out);
 
 /* ---- a16: full replan for one agent ---- */
+/* The corridor rules around FIRI for injected polytopes (corridor_oracle.cpp; shares its rule code with
+ * orc_corridor_generate).  Returns the number of polytopes kept. */
+int orc_corridor_rules(const SogmPlannerParams *pp, const double start_pva[9], const double *route, int route_len,
+                       const double *polys, const int *nfaces, const int *seg_state, double *out_box,
+                       double *out_shrunk, int *out_seg_nfaces, int *out_seg_state, double *out_polys,
+                       int *out_nfaces, double out_goal[6], int out_capacity[2]);
+
 int orc_replan(const SogmSpec *s, const SogmAstarParams *ap, const SogmPlannerParams *pp,
                const SogmQpSettings *qs, const float *grid_vt, const float pose[3], double stamp,
                const double start_pva[9], const double goal[3], double t_start, int drone_id,

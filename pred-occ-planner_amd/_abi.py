@@ -201,6 +201,8 @@ PROTOTYPES = {
     "sogm_bezier_qp_solve": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_bezier_qp_solve_timed": (_i, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_linprog_batched": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sogm_corridor_rules_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp]),
     "sogm_replan": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_create": (_i, [C.POINTER(SogmGridMapParams), _i, _i, C.POINTER(_vp)]),
     "sogm_gridmap_destroy": (None, [_vp]),

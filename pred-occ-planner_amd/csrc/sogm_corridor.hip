@@ -1192,6 +1192,24 @@ __device__ inline void segment_box(const SogmPlannerParams &pp, const double *sp
   }
 }
 
+// ShrinkCorridor(hPoly, path) (baseline.cpp:206-213; baseline_fake.cpp:211-223 keeps the faces that look along the
+// path or along z): whole wave, one face per lane; w = the segment's two waypoints, poly = its nf planes (LDS).  The
+// caller synchronises the wave before it reads poly again.
+__device__ inline void shrink_corridor(const SogmPlannerParams &pp, const double *w, double *poly, int nf) {
+  const int    lane    = threadIdx.x & 63;
+  const double path[3] = {w[3] - w[0], w[4] - w[1], w[5] - w[2]};
+  for (int f = lane; f < nf; f += 64) {
+    double      *h   = poly + f * 4;
+    const double nrm = sogm_det::sqrt_rn(dot3(h, h));
+    if (pp.fake_planner) {
+      const double pn = sogm_det::sqrt_rn(dot3(path, path));
+      if (dot3(h, path) / nrm / pn > 0.8) continue;
+      if (dabs(h[2]) / nrm > 0.8) continue;
+    }
+    h[3] += nrm * pp.shrink_size;
+  }
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1673,19 +1691,7 @@ __device__ __forceinline__ void corridor_segment_body(const MapView &m, const So
     nf       = pp.max_faces;
     overflow = 1;
   }
-  {
-    const double path[3] = {s_w[3] - s_w[0], s_w[4] - s_w[1], s_w[5] - s_w[2]};
-    for (int f = lane; f < nf; f += 64) {  // one face per lane
-      double      *h   = s_poly + f * 4;
-      const double nrm = sogm_det::sqrt_rn(dot3(h, h));
-      if (pp.fake_planner) {
-        const double pn = sogm_det::sqrt_rn(dot3(path, path));
-        if (dot3(h, path) / nrm / pn > 0.8) continue;
-        if (dabs(h[2]) / nrm > 0.8) continue;
-      }
-      h[3] += nrm * pp.shrink_size;
-    }
-  }
+  shrink_corridor(pp, s_w, s_poly, nf);
   wave_lds_sync();
   const bool valid = corridorValidW(s_poly, nf, nullptr, 0, sc);  // whole wave
   {
@@ -1812,6 +1818,63 @@ __global__ __launch_bounds__(64) void k_corridor_finalize(
   int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
   SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
   corridor_finalize_body(pp, ws, io, blockIdx.x + agent0, sc);
+}
+
+// Test hook (sogm_corridor_rules_batched): the rules around FIRI for polytopes the caller injects, one wave per problem.
+// The wave lays a CorridorWorkspace view over the caller's arrays, then per segment runs segment_box, shrink_corridor and
+// corridorValidW as corridor_segment_body does after FIRI, and ends in corridor_finalize_body: the replan's device code,
+// with the caller's polytopes where FIRI's would be.
+#define RULES_MAX_FACES 64  // two joined polytopes + sdlp's plane 0 fit LP_MAX_ROWS
+struct CorridorRules {
+  const SogmPlannerParams *pp;         // [n]
+  const double            *polys_in;   // [n][SOGM_MAX_PIECES][max_faces][4] un-shrunk
+  const int32_t           *nfaces_in;  // [n][SOGM_MAX_PIECES]
+  const int32_t           *state_in;   // [n][SOGM_MAX_PIECES] or null; -3 = "capacity exceeded" in this segment
+  double                  *out_box;    // [n][SOGM_MAX_PIECES][6] llc, lhc
+};
+__global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, CorridorWorkspace ws, CorridorIO io) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double       *s_lp   = (double *)smem;
+  double       *s_rows = s_lp + LP_WORK_DOUBLES;
+  double       *s_poly = s_rows + LP_MAX_ROWS * 5;         // RULES_MAX_FACES * 4
+  double       *s_box  = s_poly + RULES_MAX_FACES * 4;     // 6
+  double       *s_w    = s_box + 6;                        // 6
+  int          *s_perm = (int *)(s_w + 6);                 // LP_MAX_ROWS
+  SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
+  const int               prob = blockIdx.x, lane = threadIdx.x;
+  const SogmPlannerParams pp   = cr.pp[prob];
+  const int               MF   = pp.max_faces;
+  const int               rl   = io.route_len[prob];
+  for (int seg = 0; seg < SOGM_MAX_PIECES; ++seg) {
+    const int slot = prob * SOGM_MAX_PIECES + seg;
+    if (seg >= rl - 1) {
+      if (lane == 0) {
+        ws.seg_state[slot]  = -2;  // no such segment
+        ws.seg_nfaces[slot] = 0;
+        for (int k = 0; k < 6; ++k) cr.out_box[slot * 6 + k] = 0.0;
+      }
+      continue;
+    }
+    int nf = cr.nfaces_in[slot];
+    nf     = nf < 0 ? 0 : (nf > MF ? MF : nf);
+    if (lane == 0) segment_box(pp, io.start_pva + prob * 9, io.route + (size_t)prob * io.route_cap * 6, seg, s_box, s_w);
+    for (int i = lane; i < nf * 4; i += 64) s_poly[i] = cr.polys_in[(size_t)slot * MF * 4 + i];
+    wave_lds_sync();
+    shrink_corridor(pp, s_w, s_poly, nf);
+    wave_lds_sync();
+    const bool valid = corridorValidW(s_poly, nf, nullptr, 0, sc);
+    double    *out   = ws.polys + (size_t)slot * MF * 4;
+    for (int i = lane; i < nf * 4; i += 64) out[i] = s_poly[i];
+    if (lane == 0) {
+      for (int k = 0; k < 6; ++k) cr.out_box[slot * 6 + k] = s_box[k];
+      ws.seg_nfaces[slot] = nf;
+      ws.seg_state[slot]  = cr.state_in && cr.state_in[slot] == -3 ? -3 : (valid ? 1 : 0);
+    }
+    wave_lds_sync();
+  }
+  __threadfence_block();  // the bookkeeping reads every lane's polytope rows back from memory
+  __syncthreads();
+  corridor_finalize_body(pp, ws, io, prob, sc);
 }
 
 // =================================================================================================
@@ -2516,6 +2579,46 @@ extern "C" int sogm_firi_batched(const double *bd, int n_bd, const double *pc_xy
                      pp, ws, fd);
   const hipError_t e = hipGetLastError();
   (void)hipFreeAsync(scratch, st);
+  SOGM_HIP_CHECK(e);
+  return SOGM_OK;
+}
+
+extern "C" int sogm_corridor_rules_batched(sogm_planner *counters_of, const SogmPlannerParams *pp_host,
+                                           const double *start_pva, const double *route, const int32_t *route_len,
+                                           int route_cap, const double *polys, const int32_t *nfaces,
+                                           const int32_t *seg_state, int n, int max_faces, double *out_box,
+                                           double *out_shrunk, int32_t *out_seg_nfaces, int32_t *out_seg_state,
+                                           double *out_polys, int32_t *out_nfaces, int32_t *out_npoly,
+                                           double *out_goal, void *stream) {
+  // route_cap > SOGM_MAX_PIECES: the rules read way-points 0 .. SOGM_MAX_PIECES at most, whatever route_len says
+  if (n < 0 || max_faces < 1 || max_faces > RULES_MAX_FACES || route_cap <= SOGM_MAX_PIECES ||
+      (n > 0 && (!pp_host || !start_pva || !route || !route_len || !polys || !nfaces || !out_box || !out_shrunk ||
+                 !out_seg_nfaces || !out_seg_state || !out_polys || !out_nfaces || !out_npoly || !out_goal)))
+    return SOGM_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i)
+    if (pp_host[i].max_faces != max_faces) return SOGM_ERR_INVALID_ARG;  // one stride for the whole batch
+  if (n == 0) return SOGM_OK;
+  hipStream_t        st   = (hipStream_t)stream;
+  SogmPlannerParams *d_pp = nullptr;
+  SOGM_HIP_CHECK(hipMallocAsync((void **)&d_pp, sizeof(SogmPlannerParams) * (size_t)n, st));
+  hipError_t e = hipMemcpyAsync(d_pp, pp_host, sizeof(SogmPlannerParams) * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // pp_host is the caller's pageable memory
+  if (e == hipSuccess) {
+    sogm::CorridorWorkspace ws{};
+    ws.polys      = out_shrunk;
+    ws.seg_nfaces = out_seg_nfaces;
+    ws.seg_state  = out_seg_state;
+    ws.counters   = counters_of ? counters_of->cw.counters : nullptr;
+    const sogm::CorridorIO    io{.start_pva = start_pva, .route = route, .route_len = route_len, .route_cap = route_cap,
+                                 .out_polys = out_polys, .out_nfaces = out_nfaces, .out_npoly = out_npoly,
+                                 .out_goal = out_goal};
+    const sogm::CorridorRules cr{d_pp, polys, nfaces, seg_state, out_box};
+    const size_t lds = sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5 + RULES_MAX_FACES * 4 + 12) +
+                       sizeof(int) * LP_MAX_ROWS;
+    hipLaunchKernelGGL(sogm::k_corridor_rules, dim3(n), dim3(64), lds, st, cr, ws, io);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(d_pp, st);
   SOGM_HIP_CHECK(e);
   return SOGM_OK;
 }

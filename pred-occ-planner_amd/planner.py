@@ -45,6 +45,28 @@ def firi_batched(bd, pc, pc_range, a, b, r=None, iterations=2, epsilon=1.0e-6, m
     return hp, nf, st, r
 
 
+def corridor_rules_batched(pps, start_pva, route, route_len, polys, nfaces, seg_state=None, planner=None):
+    """The corridor rules around FIRI (box, ShrinkCorridor, validity, intersection and goal scans) for n problems with
+    injected polytopes (sogm_corridor_rules_batched).  pps: n SogmPlannerParams with one max_faces; start_pva [n, 9],
+    route [n, route_cap, 6], route_len [n] int32, polys [n, 16, max_faces, 4], nfaces [n, 16] int32, seg_state [n, 16]
+    int32 or None — device tensors; planner: the SogmPlanner whose capacity counters are raised (or None).
+    Returns a dict of device tensors: box, shrunk, seg_nfaces, seg_state, polys, nfaces, npoly, goal."""
+    n, P, MF = int(polys.shape[0]), SOGM_MAX_PIECES, int(polys.shape[2])
+    dev = polys.device
+    pp = (_abi.SogmPlannerParams * max(n, 1))(*pps)
+    f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+    out = {"box": f64(n, P, 6), "shrunk": f64(n, P, MF, 4), "seg_nfaces": i32(n, P), "seg_state": i32(n, P),
+           "polys": f64(n, P, MF, 4), "nfaces": i32(n, P), "npoly": i32(n), "goal": f64(n, 6)}
+    check(lib().sogm_corridor_rules_batched(
+        planner._p if planner is not None else None, pp, start_pva.data_ptr(), route.data_ptr(), route_len.data_ptr(),
+        int(route.shape[1]), polys.data_ptr(), nfaces.data_ptr(), seg_state.data_ptr() if seg_state is not None else None,
+        n, MF, out["box"].data_ptr(), out["shrunk"].data_ptr(), out["seg_nfaces"].data_ptr(), out["seg_state"].data_ptr(),
+        out["polys"].data_ptr(), out["nfaces"].data_ptr(), out["npoly"].data_ptr(), out["goal"].data_ptr(), _stream()),
+        "sogm_corridor_rules_batched")
+    return out
+
+
 class SogmPlanner:
     def __init__(self, sogm_map, astar_params, planner_params, qp_settings):
         self.map = sogm_map

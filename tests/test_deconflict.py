@@ -48,8 +48,10 @@ def test_oracle_crossing_trajectories_are_unsafe(pop, orc):
     assert orc.safe_after_opt(c0, 6, recs, 1, 0, t_now) == 1
     late = pop.scene.straight_records(sc, speed=1.5, n_pieces=6, piece_dur=0.5, t_start=t_now + 1.0)
     assert orc.safe_after_opt(c0, 6, late, 8, 0, t_now) == 1
-    # once the others are on their last piece only 5 control points remain: a short stub far away
-    assert orc.safe_after_opt(c0, 6, recs, 8, 0, t_now + 2.8) in (0, 1)
+    # once the others are on their last piece only 5 control points of each remain; the second reading
+    # (tests/golden/make_safe_after_opt_fixture.py: piece 5 of every record, 5 points each) finds six of the seven stubs
+    # separable by > 0.25 m and the antipodal agent's stub ON the candidate's own line, inside its extent: unsafe
+    assert orc.safe_after_opt(c0, 6, recs, 8, 0, t_now + 2.8) == 0
 
 
 @pytest.mark.gpu
@@ -80,9 +82,13 @@ def test_safe_after_opt_gpu_matches_oracle(pop, orc):
         for k in range(5 * M):
             cpts[a, k * 3:(k + 1) * 3] = sc["starts"][a] + d * 0.25 * k + rng.normal(0, 0.02, 3)
     t_now = np.full(A, t0) + rng.uniform(0, 0.3, A)
+    # ego ids from a shuffled table: agent a's own record sits at place ego[a] != a, a foreign one (starting where the
+    # candidate starts) at place a — skipping by place instead of by drone id changes verdicts
+    ego = np.array([5, 0, 7, 1, 9, 11, 2, 10, 4, 3, 8, 6], np.int32)
+    assert sorted(ego) == list(range(A)) and not np.any(ego == np.arange(A))
     got = P.isSafeAfterOpt(sogm._dev(cpts, np.float64), sogm._dev(npoly, np.int32), sogm._dev(recs), A,
-                           sogm._dev(sc["ego_ids"], np.int32), sogm._dev(t_now, np.float64)).cpu().numpy()
-    want = np.array([orc.safe_after_opt(cpts[a], int(npoly[a]), recs, A, a, t_now[a]) if npoly[a] > 0 else 1
+                           sogm._dev(ego, np.int32), sogm._dev(t_now, np.float64)).cpu().numpy()
+    want = np.array([orc.safe_after_opt(cpts[a], int(npoly[a]), recs, A, int(ego[a]), t_now[a]) if npoly[a] > 0 else 1
                      for a in range(A)])
     assert np.array_equal(got, want), (got, want)
     assert 0 < want.sum() < A
