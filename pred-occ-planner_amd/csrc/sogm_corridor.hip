@@ -24,440 +24,14 @@
 #include <cfloat>
 
 #include "../../include/sogm_detmath.h"
+#include "sogm_lp.hpp"
 #include "sogm_planner.hpp"
 
 namespace sogm {
 namespace {
 
-#define LP_MAX_ROWS 153  // planes of one LP incl. sdlp's plane 0: 2 * max_faces(64) + 1, or 144 deconfliction rows + 8 box rows + 1; keeps the segment kernel at 4 workgroups per CU (LDS <= 40 KB)
-#define LP_WORK_DOUBLES (14 * LP_MAX_ROWS)  // planes of the four recursion levels: (5 + 4 + 3 + 2) per row
-#define FIRI_MAX_H 128  // planes selected before truncation to max_faces
-
 __device__ inline double dot3(const double *a, const double *b) {
   return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-__device__ inline double dabs(double x) { return x < 0 ? -x : x; }
-
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---------------------------------------------------------------------------------------------
-// sdlp::linprog<d> (traj_utils/include/traj_utils/sdlp.hpp:709-787) executed by a whole wave.
-//
-// Hohmeyer's projective Seidel LP: planes carry d+1 homogeneous coefficients, plane 0 is "x_d >= 0", the
-// objective is n.x / d.x; a violated plane recurses into the problem on that plane with the coordinate of its
-// largest coefficient eliminated (linfracprog<d>, :526-662), the 1-D problem is a wedge on the projective line
-// (wedge / lp_base_case, :260-446).  All 64 lanes call with identical arguments; the arithmetic and every
-// decision are those of the sequential code (same operation order as oracle/lp_oracle.cpp, bit for bit):
-//   * sdlp's doubly linked list (next/prev, shared by all recursion levels) is the array ord[position] ->
-//     plane; move_to_front (:132-150) of the plane at position q rotates ord[1..q] by one, and "continue with
-//     the successor of the returned plane" is position q + 1 in either of its branches;
-//   * opt does not change between two violated planes, so "the next violated plane in list order" is found 64
-//     positions at a time with a ballot (first set bit = the sequential scan's hit); the same holds for the
-//     wedge, whose state (cw, ccw) only changes at an "offensive" plane;
-//   * the planes in front of the violated one are projected one per lane (:604-618);
-//   * objective vectors and optima live in registers (compile-time indices, select chains for imax).
-// Deviation from the reference (documented in DESIGN.md): the insertion order is a fixed LCG Fisher-Yates
-// permutation of the row count instead of sdlp's process-global mt19937_64 (call-history dependent).
-// ---------------------------------------------------------------------------------------------
-#define SDLP_EPS 1.0e-12
-enum { SDLP_MINIMUM = 0, SDLP_INFEASIBLE = 1, SDLP_UNBOUNDED = 2, SDLP_AMBIGUOUS = 3 };
-
-// lp_no_con<d> (:97-129) incl. unit<d> (:76-94)
-template <int D>
-__device__ __forceinline__ int lp_no_con(const double (&nv)[D + 1], const double (&dv)[D + 1],
-                                         double (&opt)[D + 1]) {
-  double n_dot_d = 0.0, d_dot_d = 0.0;
-#pragma unroll
-  for (int i = 0; i <= D; ++i) {
-    n_dot_d += nv[i] * dv[i];
-    d_dot_d += dv[i] * dv[i];
-  }
-  if (d_dot_d < SDLP_EPS * SDLP_EPS) {
-    n_dot_d = 0.0;
-    d_dot_d = 1.0;
-  }
-#pragma unroll
-  for (int i = 0; i <= D; ++i) opt[i] = -nv[i] + dv[i] * n_dot_d / d_dot_d;
-  double mag = 0.0;
-#pragma unroll
-  for (int i = 0; i <= D; ++i) mag += opt[i] * opt[i];
-  if (mag < (D + 1) * SDLP_EPS * SDLP_EPS) {
-    opt[D] = 1.0;
-    return SDLP_AMBIGUOUS;
-  }
-  mag = 1.0 / sogm_det::sqrt_rn(mag);
-#pragma unroll
-  for (int i = 0; i <= D; ++i) opt[i] *= mag;
-  return SDLP_MINIMUM;
-}
-
-// move_to_front (:132-150) on the position array: the plane at position q goes to position 1
-__device__ __forceinline__ void lp_move_to_front(int *ord, int q) {
-  if (q > 1) {  // q == 0: plane 0; q == 1: already next[0]
-    const int lane = threadIdx.x & 63;
-    const int iq   = ord[q];
-    const int r0 = 1 + lane, r1 = 65 + lane, r2 = 129 + lane;  // LP_MAX_ROWS <= 193 positions
-    const int v0 = r0 < q ? ord[r0] : 0;
-    const int v1 = r1 < q ? ord[r1] : 0;
-    const int v2 = r2 < q ? ord[r2] : 0;
-    wave_lds_sync();
-    if (r0 < q) ord[r0 + 1] = v0;
-    if (r1 < q) ord[r1 + 1] = v1;
-    if (r2 < q) ord[r2 + 1] = v2;
-    if (lane == 0) ord[1] = iq;
-    wave_lds_sync();
-  }
-}
-
-__device__ __forceinline__ double dot2(const double a[2], const double b[2]) { return a[0] * b[0] + a[1] * b[1]; }
-__device__ __forceinline__ double cross2(const double a[2], const double b[2]) { return a[0] * b[1] - a[1] * b[0]; }
-// unit2 (:61-73); b may alias a
-__device__ __forceinline__ bool unit2(const double a[2], double b[2]) {
-  const double a0 = a[0], a1 = a[1];
-  const double mag = sogm_det::sqrt_rn(a0 * a0 + a1 * a1);
-  if (mag < 2.0 * SDLP_EPS) return true;
-  b[0] = a0 / mag;
-  b[1] = a1 / mag;
-  return false;
-}
-
-// lp_min_lin_rat (:152-258)
-__device__ __forceinline__ void lp_min_lin_rat(bool degen, const double cw[2], const double ccw[2],
-                                               const double nv[2], const double dv[2], double opt[2]) {
-  const double d_cw = dot2(cw, dv), d_ccw = dot2(ccw, dv);
-  const double n_cw = dot2(cw, nv), n_ccw = dot2(ccw, nv);
-  bool take_cw;
-  if (degen) {
-    take_cw = n_cw / d_cw < n_ccw / d_ccw;
-  } else if (dabs(d_cw) > 2.0 * SDLP_EPS && dabs(d_ccw) > 2.0 * SDLP_EPS) {
-    if (d_cw * d_ccw > 0.0) {
-      take_cw = n_cw / d_cw < n_ccw / d_ccw;
-    } else {
-      if (d_cw > 0.0) {
-        opt[0] = -dv[1];
-        opt[1] = dv[0];
-      } else {
-        opt[0] = dv[1];
-        opt[1] = -dv[0];
-      }
-      return;
-    }
-  } else if (dabs(d_cw) > 2.0 * SDLP_EPS) {
-    take_cw = n_ccw * d_cw > 0.0;
-  } else if (dabs(d_ccw) > 2.0 * SDLP_EPS) {
-    take_cw = !(n_cw * d_ccw > 2.0 * SDLP_EPS);
-  } else {
-    take_cw = cross2(dv, nv) > 0.0;
-  }
-  opt[0] = take_cw ? cw[0] : ccw[0];
-  opt[1] = take_cw ? cw[1] : ccw[1];
-}
-
-// first position in [p, count) whose lane predicate holds (-1 if none); pred(r) is evaluated one position per lane
-template <class F>
-__device__ __forceinline__ int lp_first(int p, int count, F pred) {
-  const int lane = threadIdx.x & 63;
-  for (int base = p; base < count; base += 64) {
-    const int                r  = base + lane;
-    const bool               ok = r < count ? pred(r) : false;
-    const unsigned long long mk = __ballot(ok);
-    if (mk) return base + __ffsll((long long)mk) - 1;
-  }
-  return -1;
-}
-
-template <int D>
-struct Lfp {
-  // halves: LDS, stride D+1, indexed by plane; the list is ord[0..count).  work: planes of the lower levels.
-  __device__ __forceinline__ static int solve(const double *halves, int count, const double (&nv_in)[D + 1],
-                              const double (&dv_in)[D + 1], double (&opt)[D + 1], double *work, int *ord) {
-    const int lane = threadIdx.x & 63;
-    // the objective by value: a select between two entries of the CALLER's array would be folded into an
-    // indexed load before inlining and demote that array to scratch memory
-    double nv[D + 1], dv[D + 1];
-#pragma unroll
-    for (int j = 0; j <= D; ++j) {
-      nv[j] = nv_in[j];
-      dv[j] = dv_in[j];
-    }
-    double    val  = 0.0;
-#pragma unroll
-    for (int j = 0; j <= D; ++j) val += dv[j] * dv[j];
-    const bool d_vec_zero = val < (D + 1) * SDLP_EPS * SDLP_EPS;
-    int        status     = lp_no_con<D>(nv, dv, opt);
-    if (count <= 0) return status;
-    double *new_halves = work;  // [LP_MAX_ROWS][D]
-    int     p          = 0;
-    while (p < count) {
-      const int q = lp_first(p, count, [&](int r) {
-        const double *pl = halves + ord[r] * (D + 1);
-        double        v  = 0.0;
-#pragma unroll
-        for (int j = 0; j <= D; ++j) v += opt[j] * pl[j];
-        return v < -(D + 1) * SDLP_EPS;
-      });
-      if (q < 0) break;
-      const int     i  = ord[q];
-      const double *pi = halves + i * (D + 1);
-      double        pv[D + 1];
-#pragma unroll
-      for (int j = 0; j <= D; ++j) pv[j] = pi[j];
-      int    imax = 0;  // findimax (:449-464); the imax-th entries of the plane and of both objective vectors
-      double rmax = dabs(pv[0]), pmax = pv[0], nmax = nv[0], dmax = dv[0];  // ride along (no indexed access)
-#pragma unroll
-      for (int j = 1; j <= D; ++j) {
-        const double ab = dabs(pv[j]);
-        if (ab > rmax) {
-          imax = j;
-          rmax = ab;
-          pmax = pv[j];
-          nmax = nv[j];
-          dmax = dv[j];
-        }
-      }
-      if (i != 0) {  // project the planes in front of i (:604-618), one per lane
-        const double fac = 1.0 / pmax;
-        for (int r = lane; r < q; r += 64) {
-          const int     j    = ord[r];
-          const double *old  = halves + j * (D + 1);
-          const double  crit = old[imax] * fac;
-          double       *np   = new_halves + j * D;
-#pragma unroll
-          for (int l = 0; l < D; ++l) {
-            const int k = l < imax ? l : l + 1;
-            np[l]       = old[k] - (l < imax ? pv[l] : pv[l + 1]) * crit;
-          }
-        }
-      }
-      wave_lds_sync();
-      double nn[D], nd[D];
-      if (d_vec_zero) {  // vector_down (:485-507)
-        double ve = 0.0, ee = 0.0;
-#pragma unroll
-        for (int j = 0; j <= D; ++j) {
-          ve += nv[j] * pv[j];
-          ee += pv[j] * pv[j];
-        }
-        const double fac = ve / ee;
-#pragma unroll
-        for (int l = 0; l < D; ++l) {
-          nn[l] = (l < imax ? nv[l] : nv[l + 1]) - (l < imax ? pv[l] : pv[l + 1]) * fac;
-          nd[l] = 0.0;
-        }
-      } else {  // plane_down (:509-524) for numerator and denominator
-        const double critn = nmax / pmax;
-        const double critd = dmax / pmax;
-#pragma unroll
-        for (int l = 0; l < D; ++l) {
-          const double e = l < imax ? pv[l] : pv[l + 1];
-          nn[l]          = (l < imax ? nv[l] : nv[l + 1]) - e * critn;
-          nd[l]          = (l < imax ? dv[l] : dv[l + 1]) - e * critd;
-        }
-      }
-      double nopt[D];
-      status = Lfp<D - 1>::solve(new_halves, q, nn, nd, nopt, work + LP_MAX_ROWS * D, ord);
-      if (status == SDLP_INFEASIBLE) return status;
-      // vector_up (:466-483) then the inline unit (:641-651)
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j <= D; ++j) {
-        const double lo = nopt[j < D ? j : 0];       // low_vector[j]     (used when j < imax)
-        const double hi = nopt[j > 0 ? j - 1 : 0];   // low_vector[j - 1] (used when j > imax)
-        const double v  = j < imax ? lo : hi;
-        const double na = acc - pv[j] * v;
-        acc             = j != imax ? na : acc;
-        opt[j]          = v;
-      }
-      acc /= pmax;
-#pragma unroll
-      for (int j = 0; j <= D; ++j) opt[j] = j == imax ? acc : opt[j];
-      double mag = 0.0;
-#pragma unroll
-      for (int j = 0; j <= D; ++j) mag += opt[j] * opt[j];
-      mag = 1.0 / sogm_det::sqrt_rn(mag);
-#pragma unroll
-      for (int j = 0; j <= D; ++j) opt[j] *= mag;
-      lp_move_to_front(ord, q);
-      p = q + 1;
-    }
-    return status;
-  }
-};
-
-// linfracprog<1> (:664-684) = lp_base_case (:378-446) over wedge (:260-375); halves stride 2
-template <>
-struct Lfp<1> {
-  __device__ __forceinline__ static int solve(const double *halves, int count, const double (&nv)[2], const double (&dv)[2],
-                              double (&opt)[2], double *, int *ord) {
-    if (count <= 0) return lp_no_con<1>(nv, dv, opt);
-    const double e2 = 2.0 * SDLP_EPS;
-    double       cw[2], ccw[2];
-    bool         degen = false;
-    {  // the first plane of the list that is not (numerically) zero spans the initial half circle
-      const int q0 = lp_first(0, count, [&](int r) {
-        const double *h = halves + 2 * ord[r];
-        return !(sogm_det::sqrt_rn(h[0] * h[0] + h[1] * h[1]) < e2);
-      });
-      if (q0 < 0) return lp_no_con<1>(nv, dv, opt);  // wedge: UNBOUNDED
-      const double *h = halves + 2 * ord[q0];
-      unit2(h, ccw);
-      cw[0]  = ccw[1];
-      cw[1]  = -ccw[0];
-      ccw[0] = -cw[0];
-      ccw[1] = -cw[1];
-    }
-    int p = 0;
-    while (p < count) {
-      const int q = lp_first(p, count, [&](int r) {
-        const double *h    = halves + 2 * ord[r];
-        const double  d_cw = dot2(cw, h), d_ccw = dot2(ccw, h);
-        if (d_ccw >= e2) return d_cw <= -e2;
-        if (d_cw >= e2) return d_ccw <= -e2;
-        if (d_ccw <= -e2 && d_cw <= -e2) return true;
-        return d_cw <= -e2 || d_ccw <= -e2 || cross2(cw, h) < 0.0;
-      });
-      if (q < 0) break;
-      const double h[2]  = {halves[2 * ord[q]], halves[2 * ord[q] + 1]};
-      const double d_cw = dot2(cw, h), d_ccw = dot2(ccw, h);
-      if (d_ccw >= e2) {
-        cw[0] = h[1];
-        cw[1] = -h[0];
-        unit2(cw, cw);
-      } else if (d_cw >= e2) {
-        ccw[0] = -h[1];
-        ccw[1] = h[0];
-        unit2(ccw, ccw);
-      } else if (d_ccw <= -e2 && d_cw <= -e2) {
-        return SDLP_INFEASIBLE;
-      } else {
-        if (d_cw <= -e2)
-          unit2(ccw, cw);
-        else if (d_ccw <= -e2)
-          unit2(cw, ccw);
-        degen = true;
-      }
-      lp_move_to_front(ord, q);
-      p = q + 1;
-      if (degen) break;
-    }
-    if (degen) {
-      while (p < count) {
-        const int q = lp_first(p, count, [&](int r) {
-          const double *h = halves + 2 * ord[r];
-          return dot2(cw, h) < -e2 || dot2(ccw, h) < -e2;
-        });
-        if (q < 0) break;
-        const double h[2] = {halves[2 * ord[q]], halves[2 * ord[q] + 1]};
-        const double d_cw = dot2(cw, h), d_ccw = dot2(ccw, h);
-        if (d_cw < -e2) {
-          if (d_ccw < -e2) return SDLP_INFEASIBLE;
-          cw[0] = ccw[0];
-          cw[1] = ccw[1];
-        } else {
-          ccw[0] = cw[0];
-          ccw[1] = cw[1];
-        }
-        p = q + 1;
-      }
-    }
-    // lp_base_case (:403-445)
-    if (dabs(cross2(nv, dv)) < 2.0 * SDLP_EPS * SDLP_EPS) {
-      if (dot2(nv, nv) < 2.0 * SDLP_EPS * SDLP_EPS || dot2(dv, dv) > 2.0 * SDLP_EPS * SDLP_EPS) {
-        opt[0] = cw[0];
-        opt[1] = cw[1];
-        return SDLP_AMBIGUOUS;
-      }
-      if (!degen && cross2(cw, nv) <= 0.0 && cross2(nv, ccw) <= 0.0) {
-        opt[0] = -nv[0];
-        opt[1] = -nv[1];
-      } else if (dot2(nv, cw) > dot2(nv, ccw)) {
-        opt[0] = ccw[0];
-        opt[1] = ccw[1];
-      } else {
-        opt[0] = cw[0];
-        opt[1] = cw[1];
-      }
-      return SDLP_MINIMUM;
-    }
-    lp_min_lin_rat(degen, cw, ccw, nv, dv, opt);
-    return SDLP_MINIMUM;
-  }
-};
-
-// linprog<D> (:709-787): min c^T x s.t. A[i][0..D) x <= rhs[i]  (A row-major, stride D, in LDS).
-// work: LP_WORK_DOUBLES doubles (LDS), ord: LP_MAX_ROWS ints (LDS); rows < LP_MAX_ROWS.
-// Returns +inf infeasible, -inf unbounded / optimum at infinity, else the minimum.  Whole wave.
-template <int D>
-__device__ __forceinline__ double linprog_wave(const double *c, int rows, const double *A, const double *rhsv,
-                                               double *x, double *work, int *ord) {
-  const int lane = threadIdx.x & 63;
-  for (int j = 0; j < D; ++j) x[j] = 0.0;
-  if (rows <= 0) {
-    double mx = 0;
-    for (int j = 0; j < D; ++j) mx = dabs(c[j]) > mx ? dabs(c[j]) : mx;
-    return mx > 0.0 ? -INFINITY : 0.0;
-  }
-  const int m      = rows + 1;
-  double   *halves = work;  // [LP_MAX_ROWS][D + 1]
-  if (lane == 0) {
-    ord[0] = 0;
-    for (int i = 0; i < rows; ++i) ord[1 + i] = i + 1;
-    unsigned long long s = 0x9E3779B97F4A7C15ULL;  // the fixed insertion order (oracle: fixed_permutation)
-    for (int i = rows - 1; i > 0; --i) {
-      s           = s * 6364136223846793005ULL + 1442695040888963407ULL;
-      const int j = (int)((s >> 33) % (unsigned long long)(i + 1));
-      const int t = ord[1 + i];
-      ord[1 + i]  = ord[1 + j];
-      ord[1 + j]  = t;
-    }
-    for (int j = 0; j < D; ++j) halves[j] = 0.0;
-    halves[D] = 1.0;
-  }
-  for (int i = 1 + lane; i < m; i += 64) {  // halves.col(i) = (-A_i, b_i) normalised (:737-740)
-    const double *src = A + (i - 1) * D;
-    double        h[D + 1];
-#pragma unroll
-    for (int j = 0; j < D; ++j) h[j] = -src[j];
-    h[D]      = rhsv[i - 1];
-    double nn = 0.0;
-#pragma unroll
-    for (int j = 0; j <= D; ++j) nn += h[j] * h[j];
-    nn          = sogm_det::sqrt_rn(nn);
-    double *dst = halves + i * (D + 1);
-#pragma unroll
-    for (int j = 0; j <= D; ++j) dst[j] = nn > 0.0 ? h[j] / nn : h[j];
-  }
-  wave_lds_sync();
-  double nv[D + 1], dv[D + 1], opt[D + 1];
-#pragma unroll
-  for (int j = 0; j < D; ++j) {
-    nv[j] = c[j];
-    dv[j] = 0.0;
-  }
-  nv[D] = 0.0;
-  dv[D] = 1.0;
-  const int status = Lfp<D>::solve(halves, m, nv, dv, opt, work + LP_MAX_ROWS * (D + 1), ord);
-  double    minimum = INFINITY;
-  if (status != SDLP_INFEASIBLE) {
-    if (opt[D] != 0.0 && status != SDLP_UNBOUNDED) {
-      minimum = 0.0;
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        x[j] = opt[j] / opt[D];
-        minimum += c[j] * x[j];
-      }
-    }
-    if (opt[D] == 0.0 || status == SDLP_UNBOUNDED) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) x[j] = opt[j];
-      minimum = -INFINITY;
-    }
-  }
-  return minimum;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -720,7 +294,7 @@ __device__ __forceinline__ int lineSearchLO(const MvieData &D, double *x, double
 // L-BFGS (lbfgs.hpp lbfgs_optimize with the parameters of firi.hpp:191-199), executed replicated
 // by every lane of the wave (uniform control flow; only costMVIE is lane-parallel).  Everything that
 // is indexed dynamically lives in LDS with lane 0 as the single writer, so nothing spills to scratch:
-//   lm[0..162) = s history, lm[162..324) = y history
+//   lm = SegmentLds's `lm`: s history [18][9], then y history [18][9]
 #define LBFGS_FENCE()                                        \
   do {                                                       \
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   \
@@ -953,23 +527,13 @@ __device__ void jacobiEig3(double S[3][3], double V[3][3], double w[3]) {
   for (int i = 0; i < 3; ++i) w[i] = S[i][i];
 }
 
-// LDS scratch handed to lane-0 solvers
-struct SolverScratch {
-  double *lp_work;  // LP_WORK_DOUBLES
-  int    *perm;     // LP_MAX_ROWS
-  double *rows;     // LP_MAX_ROWS * 5   (normalised Alp rows + blp / mvie A)
-  double *lm;       // 2 * 18 * 9
-};
-
 // maxVolInsEllipsoid (firi.hpp:146-236); hPoly: M x 4 in LDS.  Called by the WHOLE wave: the
 // deepest-point LP and the final 3x3 SVD run on lane 0, the L-BFGS runs replicated on all lanes
 // with the cost evaluated one face per lane.  R, p, r are meaningful on lane 0 only.
 __device__ __forceinline__ bool maxVolInsEllipsoid(const double *hPoly, int M, double R[3][3], double p[3],
-                                   double r[3], const SolverScratch &sc, long long *dbg) {
+                                   double r[3], const LpScratch &sc, double *lm, double *sh, long long *dbg) {
   const int lane = threadIdx.x & 63;
-  double   *Alp  = sc.rows;                    // M x 4
-  double   *blp  = sc.rows + LP_MAX_ROWS * 4;  // M
-  double   *sh   = sc.lm + 2 * 18 * 9;         // 16 doubles of hand-off space after the history
+  double   *Alp = sc.A(), *blp = sc.b();  // M x 4 (normalised rows, then the MVIE's A), M; lm, sh: SegmentLds's lm and handoff
   // deepest interior point: rows one per lane, LP solved by the whole wave
   for (int i = lane; i < M; i += 64) {
     const double *h  = hPoly + i * 4;
@@ -981,7 +545,7 @@ __device__ __forceinline__ bool maxVolInsEllipsoid(const double *hPoly, int M, d
   wave_lds_sync();
   const double clp[4] = {0, 0, 0, -1.0};
   double       xlp[4];
-  const double maxdepth = -linprog_wave<4>(clp, M, Alp, blp, xlp, sc.lp_work, sc.perm);
+  const double maxdepth = -linprog_wave<4>(clp, M, Alp, blp, xlp, sc.work, sc.perm);
   wave_lds_sync();
   if (lane == 0) {
     const bool   ok = !(!(maxdepth > 0.0) || maxdepth == INFINITY || maxdepth == -INFINITY);
@@ -1040,7 +604,7 @@ __device__ __forceinline__ bool maxVolInsEllipsoid(const double *hPoly, int M, d
 #ifdef SOGM_PROFILE_MVIE
   const long long tcl0 = clock64();
 #endif
-  const int       ret = lbfgsMVIE(D, x, sc.lm, sc.lp_work, &n_it, &n_ev);  // LP work area: idle by now
+  const int       ret = lbfgsMVIE(D, x, lm, sc.work, &n_it, &n_ev);  // LP work area: idle by now
   if (dbg && lane == 0) {
     dbg[3] = n_it;
     dbg[4] = n_ev;
@@ -1105,12 +669,11 @@ __device__ __forceinline__ bool maxVolInsEllipsoid(const double *hPoly, int M, d
 
 // checkCorridorValidity (baseline.cpp:191-204; poly rows h0 x + h1 y + h2 z + h3 <= 0) and
 // checkGoalReachability (baseline.cpp:143-182), executed by the whole wave (linprog_wave)
-__device__ bool corridorValidW(const double *polyA, int mA, const double *polyB, int mB,
-                               const SolverScratch &sc) {
+__device__ bool corridorValidW(const double *polyA, int mA, const double *polyB, int mB, const LpScratch &sc) {
   const int    lane = threadIdx.x & 63;
   const double c[3] = {0, 0, 0};
   double       x[3];
-  double      *A = sc.rows, *b = sc.rows + LP_MAX_ROWS * 4;
+  double      *A = sc.A(), *b = sc.b();
   for (int i = lane; i < mA + mB; i += 64) {
     const double *h = i < mA ? polyA + i * 4 : polyB + (i - mA) * 4;
     A[i * 3 + 0]    = h[0];
@@ -1119,12 +682,11 @@ __device__ bool corridorValidW(const double *polyA, int mA, const double *polyB,
     b[i]            = -h[3];
   }
   wave_lds_sync();
-  const double v = linprog_wave<3>(c, mA + mB, A, b, x, sc.lp_work, sc.perm);
+  const double v = linprog_wave<3>(c, mA + mB, A, b, x, sc.work, sc.perm);
   wave_lds_sync();
   return !(v == INFINITY || v == -INFINITY);
 }
-__device__ bool goalReachableW(const double *poly, int m, const double *start, double *goal,
-                               const SolverScratch &sc) {
+__device__ bool goalReachableW(const double *poly, int m, const double *start, double *goal, const LpScratch &sc) {
   const int lane = threadIdx.x & 63;
   if (m <= 0) return true;
   double mx = -INFINITY;
@@ -1134,7 +696,7 @@ __device__ bool goalReachableW(const double *poly, int m, const double *start, d
     mx              = v > mx ? v : mx;
   }
   if (mx <= 0) return true;
-  double *A = sc.rows, *b = sc.rows + LP_MAX_ROWS * 4;
+  double *A = sc.A(), *b = sc.b();
   for (int i = lane; i < m; i += 64) {
     const double *h = poly + i * 4;
     A[i * 3 + 0]    = h[0];
@@ -1145,10 +707,10 @@ __device__ bool goalReachableW(const double *poly, int m, const double *start, d
   wave_lds_sync();
   double c[3] = {-goal[0] + start[0], -goal[1] + start[1], -goal[2] + start[2]};
   double gmax[3], gmin[3];
-  linprog_wave<3>(c, m, A, b, gmax, sc.lp_work, sc.perm);
+  linprog_wave<3>(c, m, A, b, gmax, sc.work, sc.perm);
   wave_lds_sync();
   for (int j = 0; j < 3; ++j) c[j] = goal[j] - start[j];
-  linprog_wave<3>(c, m, A, b, gmin, sc.lp_work, sc.perm);
+  linprog_wave<3>(c, m, A, b, gmin, sc.work, sc.perm);
   wave_lds_sync();
   for (int j = 0; j < 3; ++j) goal[j] = 0.5 * (gmax[j] + gmin[j]);
   return false;
@@ -1343,9 +905,6 @@ __global__ __launch_bounds__(256) void k_corridor_points(MapView m, SogmPlannerP
   corridor_points_body<4>(m, pp, ws, io, blockIdx.y + agent0, blockIdx.x);
 }
 
-namespace {
-}  // namespace
-
 // =================================================================================================
 // Kernel A: one workgroup per (segment, agent)
 // =================================================================================================
@@ -1368,9 +927,6 @@ struct FiriDirect {
   double         epsilon;
 };
 
-template <int MB>
-__host__ __device__ constexpr int firi_small_doubles() { return 34 + 9 * MB; }
-
 template <int MB, bool DIRECT>
 __device__ __forceinline__ void corridor_segment_body(const MapView &m, const SogmPlannerParams &pp,
                                                       const CorridorWorkspace &ws, const CorridorIO &io, int agent,
@@ -1384,32 +940,16 @@ __device__ __forceinline__ void corridor_segment_body(const MapView &m, const So
       return;
     }
   }
-  constexpr int  SMALL   = MB == 6 ? 96 : firi_small_doubles<MB>();
-  double        *s_lp    = (double *)smem;                    // LP_WORK_DOUBLES
-  double        *s_rows  = s_lp + LP_WORK_DOUBLES;            // LP_MAX_ROWS * 5
-  double        *s_lm    = s_rows + LP_MAX_ROWS * 5;          // 324 history + 16 hand-off + 36 alpha/ys
-  double        *s_fH    = s_lm + 2 * 18 * 9 + 16 + 36;       // FIRI_MAX_H * 4
-  double        *s_poly  = s_fH + FIRI_MAX_H * 4;             // FIRI_MAX_H * 4
-  double        *s_small = s_poly + FIRI_MAX_H * 4;           // SMALL doubles of shared small state
+  using L = SegmentLds<MB>;
+  double *base = (double *)smem, *s_fH = base + L::fH, *s_poly = base + L::poly, *s_small = base + L::small;
   // "point not yet covered" flags of the greedy selection: one BIT per obstacle point, 64 per word — the 64 lanes of
   // a trip of the point loops share one word, which lane 0 rewrites from a ballot (no atomics, 2 KiB for 16 k points)
-  unsigned long long *s_fw = (unsigned long long *)(s_small + SMALL);  // (pc_capacity + 63) / 64 words
-  int           *s_perm  = (int *)(s_fw + (pp.pc_capacity + 63) / 64);   // LP_MAX_ROWS
-  int           *s_int   = s_perm + LP_MAX_ROWS;              // 16 ints
-  SolverScratch  sc{s_lp, s_perm, s_rows, s_lm};
-
-  // shared small state layout
-  double *s_fwd  = s_small;                 // 9  forward
-  double *s_fa   = s_small + 9;             // 3  fwd_a
-  double *s_fb   = s_small + 12;            // 3  fwd_b
-  double *s_p    = s_small + 15;            // 3
-  double *s_fh   = s_small + 18;            // 4  current plane
-  double *s_bd   = s_small + 22;            // 4 MB  bd
-  double *s_fB   = s_bd + 4 * MB;           // 3 MB  forwardB
-  double *s_fD   = s_fB + 3 * MB;           // MB    forwardD
-  double *s_dD   = s_fD + MB;               // MB    distDs
-  double *s_box  = s_dD + MB;               // 6  llc, lhc
-  double *s_w    = s_box + 6;               // 6  w0, w1 (a, b)
+  unsigned long long *s_fw  = (unsigned long long *)(base + L::flags);
+  int                *s_int = (int *)(smem + L::ints(pp.pc_capacity));  // 16 ints
+  const LpScratch     sc{base + LpLds::work, base + LpLds::rows, (int *)(smem + L::perm(pp.pc_capacity))};
+  double *s_fwd = s_small + L::fwd, *s_fa = s_small + L::fa, *s_fb = s_small + L::fb, *s_p = s_small + L::p;
+  double *s_fh = s_small + L::fh, *s_bd = s_small + L::bd, *s_fB = s_small + L::fB, *s_fD = s_small + L::fD;
+  double *s_dD = s_small + L::dD, *s_box = s_small + L::box, *s_w = s_small + L::w;
 
   const double   *rt    = DIRECT ? nullptr : io.route + (size_t)agent * io.route_cap * 6;
   const double   *sp    = DIRECT ? nullptr : io.start_pva + agent * 9;
@@ -1661,7 +1201,7 @@ __device__ __forceinline__ void corridor_segment_body(const MapView &m, const So
       {
         const int       mm  = nH < LP_MAX_ROWS - 9 ? nH : LP_MAX_ROWS - 9;
         const long long tm0 = wall_clock64();
-        maxVolInsEllipsoid(s_poly, mm, R, p, r, sc, dbg);
+        maxVolInsEllipsoid(s_poly, mm, R, p, r, sc, base + L::lm, base + L::handoff, dbg);
         if (lane == 0) dbg[7] = wall_clock64() - tm0;
       }
       __syncthreads();
@@ -1716,7 +1256,6 @@ __global__ __launch_bounds__(64) void k_corridor_segment(
   corridor_segment_body<6, false>(m, pp, ws, io, blockIdx.y + agent0, blockIdx.x, smem, FiriDirect{});
 }
 
-#define FIRI_DIRECT_BD_MAX 32
 __global__ __launch_bounds__(64) void k_firi_direct(MapView m, SogmPlannerParams pp, CorridorWorkspace ws,
                                                     FiriDirect fd) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1727,7 +1266,7 @@ __global__ __launch_bounds__(64) void k_firi_direct(MapView m, SogmPlannerParams
 // Kernel B: per agent bookkeeping (baseline_fake.cpp:364-414 / baseline.cpp:362-403)
 // =================================================================================================
 __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                                                       const CorridorIO &io, int agent, const SolverScratch &sc) {
+                                                       const CorridorIO &io, int agent, const LpScratch &sc) {
   // The sequential bookkeeping below is executed by all 64 lanes with identical data (uniform control flow);
   // the LPs inside are solved by the whole wave, outputs are written by lane 0 / copied lane-parallel.
   const bool    w0    = threadIdx.x == 0;
@@ -1813,18 +1352,13 @@ __global__ __launch_bounds__(64) void k_corridor_finalize(
   const CorridorIO io{.start_pva = start_pva, .route = route, .route_len = route_len, .route_cap = route_cap,
                       .out_polys = out_polys, .out_nfaces = out_nfaces, .out_npoly = out_npoly, .out_goal = out_goal};
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double       *s_lp   = (double *)smem;
-  double       *s_rows = s_lp + LP_WORK_DOUBLES;
-  int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
-  SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
-  corridor_finalize_body(pp, ws, io, blockIdx.x + agent0, sc);
+  corridor_finalize_body(pp, ws, io, blockIdx.x + agent0, LpLds::carve(smem));
 }
 
 // Test hook (sogm_corridor_rules_batched): the rules around FIRI for polytopes the caller injects, one wave per problem.
 // The wave lays a CorridorWorkspace view over the caller's arrays, then per segment runs segment_box, shrink_corridor and
 // corridorValidW as corridor_segment_body does after FIRI, and ends in corridor_finalize_body: the replan's device code,
 // with the caller's polytopes where FIRI's would be.
-#define RULES_MAX_FACES 64  // two joined polytopes + sdlp's plane 0 fit LP_MAX_ROWS
 struct CorridorRules {
   const SogmPlannerParams *pp;         // [n]
   const double            *polys_in;   // [n][SOGM_MAX_PIECES][max_faces][4] un-shrunk
@@ -1834,13 +1368,8 @@ struct CorridorRules {
 };
 __global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, CorridorWorkspace ws, CorridorIO io) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double       *s_lp   = (double *)smem;
-  double       *s_rows = s_lp + LP_WORK_DOUBLES;
-  double       *s_poly = s_rows + LP_MAX_ROWS * 5;         // RULES_MAX_FACES * 4
-  double       *s_box  = s_poly + RULES_MAX_FACES * 4;     // 6
-  double       *s_w    = s_box + 6;                        // 6
-  int          *s_perm = (int *)(s_w + 6);                 // LP_MAX_ROWS
-  SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
+  double *base = (double *)smem, *s_poly = base + RulesLds::poly, *s_box = base + RulesLds::box, *s_w = base + RulesLds::w;
+  const LpScratch sc{base + LpLds::work, base + LpLds::rows, (int *)(smem + RulesLds::perm)};
   const int               prob = blockIdx.x, lane = threadIdx.x;
   const SogmPlannerParams pp   = cr.pp[prob];
   const int               MF   = pp.max_faces;
@@ -1887,8 +1416,31 @@ __global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, Corrido
 // Waiting is a bounded spin (s_sleep polling of one word); a timeout raises FlowCtl::err and every kernel of the
 // tick drains.
 // =================================================================================================
-// Called by ALL lanes of a wave (uniform control flow; every value that steers a branch goes through
-// readfirstlane so that the compiler sees a scalar condition): returns the published value, or -1 on failure.
+// One segment slot of an agent, run by a one-wave workgroup of k_corridor_flow or k_flight_light: its obstacle points, its
+// polytope, its completion counted in seg_done[agent] and — if that made it the agent's last slot (`cumulative`: the counter
+// runs on over the flight's ticks) — the per-agent bookkeeping, with the LP view laid over the segment layout's head
+// (SegmentLds).  True if this wave finalised the agent: publishing it is the caller's.  stamps: the flight's (null: none).
+__device__ __forceinline__ bool corridor_slot(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
+                                              const CorridorIO &io, int agent, int seg, char *smem, int *seg_done,
+                                              bool cumulative, long long *stamps) {
+  if (seg < io.route_len[agent] - 1) {
+    corridor_points_body<1>(m, pp, ws, io, agent, seg);
+    __threadfence_block();
+    __syncthreads();
+  }
+  if (stamps && threadIdx.x == 0) stamps[13] = wall_clock64();
+  corridor_segment_body<6, false>(m, pp, ws, io, agent, seg, smem, FiriDirect{});
+  __syncthreads();
+  if (stamps && threadIdx.x == 0) stamps[14] = wall_clock64();
+  __threadfence();  // this segment's polytope is visible before its completion is counted
+  const int done = flow_ticket(&seg_done[agent]);
+  if ((cumulative ? done & (SOGM_MAX_PIECES - 1) : done) != SOGM_MAX_PIECES - 1) return false;
+  __threadfence();  // the other segments' polytopes (their completions were counted before ours)
+  corridor_finalize_body(pp, ws, io, agent, LpLds::carve(smem));
+  __syncthreads();
+  return true;
+}
+
 __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerParams pp, CorridorWorkspace ws,
                                                       FlowCtl fc, CorridorIO io, int n_agents) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1902,43 +1454,13 @@ __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerPara
     __threadfence();        // the search's outputs (route, route_len) were published before the ready slot
     const int seg = k % SOGM_MAX_PIECES;
     if (seg == 0 && lane == 0) fc.ts[agent * 8 + 2] = wall_clock64();
-    if (seg < io.route_len[agent] - 1) {
-      corridor_points_body<1>(m, pp, ws, io, agent, seg);
-      __threadfence_block();
-      __syncthreads();
-    }
-    corridor_segment_body<6, false>(m, pp, ws, io, agent, seg, smem, FiriDirect{});
-    __syncthreads();
-    __threadfence();  // this segment's polytope is visible before its completion is counted
-    const int last = flow_ticket(&fc.seg_done[agent]) == SOGM_MAX_PIECES - 1;
-    if (last) {
-      __threadfence();  // the other segments' polytopes (their completions were counted before ours)
-      double       *s_lp   = (double *)smem;
-      double       *s_rows = s_lp + LP_WORK_DOUBLES;
-      int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);  // the head of s_lm: free between segments
-      SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
-      corridor_finalize_body(pp, ws, io, agent, sc);
-      __syncthreads();
+    if (corridor_slot(m, pp, ws, io, agent, seg, smem, fc.seg_done, false, nullptr)) {
       if (lane == 0) fc.ts[agent * 8 + 3] = wall_clock64();
       __threadfence();
       if (lane == 0) publish_next(fc.q_ready, &fc.hdr[FLOW_Q_READY_N], agent);
     }
     __syncthreads();
   }
-}
-
-// LDS of a wave that only solves LPs (validity / reachability / separation): sdlp work area, rows, permutation
-constexpr size_t lp_wave_lds() {
-  return sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5) + sizeof(int) * LP_MAX_ROWS;
-}
-size_t corridor_segment_lds(int pc_capacity) {
-  return sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5 + 2 * 18 * 9 + 16 + 36 + 2 * FIRI_MAX_H * 4 + 96) +
-         sizeof(int) * (LP_MAX_ROWS + 16) + 8 * (((size_t)pc_capacity + 63) / 64);
-}
-size_t firi_direct_lds(int pc_capacity) {
-  return sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5 + 2 * 18 * 9 + 16 + 36 + 2 * FIRI_MAX_H * 4 +
-                           firi_small_doubles<FIRI_DIRECT_BD_MAX>()) +
-         sizeof(int) * (LP_MAX_ROWS + 16) + 8 * (((size_t)pc_capacity + 63) / 64);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1950,12 +1472,10 @@ size_t firi_direct_lds(int pc_capacity) {
 // rows): the projective LP reports a feasible point at infinity (two crossing segments: the plane through both)
 // as "-inf", GLPK's affine model calls that infeasible; with the box the result is finite or +inf.
 // ------------------------------------------------------------------------------------------------
-#define DECONFLICT_MAX_ROWS (LP_MAX_ROWS - 9)  // 144 point rows + 8 box rows + sdlp's plane 0
 // One (new trajectory of agent a, record r) pair, executed by one wave: true = NOT separable (unsafe).
-// ca: the agent's 5 M control points; s_lp / s_rows / s_perm: the wave's LP scratch in LDS.
+// ca: the agent's 5 M control points; sc: the wave's LP scratch in LDS.
 __device__ __forceinline__ bool deconflict_pair_unsafe(const double *ca, int M, const SogmTrajRecord &r, int ego_id,
-                                                       double now, double *s_lp, double *s_rows, int *s_perm,
-                                                       unsigned long long *counters) {
+                                                       double now, const LpScratch &sc, unsigned long long *counters) {
   if (M <= 0) return false;  // nothing optimised for this agent
   if (r.n_pieces <= 0 || r.drone_id == ego_id) return false;
   double time_end = r.time_start;
@@ -1975,7 +1495,7 @@ __device__ __forceinline__ bool deconflict_pair_unsafe(const double *ca, int M, 
     if ((threadIdx.x & 63) == 0 && counters) atomicAdd(&counters[SOGM_CNT_DECONFLICT_CAPACITY], 1ull);
     return true;
   }
-  double       *A = s_rows, *b = s_rows + LP_MAX_ROWS * 4;
+  double       *A = sc.A(), *b = sc.b();
   const double *cb = r.cpts + piece * 15;
   // Disjoint bounding boxes are separated by an axis-aligned plane (the LP is feasible): most pairs of
   // a swarm end here without touching the LP.  64-lane min/max over the two point sets.
@@ -2054,7 +1574,7 @@ __device__ __forceinline__ bool deconflict_pair_unsafe(const double *ca, int M, 
   wave_lds_sync();
   const double c[4] = {0, 0, 0, 0};
   double       x[4];
-  const double v = linprog_wave<4>(c, nA + nB + 8, A, b, x, s_lp, s_perm);  // the whole wave solves the LP
+  const double v = linprog_wave<4>(c, nA + nB + 8, A, b, x, sc.work, sc.perm);  // the whole wave solves the LP
   wave_lds_sync();
   return v == INFINITY || v == -INFINITY;
 }
@@ -2142,12 +1662,9 @@ __global__ __launch_bounds__(64) void k_safe_after_opt(const double *__restrict_
                                                        int32_t *__restrict__ out_safe, int agent0,
                                                        unsigned long long *counters) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-  double *s_lp   = s_dyn;                   // LP_WORK_DOUBLES
-  double *s_rows = s_lp + LP_WORK_DOUBLES;  // LP_MAX_ROWS * 5
-  int    *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
   const int a = blockIdx.y + agent0, i = blockIdx.x;
-  if (deconflict_pair_unsafe(cpts + (size_t)a * SOGM_MAX_PIECES * 15, npoly[a], rec[i], ego_ids[a], t_now[a], s_lp,
-                             s_rows, s_perm, counters) &&
+  if (deconflict_pair_unsafe(cpts + (size_t)a * SOGM_MAX_PIECES * 15, npoly[a], rec[i], ego_ids[a], t_now[a],
+                             LpLds::carve(s_dyn), counters) &&
       threadIdx.x == 0)
     out_safe[a] = 0;  // every writer writes 0
 }
@@ -2155,7 +1672,7 @@ __global__ __launch_bounds__(64) void k_safe_after_opt(const double *__restrict_
 // What the finishing role does for one agent (one wave): ParticleATC::isSafeAfterOpt against every record of the swarm
 // (when a swarm is set), then the agent's SogmTrajRecord / ok flag and the publication — shared by k_finish_flow
 // (sogm_replan) and k_flight_light (sogm_flight_run).  Returns bit 0 = safe, bit 1 = replan() returned true.
-__device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, double *s_lp, double *s_rows, int *s_perm, int lane) {
+__device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, const LpScratch &sc, int lane) {
   const int M    = f.npoly[a];
   int       safe = 1;
   const bool solved = f.ret[a] != 0 && M > 0 && (f.status[a] == 1 || f.status[a] == 2);
@@ -2166,7 +1683,7 @@ __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, double *
     const int     nA  = 5 * M;
     // set A once per agent: its points in LDS (the LP scratch is idle until a pair needs the LP), its box and
     // its projections on the ten fixed normals as wave-uniform values
-    double *sA = s_lp;
+    double *sA = sc.work;
     double  boxA[6], prA[10][2];
     auto stage_A = [&]() {
       for (int q = lane; q < nA * 3; q += 64) sA[q] = ca[q];
@@ -2223,7 +1740,7 @@ __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, double *
       while (m != 0 && safe) {
         const int j = __builtin_ctzll(m);
         m &= m - 1;
-        if (deconflict_pair_unsafe(ca, M, f.swarm[i0 + j], ego, now, s_lp, s_rows, s_perm, f.counters)) safe = 0;
+        if (deconflict_pair_unsafe(ca, M, f.swarm[i0 + j], ego, now, sc, f.counters)) safe = 0;
         lp_ran = true;
       }
       if (lp_ran && safe && i0 + 64 < f.n_swarm) stage_A();  // the LP used the scratch that held set A
@@ -2280,17 +1797,14 @@ __device__ __forceinline__ void finish_count(const FinishArgs &f, int a, bool sa
 // finish_agent (what k_safe_after_opt + k_pack_records do in the grouped path) and hands the agent to the pre-stamp.
 __global__ __launch_bounds__(64) void k_finish_flow(FlowCtl fc, FinishArgs f, int n_agents) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-  double   *s_lp   = s_dyn;
-  double   *s_rows = s_lp + LP_WORK_DOUBLES;
-  int      *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
-  const int lane   = threadIdx.x;
+  const int lane = threadIdx.x;
   for (;;) {
     const int k = flow_ticket(&fc.hdr[FLOW_F_TICKET]);
     if (k >= n_agents) break;
     const int a = flow_wait_slot(fc.f_ready + k, &fc.hdr[FLOW_ERR]);
     if (a < 0) break;
     __threadfence();
-    const int  code = finish_agent(f, a, s_lp, s_rows, s_perm, lane);
+    const int  code = finish_agent(f, a, LpLds::carve(s_dyn), lane);
     const bool safe = (code & 1) != 0;
     if (fc.p_ready) {  // the agent's record is final: hand it to the pre-stamp
       __threadfence();
@@ -2352,9 +1866,7 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       f.pub_table  = d.tables ? d.tables + (size_t)(k & 3) * d.n_total + d.agent0 : nullptr;
       f.out        = d.log_records + (size_t)kl * fl.n_agents;
       f.out_ok     = d.log_ok + (size_t)kl * fl.n_agents;
-      double *s_lp = (double *)smem, *s_rows = s_lp + LP_WORK_DOUBLES;
-      int    *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
-      const int code = finish_agent(f, a, s_lp, s_rows, s_perm, lane);
+      const int code = finish_agent(f, a, LpLds::carve(smem), lane);
       __syncthreads();
       __threadfence();  // the record (own, ver(k), log) is out before the tick counts as finished
       if (lane == 0) {
@@ -2411,25 +1923,7 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       sdbg[14] = 0;
       sdbg[15] = (long long)(unsigned)__builtin_amdgcn_s_getreg(63492) | ((long long)(unsigned)__builtin_amdgcn_s_getreg(63508) << 32);
     }
-    if (seg < d.cor.route_len[a] - 1) {
-      corridor_points_body<1>(m, pp, ws, d.cor, a, seg);
-      __threadfence_block();
-      __syncthreads();
-    }
-    if (lane == 0) sdbg[13] = wall_clock64();
-    corridor_segment_body<6, false>(m, pp, ws, d.cor, a, seg, smem, FiriDirect{});
-    __syncthreads();
-    if (lane == 0) sdbg[14] = wall_clock64();
-    __threadfence();
-    const int last = (flow_ticket(&fl.seg_done[a]) & (SOGM_MAX_PIECES - 1)) == SOGM_MAX_PIECES - 1;
-    if (last) {
-      __threadfence();
-      double       *s_lp   = (double *)smem;
-      double       *s_rows = s_lp + LP_WORK_DOUBLES;
-      int          *s_perm = (int *)(s_rows + LP_MAX_ROWS * 5);
-      SolverScratch sc{s_lp, s_perm, s_rows, nullptr};
-      corridor_finalize_body(pp, ws, d.cor, a, sc);
-      __syncthreads();
+    if (corridor_slot(m, pp, ws, d.cor, a, seg, smem, fl.seg_done, true, sdbg)) {
       if (lane == 0) {
         fl.ts[a * FL_TS + 3] = wall_clock64();
         fl_publish(fl.q_ring, fl.ring_mask, &fl.hdr[FL_Q_READY], a);
@@ -2452,10 +1946,8 @@ __global__ __launch_bounds__(64) void k_linprog(const double *__restrict__ c, co
                                                 const int32_t *__restrict__ row_range,
                                                 double *__restrict__ out_x, double *__restrict__ out_min) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-  double   *s_lp   = s_dyn;                   // LP_WORK_DOUBLES
-  double   *s_rows = s_lp + LP_WORK_DOUBLES;  // LP_MAX_ROWS * 5
-  int      *s_ord  = (int *)(s_rows + LP_MAX_ROWS * 5);
-  const int p = blockIdx.x, lane = threadIdx.x;
+  const LpScratch sc = LpLds::carve(s_dyn);
+  const int       p = blockIdx.x, lane = threadIdx.x;
   const int r0 = row_range[2 * p], rows = row_range[2 * p + 1] - r0;
   if (rows >= LP_MAX_ROWS || rows < 0) {  // capacity: NaN, never a silent answer
     if (lane == 0) {
@@ -2464,15 +1956,14 @@ __global__ __launch_bounds__(64) void k_linprog(const double *__restrict__ c, co
     }
     return;
   }
-  double *sA = s_rows, *sb = s_rows + LP_MAX_ROWS * 4;
   for (int i = lane; i < rows; i += 64) {
-    for (int j = 0; j < D; ++j) sA[i * D + j] = A[(size_t)(r0 + i) * D + j];
-    sb[i] = b[r0 + i];
+    for (int j = 0; j < D; ++j) sc.A()[i * D + j] = A[(size_t)(r0 + i) * D + j];
+    sc.b()[i] = b[r0 + i];
   }
   wave_lds_sync();
   double cv[D], x[D];
   for (int j = 0; j < D; ++j) cv[j] = c[p * D + j];
-  const double v = linprog_wave<D>(cv, rows, sA, sb, x, s_lp, s_ord);
+  const double v = linprog_wave<D>(cv, rows, sc.A(), sc.b(), x, sc.work, sc.perm);
   if (lane == 0) {
     out_min[p] = v;
     for (int j = 0; j < D; ++j) out_x[p * D + j] = x[j];
@@ -2489,7 +1980,7 @@ hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *np
                              hipStream_t st, int agent0, unsigned long long *counters) {
   hipLaunchKernelGGL(k_fill_i32, dim3((n_agents + 63) / 64), dim3(64), 0, st, out_safe, n_agents, 1, agent0);
   if (n_rec > 0)
-    hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), lp_wave_lds(), st, cpts, npoly, rec, n_rec,
+    hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), LpLds::bytes(), st, cpts, npoly, rec, n_rec,
                        ego_ids, t_now, out_safe, agent0, counters);
   return hipGetLastError();
 }
@@ -2501,19 +1992,19 @@ hipError_t launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st) {
 
 hipError_t launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
                                 const FlowCtl &fc, int n_agents, int n_workgroups, const CorridorIO &io, hipStream_t st) {
-  hipLaunchKernelGGL(k_corridor_flow, dim3(n_workgroups), dim3(64), corridor_segment_lds(pp.pc_capacity), st, m, pp,
+  hipLaunchKernelGGL(k_corridor_flow, dim3(n_workgroups), dim3(64), SegmentLds<6>::bytes(pp.pc_capacity), st, m, pp,
                      ws, fc, io, n_agents);
   return hipGetLastError();
 }
 
 hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st) {
-  hipLaunchKernelGGL(k_finish_flow, dim3(n_workgroups), dim3(64), lp_wave_lds(), st, fc, f, n_agents);
+  hipLaunchKernelGGL(k_finish_flow, dim3(n_workgroups), dim3(64), LpLds::bytes(), st, fc, f, n_agents);
   return hipGetLastError();
 }
 
 hipError_t launch_flight_light(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlightCtl &fl,
                                const FlightLightDev &d, int n_workgroups, hipStream_t st) {
-  hipLaunchKernelGGL(k_flight_light, dim3(n_workgroups), dim3(64), corridor_segment_lds(pp.pc_capacity), st, m, pp, ws, fl, d);
+  hipLaunchKernelGGL(k_flight_light, dim3(n_workgroups), dim3(64), SegmentLds<6>::bytes(pp.pc_capacity), st, m, pp, ws, fl, d);
   return hipGetLastError();
 }
 
@@ -2526,10 +2017,10 @@ hipError_t launch_corridor(const MapView &m, const SogmPlannerParams &pp, const 
   if (e == hipSuccess && ev_map_read) e = hipEventRecord(ev_map_read, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_corridor_segment, dim3(SOGM_MAX_PIECES, n_agents), dim3(64),
-                     corridor_segment_lds(pp.pc_capacity), st, m, pp, ws, io.start_pva, io.t_start, io.route,
+                     SegmentLds<6>::bytes(pp.pc_capacity), st, m, pp, ws, io.start_pva, io.t_start, io.route,
                      io.route_len, io.route_cap, agent0);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_corridor_finalize, dim3(n_agents), dim3(64), lp_wave_lds(), st, pp, ws, io.start_pva, io.route,
+  hipLaunchKernelGGL(k_corridor_finalize, dim3(n_agents), dim3(64), LpLds::bytes(), st, pp, ws, io.start_pva, io.route,
                      io.route_len, io.route_cap, io.out_polys, io.out_nfaces, io.out_npoly, io.out_goal, agent0);
   return hipGetLastError();
 }
@@ -2542,7 +2033,7 @@ extern "C" int sogm_linprog_batched(int d, const double *c, const double *A, con
   if ((d != 3 && d != 4) || n < 0 || (n > 0 && (!c || !row_range || !out_x || !out_min)))
     return SOGM_ERR_INVALID_ARG;
   if (n == 0) return SOGM_OK;
-  const size_t lds = sogm::lp_wave_lds();
+  const size_t lds = sogm::LpLds::bytes();
   hipStream_t  st  = (hipStream_t)stream;
   if (d == 3)
     hipLaunchKernelGGL(sogm::k_linprog<3>, dim3(n), dim3(64), lds, st, c, A, b, row_range, out_x, out_min);
@@ -2575,7 +2066,7 @@ extern "C" int sogm_firi_batched(const double *bd, int n_bd, const double *pc_xy
   pp.pc_capacity = max_points;
   sogm::FiriDirect fd{bd, n_bd, pc_xyz, pc_range, a, b, r, iterations, out_hpoly, out_nfaces, out_status,
                       max_faces, 0, epsilon};
-  hipLaunchKernelGGL(sogm::k_firi_direct, dim3(n), dim3(64), sogm::firi_direct_lds(max_points), st, sogm::MapView{},
+  hipLaunchKernelGGL(sogm::k_firi_direct, dim3(n), dim3(64), sogm::SegmentLds<FIRI_DIRECT_BD_MAX>::bytes(max_points), st, sogm::MapView{},
                      pp, ws, fd);
   const hipError_t e = hipGetLastError();
   (void)hipFreeAsync(scratch, st);
@@ -2613,9 +2104,7 @@ extern "C" int sogm_corridor_rules_batched(sogm_planner *counters_of, const Sogm
                                  .out_polys = out_polys, .out_nfaces = out_nfaces, .out_npoly = out_npoly,
                                  .out_goal = out_goal};
     const sogm::CorridorRules cr{d_pp, polys, nfaces, seg_state, out_box};
-    const size_t lds = sizeof(double) * (LP_WORK_DOUBLES + LP_MAX_ROWS * 5 + RULES_MAX_FACES * 4 + 12) +
-                       sizeof(int) * LP_MAX_ROWS;
-    hipLaunchKernelGGL(sogm::k_corridor_rules, dim3(n), dim3(64), lds, st, cr, ws, io);
+    hipLaunchKernelGGL(sogm::k_corridor_rules, dim3(n), dim3(64), sogm::RulesLds::bytes(), st, cr, ws, io);
     e = hipGetLastError();
   }
   (void)hipFreeAsync(d_pp, st);
@@ -2627,7 +2116,7 @@ extern "C" int sogm_corridor_rules_batched(sogm_planner *counters_of, const Sogm
 extern "C" int sogm_debug_corridor_occupancy(int pc_capacity) {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)sogm::k_corridor_segment, 64,
-                                                   sogm::corridor_segment_lds(pc_capacity)) != hipSuccess)
+                                                   sogm::SegmentLds<6>::bytes(pc_capacity)) != hipSuccess)
     return -1;
   return n;
 }

@@ -103,3 +103,79 @@ def test_corridor_box_with_more_than_4096_points_gives_the_uncapped_answer(pop, 
     assert P.counters()["corridor_capacity"] == 0
     P.close()
     m.close()
+
+
+def test_corridors_at_a_point_capacity_that_moves_the_lds_layout(pop, orc):
+    """The segment kernel's LDS ends in regions whose offsets depend on pc_capacity (the flag words of the greedy
+    selection, one bit per point, then the LP's permutation and 16 ints).  Every other test runs at the default 16384;
+    here a second planner gets the smallest capacity above every box's point count that is no multiple of 64, so
+    that the permutation sits elsewhere: its polytopes must be the default capacity's and the oracle's, bit for bit,
+    on the grouped path and on the dataflow replan (k_corridor_flow; k_finish_flow behind it)."""
+    import ctypes as C
+    import torch
+    sogm = importlib.import_module("pred-occ-planner_amd.sogm")
+    planner = importlib.import_module("pred-occ-planner_amd.planner")
+    A, seed, fake = 6, 5, False
+    spec = pop.config.make_spec("parity")
+    sc, pva = hard_cases(pop, A, seed)
+    recs = pop.scene.straight_records(sc)
+    dev = sogm.upload_scene(sc)
+    m = sogm.SogmMap(spec, A)
+    m.updateMap(dev["cloud"], dev["cloud_range"], dev["cylinders"], dev["n_cyl"], dev["poses"], dev["stamps"])
+    m.addOtherAgents(sogm._dev(recs), A, dev["ego_ids"])
+    ap, qs = pop.config.make_astar_params(), pop.config.make_qp_settings()
+    t_start = sc["stamps"] + 0.05
+    d_pva, d_ts, d_goals = sogm._dev(pva, np.float64), sogm._dev(t_start, np.float64), sogm._dev(sc["goals"], np.float64)
+    lib = pop.lib()
+    lib.sogm_debug_corridor_stats.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sogm_debug_planner_buffer.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+
+    def grouped(P):
+        s = P.search(d_pva, d_goals, d_ts)
+        c = {k: v.cpu().numpy() for k, v in P.generateCorridors(d_pva, d_ts, s["route"], s["route_len"]).items()}
+        dbg = np.zeros((A * 16, 16), np.int64)
+        assert lib.sogm_debug_corridor_stats(P._p, dbg.ctypes.data) == 0
+        return c, s["route"].cpu().numpy(), s["route_len"].cpu().numpy(), dbg[dbg[:, 10] > 0, 0]
+
+    pp = pop.config.make_planner_params(fake)
+    P = planner.SogmPlanner(m, ap, pp, qs)
+    c0, route, rlen, npts = grouped(P)
+    P.close()
+    cap = int(npts.max() // 64 + 1) * 64 + 1
+    pp2 = pop.config.make_planner_params(fake)
+    pp2.pc_capacity = cap
+    assert npts.max() < cap and cap % 64 != 0 and cap != pp.pc_capacity
+    P = planner.SogmPlanner(m, ap, pp2, qs)
+    c1, route1, rlen1, npts1 = grouped(P)
+    assert np.array_equal(route, route1) and np.array_equal(rlen, rlen1) and np.array_equal(npts, npts1)
+    for k in ("npoly", "nfaces", "polys", "goal"):
+        assert np.array_equal(c0[k], c1[k]), k
+    grids = oracle_grids(pop, orc, spec, sc, recs)
+    for a in range(A):
+        w = orc.corridor_generate(spec, pp2, grids[a], sc["poses"][a], sc["stamps"][a], pva[a], t_start[a],
+                                  route[a, :rlen[a]])
+        assert c1["npoly"][a] == w["npoly"] and np.array_equal(c1["nfaces"][a], w["nfaces"]), a
+        for i in range(w["npoly"]):
+            nf = w["nfaces"][i]
+            assert np.array_equal(c1["polys"][a, i, :nf], w["polys"][i, :nf]), (a, i)
+        assert np.array_equal(c1["goal"][a], w["goal"]), a
+    assert c1["npoly"].sum() > 0 and P.counters()["corridor_capacity"] == 0
+    # the same planner through sogm_replan: the dataflow kernels, their corridor outputs read back
+    P.replan(d_pva, d_goals, d_ts, dev["ego_ids"])
+    torch.cuda.synchronize()
+    assert P.flow_error() == 0
+    MF = pp2.max_faces
+    flow = {0: np.zeros((A, 16, MF, 4), np.float64), 1: np.zeros((A, 16), np.int32), 2: np.zeros((A,), np.int32),
+            3: np.zeros((A, 6), np.float64), 5: np.zeros((A,), np.int32)}
+    for k, buf in flow.items():
+        assert lib.sogm_debug_planner_buffer(P._p, k, buf.ctypes.data_as(C.c_void_p), buf.nbytes) == 0, k
+    assert np.array_equal(flow[5], rlen)          # the replan's own search found the same routes
+    assert np.array_equal(flow[2], c1["npoly"]) and np.array_equal(flow[1], c1["nfaces"])
+    assert np.array_equal(flow[3], c1["goal"])
+    for a in range(A):
+        for i in range(c1["npoly"][a]):
+            nf = c1["nfaces"][a, i]
+            assert np.array_equal(flow[0][a, i, :nf], c1["polys"][a, i, :nf]), (a, i)
+    assert P.counters()["corridor_capacity"] == 0
+    P.close()
+    m.close()
