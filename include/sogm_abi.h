@@ -499,6 +499,57 @@ int sogm_tick_inputs(const SogmTrajRecord *own_records, int n, double stamp, dou
 int sogm_merge_latest(const SogmTrajRecord *new_records, const int32_t *ok, SogmTrajRecord *own_inout,
                       SogmTrajRecord *all_or_null, int n, void *stream);
 
+/*
+ * FiniteStateMachine::FSMCallback (plan_manager/src/plan_manager.cpp:92-233) for a batch of agents, on the device:
+ * one state record per agent and two launches per tick around the map update and sogm_replan.  The rules themselves
+ * are written once, in csrc/sogm_fsm.hpp (fsm_due / fsm_step; the header compiles on the host too).  Each entry is ONE
+ * launch, one lane per agent, stream-ordered, no host synchronisation.
+ */
+typedef struct SogmFsmParams {
+  double  replan_duration;     /* fsm/replan_duration: EXEC_TRAJ asks for a replan after this long (:137-150)       */
+  double  replan_start_time;   /* fsm/replan_start_time: REPLAN plans from now + this (:165-175)                    */
+  double  goal_tolerance;      /* fsm/goal_tolerance: isGoalReached, |position - goal| < tolerance                  */
+  double  new_plan_interval;   /* NEW_PLAN plans when more than this has passed since traj_start (:110-135; 1.0 s)  */
+  int32_t replan_max_failures; /* fsm/replan_max_failures: more failures in a row -> hover record, NEW_PLAN (:176-199) */
+  int32_t reserved_;
+} SogmFsmParams;
+typedef struct SogmFsmState { /* 24 bytes */
+  double  traj_start; /* traj_start_time_                                             */
+  int32_t status;     /* 0 NEW_PLAN, 1 EXEC_TRAJ, 2 REPLAN, 3 GOAL_REACHED            */
+  int32_t fail;       /* num_replan_failures_                                         */
+  int32_t success;    /* the member is_success_ (written by NEW_PLAN only, :110-135)  */
+  int32_t reserved_;
+} SogmFsmState;
+/* values of sogm_fsm_apply's out_pub */
+#define SOGM_FSM_PUB_NONE  0
+#define SOGM_FSM_PUB_NEW   1 /* the tick's new record (plan_manager.cpp:364-399)               */
+#define SOGM_FSM_PUB_HOVER 2 /* publishEmptyTrajectory's hover record (plan_manager.cpp:404-424) */
+/*
+ * sogm_fsm_init — dev state [n]: every agent in NEW_PLAN with traj_start = traj_start0, no failures (the machine once
+ * INIT and WAIT_TARGET have passed: inputs received, goal set, execution triggered, plan_manager.cpp:96-108).
+ * sogm_fsm_inputs — the head of one FSMCallback: which agents plan in this tick and from where.  out_due [n]: bit 0 a
+ * NEW_PLAN agent whose new_plan_interval has passed (:110-135), bit 1 a REPLAN agent (:164-175); out_t_start [n] the
+ * planning start time (stamp, or stamp + replan_start_time in REPLAN); out_pva [n][9] own_records[a] sampled there and
+ * out_pos_now [n][3] sampled at stamp (sogm_traj_eval's arithmetic), an agent without a valid sample takes
+ * hover_inout[a] for both (odom, :127-133); hover_inout [n][9] is then refreshed to {position now, 0, 0}; out_now [n] =
+ * stamp; out_poses [n][3] fp32 the map centres (position now); out_reached [n] int32 = |position now - goals[a]| <
+ * goal_tolerance (isGoalReached).  dev goals [n][3] fp64.
+ * sogm_fsm_apply — the rest of the FSMCallback and its publication: the state update from this tick's results (dev int32
+ * [n]: due = sogm_fsm_inputs' out_due, ok = sogm_replan's out_ok — looked at only where the agent was due —, safe =
+ * sogm_traj_safe's output, reached), then own_inout[a] becomes new_records[a] (out_pub[a] = SOGM_FSM_PUB_NEW), the
+ * hover record of publishEmptyTrajectory (:404-424: one 0.5 s piece, five control points at pos_now[a], start time
+ * out_hover_start[a]; SOGM_FSM_PUB_HOVER) or stays untouched (SOGM_FSM_PUB_NONE, out_hover_start[a] = 0).
+ */
+int sogm_fsm_init(SogmFsmState *state, int n, double traj_start0, void *stream);
+int sogm_fsm_inputs(const SogmFsmParams *prm, const SogmFsmState *state, const SogmTrajRecord *own_records,
+                    const double *goals, int n, double stamp, double *hover_inout, double *out_now, double *out_t_start,
+                    double *out_pva, float *out_poses, double *out_pos_now, int32_t *out_due, int32_t *out_reached,
+                    void *stream);
+int sogm_fsm_apply(const SogmFsmParams *prm, SogmFsmState *state_inout, const int32_t *due, const int32_t *ok,
+                   const int32_t *safe, const int32_t *reached, const SogmTrajRecord *new_records,
+                   const int32_t *drone_ids, const double *pos_now, SogmTrajRecord *own_inout, int32_t *out_pub,
+                   double *out_hover_start, int n, double stamp, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* queries                                                                                     */
 /* ------------------------------------------------------------------------------------------ */
@@ -670,6 +721,17 @@ int sogm_safe_after_opt(sogm_planner *p, const double *cpts, const int32_t *npol
  */
 int sogm_planner_set_swarm(sogm_planner *p, const SogmTrajRecord *records, int n_records,
                            const int32_t *ego_ids, const double *t_now);
+/*
+ * The reference plans only in NEW_PLAN (once per new_plan_interval) and REPLAN (plan_manager.cpp:110-135,164-175): with a
+ * mask set, later sogm_replan() calls plan only the agents with due[a] != 0 (dev int32 [n_agents], read by those calls:
+ * sogm_fsm_inputs' out_due).  An agent that is not due ends like a replan whose search found no path — out_ok 0, an
+ * empty record, its published record kept — without expanding a node, and moves none of sogm_planner_counters.
+ * NULL (the default): every agent plans.  sogm_flight_run ignores the mask.
+ * The planner keeps the POINTER, not a copy: the mask stays in force for every later sogm_replan() until another call
+ * replaces it or passes NULL, each of those calls reads the buffer's contents as they are when its searches run (stream
+ * order), and the buffer must stay allocated until they have completed or the mask has been replaced.
+ */
+int sogm_planner_set_due(sogm_planner *p, const int32_t *due_dev_or_null);
 
 /*
  * Cumulative counters of sogm_replan() since creation / the last reset: where each replan ended (the early

@@ -143,6 +143,20 @@ SOGM_AUDIT_AGENT, SOGM_AUDIT_OBSTACLE = 0, 1
 AUDIT_AGENT_BYTES = C.sizeof(SogmAuditAgent)  # 104
 AUDIT_EVENT_BYTES = C.sizeof(SogmAuditEvent)  # 24
 
+
+class SogmFsmParams(C.Structure):
+    _fields_ = [("replan_duration", C.c_double), ("replan_start_time", C.c_double), ("goal_tolerance", C.c_double),
+                ("new_plan_interval", C.c_double), ("replan_max_failures", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SogmFsmState(C.Structure):
+    _fields_ = [("traj_start", C.c_double), ("status", C.c_int32), ("fail", C.c_int32), ("success", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+FSM_STATE_BYTES = C.sizeof(SogmFsmState)  # 24
+FSM_PUB_NONE, FSM_PUB_NEW, FSM_PUB_HOVER = 0, 1, 2  # sogm_fsm_apply's out_pub
+
 FLIGHT_MAX_TICKS = 64
 FLIGHT_HDR_ERR, FLIGHT_HDR_FINISHED, FLIGHT_HDR_LATE_WGS = 4, 5, 15  # sogm_flight_stats out_hdr indices
 FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "chain", "ticks")
@@ -186,6 +200,11 @@ PROTOTYPES = {
     "sogm_download_reference_layout": (_i, [_vp, _i, _vp]),
     "sogm_tick_inputs": (_i, [_vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_merge_latest": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "sogm_fsm_init": (_i, [_vp, _i, C.c_double, _vp]),
+    "sogm_fsm_inputs": (_i, [C.POINTER(SogmFsmParams), _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp]),
+    "sogm_fsm_apply": (_i, [C.POINTER(SogmFsmParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                            C.c_double, _vp]),
     "sogm_map_state": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_float), _vp]),
     "sogm_traj_eval": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "sogm_firi_batched": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -224,6 +243,7 @@ PROTOTYPES = {
     "sogm_flight_prepare": (_i, [_vp, _i]),
     "sogm_flight_stats": (_i, [_vp, _vp, _vp]),
     "sogm_planner_set_swarm": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "sogm_planner_set_due": (_i, [_vp, _vp]),
     "sogm_audit_init_agents": (_i, [_vp, _i, _vp]),
     "sogm_swarm_audit": (_i, [C.POINTER(SogmAuditParams), _vp, _i, _i, _vp, C.c_double, _i, C.c_double, _i, _i, _vp, _vp,
                               _vp, _i, _vp, _vp, _vp, _vp]),

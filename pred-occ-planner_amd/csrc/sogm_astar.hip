@@ -315,10 +315,14 @@ __device__ inline void pos_to_index(const double *p, const double *center, doubl
 // pending (vbase: 0 for the per-tick launches, whose verdicts are zeroed per replan; 4 x (tick + 1) in a flight, where
 // the word is never reset).  Returns true (uniformly) when THIS workgroup wrote the agent's search outputs — the caller
 // publishes the agent — and false when it leaves them to the other attempt.
+// `skip` (uniform over the workgroup; sogm_planner_set_due left the agent out): no attempt runs, and the agent goes the way
+// of one whose attempts all returned NO_PATH without an expansion — the first attempt announces "no path", the attempt
+// whose result counts writes ret = NO_PATH, an empty route and the statistics of no search at all: 0 nodes, 0 expansions,
+// 0 searches, in the dataflow and the grouped form alike.
 __device__ __forceinline__ bool astar_search_wg(
     const MapView &m, const SogmAstarParams &ap, double corridor_tau, const AstarWorkspace &wsp, const SearchIO &io,
     int32_t *__restrict__ out_trace, int trace_cap, int agent, int second, bool spec, int vbase, int *flow_err,
-    int search_mode) {
+    int search_mode, bool skip = false) {
   const int  tid    = threadIdx.x;
 
   __shared__ double             s_f[ASTAR_POOL_MAX];     // f-score mirror of every allocated node
@@ -416,7 +420,7 @@ __device__ __forceinline__ bool astar_search_wg(
   // search_mode 0: the replan's call pattern (init_search = true, then false if NO_PATH, baseline_fake.cpp:284-291);
   // 1 / 2: exactly one search(…, init = true / false, …) for the per-object shim
   const int attempt_lo = spec ? second : ((search_mode & 3) == 2 ? 1 : 0);
-  const int attempt_hi = spec ? second + 1 : ((search_mode & 3) == 1 ? 1 : 2);
+  const int attempt_hi = skip ? attempt_lo : spec ? second + 1 : ((search_mode & 3) == 1 ? 1 : 2);
   bool      dropped    = false;  // second attempt: the first one found a path
   for (int attempt = attempt_lo; attempt < attempt_hi; ++attempt) {
     // reset(): clear the hash table (all lanes)
@@ -917,7 +921,7 @@ __device__ __forceinline__ bool astar_search_wg(
       }
       __syncthreads();
       if (s_ret != 2) return false;
-      if (tid == ASTAR_MASTER) searches = 2;  // as the sequential pattern counts them
+      if (tid == ASTAR_MASTER) searches = skip ? 0 : 2;  // as the sequential pattern counts them
     }
   }
 
@@ -989,10 +993,10 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
     const double *__restrict__ t_start, int32_t *__restrict__ out_ret,
     double *__restrict__ out_route, int32_t *__restrict__ out_route_len, int route_cap,
     int32_t *__restrict__ out_stats, int32_t *__restrict__ out_trace, int trace_cap, int agent0, FlowCtl fc,
-    int search_mode) {
+    int search_mode, const int32_t *__restrict__ due) {
   const SearchIO io{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = out_ret,
                     .out_route = out_route, .out_route_len = out_route_len, .route_cap = route_cap,
-                    .out_stats = out_stats};
+                    .out_stats = out_stats, .due = due};
   // search_mode bit 3 (dataflow replan): the launch has 2 x n workgroups; workgroup b >= n runs the SECOND attempt of
   // agent b - n speculatively beside the first
   const bool spec   = (search_mode & 8) != 0;
@@ -1000,6 +1004,9 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
   const int  second = spec && (int)blockIdx.x >= n_half ? 1 : 0;
   const int  agent  = ((int)blockIdx.x - second * n_half) + agent0;
   const int  tid    = threadIdx.x;
+  // sogm_planner_set_due: an agent that is not due is not searched.  The mask was written in front of this launch in
+  // stream order (no workgroup of this tick writes it): one plain load per workgroup, here, ahead of every hand-over
+  const bool skip   = io.due != nullptr && io.due[agent] == 0;
   // dataflow replan: tell the gate kernel that this workgroup holds its CU resources (the corridor kernel's
   // waiting workgroups must not be dispatched before every search is resident, or they could starve it)
   if (fc.reset_gen) {
@@ -1034,7 +1041,7 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_astar(
     if (!s_map_ok) return;
   }
   const bool mine = astar_search_wg(m, ap, corridor_tau, wsp, io, out_trace, trace_cap, agent, second, spec, 0,
-                                    fc.hdr ? &fc.hdr[FLOW_ERR] : nullptr, search_mode);
+                                    fc.hdr ? &fc.hdr[FLOW_ERR] : nullptr, search_mode, skip);
   if (mine && fc.hdr && tid == ASTAR_MASTER) {  // publish the agent, in completion order, to the corridor kernel
     fc.ts[agent * 8 + 1] = wall_clock64();
     publish_next(fc.a_ready, &fc.hdr[FLOW_A_READY_N], agent);
@@ -1097,7 +1104,7 @@ hipError_t launch_astar(const MapView &m, const SogmAstarParams &ap, double corr
   if (!spec) search_mode &= ~8;
   hipLaunchKernelGGL(k_astar, dim3(spec ? 2 * n_agents : n_agents), dim3(ASTAR_THREADS), 0, st, m, ap, corridor_tau, wsp,
                      io.start_pva, io.goal, io.t_start, io.out_ret, io.out_route, io.out_route_len, io.route_cap,
-                     io.out_stats, out_trace, trace_cap, agent0, fc ? *fc : none, search_mode);
+                     io.out_stats, out_trace, trace_cap, agent0, fc ? *fc : none, search_mode, io.due);
   return hipGetLastError();
 }
 

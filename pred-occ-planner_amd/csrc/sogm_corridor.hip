@@ -1785,6 +1785,7 @@ __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, const Lp
 // where this replan ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe); one lane
 __device__ __forceinline__ void finish_count(const FinishArgs &f, int a, bool safe) {
   if (!f.counters) return;
+  if (f.due && f.due[a] == 0) return;  // left out by sogm_planner_set_due's mask: not a replan that was asked for
   const int M = f.npoly[a];
   int       k = SOGM_CNT_REPLAN_OK;
   if (f.ret[a] == 0) k = SOGM_CNT_FAIL_SEARCH;

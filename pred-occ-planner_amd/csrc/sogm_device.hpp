@@ -435,7 +435,7 @@ __device__ inline void bezier_pos(const SogmTrajRecord &r, double t, double out[
   }
 }
 
-// (shared by sogm_map.hip and sogm_audit.hip)
+// (shared by sogm_map.hip, sogm_audit.hip and sogm_fsm.hip)
 // Bezier pos / vel / acc of a trajectory record at an absolute time (bernstein.cpp:25-59)
 // returns false (and zeros) for an empty record
 __device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, double out[9]) {

@@ -62,7 +62,8 @@ __global__ void k_pack_records(int A, FinishArgs f, int agent0) {
   if (a >= A) return;
   const int32_t *ret = f.ret, *npoly = f.npoly, *status = f.status;
   const int32_t *safe = f.swarm ? f.out_safe : nullptr;  // (launch_deconflict ran in front of this kernel only with a swarm)
-  if (unsigned long long *counters = f.counters) {  // where this replan ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe)
+  // (an agent sogm_planner_set_due's mask left out was not asked to plan: it is not counted)
+  if (unsigned long long *counters = (f.due && f.due[a] == 0) ? nullptr : f.counters) {  // where this replan ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe)
     int k = SOGM_CNT_REPLAN_OK;
     if (ret[a] == 0) k = SOGM_CNT_FAIL_SEARCH;
     else if (npoly[a] <= 0) k = SOGM_CNT_FAIL_CORRIDOR;
@@ -289,7 +290,7 @@ static int launched(const char *what, hipError_t e) {
 static sogm::SearchIO search_io(const sogm_planner *p, const double *start_pva, const double *goal, const double *t_start) {
   return sogm::SearchIO{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = p->d_ret,
                         .out_route = p->d_route, .out_route_len = p->d_route_len, .route_cap = p->route_cap,
-                        .out_stats = p->d_stats};
+                        .out_stats = p->d_stats, .due = p->due};
 }
 static sogm::CorridorIO corridor_io(const sogm_planner *p, const double *start_pva, const double *t_start) {
   return sogm::CorridorIO{.start_pva = start_pva, .t_start = t_start, .route = p->d_route,
@@ -307,7 +308,8 @@ static sogm::FinishArgs finish_args(const sogm_planner *p, const double *t_start
                           .status = p->d_status, .cpts = p->d_cpts, .swarm = p->swarm, .n_swarm = p->n_swarm,
                           .swarm_ego = p->swarm_ego, .swarm_now = p->swarm_now, .t_start = t_start,
                           .drone_ids = drone_ids, .out = out, .out_ok = out_ok, .out_safe = p->d_safe,
-                          .counters = p->cw.counters, .pub_own = p->pub_own, .pub_table = p->pub_table};
+                          .counters = p->cw.counters, .pub_own = p->pub_own, .pub_table = p->pub_table,
+                          .due = p->due};
 }
 
 int sogm_astar_search(sogm_planner *p, const double *start_pva, const double *goal,
@@ -567,6 +569,12 @@ int sogm_planner_set_prestamp(sogm_planner *p, const SogmPrestamp *ps) {
   p->ps.pva          = ps->out_pva;
   p->ps.poses_host   = ps->out_poses;
   p->ps_on           = 1;
+  return SOGM_OK;
+}
+
+int sogm_planner_set_due(sogm_planner *p, const int32_t *due_dev_or_null) {
+  if (!p) return SOGM_ERR_INVALID_ARG;
+  p->due = due_dev_or_null;
   return SOGM_OK;
 }
 

@@ -95,6 +95,9 @@ struct SearchIO {  // search: start state, goal and start time in, return code /
   int32_t      *out_route_len;
   int           route_cap;
   int32_t      *out_stats;
+  // sogm_planner_set_due's mask (null: every agent searches).  Only launch_astar hands it to its kernel: sogm_replan's
+  // searches.  launch_flight_search does not, which is how sogm_flight_run ignores the mask.
+  const int32_t *due;
 };
 struct CorridorIO {  // corridors: the search's route in, polytopes and the local goal out
   const double  *start_pva, *t_start, *route;
@@ -127,6 +130,7 @@ struct FinishArgs {
   int32_t              *out_ok, *out_safe;
   unsigned long long   *counters;
   SogmTrajRecord       *pub_own, *pub_table;
+  const int32_t        *due;  // sogm_planner_set_due's mask (null: every agent was asked to plan): who is counted
 };
 // the light roles' arguments (k_flight_light): corridor stage buffers + the finishing role's
 struct FlightLightDev {
@@ -256,6 +260,8 @@ struct sogm_planner {
   const double         *swarm_now;
   // publication inside the replan (sogm_planner_set_publish): the host's own-record table and the next swarm table
   SogmTrajRecord       *pub_own, *pub_table;
+  // the agents sogm_replan plans (sogm_planner_set_due): dev [A], != 0 = due; null = all
+  const int32_t        *due;
   // agent groups: sogm_replan runs each group's search -> corridors -> QP chain on its own stream,
   // so one slow agent (a long A* search, an infeasible QP) only delays its own group
   int         n_groups;

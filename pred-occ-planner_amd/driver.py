@@ -365,7 +365,7 @@ class SwarmTick:
     def __init__(self, grid="cfg2", agents_per_rank=None, rank=0, world=1, device=0, seed=0x5069,
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
-                 moving_world=None, neighbour_lag=1, audit=False):
+                 moving_world=None, neighbour_lag=1, audit=False, device_fsm=False):
         self.rank, self.world, self.dist = rank, world, dist
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
@@ -432,6 +432,17 @@ class SwarmTick:
         self.success = torch.zeros((self.A_loc,), dtype=torch.bool, device=d)
         self.traj_start = torch.full((self.A_loc,), float(self.scene["stamps"][0]) - 2.0, dtype=torch.float64, device=d)
         self.t0 = float(self.scene["stamps"][0])
+        # fsm=True, device_fsm=True: the same machines as device records behind the C ABI (fsm.FsmState, step_fsm_device);
+        # the replan then plans only the agents that are due
+        if device_fsm and not fsm:
+            raise ValueError("SwarmTick(device_fsm=True) needs fsm=True: it chooses where the state machines run")
+        self.device_fsm = bool(device_fsm)
+        self.fsm_dev = None
+        if self.device_fsm:
+            from . import fsm as fsm_mod
+            self.fsm_dev = fsm_mod.FsmState(self.A_loc, self.t0 - 2.0, fsm_mod.make_params(
+                TICK_PERIOD, REPLAN_START_TIME, GOAL_TOLERANCE, 1.0, REPLAN_MAX_FAILURES), device=d)
+            self.status, self.fail, self.traj_start = self.fsm_dev.status, self.fsm_dev.fail, self.fsm_dev.traj_start
         self.tick = 0
         self.n_ok_total = 0
         # several ranks (or a process group of one): the swarm table is refreshed by the all-gather, not locally
@@ -534,8 +545,44 @@ class SwarmTick:
         self.tick += 1
         return ok.to(torch.int32)
 
+    def step_fsm_device(self):
+        """step_fsm with the machines on the device: sogm_fsm_inputs -> map update -> overlay -> isTrajSafe -> replan of
+        the agents that are due (sogm_planner_set_due) -> sogm_fsm_apply -> exchange / audit.  Same records, states and
+        masked ok as step_fsm, tick for tick; the searches, corridors and QPs of EXEC_TRAJ / GOAL_REACHED agents, whose
+        results step_fsm throws away, are not run.  Stream-ordered, no host sync.
+        last_fsm differs from step_fsm's in two ways: "reached", "due", "hover_start", "t_start" and "pos" are the
+        tick's device buffers themselves, rewritten by the next step() (clone what must outlive it; "ok" and the "pub_*"
+        flags and "safe" are fresh tensors), and "hover_start" is 0 where no hover record was published (step_fsm leaves
+        traj_start there); it also has "due" (sogm_fsm_inputs' bits)."""
+        stamp = self.t0 + self.tick * TICK_PERIOD
+        f, ego = self.fsm_dev, self.dev["ego_ids"]
+        f.inputs(self.own, self.goals, stamp, self.hover, self.now, self.t_start, self.pva, self.poses)
+        if getattr(self.compute, "use_world", False):
+            self.map.updateWorld(self.compute.world(self.tick), self.poses, self.now)
+        else:
+            self.map.updateMap(self.dev["cloud"], self.dev["cloud_range"], self.dev["cylinders"], self.dev["n_cyl"],
+                               self.poses, self.now)
+        self.map.addOtherAgents(self.all, self.A_tot, ego)
+        safe = self.map.isTrajSafe(self.own, self.now, COLLI_CHECK_DURATION)
+        self.planner.set_due(f.due)
+        self.planner.replan(self.pva, self.goals, self.t_start, ego, self.new, self.ok)   # ok = 0 where not due
+        f.apply(self.ok, safe, self.new, ego, self.own, stamp)
+        ok = self.ok.clone()  # self.ok is rewritten by the next tick
+        # what this FSMCallback saw and did, as step_fsm reports it; "reached", "due", "hover_start", "t_start" and "pos"
+        # are the live buffers that the next tick rewrites, not copies: a reader that keeps them over a step() clones them
+        self.last_fsm = {"now": stamp, "ok": ok, "safe": safe, "reached": f.reached, "due": f.due,
+                         "pub_new": f.pub == _abi.FSM_PUB_NEW, "pub_hover": f.pub == _abi.FSM_PUB_HOVER,
+                         "hover_start": f.hover_start, "t_start": self.t_start, "pos": f.pos_now}
+        self._exchange()
+        if self.auditor is not None:
+            self._audit_tick(self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all())
+        self.tick += 1
+        return ok
+
     def step(self):
         """One replan tick for every agent of this rank.  Everything is stream-ordered on the GPU."""
+        if self.device_fsm:
+            return self.step_fsm_device()
         if self.fsm:
             return self.step_fsm()
         stamp = self.t0 + self.tick * TICK_PERIOD

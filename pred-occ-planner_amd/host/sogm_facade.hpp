@@ -356,6 +356,9 @@ class Planner {
   void setPrestamp(const SogmPrestamp *next_tick) {
     check(sogm_planner_set_prestamp(p_, next_tick), "sogm_planner_set_prestamp");
   }
+  // The reference plans only in NEW_PLAN and REPLAN (plan_manager.cpp:110-135,164-175): later replan() calls plan only
+  // the agents with due[a] != 0 (dev int32 [n_agents], e.g. Fsm::due()); nullptr = every agent (sogm_planner_set_due)
+  void setDue(const int32_t *due_dev_or_null) { check(sogm_planner_set_due(p_, due_dev_or_null), "sogm_planner_set_due"); }
   // n ticks of every agent in one call, every agent on its own clock (the reference's drones each run their own FSM,
   // plan_manager.cpp:92-233): sogm_flight_run, see sogm_abi.h "Flight".  Returns the device's verdict after a
   // synchronisation when `wait` is set: false = a device-side wait timed out (sogm_flight_stats hdr[4]).
@@ -376,6 +379,75 @@ class Planner {
   RiskMap          &map_;
   SogmPlannerParams pp_;
   sogm_planner     *p_ = nullptr;
+};
+
+// FiniteStateMachine::FSMCallback (plan_manager/src/plan_manager.cpp:92-233) for n agents: owns the machines' records and
+// the tick's per-agent flags on the device.  A tick is inputs() -> map update, sogm_traj_safe ->
+// Planner::setDue(due()) + Planner::replan -> apply(); both calls are one launch on the caller's stream.
+class Fsm {
+ public:
+  Fsm(int n, const SogmFsmParams &prm, double traj_start0, hipStream_t st = nullptr) : n_(n), prm_(prm) {
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    try {
+      alloc(&state_, nn * sizeof(SogmFsmState));
+      alloc(&due_, nn * sizeof(int32_t));
+      alloc(&reached_, nn * sizeof(int32_t));
+      alloc(&pub_, nn * sizeof(int32_t));
+      alloc(&pos_now_, nn * 3 * sizeof(double));
+      alloc(&hover_start_, nn * sizeof(double));
+      check(sogm_fsm_init(state_, n_, traj_start0, st), "sogm_fsm_init");
+    } catch (...) {
+      release();  // (no destructor runs for a constructor that throws)
+      throw;
+    }
+  }
+  ~Fsm() { release(); }
+  Fsm(const Fsm &)            = delete;
+  Fsm &operator=(const Fsm &) = delete;
+
+  // the head of the tick (:110-135, :165-175): who is due and the replan's start states, start times and map centres
+  void inputs(const SogmTrajRecord *own_records, const double *goals, double stamp, double *hover_inout, double *out_now,
+              double *out_t_start, double *out_pva, float *out_poses, hipStream_t st = nullptr) {
+    check(sogm_fsm_inputs(&prm_, state_, own_records, goals, n_, stamp, hover_inout, out_now, out_t_start, out_pva,
+                          out_poses, pos_now_, due_, reached_, st), "sogm_fsm_inputs");
+  }
+  // the state update and the publication into own_inout (the new record, publishEmptyTrajectory's, or nothing)
+  void apply(const int32_t *ok, const int32_t *safe, const SogmTrajRecord *new_records, const int32_t *drone_ids,
+             SogmTrajRecord *own_inout, double stamp, hipStream_t st = nullptr) {
+    check(sogm_fsm_apply(&prm_, state_, due_, ok, safe, reached_, new_records, drone_ids, pos_now_, own_inout, pub_,
+                         hover_start_, n_, stamp, st), "sogm_fsm_apply");
+  }
+  // device arrays [n] of the last inputs() / apply()
+  const int32_t *due() const { return due_; }
+  const int32_t *reached() const { return reached_; }
+  const int32_t *published() const { return pub_; }  // SOGM_FSM_PUB_*
+  const double  *posNow() const { return pos_now_; }  // [n][3]
+  const double  *hoverStart() const { return hover_start_; }  // start time of the hover record where published() says HOVER
+  // the machines as they stand (synchronises the stream)
+  std::vector<SogmFsmState> states(hipStream_t st = nullptr) const {
+    std::vector<SogmFsmState> out((size_t)n_);
+    if (n_ > 0) {
+      if (hipMemcpyAsync(out.data(), state_, out.size() * sizeof(SogmFsmState), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        throw std::runtime_error("sogm_host::Fsm::states: copy failed");
+    }
+    return out;
+  }
+
+ private:
+  template <typename T>
+  static void alloc(T **p, size_t bytes) {
+    if (hipMalloc((void **)p, bytes) != hipSuccess) throw std::runtime_error("sogm_host::Fsm: hipMalloc failed");
+  }
+  void release() {
+    for (void *q : {(void *)state_, (void *)due_, (void *)reached_, (void *)pub_, (void *)pos_now_, (void *)hover_start_})
+      if (q) (void)hipFree(q);
+  }
+  int            n_;
+  SogmFsmParams  prm_;
+  SogmFsmState  *state_ = nullptr;
+  int32_t       *due_ = nullptr, *reached_ = nullptr, *pub_ = nullptr;
+  double        *pos_now_ = nullptr, *hover_start_ = nullptr;
 };
 
 // Flight audit (sogm_abi.h "flight audit"): owns the accumulators of n_local agents and the event list on the device;

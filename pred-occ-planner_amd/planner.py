@@ -196,6 +196,13 @@ class SogmPlanner:
             check(lib().sogm_planner_set_swarm(self._p, records.data_ptr(), n_records, ego_ids.data_ptr(),
                                                t_now.data_ptr()), "sogm_planner_set_swarm")
 
+    def set_due(self, due=None):
+        """Later replan() calls plan only the agents with due[a] != 0 (device int32 [A], read by those calls and kept
+        alive here; sogm_planner_set_due); the others end like a failed search — ok 0, an empty record — without
+        searching and are not counted.  None: every agent plans."""
+        self._due = due
+        check(lib().sogm_planner_set_due(self._p, due.data_ptr() if due is not None else None), "sogm_planner_set_due")
+
     def setPublish(self, own_records, next_table=None):
         """replan() then also merges every successful record into `own_records` and writes each agent's current
         record into `next_table` (sogm_planner_set_publish); None switches it off.  Tensors are kept alive here."""
