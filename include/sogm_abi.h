@@ -726,7 +726,8 @@ int sogm_planner_set_swarm(sogm_planner *p, const SogmTrajRecord *records, int n
  * mask set, later sogm_replan() calls plan only the agents with due[a] != 0 (dev int32 [n_agents], read by those calls:
  * sogm_fsm_inputs' out_due).  An agent that is not due ends like a replan whose search found no path — out_ok 0, an
  * empty record, its published record kept — without expanding a node, and moves none of sogm_planner_counters.
- * NULL (the default): every agent plans.  sogm_flight_run ignores the mask.
+ * NULL (the default): every agent plans.  sogm_flight_run does not look at the mask: a flight runs the machines itself,
+ * per agent, once they are registered with sogm_planner_set_flight_fsm.
  * The planner keeps the POINTER, not a copy: the mask stays in force for every later sogm_replan() until another call
  * replaces it or passes NULL, each of those calls reads the buffer's contents as they are when its searches run (stream
  * order), and the buffer must stay allocated until they have completed or the mask has been replaced.
@@ -874,6 +875,40 @@ typedef struct SogmFlight {
                                             one process owns every row, or the host all-gathers between calls of two ticks */
 } SogmFlight;
 int sogm_flight_run(sogm_planner *p, const SogmFlight *flight, void *stream);
+/*
+ * The flight under the per-agent FSM (opt-in; without it a flight replans every agent in every tick, as above).  With a
+ * SogmFlightFsm registered, agent a's tick k of a later sogm_flight_run is ONE FiniteStateMachine::FSMCallback
+ * (plan_manager/src/plan_manager.cpp:92-233) under the flight's staleness rule:
+ *   head    sogm_fsm_inputs for the agent, from state_inout[a] and its own record of tick k - 1: who is due, the planning
+ *           start time (the stamp, or stamp + prm.replan_start_time in REPLAN — SogmFlight::replan_start_offset is not
+ *           used), the start state sampled there, and the position at the stamp: the map centre, the refreshed hover row
+ *           and the goal test;
+ *   map     as without the mode (every agent, due or not: isTrajSafe needs it);
+ *   search  only where the agent is due; an agent that is not due goes the way sogm_planner_set_due describes (no
+ *           expansion, statistics 0/0/0/0, corridors / QP / finish see a failed search, no outcome counter moves);
+ *   finish  BaselinePlanner::isTrajSafe(check_duration) (baseline.cpp:45-68, sogm_traj_safe's verdict bit for bit) of the
+ *           record the agent executes against its complete map of this tick, the replan's finish, then sogm_fsm_apply for
+ *           the agent: the state back into state_inout[a], and for SOGM_FSM_PUB_HOVER publishEmptyTrajectory's record
+ *           (plan_manager.cpp:404-424) into own_inout[a] and the agent's row of ver(k).
+ * log_ok[k][a] is then the replan's ok as the due gate leaves it (0 where the agent was not due) and log_records[k][a] the
+ * replan's output record (empty where the agent was not due or its replan failed): a lock-step tick's sogm_replan outputs
+ * under sogm_planner_set_due.  No kernel gains a wait: the head's results travel in per-agent arrays beside the start state.
+ * The struct is COPIED at the call and its pointers are kept: it is in force for every later sogm_flight_run until another
+ * call replaces it or passes NULL (off, the default); sogm_replan never looks at it.  SOGM_ERR_INVALID_ARG (with a
+ * sogm_last_error text): state_inout NULL, a parameter that is negative or not finite; sogm_flight_run returns the same
+ * while the mode is on and n_total != n_agents (flights of several ranks under the FSM are not supported).
+ */
+typedef struct SogmFlightFsm {
+  SogmFsmParams   prm;
+  double          check_duration;   /* isTrajSafe's horizon, fsm/colli_check_duration (0.2) */
+  SogmFsmState   *state_inout;      /* dev [A]: in = states before the call's first tick, out = after its last */
+  /* per-tick logs of the NEXT flight, dev, each may be NULL; [n_ticks][A] unless noted */
+  SogmFsmState   *log_state;        /* state after the tick */
+  int32_t        *log_due, *log_safe, *log_reached, *log_pub;
+  double         *log_hover_start;
+  SogmTrajRecord *log_own;          /* the record the agent executes after the tick (own_inout[a] at its finish) */
+} SogmFlightFsm;
+int sogm_planner_set_flight_fsm(sogm_planner *p, const SogmFlightFsm *fsm_or_null);
 /* Optional: creates the flight's control block and its five streams (four masked ones + the exchange stream), runs an empty
  * kernel on each, so that their hardware queues exist before any flight is in the air, and allocates what the first
  * sogm_flight_run would allocate (crop lists for frames of up to max_cloud_points points, the stamp's scratch) — the first

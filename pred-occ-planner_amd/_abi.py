@@ -154,6 +154,12 @@ class SogmFsmState(C.Structure):
                 ("reserved_", C.c_int32)]
 
 
+class SogmFlightFsm(C.Structure):
+    _fields_ = [("prm", SogmFsmParams), ("check_duration", C.c_double), ("state_inout", C.c_void_p),
+                ("log_state", C.c_void_p), ("log_due", C.c_void_p), ("log_safe", C.c_void_p), ("log_reached", C.c_void_p),
+                ("log_pub", C.c_void_p), ("log_hover_start", C.c_void_p), ("log_own", C.c_void_p)]
+
+
 FSM_STATE_BYTES = C.sizeof(SogmFsmState)  # 24
 FSM_PUB_NONE, FSM_PUB_NEW, FSM_PUB_HOVER = 0, 1, 2  # sogm_fsm_apply's out_pub
 
@@ -244,6 +250,7 @@ PROTOTYPES = {
     "sogm_flight_stats": (_i, [_vp, _vp, _vp]),
     "sogm_planner_set_swarm": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sogm_planner_set_due": (_i, [_vp, _vp]),
+    "sogm_planner_set_flight_fsm": (_i, [_vp, C.POINTER(SogmFlightFsm)]),
     "sogm_audit_init_agents": (_i, [_vp, _i, _vp]),
     "sogm_swarm_audit": (_i, [C.POINTER(SogmAuditParams), _vp, _i, _i, _vp, C.c_double, _i, C.c_double, _i, _i, _vp, _vp,
                               _vp, _i, _vp, _vp, _vp, _vp]),

@@ -1056,10 +1056,10 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_flight_search(
     MapView m, SogmAstarParams ap, double corridor_tau, AstarWorkspace wsp, FlightCtl fl,
     const double *__restrict__ start_pva, const double *__restrict__ goal, const double *__restrict__ t_start,
     int32_t *__restrict__ out_ret, double *__restrict__ out_route, int32_t *__restrict__ out_route_len, int route_cap,
-    int32_t *__restrict__ out_stats, int spec) {
+    int32_t *__restrict__ out_stats, int spec, const int32_t *due) {
   const SearchIO io{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = out_ret,
                     .out_route = out_route, .out_route_len = out_route_len, .route_cap = route_cap,
-                    .out_stats = out_stats};
+                    .out_stats = out_stats, .due = due};
   __shared__ int s_item;
   const int tid   = threadIdx.x;
   const int per   = spec ? 2 : 1;
@@ -1076,8 +1076,11 @@ __global__ __launch_bounds__(ASTAR_THREADS) void k_flight_search(
     const int second = spec ? (t & 1) : 0;
     const int k      = fl.tick_of[agent];
     if (tid == 0 && !second) fl.ts[agent * FL_TS + 0] = wall_clock64();
+    // the FSM mode (sogm_planner_set_flight_fsm): the head of the agent's tick wrote its due bits in front of the map's
+    // first descriptor; read here, behind the acquire of the agent's ring entry (not __restrict__: rewritten every tick)
+    const bool skip = io.due != nullptr && io.due[agent] == 0;
     const bool mine = astar_search_wg(m, ap, corridor_tau, wsp, io, nullptr, 0, agent, second, spec != 0, 4 * (k + 1),
-                                      &fl.hdr[FL_ERR], 0);
+                                      &fl.hdr[FL_ERR], 0, skip);
     if (mine && tid == ASTAR_MASTER) {
       fl.ts[agent * FL_TS + 1] = wall_clock64();
       wq_push(fl.lw, &fl.hdr[FL_LW_TAIL], wk_pack(WK_CORRIDOR, 0, agent), SOGM_MAX_PIECES);
@@ -1089,7 +1092,7 @@ hipError_t launch_flight_search(const MapView &m, const SogmAstarParams &ap, dou
                                 const FlightCtl &fl, int n_workgroups, const SearchIO &io, int spec, hipStream_t st) {
   hipLaunchKernelGGL(k_flight_search, dim3(n_workgroups), dim3(ASTAR_THREADS), 0, st, m, ap, corridor_tau, wsp, fl,
                      io.start_pva, io.goal, io.t_start, io.out_ret, io.out_route, io.out_route_len, io.route_cap,
-                     io.out_stats, spec);
+                     io.out_stats, spec, io.due);
   return hipGetLastError();
 }
 

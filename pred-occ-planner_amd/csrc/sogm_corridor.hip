@@ -24,6 +24,7 @@
 #include <cfloat>
 
 #include "../../include/sogm_detmath.h"
+#include "sogm_fsm.hpp"
 #include "sogm_lp.hpp"
 #include "sogm_planner.hpp"
 
@@ -1818,6 +1819,51 @@ __global__ __launch_bounds__(64) void k_finish_flow(FlowCtl fc, FinishArgs f, in
   }
 }
 
+// The finish of a flight under the per-agent FSM (sogm_planner_set_flight_fsm), one wave, in two halves around finish_agent.
+// Before it (finish_agent overwrites own[a]): BaselinePlanner::isTrajSafe of the record the agent executes against its
+// complete map of this tick — traj_safe_agent, a lane per sample of the accumulated time sequence, the verdict is the AND.
+__device__ inline int flight_fsm_traj_safe(const MapView &m, const FlightFsmDev &u, const FinishArgs &f, int a, int lane) {
+  const int mine = traj_safe_agent(m, a, f.pub_own[a], f.swarm_now[a], u.check_duration, lane, 64);
+  return __ballot(mine == 0) == 0ull ? 1 : 0;
+}
+// Behind it: sogm_fsm_apply for the agent — fsm_step on lane 0, the state back into the caller's record, the hover record
+// (publishEmptyTrajectory) into own[a] and the agent's row of ver(k); SOGM_FSM_PUB_NEW needs nothing: due && ok publishes in
+// both planning states and finish_agent has published — and the tick's row of the logs.
+__device__ inline void flight_fsm_apply(const FlightFsmDev &u, const FinishArgs &f, int a, size_t row, bool ok, int safe,
+                                        int lane) {
+  const double stamp = f.swarm_now[a];
+  int          kind  = 0;
+  double       start = 0.0;
+  if (lane == 0) {
+    SogmFsmState  s       = u.state[a];
+    const int32_t due     = u.due[a], reached = u.reached[a];
+    const FsmPub  pub     = fsm_step(s, due, ok, safe != 0, reached != 0, stamp, u.prm);
+    u.state[a]            = s;
+    kind                  = pub.kind;
+    start                 = pub.hover_start;
+    if (u.log_state) u.log_state[row] = s;
+    if (u.log_due) u.log_due[row] = due;
+    if (u.log_safe) u.log_safe[row] = safe;
+    if (u.log_reached) u.log_reached[row] = reached;
+    if (u.log_pub) u.log_pub[row] = pub.kind;
+    if (u.log_hover_start) u.log_hover_start[row] = pub.hover_start;
+  }
+  kind  = __shfl(kind, 0, 64);
+  start = __shfl(start, 0, 64);
+  if (kind == SOGM_FSM_PUB_HOVER) {  // (wave-uniform)
+    const double p[3] = {u.pos_now[a * 3], u.pos_now[a * 3 + 1], u.pos_now[a * 3 + 2]};
+    fsm_hover_record(f.pub_own[a], f.drone_ids[a], p, start, lane, 64);
+    if (f.pub_table) fsm_hover_record(f.pub_table[a], f.drone_ids[a], p, start, lane, 64);
+  }
+  if (u.log_own) {  // what the agent executes after the tick: own[a] as this wave's lanes have just left it
+    __threadfence();
+    constexpr int W   = (int)(sizeof(SogmTrajRecord) / 16);
+    const uint4  *src = reinterpret_cast<const uint4 *>(f.pub_own + a);
+    uint4        *dst = reinterpret_cast<uint4 *>(u.log_own + row);
+    for (int w = lane; w < W; w += 64) dst[w] = src[w];
+  }
+}
+
 // Flight kernel L (sogm_flight_run): role-less one-wave workgroups over the corridor + finish work queue.  A wave takes a
 // ticket (one atomicAdd), waits for the descriptor at that position and does what it says.  WK_CORRIDOR: one of the 16
 // segment slots of an agent whose search is done, as in k_corridor_flow; the wave that completes the agent's last slot
@@ -1867,7 +1913,11 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       f.pub_table  = d.tables ? d.tables + (size_t)(k & 3) * d.n_total + d.agent0 : nullptr;
       f.out        = d.log_records + (size_t)kl * fl.n_agents;
       f.out_ok     = d.log_ok + (size_t)kl * fl.n_agents;
+      // the FSM mode (d.fsm.state set): isTrajSafe in front of finish_agent, the state update and the hover record behind it
+      int traj_safe = 1;
+      if (d.fsm.state) traj_safe = flight_fsm_traj_safe(m, d.fsm, f, a, lane);
       const int code = finish_agent(f, a, LpLds::carve(smem), lane);
+      if (d.fsm.state) flight_fsm_apply(d.fsm, f, a, (size_t)kl * fl.n_agents + a, (code & 2) != 0, traj_safe, lane);
       __syncthreads();
       __threadfence();  // the record (own, ver(k), log) is out before the tick counts as finished
       if (lane == 0) {

@@ -435,6 +435,32 @@ __device__ inline void bezier_pos(const SogmTrajRecord &r, double t, double out[
   }
 }
 
+// BaselinePlanner::isTrajSafe (plan_manager/src/baseline.cpp:45-68) for one agent: the executed record is sampled every
+// 0.1 s from "now" up to min(T, duration) and the agent's SOGM queried at the sample's time after the map stamp.  The sample
+// times are the reference's ACCUMULATED sum (t += 0.1 from t0): every caller walks the whole sequence and evaluates the
+// samples first, first + stride, ... of it — (0, 1): all of them, returning at the first hit (k_traj_safe's lane);
+// (lane, 64): a wave's share (the finish of a flight under the FSM mode, which ORs the lanes' verdicts).  Returns 1 while no
+// evaluated sample is occupied.
+__device__ inline int traj_safe_agent(const MapView &m, int a, const SogmTrajRecord &r, double t_now, double T, int first,
+                                      int stride) {
+  if (r.n_pieces <= 0) return 1;  // nothing is being executed
+  double t0 = t_now - r.time_start;
+  if (t0 < 0) t0 = 0;
+  if (t0 > T) return 1;
+  double dur = 0;
+  for (int k = 0; k < r.n_pieces; ++k) dur += r.duration[k];
+  T = T > dur ? dur : T;
+  int j = 0;
+  for (double t = t0; t < T; t += 0.1, ++j) {
+    if (j % stride != first) continue;
+    double p[3];
+    bezier_pos(r, t, p);
+    const double dt = t + r.time_start - m.stamps[a];
+    if (query_clear_time(m, a, p[0], p[1], p[2], dt) == 1) return 0;
+  }
+  return 1;
+}
+
 // (shared by sogm_map.hip, sogm_audit.hip and sogm_fsm.hip)
 // Bezier pos / vel / acc of a trajectory record at an absolute time (bernstein.cpp:25-59)
 // returns false (and zeros) for an empty record

@@ -30,27 +30,10 @@ __global__ __launch_bounds__(64) void k_fsm_inputs(SogmFsmParams prm, const Sogm
                                                    int32_t *__restrict__ due, int32_t *__restrict__ reached) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= n) return;
-  const FsmDue d = fsm_due(state[a], stamp, prm);
-  double       hov[9], pn[9], o[9];
+  double hov[9];
   for (int k = 0; k < 9; ++k) hov[k] = hover[a * 9 + k];
-  if (!traj_eval_record(own[a], stamp, pn))
-    for (int k = 0; k < 9; ++k) pn[k] = hov[k];
-  if (!traj_eval_record(own[a], d.t_start, o))
-    for (int k = 0; k < 9; ++k) o[k] = hov[k];
-  for (int k = 0; k < 9; ++k) pva[a * 9 + k] = o[k];
-  for (int k = 0; k < 3; ++k) {
-    hover[a * 9 + k]     = pn[k];
-    hover[a * 9 + 3 + k] = 0.0;
-    hover[a * 9 + 6 + k] = 0.0;
-    poses[a * 3 + k]     = (float)pn[k];
-    pos_now[a * 3 + k]   = pn[k];
-  }
-  now[a]     = stamp;
-  t_start[a] = d.t_start;
-  due[a]     = d.bits;
-  // isGoalReached: |position - goal| < goal_tolerance
-  const double dx = pn[0] - goals[a * 3], dy = pn[1] - goals[a * 3 + 1], dz = pn[2] - goals[a * 3 + 2];
-  reached[a] = sogm_det::sqrt_rn((dx * dx + dy * dy) + dz * dz) < prm.goal_tolerance ? 1 : 0;
+  fsm_inputs_agent(prm, state[a], own[a], hov, goals + a * 3, a, stamp, hover, now, t_start, pva, poses, pos_now, due, reached,
+                   [](const SogmTrajRecord &r, double t, double *o) { return traj_eval_record(r, t, o); });
 }
 
 // The rest of the tick, one wave per agent: lane 0 runs fsm_step, then the wave publishes — the tick's new record
@@ -84,15 +67,8 @@ __global__ __launch_bounds__(64) void k_fsm_apply(SogmFsmParams prm, SogmFsmStat
     uint4        *dst = reinterpret_cast<uint4 *>(own + a);
     for (int w = lane; w < W; w += 64) dst[w] = src[w];
   } else if (kind == SOGM_FSM_PUB_HOVER) {
-    SogmTrajRecord &r = own[a];
-    const double    p[3] = {pos_now[a * 3], pos_now[a * 3 + 1], pos_now[a * 3 + 2]};
-    for (int i = lane; i < SOGM_MAX_PIECES; i += 64) r.duration[i] = i == 0 ? 0.5 : 0.0;
-    for (int i = lane; i < SOGM_MAX_PIECES * 15; i += 64) r.cpts[i] = i < 15 ? p[i % 3] : 0.0;
-    if (lane == 0) {
-      r.drone_id   = drone_ids[a];
-      r.n_pieces   = 1;
-      r.time_start = s_start;
-    }
+    const double p[3] = {pos_now[a * 3], pos_now[a * 3 + 1], pos_now[a * 3 + 2]};
+    fsm_hover_record(own[a], drone_ids[a], p, s_start, lane, 64);
   }
 }
 

@@ -3,6 +3,10 @@
 // update and what is published).  The kernels behind sogm_fsm_inputs / sogm_fsm_apply call them per agent; the host
 // compiles them too (tests/fsm_rules_host_test.cpp).  Plain fp64 compares and single additions / subtractions: nothing a
 // contraction could change.
+// Below the rules, the per-agent bodies around them — fsm_inputs_agent (the head of a tick) and fsm_hover_record
+// (publishEmptyTrajectory's record) — which the stand-alone kernels of sogm_fsm.hip and the flight's kernels
+// (sogm_planner_set_flight_fsm: the head of k_flight_map, the finish of k_flight_light) both call; the host compiles these
+// too (tests/flight_fsm_host_test.cpp).
 #pragma once
 
 #include <cstdint>
@@ -14,6 +18,7 @@
 #endif
 
 #include "../../include/sogm_abi.h"
+#include "../../include/sogm_detmath.h"
 
 namespace sogm {
 
@@ -80,6 +85,51 @@ SOGM_FSM_HD inline FsmPub fsm_step(SogmFsmState &s, int32_t due, bool ok, bool s
     if (reached) s.status = FSM_GOAL_REACHED;  // tested last: a reached goal wins over the lapse
   }
   return pub;
+}
+
+// The head of one FSMCallback for one agent (k_fsm_inputs' lane, the admitting wave of a flight under the FSM mode): who
+// plans and from when (fsm_due), the own record sampled at the stamp (where the agent is: map centre, hover point, goal
+// test) and at the planning start time (the replan's start state, :169-175); an agent that executes nothing stands where it
+// hovers (odom, :127-133).  `hov` is a COPY of the agent's hover row (the row itself is refreshed here); `eval(rec, t, out9)`
+// is sogm_device.hpp's traj_eval_record on the device (a host caller brings its own reading of Bezier::getPos / Vel / Acc).
+template <class Eval>
+SOGM_FSM_HD inline void fsm_inputs_agent(const SogmFsmParams &prm, const SogmFsmState &s, const SogmTrajRecord &rec,
+                                         const double *hov, const double *goal, int a, double stamp, double *hover,
+                                         double *now, double *t_start, double *pva, float *poses, double *pos_now,
+                                         int32_t *due, int32_t *reached, Eval eval) {
+  const FsmDue d = fsm_due(s, stamp, prm);
+  double       pn[9], o[9];
+  if (!eval(rec, stamp, pn))
+    for (int k = 0; k < 9; ++k) pn[k] = hov[k];
+  if (!eval(rec, d.t_start, o))
+    for (int k = 0; k < 9; ++k) o[k] = hov[k];
+  for (int k = 0; k < 9; ++k) pva[a * 9 + k] = o[k];
+  for (int k = 0; k < 3; ++k) {
+    hover[a * 9 + k]     = pn[k];
+    hover[a * 9 + 3 + k] = 0.0;
+    hover[a * 9 + 6 + k] = 0.0;
+    poses[a * 3 + k]     = (float)pn[k];
+    pos_now[a * 3 + k]   = pn[k];
+  }
+  now[a]     = stamp;
+  t_start[a] = d.t_start;
+  due[a]     = d.bits;
+  // isGoalReached: |position - goal| < goal_tolerance
+  const double dx = pn[0] - goal[0], dy = pn[1] - goal[1], dz = pn[2] - goal[2];
+  reached[a] = sogm_det::sqrt_rn((dx * dx + dy * dy) + dz * dz) < prm.goal_tolerance ? 1 : 0;
+}
+
+// publishEmptyTrajectory's record (plan_manager.cpp:404-424): one 0.5 s piece whose five control points sit at the agent's
+// position `p`, start time `start`.  Lane `lane` of `n_lanes` writes its share of the words (a host caller: 0 of 1).
+SOGM_FSM_HD inline void fsm_hover_record(SogmTrajRecord &r, int32_t drone_id, const double *p, double start, int lane,
+                                         int n_lanes) {
+  for (int i = lane; i < SOGM_MAX_PIECES; i += n_lanes) r.duration[i] = i == 0 ? 0.5 : 0.0;
+  for (int i = lane; i < SOGM_MAX_PIECES * 15; i += n_lanes) r.cpts[i] = i < 15 ? p[i % 3] : 0.0;
+  if (lane == 0) {
+    r.drone_id   = drone_id;
+    r.n_pieces   = 1;
+    r.time_start = start;
+  }
 }
 
 }  // namespace sogm

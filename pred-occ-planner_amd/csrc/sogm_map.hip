@@ -21,6 +21,7 @@
 #include <new>
 
 #include "sogm_device.hpp"
+#include "sogm_fsm.hpp"
 #include "sogm_planner.hpp"  // FlowCtl: the pre-stamp consumes the dataflow replan's list of finished agents
 
 namespace sogm {
@@ -1386,7 +1387,12 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
       __syncthreads();
       const double stamp = d.t0 + k * d.period;
       if (lane == 0) {
-        tick_inputs_agent(s_rec, s_hov, agent, stamp, d.start_offset, d.hover, d.now, d.t_start, d.pva, d.poses);
+        if (d.fsm.state)  // the head of one FSMCallback (sogm_planner_set_flight_fsm): k_fsm_inputs' body for this agent
+          fsm_inputs_agent(d.fsm.prm, d.fsm.state[agent], s_rec, s_hov, d.fsm.goals + agent * 3, agent, stamp, d.hover, d.now,
+                           d.t_start, d.pva, d.poses, d.fsm.pos_now, d.fsm.due, d.fsm.reached,
+                           [](const SogmTrajRecord &r, double t, double *o) { return traj_eval_record(r, t, o); });
+        else
+          tick_inputs_agent(s_rec, s_hov, agent, stamp, d.start_offset, d.hover, d.now, d.t_start, d.pva, d.poses);
         d.stamps[agent] = stamp;
       }
       __threadfence();
@@ -1547,31 +1553,7 @@ __global__ __launch_bounds__(64) void k_traj_safe(MapView m, const SogmTrajRecor
                                                   int32_t *__restrict__ out) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= m.n_agents) return;
-  const SogmTrajRecord &r = rec[a];
-  if (r.n_pieces <= 0) {  // nothing is being executed
-    out[a] = 1;
-    return;
-  }
-  double t0 = t_now[a] - r.time_start;
-  if (t0 < 0) t0 = 0;
-  if (t0 > T) {
-    out[a] = 1;
-    return;
-  }
-  double dur = 0;
-  for (int k = 0; k < r.n_pieces; ++k) dur += r.duration[k];
-  T = T > dur ? dur : T;
-  int safe = 1;
-  for (double t = t0; t < T; t += 0.1) {
-    double p[3];
-    bezier_pos(r, t, p);
-    const double dt = t + r.time_start - m.stamps[a];
-    if (query_clear_time(m, a, p[0], p[1], p[2], dt) == 1) {
-      safe = 0;
-      break;
-    }
-  }
-  out[a] = safe;
+  out[a] = traj_safe_agent(m, a, rec[a], t_now[a], T, 0, 1);
 }
 
 // row length of the stamp's occupancy bitmask (one row per agent): k_stamp_marks reads 256 words per trip

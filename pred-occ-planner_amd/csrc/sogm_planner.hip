@@ -4,6 +4,7 @@
 // (replan_impl).  SOGM_ERR_STATE from an entry point means a call-order error (no map update before planning).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -578,6 +579,33 @@ int sogm_planner_set_due(sogm_planner *p, const int32_t *due_dev_or_null) {
   return SOGM_OK;
 }
 
+int sogm_planner_set_flight_fsm(sogm_planner *p, const SogmFlightFsm *fsm) {
+  if (!p) return SOGM_ERR_INVALID_ARG;
+  if (!fsm) {
+    p->fl_fsm_on = 0;
+    p->fl_fsm    = SogmFlightFsm{};
+    return SOGM_OK;
+  }
+  if (!fsm->state_inout) {
+    sogm::set_error_text("sogm_planner_set_flight_fsm: state_inout is NULL");
+    return SOGM_ERR_INVALID_ARG;
+  }
+  const double v[5] = {fsm->prm.replan_duration, fsm->prm.replan_start_time, fsm->prm.goal_tolerance,
+                       fsm->prm.new_plan_interval, fsm->check_duration};
+  for (double x : v)
+    if (!std::isfinite(x) || x < 0.0) {
+      sogm::set_error_text("sogm_planner_set_flight_fsm: the parameters must be finite and not negative");
+      return SOGM_ERR_INVALID_ARG;
+    }
+  if (fsm->prm.replan_max_failures < 0) {
+    sogm::set_error_text("sogm_planner_set_flight_fsm: replan_max_failures must not be negative");
+    return SOGM_ERR_INVALID_ARG;
+  }
+  p->fl_fsm    = *fsm;
+  p->fl_fsm_on = 1;
+  return SOGM_OK;
+}
+
 int sogm_planner_set_swarm(sogm_planner *p, const SogmTrajRecord *records, int n_records,
                            const int32_t *ego_ids, const double *t_now) {
   if (!p || n_records < 0 || (records && (!ego_ids || !t_now))) return SOGM_ERR_INVALID_ARG;
@@ -1141,6 +1169,10 @@ static int flight_setup(sogm_planner *p) {
   SOGM_HIP_CHECK(p->res.device(&p->d_fl_pva, sizeof(double) * 9 * (size_t)A));
   SOGM_HIP_CHECK(p->res.device(&p->d_fl_tstart, sizeof(double) * (size_t)A));
   SOGM_HIP_CHECK(p->res.device(&p->d_fl_now, sizeof(double) * (size_t)A));
+  // the head's hand-over arrays of the FSM mode (sogm_planner_set_flight_fsm)
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_due, sizeof(int32_t) * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_reached, sizeof(int32_t) * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_fl_posnow, sizeof(double) * 3 * (size_t)A));
   // the four streams and their compute units: QP, search, map take flight_*_units units of 16 CUs, corridor + finish
   // the rest; workgroups = what the partition holds at once (every workgroup of a flight kernel is resident from the
   // start: nothing waits for a workgroup that is not running)
@@ -1201,6 +1233,10 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
   sogm_ctx *c = p->map;
   const int A = c->n_agents;
   if (f->n_total < A || f->agent0 < 0 || f->agent0 + A > f->n_total) return SOGM_ERR_INVALID_ARG;
+  if (p->fl_fsm_on && f->n_total != A) {
+    sogm::set_error_text("sogm_flight_run: under sogm_planner_set_flight_fsm a flight has n_total == n_agents (one process owns every row)");
+    return SOGM_ERR_INVALID_ARG;
+  }
   const bool xchg = f->n_total != A && f->nccl_comm != nullptr;  // the exchange runs behind the call (k_flight_xwait / xsignal)
   const int lag = c->tune_i(SOGM_TUNE_FLIGHT_NEIGHBOUR_LAG) == 1 ? 1 : 2;
   if (f->n_total != A && !xchg && f->n_ticks > lag) {
@@ -1324,6 +1360,17 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
   md.pace_ticks  = (int)(c->tune[SOGM_TUNE_FLIGHT_PACE_US] * 100.0);
   md.agent_bytes = agent_bytes;
   md.reset_stat  = c->d_reset_stat;
+  // the per-agent FSM (sogm_planner_set_flight_fsm); all null: off
+  sogm::FlightFsmDev fd{};
+  if (p->fl_fsm_on) {
+    const SogmFlightFsm &u = p->fl_fsm;
+    fd = sogm::FlightFsmDev{.prm = u.prm, .check_duration = u.check_duration, .state = u.state_inout, .goals = f->goals,
+                            .due = p->d_fl_due, .reached = p->d_fl_reached, .pos_now = p->d_fl_posnow,
+                            .log_state = u.log_state, .log_due = u.log_due, .log_safe = u.log_safe,
+                            .log_reached = u.log_reached, .log_pub = u.log_pub, .log_hover_start = u.log_hover_start,
+                            .log_own = u.log_own};
+  }
+  md.fsm = fd;
   const MapView mv = view_of(c);
   // frames + control block, in stream order on the caller's stream
   SOGM_HIP_CHECK(hipMemcpyAsync(p->d_fl_worlds, p->h_fl_worlds, sizeof(FlightWorld) * (size_t)f->n_ticks, hipMemcpyHostToDevice, main));
@@ -1342,9 +1389,11 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
   // QP first, then search (each wants whole CUs), then the one-wave kernels: with masks the order is immaterial
   const int spec = c->tune_i(SOGM_TUNE_FLIGHT_SPEC) != 0 ? 1 : 0;
   hipError_t e = sogm::launch_flight_qp(p->pp, p->qs, p->qw, p->qc, fl, p->fl_wgs[0], qp_io(p, p->d_fl_pva), p->fl_stream[0]);
-  if (e == hipSuccess)
-    e = sogm::launch_flight_search(mv, p->ap, p->pp.corridor_tau, astar_ws(p), fl, p->fl_wgs[1],
-                                   search_io(p, p->d_fl_pva, f->goals, p->d_fl_tstart), spec, p->fl_stream[1]);
+  if (e == hipSuccess) {
+    sogm::SearchIO sio = search_io(p, p->d_fl_pva, f->goals, p->d_fl_tstart);
+    sio.due            = fd.state ? fd.due : nullptr;  // (never sogm_planner_set_due's mask)
+    e = sogm::launch_flight_search(mv, p->ap, p->pp.corridor_tau, astar_ws(p), fl, p->fl_wgs[1], sio, spec, p->fl_stream[1]);
+  }
   if (int rc = launched("sogm_flight_run: launch", e)) {
     (void)hipDeviceSynchronize();
     return rc;
@@ -1356,7 +1405,9 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
   ld.fin = sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
                             .status = p->d_status, .cpts = p->d_cpts, .n_swarm = f->n_total, .swarm_ego = f->drone_ids,
                             .swarm_now = p->d_fl_now, .t_start = p->d_fl_tstart, .drone_ids = f->drone_ids,
-                            .out_safe = p->d_safe, .counters = p->cw.counters, .pub_own = f->own_inout};
+                            .out_safe = p->d_safe, .counters = p->cw.counters, .pub_own = f->own_inout,
+                            .due = fd.state ? fd.due : nullptr};
+  ld.fsm         = fd;
   ld.tables      = f->tables;
   ld.n_total     = f->n_total;
   ld.agent0      = f->agent0;

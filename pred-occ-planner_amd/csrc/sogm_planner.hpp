@@ -53,6 +53,23 @@ __device__ inline void fl_wg_started(const FlightCtl &fl, int kernel) {
   }
 }
 #endif
+// The flight under the per-agent FSM (sogm_planner_set_flight_fsm; state == null: off, the flight as it is without it).
+// What the head of an agent's tick hands to its search and its finish travels in the per-agent arrays due / reached /
+// pos_now, like pva and t_start: written by the head in front of its wq_push, read behind the acquire the reader
+// performs anyway.  Only the agent's own chain touches state[a]: the head reads it, the finish writes it.
+struct FlightFsmDev {
+  SogmFsmParams   prm;
+  double          check_duration;  // isTrajSafe's horizon
+  SogmFsmState   *state;           // [A] the caller's records
+  const double   *goals;           // [A][3]
+  int32_t        *due, *reached;   // [A] fsm_due's bits / isGoalReached of the agent's current tick
+  double         *pos_now;         // [A][3] where the agent is at its current tick's stamp
+  // the call's logs, each may be null; row of tick first_tick + i at [i][A]
+  SogmFsmState   *log_state;
+  int32_t        *log_due, *log_safe, *log_reached, *log_pub;
+  double         *log_hover_start;
+  SogmTrajRecord *log_own;
+};
 // the map role's arguments (csrc/sogm_map.hip, k_flight_map)
 struct FlightMapDev {
   void                 *grid;          // the context's current grid (all agents)
@@ -82,6 +99,7 @@ struct FlightMapDev {
   int                   pace_ticks;    // 100 MHz ticks between two admissions (0 = as fast as the heads run)
   size_t                agent_bytes;
   unsigned long long   *reset_stat;    // the context's reset statistics (sogm_sparse_reset_state / sogm_map_traffic), or null
+  FlightFsmDev          fsm;           // the head of a tick under the FSM mode (fsm.state null: tick_inputs_agent, as before)
 };
 hipError_t launch_flight_map(const GridGeom &g, const FlightCtl &fl, const FlightMapDev &d, int n_workgroups, hipStream_t st);
 
@@ -95,8 +113,9 @@ struct SearchIO {  // search: start state, goal and start time in, return code /
   int32_t      *out_route_len;
   int           route_cap;
   int32_t      *out_stats;
-  // sogm_planner_set_due's mask (null: every agent searches).  Only launch_astar hands it to its kernel: sogm_replan's
-  // searches.  launch_flight_search does not, which is how sogm_flight_run ignores the mask.
+  // who searches (null: every agent).  launch_astar: sogm_planner_set_due's mask, sogm_replan's searches.
+  // launch_flight_search: the due bits the head of the agent's tick wrote under sogm_planner_set_flight_fsm — never
+  // sogm_planner_set_due's mask, which a flight does not look at.
   const int32_t *due;
 };
 struct CorridorIO {  // corridors: the search's route in, polytopes and the local goal out
@@ -140,6 +159,7 @@ struct FlightLightDev {
   int             n_total, agent0;
   SogmTrajRecord *log_records;  // [n_ticks][A]
   int32_t        *log_ok;       // [n_ticks][A]
+  FlightFsmDev    fsm;          // the finish under the FSM mode (fsm.state null: off)
 };
 struct CorridorWorkspace;
 hipError_t launch_flight_light(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlightCtl &fl,
@@ -299,4 +319,9 @@ struct sogm_planner {
   int                 fl_wgs[4];     // workgroups of each kernel
   int                 fl_epoch = 0;  // number of the last sogm_flight_run call (FlightCtl::epoch)
   int                *fl_xready = nullptr;  // [FLIGHT_MAX_TICKS] FlightCtl::xready of a multi-rank flight
+  // sogm_planner_set_flight_fsm: the caller's struct (fl_fsm_on: registered) and the head's hand-over arrays (flight_setup)
+  int                 fl_fsm_on = 0;
+  SogmFlightFsm       fl_fsm{};
+  int32_t            *d_fl_due = nullptr, *d_fl_reached = nullptr;
+  double             *d_fl_posnow = nullptr;
 };

@@ -632,10 +632,21 @@ class SwarmTick:
         """The next n_ticks ticks of every agent in ONE call (sogm_abi.h "Flight"): agent a's tick k starts when its own tick
         k - 1 is finished and every agent has finished tick k - 2; it reads the neighbours' records of tick k - 2.  Needs
         world frames (moving_world True / False) and a flight flown from tick 0 through fly() only.  Returns (ok [n, A]
-        int32, records uint8 [n, A, 2064]) device tensors — valid once the stream has run the flight."""
+        int32, records uint8 [n, A, 2064]) device tensors — valid once the stream has run the flight.
+        With fsm=True, device_fsm=True every agent-tick is one FSMCallback (sogm_planner_set_flight_fsm): only the agents
+        that are due replan, ok / records are the replan's outputs behind the due gate, self.status / fail / traj_start /
+        own hold the state after the flight, self.flight_fsm_log the call's per-tick log (fsm.FsmState.flight_logs plus
+        "ok" and "new") and self.last_fsm its last tick; with audit=True the audited tables are the log's "own".
+        last_fsm after a flight has the keys "now", "ok", "safe", "reached", "due", "pub_new", "pub_hover" and
+        "hover_start" — step_fsm_device's without "t_start" and "pos", which the head of a flight's tick keeps in the
+        planner's own per-agent arrays and SogmFlightFsm does not log."""
         c = self.compute
         assert getattr(c, "use_world", False), "fly() needs world frames (moving_world=True / False)"
-        assert not self.fsm
+        # the closed loop flies with the machines on the device only (sogm_planner_set_flight_fsm); the torch machines of
+        # fsm=True, device_fsm=False have no flight
+        assert not self.fsm or self.device_fsm
+        if self.device_fsm and self.world > 1:
+            raise NotImplementedError("fly() under the FSM over several ranks: fly step() ticks instead")
         if self.world > 1:
             if self.auditor is not None:
                 # log_r holds this rank's rows only and the four-table ring does not keep the other ranks' versions
@@ -651,9 +662,30 @@ class SwarmTick:
         log_ok = torch.zeros((n_ticks, self.A_loc), dtype=torch.int32, device="cuda")
         worlds = [c.world(self.tick + i) for i in range(n_ticks)]
         executed = self.own.clone() if self.auditor is not None else None   # the table before the call
-        self.planner.flight(worlds, self.tick, self.t0, TICK_PERIOD, REPLAN_START_TIME, self.goals, self.dev["ego_ids"],
-                            self.hover, self.own, self._fl_tables, log_r, log_ok)
-        if self.auditor is not None:
+        fsm_log = None
+        if self.device_fsm:
+            # every agent's tick is one FSMCallback: the machines' records are read and left in place (self.status / fail /
+            # traj_start are views of them), the per-tick log of the call is kept in self.flight_fsm_log
+            fsm_log = self.fsm_dev.flight_logs(n_ticks)
+            self.planner.set_flight_fsm(self.fsm_dev.prm, COLLI_CHECK_DURATION, self.fsm_dev.state, fsm_log)
+        try:
+            self.planner.flight(worlds, self.tick, self.t0, TICK_PERIOD, REPLAN_START_TIME, self.goals,
+                                self.dev["ego_ids"], self.hover, self.own, self._fl_tables, log_r, log_ok)
+        finally:
+            if self.device_fsm:
+                self.planner.set_flight_fsm(None)   # (copied at the call: the flight in the air keeps its mode)
+        if fsm_log is not None:
+            # log_ok / log_r: the replan's outputs as the due gate leaves them (what step_fsm_device has in ok / new)
+            fsm_log["ok"], fsm_log["new"] = log_ok, log_r
+            self.flight_fsm_log = fsm_log
+            self.last_fsm = {"now": self.t0 + (self.tick + n_ticks - 1) * TICK_PERIOD, "ok": log_ok[-1],
+                             "safe": fsm_log["safe"][-1], "reached": fsm_log["reached"][-1], "due": fsm_log["due"][-1],
+                             "pub_new": fsm_log["pub"][-1] == _abi.FSM_PUB_NEW,
+                             "pub_hover": fsm_log["pub"][-1] == _abi.FSM_PUB_HOVER,
+                             "hover_start": fsm_log["hover_start"][-1]}
+            if self.auditor is not None:
+                self.auditor.add(fsm_log["own"], self.t0, self.tick, TICK_PERIOD)   # the executed tables themselves
+        elif self.auditor is not None:
             # the flight's executed tables: latest-wins merges of its log, one launch per tick, then one audit call
             tables = torch.empty((n_ticks, self.A_tot, _abi.TRAJ_RECORD_BYTES), dtype=torch.uint8, device="cuda")
             for i in range(n_ticks):

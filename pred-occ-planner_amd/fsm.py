@@ -52,6 +52,15 @@ class FsmState:
                                    self.pos_now.data_ptr(), own.data_ptr(), self.pub.data_ptr(),
                                    self.hover_start.data_ptr(), self.n, float(stamp), _stream()), "sogm_fsm_apply")
 
+    def flight_logs(self, n_ticks):
+        """the per-tick logs of a flight under the FSM (planner.set_flight_fsm): zeroed device tensors [n_ticks, n]"""
+        dev = self.state.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        return {"state": z((n_ticks, self.n, _abi.FSM_STATE_BYTES), torch.uint8), "due": z((n_ticks, self.n), torch.int32),
+                "safe": z((n_ticks, self.n), torch.int32), "reached": z((n_ticks, self.n), torch.int32),
+                "pub": z((n_ticks, self.n), torch.int32), "hover_start": z((n_ticks, self.n), torch.float64),
+                "own": z((n_ticks, self.n, _abi.TRAJ_RECORD_BYTES), torch.uint8)}
+
     # views of the state records (device tensors sharing the records' memory)
     @property
     def traj_start(self):

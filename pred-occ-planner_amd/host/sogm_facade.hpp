@@ -359,6 +359,12 @@ class Planner {
   // The reference plans only in NEW_PLAN and REPLAN (plan_manager.cpp:110-135,164-175): later replan() calls plan only
   // the agents with due[a] != 0 (dev int32 [n_agents], e.g. Fsm::due()); nullptr = every agent (sogm_planner_set_due)
   void setDue(const int32_t *due_dev_or_null) { check(sogm_planner_set_due(p_, due_dev_or_null), "sogm_planner_set_due"); }
+  // Later flight() calls fly under the per-agent FSM: every agent-tick is one FSMCallback, only the agents that are due
+  // replan (sogm_planner_set_flight_fsm; the struct is copied, its device pointers — e.g. Fsm::state() — are kept);
+  // nullptr = off: every agent replans in every tick.  replan() never looks at it.
+  void setFlightFsm(const SogmFlightFsm *fsm_or_null) {
+    check(sogm_planner_set_flight_fsm(p_, fsm_or_null), "sogm_planner_set_flight_fsm");
+  }
   // n ticks of every agent in one call, every agent on its own clock (the reference's drones each run their own FSM,
   // plan_manager.cpp:92-233): sogm_flight_run, see sogm_abi.h "Flight".  Returns the device's verdict after a
   // synchronisation when `wait` is set: false = a device-side wait timed out (sogm_flight_stats hdr[4]).
@@ -419,6 +425,7 @@ class Fsm {
   }
   // device arrays [n] of the last inputs() / apply()
   const int32_t *due() const { return due_; }
+  SogmFsmState  *state() { return state_; }  // the machines' records, dev [n] (SogmFlightFsm::state_inout for a flight)
   const int32_t *reached() const { return reached_; }
   const int32_t *published() const { return pub_; }  // SOGM_FSM_PUB_*
   const double  *posNow() const { return pos_now_; }  // [n][3]

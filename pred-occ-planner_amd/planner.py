@@ -203,6 +203,24 @@ class SogmPlanner:
         self._due = due
         check(lib().sogm_planner_set_due(self._p, due.data_ptr() if due is not None else None), "sogm_planner_set_due")
 
+    def set_flight_fsm(self, prm=None, check_duration=0.2, state=None, logs=None):
+        """Later flight() calls fly under the per-agent FSM (sogm_planner_set_flight_fsm): `prm` an _abi.SogmFsmParams,
+        `state` the machines' records (device uint8 [A, 24], read before the call's first tick and left as they are after
+        its last), `logs` a dict of device tensors [n_ticks, A] for the NEXT flight — any of "state" (uint8 [n, A, 24]),
+        "due", "safe", "reached", "pub" (int32), "hover_start" (float64), "own" (uint8 [n, A, 2064]).  The tensors are
+        kept alive here.  prm=None switches the mode off."""
+        if prm is None:
+            self._flight_fsm = None
+            check(lib().sogm_planner_set_flight_fsm(self._p, None), "sogm_planner_set_flight_fsm")
+            return
+        logs = dict(logs or {})
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        f = _abi.SogmFlightFsm(prm, float(check_duration), ptr(state), ptr(logs.get("state")), ptr(logs.get("due")),
+                               ptr(logs.get("safe")), ptr(logs.get("reached")), ptr(logs.get("pub")),
+                               ptr(logs.get("hover_start")), ptr(logs.get("own")))
+        self._flight_fsm = (state, logs)
+        check(lib().sogm_planner_set_flight_fsm(self._p, C.byref(f)), "sogm_planner_set_flight_fsm")
+
     def setPublish(self, own_records, next_table=None):
         """replan() then also merges every successful record into `own_records` and writes each agent's current
         record into `next_table` (sogm_planner_set_publish); None switches it off.  Tensors are kept alive here."""

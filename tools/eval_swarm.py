@@ -1,7 +1,10 @@
 """Fly a swarm with the flight audit on and print ONE JSON line: the audit's report (arrivals, collisions of each kind,
 minimum separation and gap) and its cost.
 
-    python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight [--frozen] [--events N]
+    python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight|flight_fsm [--frozen] [--events N]
+
+flight_fsm: the flight with every agent-tick one FSMCallback on the device (sogm_planner_set_flight_fsm) — the closed loop
+of `fsm` on the schedule of `flight`.
 
 ms_per_tick: the same swarm flown twice back to back in this process, audit off then audit on (hip events around the
 whole run after a warm-up swarm); audit_ms_per_tick: device time of the audit's own launches in the audited run (hip
@@ -18,8 +21,9 @@ sys.path.insert(0, ROOT)
 
 def run(driver, args, audit):
     import torch
-    sw = driver.SwarmTick(args.grid, args.agents, moving_world=not args.frozen, prestamp=False if args.mode == "flight" else None,
-                          fsm=args.mode == "fsm", audit=audit)
+    flight = args.mode in ("flight", "flight_fsm")
+    sw = driver.SwarmTick(args.grid, args.agents, moving_world=not args.frozen, prestamp=False if flight else None,
+                          fsm=args.mode in ("fsm", "flight_fsm"), device_fsm=args.mode == "flight_fsm", audit=audit)
     sw.compute.prepare(0, args.ticks)
     audit_ms = []
     if audit:   # time every audit call with events of its own on the same stream
@@ -35,7 +39,7 @@ def run(driver, args, audit):
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     start.record()
-    if args.mode == "flight":
+    if flight:
         done = 0
         while done < args.ticks:
             n = min(60, args.ticks - done)
@@ -58,7 +62,7 @@ def main():
     ap.add_argument("grid")
     ap.add_argument("agents", type=int)
     ap.add_argument("ticks", type=int)
-    ap.add_argument("mode", choices=("lockstep", "fsm", "flight"))
+    ap.add_argument("mode", choices=("lockstep", "fsm", "flight", "flight_fsm"))
     ap.add_argument("--frozen", action="store_true", help="a frozen world (moving_world=False)")
     ap.add_argument("--events", type=int, default=20, help="events printed (the report counts all)")
     args = ap.parse_args()
