@@ -36,14 +36,10 @@ __global__ __launch_bounds__(AUDIT_WG) void k_audit_pos(AuditDims d, const SogmT
                                                         const double *__restrict__ fallback, double *__restrict__ pos) {
   __shared__ __attribute__((aligned(16))) SogmTrajRecord s_rec[2];   // [0] tick k's record, [1] the one before
   const int a = blockIdx.x, k = blockIdx.y;
-  constexpr int W = (int)(sizeof(SogmTrajRecord) / 16);
   const SogmTrajRecord *prev = k > 0 ? tables + (size_t)(k - 1) * d.n_total + a : (prev_table ? prev_table + a : nullptr);
-  const uint4 *src0 = reinterpret_cast<const uint4 *>(tables + (size_t)k * d.n_total + a);
-  uint4       *dst  = reinterpret_cast<uint4 *>(s_rec);
-  for (int w = threadIdx.x; w < W; w += AUDIT_WG) dst[w] = src0[w];
+  copy_record(&s_rec[0], tables + (size_t)k * d.n_total + a, threadIdx.x, AUDIT_WG);
   if (prev) {
-    const uint4 *src1 = reinterpret_cast<const uint4 *>(prev);
-    for (int w = threadIdx.x; w < W; w += AUDIT_WG) dst[W + w] = src1[w];
+    copy_record(&s_rec[1], prev, threadIdx.x, AUDIT_WG);
   } else if (threadIdx.x == 0) {
     s_rec[1].n_pieces = 0;
   }

@@ -1773,12 +1773,8 @@ __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, const Lp
       r->n_pieces   = good ? M : 0;
     }
   }
-  if (!good && f.pub_own && f.pub_table) {  // the table still lists the trajectory the agent goes on executing
-    constexpr int W   = (int)(sizeof(SogmTrajRecord) / 16);
-    const uint4  *src = reinterpret_cast<const uint4 *>(f.pub_own + a);
-    uint4        *t   = reinterpret_cast<uint4 *>(f.pub_table + a);
-    for (int w = lane; w < W; w += 64) t[w] = src[w];
-  }
+  if (!good && f.pub_own && f.pub_table)  // the table still lists the trajectory the agent goes on executing
+    copy_record(f.pub_table + a, f.pub_own + a, lane);
   if (lane == 0) f.out_ok[a] = good ? 1 : 0;
   return (safe ? 1 : 0) | (good ? 2 : 0);
 }
@@ -1857,10 +1853,7 @@ __device__ inline void flight_fsm_apply(const FlightFsmDev &u, const FinishArgs 
   }
   if (u.log_own) {  // what the agent executes after the tick: own[a] as this wave's lanes have just left it
     __threadfence();
-    constexpr int W   = (int)(sizeof(SogmTrajRecord) / 16);
-    const uint4  *src = reinterpret_cast<const uint4 *>(f.pub_own + a);
-    uint4        *dst = reinterpret_cast<uint4 *>(u.log_own + row);
-    for (int w = lane; w < W; w += 64) dst[w] = src[w];
+    copy_record(u.log_own + row, f.pub_own + a, lane);
   }
 }
 

@@ -461,6 +461,13 @@ __device__ inline int traj_safe_agent(const MapView &m, int a, const SogmTrajRec
   return 1;
 }
 
+// One record, 16 bytes per lane and trip (coalesced): lanes lane, lane + stride, ... of the callers' wave or workgroup.
+static_assert(sizeof(SogmTrajRecord) % 16 == 0, "a record is copied in 16-byte pieces");
+__device__ __forceinline__ void copy_record(SogmTrajRecord *dst, const SogmTrajRecord *src, int lane, int stride = 64) {
+  const uint4 *s = reinterpret_cast<const uint4 *>(src);
+  uint4       *d = reinterpret_cast<uint4 *>(dst);
+  for (int w = lane; w < (int)(sizeof(SogmTrajRecord) / 16); w += stride) d[w] = s[w];
+}
 // (shared by sogm_map.hip, sogm_audit.hip and sogm_fsm.hip)
 // Bezier pos / vel / acc of a trajectory record at an absolute time (bernstein.cpp:25-59)
 // returns false (and zeros) for an empty record
@@ -787,9 +794,11 @@ MarkLog    mark_log(sogm_ctx *c, int slot);
 inline void sync_grid(sogm_ctx *c) { c->d_grid = c->pool.grid(); }
 // zero slot `slot`'s grid on `st`: the logged sectors when the slot is tracked, the dense clear otherwise
 int  reset_slot(sogm_ctx *c, hipStream_t st, int slot, float *grid, bool polite);
-struct PrestampDev;
-// the map's part of the pre-stamp arguments (buffers allocated on first use)
-int  prestamp_buffers(sogm_ctx *c, PrestampDev *d);
+struct MapTarget;
+// where slot `slot`'s maps are built (sogm_planner.hpp): its grid and log, the stamp's scratch, and the context's map centres
+// and stamps — the NEXT ones for a pre-stamp.  Allocates the scratch and the *_next arrays on first use (`st`: the stream
+// that zeroes the new occupancy bits).
+int  map_target(sogm_ctx *c, int slot, bool next_poses, hipStream_t st, MapTarget *out);
 }  // namespace sogm
 
 #define SOGM_HIP_CHECK(expr)                    \

@@ -62,10 +62,7 @@ __global__ __launch_bounds__(64) void k_fsm_apply(SogmFsmParams prm, SogmFsmStat
   __syncthreads();
   const int kind = s_kind;  // (wave-uniform)
   if (kind == SOGM_FSM_PUB_NEW) {
-    constexpr int W   = (int)(sizeof(SogmTrajRecord) / 16);
-    const uint4  *src = reinterpret_cast<const uint4 *>(fresh + a);
-    uint4        *dst = reinterpret_cast<uint4 *>(own + a);
-    for (int w = lane; w < W; w += 64) dst[w] = src[w];
+    copy_record(own + a, fresh + a, lane);
   } else if (kind == SOGM_FSM_PUB_HOVER) {
     const double p[3] = {pos_now[a * 3], pos_now[a * 3 + 1], pos_now[a * 3 + 2]};
     fsm_hover_record(own[a], drone_ids[a], p, s_start, lane, 64);

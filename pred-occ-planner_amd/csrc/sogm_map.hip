@@ -117,18 +117,29 @@ __device__ __forceinline__ void cull_agent(const GridGeom &g, const SogmCylinder
 }
 __device__ __forceinline__ void cull_blocks_agent(const GridGeom &g, const CloudBlocks &cb, int agent, float q0, float q1,
                                                   int lane);
+// ---- The ticket bodies.  An agent's map is built by four builders — the lock-step kernels below, k_update_flow,
+// k_prestamp_flow and k_flight_map — out of the same steps: cull, bits, marks, overlay.  Each step is written once, takes the
+// map stage's structs (sogm_planner.hpp) and is the one place that unpacks them into the `__restrict__` parameters of the
+// loops; every builder that runs the step calls its body, which is why all four mark the same cells.
+// Cull (one wave): the agent's candidate cylinders around the map centre (q0, q1) and its crop of a SogmWorld cloud.
+__device__ __forceinline__ void cull_ticket(const GridGeom &g, const MapFrame &f, const MapTarget &t, int agent, float q0,
+                                            float q1, int lane) {
+  cull_agent(g, f.cyl, f.n_cyl, q0, q1, (CylCand *)t.cand + (size_t)agent * SOGM_MAX_CYL_LDS, t.n_cand + agent, lane);
+  if (f.cb.bounds) cull_blocks_agent(g, f.cb, agent, q0, q1, lane);
+}
 __global__ __launch_bounds__(64) void k_cull_cylinders(GridGeom g, const SogmCylinder *__restrict__ cyl, int n_cyl,
                                                        const float *__restrict__ poses, CylCand *__restrict__ cand,
                                                        int *__restrict__ n_cand, const double *__restrict__ stamps_in,
                                                        float *__restrict__ poses_out, double *__restrict__ stamps_out,
                                                        CloudBlocks cb, long long *__restrict__ tick_clock) {
-  const int    agent = blockIdx.x, lane = threadIdx.x;
+  const MapFrame  f{.cb = cb, .cyl = cyl, .n_cyl = n_cyl};
+  const MapTarget t{.cand = cand, .n_cand = n_cand};
+  const int       agent = blockIdx.x, lane = threadIdx.x;
   if (tick_clock && agent == 0 && lane == 0) tick_clock[0] = wall_clock64();  // the update's first kernel is running
   const float  q0 = poses[agent * 3], q1 = poses[agent * 3 + 1];
   if (lane < 3) poses_out[agent * 3 + lane] = poses[agent * 3 + lane];
   if (lane == 3) stamps_out[agent] = stamps_in[agent];
-  cull_agent(g, cyl, n_cyl, q0, q1, cand + (size_t)agent * SOGM_MAX_CYL_LDS, n_cand + agent, lane);
-  if (cb.bounds) cull_blocks_agent(g, cb, agent, q0, q1, lane);  // the agent's crop of a SogmWorld cloud
+  cull_ticket(g, f, t, agent, q0, q1, lane);
 }
 
 // The stamp in two passes (one-wave workgroups, no LDS; the candidates come from k_cull_cylinders through L1 / the
@@ -342,24 +353,35 @@ __device__ __forceinline__ void stamp_bits_blocks(const GridGeom &g, const float
     for (; j < end; j += 64) stamp_bits_point(g, box, cloud[(size_t)j * 3], cloud[(size_t)j * 3 + 1], cloud[(size_t)j * 3 + 2], mask);
   }
 }
+// Bits ticket `sub` of the agent's `n_sub` (one wave each): the listed blocks of a SogmWorld frame, or the agent's range of
+// the caller's cloud.
+template <bool WAVE_DEDUPE = false>
+__device__ __forceinline__ void bits_ticket(const GridGeom &g, const MapFrame &f, const MapTarget &t, int agent, int sub,
+                                            int n_sub, int lane) {
+  const float *pose = t.poses + agent * 3;
+  unsigned    *mask = t.bits + (size_t)agent * t.words;
+  if (f.cb.bounds) {
+    stamp_bits_blocks<WAVE_DEDUPE>(g, f.cloud, f.cb, agent, sub, n_sub, pose[0], pose[1], pose[2], mask, lane);
+  } else {
+    const int begin = f.cloud_range[agent * 2], end = f.cloud_range[agent * 2 + 1];
+    stamp_bits_range(g, f.cloud, begin + sub * 64 + lane, end, n_sub * 64, pose[0], pose[1], pose[2], mask);
+  }
+}
 __global__ __launch_bounds__(64) void k_stamp_bits(GridGeom g, const float *__restrict__ cloud,
                                                    const int32_t *__restrict__ cloud_range,
                                                    const float *__restrict__ poses, unsigned *__restrict__ bits,
                                                    int words_per_agent, int agent0) {
-  const int    agent = blockIdx.y + agent0;
-  const int    begin = cloud_range[agent * 2], end = cloud_range[agent * 2 + 1];
-  const float *pose  = poses + agent * 3;
-  stamp_bits_range(g, cloud, begin + (int)(blockIdx.x * blockDim.x + threadIdx.x), end, (int)(gridDim.x * blockDim.x),
-                   pose[0], pose[1], pose[2], bits + (size_t)agent * words_per_agent);
+  const MapFrame  f{.cloud = cloud, .cloud_range = cloud_range, .cb = {}};
+  const MapTarget t{.bits = bits, .words = words_per_agent, .poses = const_cast<float *>(poses)};
+  bits_ticket(g, f, t, (int)blockIdx.y + agent0, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_stamp_bits_blocks(GridGeom g, const float *__restrict__ cloud, CloudBlocks cb,
                                                           const float *__restrict__ poses, unsigned *__restrict__ bits,
                                                           int words_per_agent) {
-  const int    agent = blockIdx.y;
-  const float *pose  = poses + agent * 3;
-  stamp_bits_blocks<true>(g, cloud, cb, agent, (int)blockIdx.x, (int)gridDim.x, pose[0], pose[1], pose[2],
-                          bits + (size_t)agent * words_per_agent, (int)threadIdx.x);
+  const MapFrame  f{.cloud = cloud, .cb = cb};
+  const MapTarget t{.bits = bits, .words = words_per_agent, .poses = const_cast<float *>(poses)};
+  bits_ticket<true>(g, f, t, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
 }
 // xy bounds of every block of `block_points` consecutive points (sogm_cloud_block_bounds): one wave per block
 __global__ __launch_bounds__(64) void k_block_bounds(const float *__restrict__ cloud, int n_points, int block_points,
@@ -763,6 +785,16 @@ __device__ __forceinline__ void stamp_marks_trips(const GridGeom &g, void *__res
     }
   }
 }
+// Marks ticket `sub` of the agent's `n_sub` (one wave each; a trip is 256 mask words).  cand_lds: the wave's LDS candidate
+// cache, free again for the next ticket's staging when this returns; lds_secs: k_stamp_marks' sector cache.
+template <bool CACHED>
+__device__ __forceinline__ void marks_ticket(const GridGeom &g, const MapFrame &f, const MapTarget &t, int agent, int sub,
+                                             int n_sub, CylCand *cand_lds = nullptr, int cand_lds_cap = 0,
+                                             unsigned *lds_secs = nullptr) {
+  stamp_marks_trips<CACHED>(g, t.grid, t.bits, t.words, f.cyl, f.n_cyl, t.poses, (const CylCand *)t.cand, t.n_cand, agent, t.lg,
+                            sub * 256, n_sub * 256, cand_lds, cand_lds_cap, lds_secs);
+  if (cand_lds) __syncthreads();
+}
 
 __global__ __launch_bounds__(64) void k_stamp_marks(GridGeom g, void *__restrict__ grid,
                                                     unsigned *__restrict__ bits, int words_per_agent,
@@ -771,8 +803,11 @@ __global__ __launch_bounds__(64) void k_stamp_marks(GridGeom g, void *__restrict
                                                     const CylCand *__restrict__ cand_all,
                                                     const int *__restrict__ n_cand, int agent0, MarkLog lg, int lds_log) {
   extern __shared__ unsigned s_marks_secs[];  // [T][64] when the launch provides it (lds_log != 0)
-  stamp_marks_trips<false>(g, grid, bits, words_per_agent, cyl, n_cyl, poses, cand_all, n_cand, (int)blockIdx.y + agent0, lg,
-                           (int)blockIdx.x * 256, (int)gridDim.x * 256, nullptr, 0, lds_log ? s_marks_secs : nullptr);
+  const MapFrame  f{.cyl = cyl, .n_cyl = n_cyl};
+  const MapTarget t{.grid = grid, .bits = bits, .words = words_per_agent, .cand = const_cast<CylCand *>(cand_all),
+                    .n_cand = const_cast<int *>(n_cand), .lg = lg, .poses = const_cast<float *>(poses)};
+  marks_ticket<false>(g, f, t, (int)blockIdx.y + agent0, (int)blockIdx.x, (int)gridDim.x, nullptr, 0,
+                      lds_log ? s_marks_secs : nullptr);
 }
 // (the register-cached single-pass form of the slice loops: tuning key stamp_cached)
 __global__ __launch_bounds__(64) void k_stamp_marks_cached(GridGeom g, void *__restrict__ grid,
@@ -781,8 +816,10 @@ __global__ __launch_bounds__(64) void k_stamp_marks_cached(GridGeom g, void *__r
                                                            const float *__restrict__ poses,
                                                            const CylCand *__restrict__ cand_all,
                                                            const int *__restrict__ n_cand, int agent0, MarkLog lg) {
-  stamp_marks_trips<true>(g, grid, bits, words_per_agent, cyl, n_cyl, poses, cand_all, n_cand, (int)blockIdx.y + agent0, lg,
-                          (int)blockIdx.x * 256, (int)gridDim.x * 256);
+  const MapFrame  f{.cyl = cyl, .n_cyl = n_cyl};
+  const MapTarget t{.grid = grid, .bits = bits, .words = words_per_agent, .cand = const_cast<CylCand *>(cand_all),
+                    .n_cand = const_cast<int *>(n_cand), .lg = lg, .poses = const_cast<float *>(poses)};
+  marks_ticket<true>(g, f, t, (int)blockIdx.y + agent0, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -937,11 +974,24 @@ __device__ inline void splat_item(const GridGeom &g, void *__restrict__ grid, co
     cell_add(slab, vx, 1.0F, g.half);
   }
 }
+// Overlay: record r at slice `slice` into the agent's map, and ticket `sub` of the agent's `n_sub` (one wave each) over the
+// n_rec * T items of a table.
+__device__ __forceinline__ void overlay_item(const GridGeom &g, const OverlayIO &o, const MapTarget &t, int agent, int r,
+                                             int slice) {
+  splat_item(g, t.grid, o.rec[r], agent, slice, o.ego_ids, t.poses, t.stamps, o.body, o.n_body, t.lg);
+}
+__device__ __forceinline__ void overlay_ticket(const GridGeom &g, const OverlayIO &o, const MapTarget &t, int agent, int sub,
+                                               int n_sub, int lane) {
+  const int n = o.n_rec * g.T;
+  for (int i = sub * 64 + lane; i < n; i += n_sub * 64) overlay_item(g, o, t, agent, i / g.T, i % g.T);
+}
 __global__ __launch_bounds__(256) void k_splat_neighbours(
     GridGeom g, void *__restrict__ grid, const SogmTrajRecord *__restrict__ rec, int n_rec,
     const int32_t *__restrict__ ego_ids, const float *__restrict__ poses,
     const double *__restrict__ stamps, const double *__restrict__ body, int n_body, int n_agents, int agent0,
     MarkLog lg, const int *wait_stage, int *wait_err) {
+  const OverlayIO o{.rec = rec, .n_rec = n_rec, .ego_ids = ego_ids, .body = body, .n_body = n_body};
+  const MapTarget tgt{.grid = grid, .lg = lg, .poses = const_cast<float *>(poses), .stamps = const_cast<double *>(stamps)};
   const long long total  = (long long)n_agents * n_rec * g.T;
   const long long stride = (long long)gridDim.x * blockDim.x;  // (one item per lane unless the launch is narrower)
   for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < total; gid += stride) {
@@ -958,7 +1008,7 @@ __global__ __launch_bounds__(256) void k_splat_neighbours(
       // silently left without its overlay.  Every lane waits for the word of its own item's agent.
       if (!lane_wait_at_least(wait_stage + agent, FLOW_PS_DONE, wait_err, FLOW_CODE_OVERLAY_STAMP)) return;
     }
-    splat_item(g, grid, rec[r], agent, t, ego_ids, poses, stamps, body, n_body, lg);
+    overlay_item(g, o, tgt, agent, r, t);
   }
 }
 
@@ -1122,22 +1172,27 @@ __global__ __launch_bounds__(64) void k_traj_eval(const SogmTrajRecord *__restri
 // One agent's tick inputs (plan_manager.cpp:169-175): the start state sampled from its executing trajectory at
 // stamp + start_offset, or where it hovers; the map centre of the tick is that position.
 __device__ inline void tick_inputs_agent(const SogmTrajRecord &rec, const double *hov, int i, double stamp,
-                                         double start_offset, double *__restrict__ hover, double *__restrict__ now,
-                                         double *__restrict__ t_start, double *__restrict__ pva,
-                                         float *__restrict__ poses) {
-  const double ts = stamp + start_offset;
+                                         const TickInputsIO &io, float *__restrict__ poses) {
+  const double ts = stamp + io.start_offset;
   double       o[9];
   if (!traj_eval_record(rec, ts, o))
     for (int k = 0; k < 9; ++k) o[k] = hov[k];
-  for (int k = 0; k < 9; ++k) pva[i * 9 + k] = o[k];
+  for (int k = 0; k < 9; ++k) io.pva[i * 9 + k] = o[k];
   for (int k = 0; k < 3; ++k) {
-    hover[i * 9 + k]     = o[k];
-    hover[i * 9 + 3 + k] = 0.0;
-    hover[i * 9 + 6 + k] = 0.0;
-    poses[i * 3 + k]     = (float)o[k];
+    io.hover[i * 9 + k]     = o[k];
+    io.hover[i * 9 + 3 + k] = 0.0;
+    io.hover[i * 9 + 6 + k] = 0.0;
+    poses[i * 3 + k]        = (float)o[k];
   }
-  now[i]     = stamp;
-  t_start[i] = ts;
+  io.now[i]     = stamp;
+  io.t_start[i] = ts;
+}
+// The agent's executed record and hover row into the workgroup's LDS (one wave), visible to every lane on return.
+__device__ __forceinline__ void stage_record_hover(SogmTrajRecord *s_rec, double *s_hov, const SogmTrajRecord *own,
+                                                   const double *hover, int agent, int lane) {
+  copy_record(s_rec, own + agent, lane);
+  if (lane < 9) s_hov[lane] = hover[agent * 9 + lane];
+  __syncthreads();
 }
 __global__ __launch_bounds__(64) void k_tick_inputs(const SogmTrajRecord *__restrict__ own, int n, double stamp,
                                                     double start_offset, double *__restrict__ hover,
@@ -1147,14 +1202,10 @@ __global__ __launch_bounds__(64) void k_tick_inputs(const SogmTrajRecord *__rest
   __shared__ double                                      s_hov[9];
   const int i = blockIdx.x;
   if (i >= n) return;
-  constexpr int W = (int)(sizeof(SogmTrajRecord) / 16);
-  const uint4  *src = reinterpret_cast<const uint4 *>(own + i);
-  uint4        *dst = reinterpret_cast<uint4 *>(&s_rec);
-  for (int w = threadIdx.x; w < W; w += 64) dst[w] = src[w];
-  if (threadIdx.x < 9) s_hov[threadIdx.x] = hover[i * 9 + threadIdx.x];
-  __syncthreads();
+  const TickInputsIO io{.own = own, .hover = hover, .now = now, .t_start = t_start, .pva = pva, .start_offset = start_offset};
+  stage_record_hover(&s_rec, s_hov, io.own, io.hover, i, threadIdx.x);
   if (threadIdx.x != 0) return;
-  tick_inputs_agent(s_rec, s_hov, i, stamp, start_offset, hover, now, t_start, pva, poses);
+  tick_inputs_agent(s_rec, s_hov, i, stamp, io, poses);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1166,7 +1217,8 @@ __global__ __launch_bounds__(64) void k_tick_inputs(const SogmTrajRecord *__rest
 // culls the cylinders, sets the occupancy bits and writes the marks + log entries into the pool's next grid — split
 // into ps.n_bits + ps.n_marks one-wave tickets per agent (64 + 64 by default) handed out in order (a ticket only ever waits for lower ones, so
 // any number of resident waves makes progress).  The next update then only adopts the grid and adds the overlay
-// (sogm_update_prestamped).  Same kernels' code, same cells.
+// (sogm_update_prestamped).  The lock-step kernels' ticket bodies (stage_record_hover, cull_ticket, bits_ticket,
+// marks_ticket): same cells.
 // ------------------------------------------------------------------------------------------------
 // Launch gate of the pre-stamp (one lane, on its stream in front of it): every agent's corridors final — store streams
 // stay away from the searches and point scans — AND every QP workgroup and finishing wave of this replan resident:
@@ -1209,23 +1261,16 @@ __global__ __launch_bounds__(64) void k_prestamp_flow(GridGeom g, FlowCtl fc, Pr
       [[maybe_unused]] const long long ps_c0 = PS_CLK();
       if (lane == 0) pts[0] = wall_clock64();
       // next tick's inputs of this agent (k_tick_inputs), then its candidate cylinders around the new centre
-      constexpr int W   = (int)(sizeof(SogmTrajRecord) / 16);
-      const uint4  *src = reinterpret_cast<const uint4 *>(ps.own + agent);
-      uint4        *dst = reinterpret_cast<uint4 *>(&s_rec);
-      for (int w = lane; w < W; w += 64) dst[w] = src[w];
-      if (lane < 9) s_hov[lane] = ps.hover[agent * 9 + lane];
-      __syncthreads();
+      stage_record_hover(&s_rec, s_hov, ps.tick.own, ps.tick.hover, agent, lane);
       if (lane == 0) {
-        tick_inputs_agent(s_rec, s_hov, agent, ps.stamp, ps.start_offset, ps.hover, ps.now, ps.t_start, ps.pva, ps.poses);
-        ps.stamps[agent] = ps.stamp;
+        tick_inputs_agent(s_rec, s_hov, agent, ps.stamp, ps.tick, ps.tgt.poses);
+        ps.tgt.stamps[agent] = ps.stamp;
         if (ps.poses_host)
-          for (int k = 0; k < 3; ++k) ps.poses_host[agent * 3 + k] = ps.poses[agent * 3 + k];
+          for (int k = 0; k < 3; ++k) ps.poses_host[agent * 3 + k] = ps.tgt.poses[agent * 3 + k];
       }
       __threadfence();
       __syncthreads();
-      cull_agent(g, ps.cyl, ps.n_cyl, ps.poses[agent * 3], ps.poses[agent * 3 + 1],
-                 (CylCand *)ps.cand + (size_t)agent * SOGM_MAX_CYL_LDS, ps.n_cand + agent, lane);
-      if (ps.cb.bounds) cull_blocks_agent(g, ps.cb, agent, ps.poses[agent * 3], ps.poses[agent * 3 + 1], lane);
+      cull_ticket(g, ps.frame, ps.tgt, agent, ps.tgt.poses[agent * 3], ps.tgt.poses[agent * 3 + 1], lane);
       __threadfence();
       if (lane == 0) {
         pts[1] = wall_clock64();
@@ -1238,14 +1283,7 @@ __global__ __launch_bounds__(64) void k_prestamp_flow(GridGeom g, FlowCtl fc, Pr
       if (flow_wait_count(&fc.stage[agent], 1, &fc.hdr[FLOW_ERR])) break;
       [[maybe_unused]] const long long ps_t2 = PS_CLK();
       PS_ADD(1, ps_t2 - ps_t1);
-      const float p0 = ps.poses[agent * 3], p1 = ps.poses[agent * 3 + 1], p2 = ps.poses[agent * 3 + 2];
-      if (ps.cb.bounds) {
-        stamp_bits_blocks(g, ps.cloud, ps.cb, agent, s, n_bits, p0, p1, p2, ps.bits + (size_t)agent * ps.words, lane);
-      } else {
-        const int begin = ps.cloud_range[agent * 2], end = ps.cloud_range[agent * 2 + 1];
-        stamp_bits_range(g, ps.cloud, begin + s * 64 + lane, end, n_bits * 64, p0, p1, p2,
-                         ps.bits + (size_t)agent * ps.words);
-      }
+      bits_ticket(g, ps.frame, ps.tgt, agent, s, n_bits, lane);
       __threadfence();
       PS_ADD(3, PS_CLK() - ps_t2);
       if (lane == 0 && atomicAdd(&fc.stage[agent], 1) + 1 == 1 + n_bits) pts[2] = wall_clock64();
@@ -1253,9 +1291,7 @@ __global__ __launch_bounds__(64) void k_prestamp_flow(GridGeom g, FlowCtl fc, Pr
       if (flow_wait_count(&fc.stage[agent], 1 + n_bits, &fc.hdr[FLOW_ERR])) break;
       [[maybe_unused]] const long long ps_t2 = PS_CLK();
       PS_ADD(1, ps_t2 - ps_t1);
-      stamp_marks_trips<true>(g, ps.grid, ps.bits, ps.words, ps.cyl, ps.n_cyl, ps.poses, (const CylCand *)ps.cand, ps.n_cand, agent, ps.lg,
-                        (s - n_bits) * 256, n_marks * 256, s_cand, PRESTAMP_CAND_LDS);
-      __syncthreads();  // (the next ticket's staging overwrites s_cand)
+      marks_ticket<true>(g, ps.frame, ps.tgt, agent, s - n_bits, n_marks, s_cand, PRESTAMP_CAND_LDS);
       // the agent's last marks ticket to finish declares its grid complete (the next update's overlay waits for it)
       __threadfence();
       PS_ADD(4, PS_CLK() - ps_t2);
@@ -1294,8 +1330,18 @@ namespace sogm {
 //   bits    occupancy bits of slice 0 from the listed cloud blocks
 //   marks   slice 0 + T - 1 future marks per occupied voxel, logged
 //   splat   the neighbours' records of table ver(k - 2), logged -> the agent goes to the search queue
-// Same device functions as the per-tick kernels: same cells.
+// The per-tick kernels' ticket bodies (stage_record_hover, cull_ticket, bits_ticket, marks_ticket, overlay_ticket): same cells.
 // ------------------------------------------------------------------------------------------------
+// frame k of the flight as the ticket bodies read it: the tick's world record + the context's crop lists
+__device__ __forceinline__ MapFrame flight_frame(const FlightMapDev &d, int kl) {
+  const FlightWorld &w = d.worlds[kl];
+  MapFrame f{.cloud = w.cloud, .cloud_range = nullptr, .cb = d.cb, .cyl = w.cyl, .n_cyl = w.n_cyl};
+  f.cb.bounds       = w.bounds;
+  f.cb.n_blocks     = w.n_blocks;
+  f.cb.block_points = w.block_points;
+  f.cb.n_points     = w.n_points;
+  return f;
+}
 __device__ __forceinline__ void flight_reset_ticket(char *__restrict__ base, size_t agent_bytes, const unsigned *__restrict__ e,
                                                     unsigned n, int cap, int first, int stride, int lane,
                                                     unsigned long long *__restrict__ stat) {
@@ -1356,14 +1402,9 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
       const int agent = fl_wait_item_end(urgent ? fl.u_ring : fl.m_ring, fl.ring_mask, t, err, &fl.hdr[FL_END], fl.epoch, !urgent);
       if (agent < 0) break;
       __threadfence();
-      const int          k = fl.tick_of[agent], kl = k - fl.first_tick;
-      const FlightWorld &w = d.worlds[kl];
-      CloudBlocks        cb = d.cb;
-      cb.bounds       = w.bounds;
-      cb.n_blocks     = w.n_blocks;
-      cb.block_points = w.block_points;
-      cb.n_points     = w.n_points;
-      long long *ts = fl.ts + (size_t)agent * FL_TS;
+      const int      k = fl.tick_of[agent], kl = k - fl.first_tick;
+      const MapFrame frame = flight_frame(d, kl);
+      long long     *ts = fl.ts + (size_t)agent * FL_TS;
       if (lane == 0) ts[8] = wall_clock64();
       // admission, in ticket order: at most n_admit maps under construction, and no faster than one agent per pace_ticks
       // — agents then leave the map stage (and reach every later stage) at a steady rate instead of in a burst, which is
@@ -1379,27 +1420,20 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
         __hip_atomic_store(&fl.hdr[FL_ADMITTED], t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (lane == 0) ts[9] = wall_clock64();
-      constexpr int W   = (int)(sizeof(SogmTrajRecord) / 16);
-      const uint4  *src = reinterpret_cast<const uint4 *>(d.own + agent);
-      uint4        *dst = reinterpret_cast<uint4 *>(&s_rec);
-      for (int q = lane; q < W; q += 64) dst[q] = src[q];
-      if (lane < 9) s_hov[lane] = d.hover[agent * 9 + lane];
-      __syncthreads();
+      stage_record_hover(&s_rec, s_hov, d.tick.own, d.tick.hover, agent, lane);
       const double stamp = d.t0 + k * d.period;
       if (lane == 0) {
         if (d.fsm.state)  // the head of one FSMCallback (sogm_planner_set_flight_fsm): k_fsm_inputs' body for this agent
-          fsm_inputs_agent(d.fsm.prm, d.fsm.state[agent], s_rec, s_hov, d.fsm.goals + agent * 3, agent, stamp, d.hover, d.now,
-                           d.t_start, d.pva, d.poses, d.fsm.pos_now, d.fsm.due, d.fsm.reached,
+          fsm_inputs_agent(d.fsm.prm, d.fsm.state[agent], s_rec, s_hov, d.fsm.goals + agent * 3, agent, stamp, d.tick.hover,
+                           d.tick.now, d.tick.t_start, d.tick.pva, d.tgt.poses, d.fsm.pos_now, d.fsm.due, d.fsm.reached,
                            [](const SogmTrajRecord &r, double t, double *o) { return traj_eval_record(r, t, o); });
         else
-          tick_inputs_agent(s_rec, s_hov, agent, stamp, d.start_offset, d.hover, d.now, d.t_start, d.pva, d.poses);
-        d.stamps[agent] = stamp;
+          tick_inputs_agent(s_rec, s_hov, agent, stamp, d.tick, d.tgt.poses);
+        d.tgt.stamps[agent] = stamp;
       }
       __threadfence();
       __syncthreads();
-      cull_agent(g, w.cyl, w.n_cyl, d.poses[agent * 3], d.poses[agent * 3 + 1],
-                 (CylCand *)d.cand + (size_t)agent * SOGM_MAX_CYL_LDS, d.n_cand + agent, lane);
-      cull_blocks_agent(g, cb, agent, d.poses[agent * 3], d.poses[agent * 3 + 1], lane);
+      cull_ticket(g, frame, d.tgt, agent, d.tgt.poses[agent * 3], d.tgt.poses[agent * 3 + 1], lane);
       __threadfence();
       if (lane == 0) {  // the agent's grid may be reset and its occupancy bits set (neither touches what the other writes)
         ts[12] = wall_clock64();
@@ -1444,39 +1478,32 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
     const int          kind = wk_kind(desc), sub = wk_sub(desc), agent = wk_agent(desc);
     c1_prev   = c1;
     kind_prev = kind;
-    const int          k = fl.tick_of[agent], kl = k - fl.first_tick;
-    const FlightWorld &w = d.worlds[kl];
-    CloudBlocks        cb = d.cb;
-    cb.bounds       = w.bounds;
-    cb.n_blocks     = w.n_blocks;
-    cb.block_points = w.block_points;
-    cb.n_points     = w.n_points;
+    const int      k = fl.tick_of[agent], kl = k - fl.first_tick;
+    const MapFrame frame = flight_frame(d, kl);
+    const MarkLog &lg = d.tgt.lg;
     long long     *ts  = fl.ts + (size_t)agent * FL_TS;
     if (kind == WK_MAP_RESET || kind == WK_MAP_BITS) {
       if (kind == WK_MAP_RESET) {
-        const unsigned n = d.lg.n[agent];
+        const unsigned n = lg.n[agent];
         if (sub == 0 && lane == 0 && reset_stat) {
-          atomicAdd(reset_stat, (unsigned long long)(n > (unsigned)d.lg.cap ? (unsigned)d.lg.cap : n));
+          atomicAdd(reset_stat, (unsigned long long)(n > (unsigned)lg.cap ? (unsigned)lg.cap : n));
           if (agent == 0) atomicAdd(reset_stat + 1, 1ull);
         }
-        flight_reset_ticket(reinterpret_cast<char *>(d.grid) + (size_t)agent * d.agent_bytes, d.agent_bytes,
-                            d.lg.entries + (size_t)agent * d.lg.cap, n, d.lg.cap, sub, n_r, lane, reset_stat);
+        flight_reset_ticket(reinterpret_cast<char *>(d.tgt.grid) + (size_t)agent * d.agent_bytes, d.agent_bytes,
+                            lg.entries + (size_t)agent * lg.cap, n, lg.cap, sub, n_r, lane, reset_stat);
       } else {
-        stamp_bits_blocks(g, w.cloud, cb, agent, sub, n_b, d.poses[agent * 3], d.poses[agent * 3 + 1],
-                          d.poses[agent * 3 + 2], d.bits + (size_t)agent * d.words, lane);
+        bits_ticket(g, frame, d.tgt, agent, sub, n_b, lane);
       }
       __threadfence();
       if (lane == 0 && atomicAdd(&fl.stage[agent], 1) + 1 == 1 + n_r + n_b) {
         // the grid is clean and the bits are set: the log restarts, then the marks may append
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        d.lg.n[agent] = 0u;
-        ts[13]        = wall_clock64();
+        lg.n[agent] = 0u;
+        ts[13]      = wall_clock64();
         wq_push(wq, wq_tail, wk_pack(WK_MAP_MARKS, 0, agent), n_m);
       }
     } else if (kind == WK_MAP_MARKS) {
-      stamp_marks_trips<true>(g, d.grid, d.bits, d.words, w.cyl, w.n_cyl, d.poses, (const CylCand *)d.cand, d.n_cand, agent, d.lg,
-                        sub * 256, n_m * 256, s_cand, PRESTAMP_CAND_LDS);
-      __syncthreads();  // (the next descriptor's staging overwrites s_cand)
+      marks_ticket<true>(g, frame, d.tgt, agent, sub, n_m, s_cand, PRESTAMP_CAND_LDS);
       __threadfence();
       if (lane == 0 && atomicAdd(&fl.stage[agent], 1) + 1 == 1 + n_r + n_b + n_m) {
         const long long now = wall_clock64();
@@ -1502,10 +1529,10 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
       }
     } else {  // WK_MAP_SPLAT: the neighbours' records of table ver(k - 2)
       if (d.tables && d.n_total > 0) {
-        const SogmTrajRecord *tab = d.tables + (size_t)((k - fl.lag) & 3) * d.n_total;
-        const int             n   = d.n_total * g.T;
-        for (int i = sub * 64 + lane; i < n; i += n_s * 64)
-          splat_item(g, d.grid, tab[i / g.T], agent, i % g.T, d.ego_ids, d.poses, d.stamps, d.body, d.n_body, d.lg);
+        OverlayIO ov = d.ov;
+        ov.rec       = d.tables + (size_t)((k - fl.lag) & 3) * d.n_total;
+        ov.n_rec     = d.n_total;
+        overlay_ticket(g, ov, d.tgt, agent, sub, n_s, lane);
       }
       __threadfence();
       if (lane == 0 && atomicAdd(&fl.stage[agent], 1) + 1 == S) {  // the agent's map of tick k is complete
@@ -1558,34 +1585,27 @@ __global__ __launch_bounds__(64) void k_traj_safe(MapView m, const SogmTrajRecor
 
 // row length of the stamp's occupancy bitmask (one row per agent): k_stamp_marks reads 256 words per trip
 static int stamp_bits_words(const GridGeom &g) { return (((g.V + 31) / 32) + 255) & ~255; }
-static int stamp_scratch(sogm_ctx *c, hipStream_t st, int *words_out) {
-  const int A = c->n_agents;
-  const int words = stamp_bits_words(c->geom);
-  *words_out = words;
-  if (c->d_cand) return SOGM_OK;
-  Resources::Setup setup(c->res);
-  SOGM_HIP_CHECK(c->res.device(&c->d_cand, sizeof(CylCand) * SOGM_MAX_CYL_LDS * (size_t)A));
-  SOGM_HIP_CHECK(c->res.device(&c->d_ncand, sizeof(int) * (size_t)A));
-  SOGM_HIP_CHECK(c->res.device(&c->d_stamp_bits, sizeof(unsigned) * (size_t)words * A));
-  SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * (size_t)words * A, st));
-  return setup.done();
-}
-int prestamp_buffers(sogm_ctx *c, PrestampDev *d) {
+int map_target(sogm_ctx *c, int slot, bool next_poses, hipStream_t st, MapTarget *out) {
   SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (!c->d_poses_next) {
+  const size_t A = (size_t)c->n_agents;
+  const int    words = stamp_bits_words(c->geom);
+  if (next_poses && !c->d_poses_next) {
     Resources::Setup setup(c->res);
-    SOGM_HIP_CHECK(c->res.device(&c->d_poses_next, sizeof(float) * 3 * (size_t)c->n_agents));
-    SOGM_HIP_CHECK(c->res.device(&c->d_stamps_next, sizeof(double) * (size_t)c->n_agents));
+    SOGM_HIP_CHECK(c->res.device(&c->d_poses_next, sizeof(float) * 3 * A));
+    SOGM_HIP_CHECK(c->res.device(&c->d_stamps_next, sizeof(double) * A));
     setup.done();
   }
-  int words = 0;
-  if (int rc = stamp_scratch(c, nullptr, &words)) return rc;
-  d->bits   = c->d_stamp_bits;
-  d->words  = words;
-  d->cand   = c->d_cand;
-  d->n_cand = c->d_ncand;
-  d->poses  = c->d_poses_next;
-  d->stamps = c->d_stamps_next;
+  if (!c->d_cand) {
+    Resources::Setup setup(c->res);
+    SOGM_HIP_CHECK(c->res.device(&c->d_cand, sizeof(CylCand) * SOGM_MAX_CYL_LDS * A));
+    SOGM_HIP_CHECK(c->res.device(&c->d_ncand, sizeof(int) * A));
+    SOGM_HIP_CHECK(c->res.device(&c->d_stamp_bits, sizeof(unsigned) * (size_t)words * A));
+    SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * (size_t)words * A, st));
+    setup.done();
+  }
+  *out = MapTarget{.grid = (void *)c->pool.grid_of(slot), .bits = c->d_stamp_bits, .words = words, .cand = c->d_cand,
+                   .n_cand = c->d_ncand, .lg = mark_log(c, slot), .poses = next_poses ? c->d_poses_next : c->d_poses,
+                   .stamps = next_poses ? c->d_stamps_next : c->d_stamps};
   return SOGM_OK;
 }
 
@@ -1932,25 +1952,12 @@ static int clear_grid(sogm_ctx *c, hipStream_t st) { return sogm::reset_slot(c, 
 // latency of ONE ticket chain instead of after four kernels over the whole swarm; the agent's last ticket stores the
 // epoch into map_ready[agent] (release), which sogm_replan's search workgroups wait for.  A ticket only ever waits for
 // tickets of its own agent, all of which are held by resident or earlier waves: no residency assumption beyond one agent's
-// worth of waves.  Same cells, same log as the four kernels (tests/test_update_flow_gpu.py).
+// worth of waves.  The four kernels' ticket bodies (bits_ticket, marks_ticket, overlay_ticket): same cells, same log
+// (tests/test_update_flow_gpu.py).
 struct UpdateFlowDev {
-  void                 *grid;
-  unsigned             *bits;
-  int                   words;
-  const float          *cloud;
-  CloudBlocks           cb;
-  const SogmCylinder   *cyl;
-  int                   n_cyl;
-  const void           *cand;
-  const int            *n_cand;
-  MarkLog               lg;
-  const float          *poses;   // the context's copies (filed by k_cull_cylinders, the launch before)
-  const double         *stamps;
-  const SogmTrajRecord *rec;
-  int                   n_rec;
-  const int32_t        *ego_ids;
-  const double         *body;
-  int                   n_body;
+  MapTarget             tgt;      // poses / stamps: the context's copies (filed by k_cull_cylinders, the launch before)
+  MapFrame              frame;
+  OverlayIO             ov;
   int                   n_agents, n_bits, n_marks, n_splat;
   int                  *ctl;      // ticket, error and per-agent progress words (UF_* below)
   int                   chunk;    // consecutive tickets per claim
@@ -1982,14 +1989,12 @@ __global__ __launch_bounds__(64) void k_update_flow(GridGeom g, UpdateFlowDev u)
       bool      last  = false;
       if (s == 0 && lane == 0) u.ts[agent * 4] = wall_clock64();
       if (s < u.n_bits) {
-        stamp_bits_blocks(g, u.cloud, u.cb, agent, s, u.n_bits, u.poses[agent * 3], u.poses[agent * 3 + 1],
-                          u.poses[agent * 3 + 2], u.bits + (size_t)agent * u.words, lane);
+        bits_ticket(g, u.frame, u.tgt, agent, s, u.n_bits, lane);
         __threadfence();
         if (lane == 0 && atomicAdd(stage, 1) + 1 == u.n_bits) u.ts[agent * 4 + 1] = wall_clock64();
       } else if (s < u.n_bits + u.n_marks) {
         if (flow_wait_count(stage, u.n_bits, err)) return;
-        stamp_marks_trips<CACHED>(g, u.grid, u.bits, u.words, u.cyl, u.n_cyl, u.poses, (const CylCand *)u.cand, u.n_cand,
-                                  agent, u.lg, (s - u.n_bits) * 256, u.n_marks * 256);
+        marks_ticket<CACHED>(g, u.frame, u.tgt, agent, s - u.n_bits, u.n_marks);
         __threadfence();
         if (lane == 0) {
           const int n = atomicAdd(stage, 1) + 1;
@@ -1998,9 +2003,7 @@ __global__ __launch_bounds__(64) void k_update_flow(GridGeom g, UpdateFlowDev u)
         }
       } else {
         if (flow_wait_count(stage, u.n_bits + u.n_marks, err)) return;  // stores of 1.0 first, the additions after them
-        const int n = u.n_rec * g.T;
-        for (int i = (s - u.n_bits - u.n_marks) * 64 + lane; i < n; i += u.n_splat * 64)
-          splat_item(g, u.grid, u.rec[i / g.T], agent, i % g.T, u.ego_ids, u.poses, u.stamps, u.body, u.n_body, u.lg);
+        overlay_ticket(g, u.ov, u.tgt, agent, s - u.n_bits - u.n_marks, u.n_splat, lane);
         __threadfence();
         if (lane == 0) last = atomicAdd(stage, 1) + 1 == per;
       }
@@ -2080,8 +2083,9 @@ static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cl
     }
   }
   // candidate cylinders per agent, then one-wave workgroups stride over each agent's cloud range
-  int words = 0;
-  if (int rc = sogm::stamp_scratch(c, st, &words)) return rc;
+  sogm::MapTarget tgt{};
+  if (int rc = sogm::map_target(c, c->pool.current(), false, st, &tgt)) return rc;
+  const int words = tgt.words;
   const int stamp_wgs = c->tune_i(SOGM_TUNE_STAMP_WGS) > 0 ? c->tune_i(SOGM_TUNE_STAMP_WGS) : 256;  // one-wave workgroups per agent
   c->n_stamps++;
   prof_begin(c, SOGM_PROF_STAMP, st);
@@ -2091,34 +2095,21 @@ static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cl
     // the maps agent by agent on the flow's stream; the caller's stream goes on (sogm_replan's searches wait per agent,
     // everything else joins the flow's end: sogm::join_update)
     if (int rc = sogm::update_flow_setup(c)) return rc;
-    UpdateFlowDev u{};
-    u.grid    = (void *)c->d_grid;
-    u.bits    = c->d_stamp_bits;
-    u.words   = words;
-    u.cloud   = cloud_xyz;
-    u.cb      = cb;
-    u.cyl     = cylinders;
-    u.n_cyl   = n_cyl;
-    u.cand    = c->d_cand;
-    u.n_cand  = c->d_ncand;
-    u.lg      = sogm::mark_log(c, c->pool.current());
-    u.poses   = c->d_poses;
-    u.stamps  = c->d_stamps;
-    u.rec     = records;
-    u.n_rec   = fused ? n_records : 0;
-    u.ego_ids = ego_ids;
-    u.body    = c->d_body;
-    u.n_body  = c->n_body;
-    u.n_agents = A;
-    u.n_bits   = c->tune_i(SOGM_TUNE_UPDATE_BITS);
-    u.n_marks  = c->tune_i(SOGM_TUNE_UPDATE_MARKS);
-    u.n_splat  = u.n_rec > 0 ? c->tune_i(SOGM_TUNE_UPDATE_SPLAT) : 0;
-    u.ctl      = c->d_update_ctl;
-    u.ts       = c->d_update_ts;
-    u.chunk    = c->tune_i(SOGM_TUNE_UPDATE_CHUNK) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_CHUNK) : 1;
-    u.map_ready = c->d_map_ready;
-    u.epoch     = ++c->map_epoch;
-    u.order     = c->d_update_order;
+    const int           n_rec = fused ? n_records : 0;
+    const UpdateFlowDev u{
+        .tgt       = tgt,
+        .frame     = {.cloud = cloud_xyz, .cloud_range = nullptr, .cb = cb, .cyl = cylinders, .n_cyl = n_cyl},
+        .ov        = {.rec = records, .n_rec = n_rec, .ego_ids = ego_ids, .body = c->d_body, .n_body = c->n_body},
+        .n_agents  = A,
+        .n_bits    = c->tune_i(SOGM_TUNE_UPDATE_BITS),
+        .n_marks   = c->tune_i(SOGM_TUNE_UPDATE_MARKS),
+        .n_splat   = n_rec > 0 ? c->tune_i(SOGM_TUNE_UPDATE_SPLAT) : 0,
+        .ctl       = c->d_update_ctl,
+        .chunk     = c->tune_i(SOGM_TUNE_UPDATE_CHUNK) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_CHUNK) : 1,
+        .ts        = c->d_update_ts,
+        .map_ready = c->d_map_ready,
+        .epoch     = ++c->map_epoch,
+        .order     = c->d_update_order};
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
     int wgs = c->tune_i(SOGM_TUNE_UPDATE_WGS) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_WGS) : 16 * n_cu;
@@ -2145,7 +2136,7 @@ static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cl
   else
     hipLaunchKernelGGL(k_stamp_bits, dim3(bits_wgs, A), dim3(64), 0, st, c->geom, cloud_xyz, cloud_range, c->d_poses,
                        c->d_stamp_bits, words, 0);
-  const sogm::MarkLog lg = sogm::mark_log(c, c->pool.current());
+  const sogm::MarkLog lg = tgt.lg;
   // (dynamic LDS the kernel does not use bounds its waves per CU: the marks' scattered stores merge worse in L2 the more
   //  waves interleave theirs — tuning key stamp_lds_kb, 160 / kb workgroups per CU)
   const size_t marks_lds = (size_t)c->tune_i(SOGM_TUNE_STAMP_LDS_KB) * 1024;

@@ -549,12 +549,17 @@ int sogm_planner_set_prestamp(sogm_planner *p, const SogmPrestamp *ps) {
   } else if (!ps->cloud_xyz || !ps->cloud_range || ps->n_cyl < 0 || (ps->n_cyl > 0 && !ps->cylinders)) {
     return SOGM_ERR_INVALID_ARG;
   }
-  std::memset(&p->ps, 0, sizeof(p->ps));
-  p->ps.cloud        = w ? w->cloud_xyz : ps->cloud_xyz;
-  p->ps.cloud_range  = w ? nullptr : ps->cloud_range;
-  p->ps.cyl          = w ? w->cylinders : ps->cylinders;
-  p->ps.n_cyl        = w ? w->n_cyl : ps->n_cyl;
-  p->ps_world_on     = w ? 1 : 0;
+  p->ps = sogm::PrestampDev{
+      .frame      = {.cloud       = w ? w->cloud_xyz : ps->cloud_xyz,
+                     .cloud_range = w ? nullptr : ps->cloud_range,
+                     .cb          = {},  // (a world's: per replan, replan_flow)
+                     .cyl         = w ? w->cylinders : ps->cylinders,
+                     .n_cyl       = w ? w->n_cyl : ps->n_cyl},
+      .tick       = {.own = nullptr, .hover = ps->hover_inout, .now = ps->out_now, .t_start = ps->out_t_start,
+                     .pva = ps->out_pva, .start_offset = ps->replan_start_offset},
+      .stamp      = ps->next_stamp,
+      .poses_host = ps->out_poses};
+  p->ps_world_on = w ? 1 : 0;
   if (w) {
     p->ps_world = *w;
     // the crop lists grow HERE if this frame holds more blocks than any before it (world_blocks then drains the device and
@@ -562,14 +567,7 @@ int sogm_planner_set_prestamp(sogm_planner *p, const SogmPrestamp *ps) {
     sogm::CloudBlocks sized{};
     if (int rc = sogm::world_blocks(p->map, w, &sized)) return rc;
   }
-  p->ps.stamp        = ps->next_stamp;
-  p->ps.start_offset = ps->replan_start_offset;
-  p->ps.hover        = ps->hover_inout;
-  p->ps.now          = ps->out_now;
-  p->ps.t_start      = ps->out_t_start;
-  p->ps.pva          = ps->out_pva;
-  p->ps.poses_host   = ps->out_poses;
-  p->ps_on           = 1;
+  p->ps_on = 1;
   return SOGM_OK;
 }
 
@@ -787,11 +785,8 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   if (prestamp) {
     const int nxt = c->pool.front_ready();
     sogm::PrestampDev d = p->ps;
-    d.grid     = (void *)c->pool.grid_of(nxt);
-    d.lg       = sogm::mark_log(c, nxt);
-    d.own      = p->pub_own;
-    d.poses    = c->d_poses_next;
-    d.stamps   = c->d_stamps_next;
+    if (int rc = sogm::map_target(c, nxt, true, nullptr, &d.tgt)) return rc;
+    d.tick.own = p->pub_own;
     d.n_agents = A;
     {
       const double f = c->tune[SOGM_TUNE_PRESTAMP_GATE_FRAC];
@@ -808,9 +803,8 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     d.n_late       = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_AGENTS) < 0 ? 0 : c->tune_i(SOGM_TUNE_PRESTAMP_LATE_AGENTS);
     d.n_bits_late  = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_BITS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_BITS) : nb;
     d.n_marks_late = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) : nm;
-    if (int rc = sogm::prestamp_buffers(c, &d)) return rc;
     if (p->ps_world_on)  // the frame's blocks + the context's crop lists (built by each agent's first ticket)
-      if (int rc = sogm::world_blocks(c, &p->ps_world, &d.cb)) return rc;
+      if (int rc = sogm::world_blocks(c, &p->ps_world, &d.frame.cb)) return rc;
     // The pre-stamp's target grid was reset by an EARLIER replan when the pool holds three grids (the front of the ready
     // queue), yet on the resets' stream the launch would also sit behind THIS replan's reset — which is held back until
     // every agent's corridors are final and then takes a millisecond: traces showed the pre-stamp starting at 5.6 ms
@@ -1292,40 +1286,20 @@ int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
       return SOGM_ERR_STATE;
     }
   }
-  int words = 0;
-  {
-    sogm::PrestampDev tmp{};
-    if (int rc = sogm::prestamp_buffers(c, &tmp)) return rc;  // stamp scratch: bits, candidates
-    md.bits   = tmp.bits;
-    md.words  = tmp.words;
-    md.cand   = tmp.cand;
-    md.n_cand = tmp.n_cand;
-    words     = tmp.words;
-  }
-  (void)words;
+  if (int rc = sogm::map_target(c, slot, false, nullptr, &md.tgt)) return rc;
   FlightCtl fl   = p->fl;
   fl.xready      = xchg ? p->fl_xready : nullptr;
   fl.lag         = lag;
   fl.n_ticks     = f->n_ticks;
   fl.first_tick  = f->first_tick;
-  md.grid        = (void *)c->d_grid;
   md.worlds      = p->d_fl_worlds;
-  md.lg          = sogm::mark_log(c, slot);
-  md.own         = f->own_inout;
+  md.ov          = {.rec = nullptr, .n_rec = 0, .ego_ids = f->drone_ids, .body = c->d_body, .n_body = c->n_body};
   md.tables      = f->tables;
   md.n_total     = f->n_total;
-  md.ego_ids     = f->drone_ids;
-  md.body        = c->d_body;
-  md.n_body      = c->n_body;
+  md.tick        = {.own = f->own_inout, .hover = f->hover_inout, .now = p->d_fl_now, .t_start = p->d_fl_tstart,
+                    .pva = p->d_fl_pva, .start_offset = f->replan_start_offset};
   md.t0          = f->t0;
   md.period      = f->period;
-  md.start_offset = f->replan_start_offset;
-  md.hover       = f->hover_inout;
-  md.now         = p->d_fl_now;
-  md.t_start     = p->d_fl_tstart;
-  md.pva         = p->d_fl_pva;
-  md.poses       = c->d_poses;
-  md.stamps      = c->d_stamps;
   md.n_reset     = c->tune_i(SOGM_TUNE_FLIGHT_RESET);
   md.n_bits      = c->tune_i(SOGM_TUNE_FLIGHT_BITS);
   md.n_marks     = c->tune_i(SOGM_TUNE_FLIGHT_MARKS);
@@ -1483,13 +1457,13 @@ int sogm_flight_prepare(sogm_planner *p, int max_cloud_points) {
     big.n_blocks     = (max_cloud_points + 255) / 256;
     sogm::CloudBlocks cb{};
     if (int rc = sogm::world_blocks(p->map, &big, &cb)) return rc;
-    sogm::PrestampDev tmp{};
     if (p->map->sparse) {
-      if (int rc = sogm::prestamp_buffers(p->map, &tmp)) return rc;
-      // the current grid's mark log (its creation ends with a null-stream memset and synchronisation, which waits for every
-      // BLOCKING stream of the process — masked streams are — i.e. for another planner's flight) and the one dense clear that
-      // puts the grid under its log
-      sogm_ctx *c = p->map;
+      // the stamp's scratch, the current grid's mark log (its creation ends with a null-stream memset and synchronisation,
+      // which waits for every BLOCKING stream of the process — masked streams are — i.e. for another planner's flight) and the
+      // one dense clear that puts the grid under its log
+      sogm_ctx       *c = p->map;
+      sogm::MapTarget tgt{};
+      if (int rc = sogm::map_target(c, c->pool.current(), false, nullptr, &tgt)) return rc;
       if (!c->pool.loggable(c->pool.current()))
         if (int rc = sogm::launch_clear(c, nullptr, c->d_grid, false)) return rc;
     }

@@ -70,26 +70,47 @@ struct FlightFsmDev {
   double         *log_hover_start;
   SogmTrajRecord *log_own;
 };
-// the map role's arguments (csrc/sogm_map.hip, k_flight_map)
-struct FlightMapDev {
-  void                 *grid;          // the context's current grid (all agents)
-  unsigned             *bits;          // [A][words]
-  int                   words;
-  const FlightWorld    *worlds;        // dev [n_ticks]
-  CloudBlocks           cb;            // crop lists (bounds / counts per frame come from worlds[k])
-  void                 *cand;          // [A][SOGM_MAX_CYL_LDS] CylCand
-  int                  *n_cand;
-  MarkLog               lg;
-  const SogmTrajRecord *own;           // [A] executed records (latest wins)
-  const SogmTrajRecord *tables;        // [4][n_total] ring of swarm tables
-  int                   n_total;
+// The map stage's buffers, one struct per concern: the four builders of an agent's map (the lock-step kernels, k_update_flow,
+// k_prestamp_flow, k_flight_map) hand the same structs to the same ticket bodies (csrc/sogm_map.hip).
+struct MapTarget {  // where a map is built (host: sogm::map_target)
+  void     *grid;    // all agents' cells
+  unsigned *bits;    // [A][words] occupancy bits of slice 0 between the bits and the marks pass
+  int       words;
+  void     *cand;    // [A][SOGM_MAX_CYL_LDS] CylCand
+  int      *n_cand;  // [A]
+  MarkLog   lg;
+  float    *poses;   // [A][3] map centres / [A] stamps of these maps (the queries read them)
+  double   *stamps;
+};
+struct MapFrame {  // one sensor frame as the kernels read it
+  const float        *cloud;
+  const int32_t      *cloud_range;  // per-agent {begin, end} (null with cb.bounds set)
+  CloudBlocks         cb;           // SogmWorld frame: blocks + the context's crop lists (bounds null = the ranges above)
+  const SogmCylinder *cyl;
+  int                 n_cyl;
+};
+struct OverlayIO {  // the neighbours' records an overlay adds
+  const SogmTrajRecord *rec;
+  int                   n_rec;
   const int32_t        *ego_ids;
   const double         *body;
   int                   n_body;
-  double                t0, period, start_offset;
+};
+struct TickInputsIO {  // sogm_tick_inputs' arguments: the executed records in, a tick's start states out
+  const SogmTrajRecord *own;
   double               *hover, *now, *t_start, *pva;
-  float                *poses;         // the context's map centres / stamps (queries read them)
-  double               *stamps;
+  double                start_offset;
+};
+// the map role's arguments (csrc/sogm_map.hip, k_flight_map)
+struct FlightMapDev {
+  MapTarget             tgt;           // the context's current grid, centres and stamps
+  const FlightWorld    *worlds;        // dev [n_ticks]
+  CloudBlocks           cb;            // crop lists (bounds / counts per frame come from worlds[k])
+  OverlayIO             ov;            // rec / n_rec are set per tick from the two fields below
+  const SogmTrajRecord *tables;        // [4][n_total] ring of swarm tables
+  int                   n_total;
+  TickInputsIO          tick;          // own: executed records (latest wins)
+  double                t0, period;
   int                   n_reset, n_bits, n_marks, n_splat;  // one-wave tickets per agent and tick
   int                   un_reset, un_bits, un_marks, un_splat;  // ... of a map in the urgent lane
   int                   n_head_wgs;    // workgroups 0 .. n_head_wgs - 1 of the launch admit agents (heads), the rest work off the queue
@@ -104,7 +125,8 @@ struct FlightMapDev {
 hipError_t launch_flight_map(const GridGeom &g, const FlightCtl &fl, const FlightMapDev &d, int n_workgroups, hipStream_t st);
 
 // A stage's device buffers, one struct per stage: the grouped, dataflow and flight variants of a stage take the same
-// struct from the launcher down to the device body.  Field order = the kernels' argument order.  Every launch_* returns
+// struct from the launcher down to the device body (the map stage's four: MapTarget / MapFrame / OverlayIO / TickInputsIO
+// above).  Field order = the kernels' argument order.  Every launch_* returns
 // the first error it saw: hipGetLastError() clears the error as it reads it, the caller cannot ask again.
 struct SearchIO {  // search: start state, goal and start time in, return code / route / statistics out
   const double *start_pva, *goal, *t_start;
@@ -133,8 +155,9 @@ struct QpIO {  // QP: the corridors' polytopes and goal in, control points / sta
   int32_t       *out_status, *out_iters;
 };
 // `__restrict__` lives on the `__global__` parameters of the per-stage entries' kernels (k_astar, k_flight_search,
-// k_qp, k_corridor_points / _segment / _finalize), which fill the struct in their first lines: a struct member cannot
-// carry it.
+// k_qp, k_corridor_points / _segment / _finalize) and of the map stage's lock-step kernels (k_cull_cylinders, k_stamp_bits /
+// _blocks, k_stamp_marks / _cached, k_splat_neighbours, k_tick_inputs), which fill the struct in their first lines: a struct
+// member cannot carry it.
 // what finish_agent (csrc/sogm_corridor.hip) reads and writes for one agent
 struct FinishArgs {
   double                corridor_tau;
@@ -175,27 +198,15 @@ hipError_t launch_flight_qp(const SogmPlannerParams &pp, const SogmQpSettings &q
 // Arguments of the pre-stamp kernel (csrc/sogm_map.hip, k_prestamp_flow): the next tick's update inputs, the grid and
 // mark log it builds into, and where the next tick's start states go.
 struct PrestampDev {
-  void                 *grid;         // the pool's next grid (all agents)
-  unsigned             *bits;         // [A][words] occupancy bits of slice 0
-  int                   words;
-  const float          *cloud;
-  const int32_t        *cloud_range;  // per-agent {begin, end} (null with cb.bounds set)
-  CloudBlocks           cb;           // SogmWorld frame: blocks + the context's crop lists (bounds null = ranges above)
-  const SogmCylinder   *cyl;
-  int                   n_cyl;
-  void                 *cand;         // [A][1024] CylCand
-  int                  *n_cand;       // [A]
-  MarkLog               lg;
-  const SogmTrajRecord *own;          // the records the replan publishes into
-  double                stamp, start_offset;
-  double               *hover, *now, *t_start, *pva;  // sogm_tick_inputs' outputs for the next tick
-  float                *poses;        // the context's NEXT poses / stamps (swapped in by sogm_update_prestamped)
-  float                *poses_host;   // the caller's copy of the next map centres (optional)
-  double               *stamps;
-  int                   n_agents;
-  int                   n_bits, n_marks;  // one-wave tickets per agent for the two passes of the stamp
-  int                   n_late, n_bits_late, n_marks_late;  // ... and for the last n_late agents to be published
-  int                   gate_agents;  // agents whose corridors must be final before the pre-stamp starts (tuning key prestamp_gate_frac)
+  MapTarget    tgt;          // the pool's next grid and the context's NEXT poses / stamps (swapped in by sogm_update_prestamped)
+  MapFrame     frame;
+  TickInputsIO tick;         // own: the records the replan publishes into; the outputs are the next tick's
+  double       stamp;
+  float       *poses_host;   // the caller's copy of the next map centres (optional)
+  int          n_agents;
+  int          n_bits, n_marks;  // one-wave tickets per agent for the two passes of the stamp
+  int          n_late, n_bits_late, n_marks_late;  // ... and for the last n_late agents to be published
+  int          gate_agents;  // agents whose corridors must be final before the pre-stamp starts (tuning key prestamp_gate_frac)
 };
 // n_qp / n_finish: the QP workgroups and finishing waves of this replan — the pre-stamp's waves are not dispatched before
 // all of them are resident (they wait for what those produce, and a QP workgroup needs a whole CU)

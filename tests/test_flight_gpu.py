@@ -27,7 +27,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _lockstep_lag2(driver, grid, A, n, lag=2, **kw):
+def _lockstep_lag2(driver, grid, A, n, lag=2, maps=None, **kw):
+    """`maps`: a list that receives every agent's grid of the last tick (downloaded before the swarm is closed)"""
     import torch
     sw = driver.SwarmTick(grid, A, moving_world=True, prestamp=False, neighbour_lag=lag, **kw)
     oks, recs = [], []
@@ -38,6 +39,8 @@ def _lockstep_lag2(driver, grid, A, n, lag=2, **kw):
     assert sw.planner.flow_failures() == (0, 0)
     own = sw.own.cpu().numpy().copy()
     cnt = sw.planner.counters()
+    if maps is not None:
+        maps.extend(sw.map.download(a) for a in range(A))
     sw.close()
     return np.stack(oks), np.stack(recs), own, cnt
 
@@ -78,6 +81,30 @@ def test_flight_records_equal_the_lockstep_flight_with_the_same_staleness_rule(p
     assert np.array_equal(own_f, own_l) and np.array_equal(last_f, own_l)
     assert cnt_f == cnt_l
     print("flight, per-agent ms per tick:", dict(zip(pop._abi.FLIGHT_STAT_NAMES, (ms[:, :7].sum(axis=0) / ms[:, 7].sum()).round(3))))
+
+
+def test_a_flights_grids_equal_the_lockstep_rules_grids(pop):
+    """The cells themselves, not the records planned in them: a call builds no map beyond its last tick, so after fly(4) every
+    agent's grid is its map of tick 3 — frame 3's stamp plus the overlay of table ver(1), the first table that holds records
+    (the smallest flight whose overlay adds anything) — and must equal, cell for cell, the grid the per-tick entry points leave
+    after the same four ticks (stores of 1.0 and additions of 1.0f: exact in any order)."""
+    import torch
+    driver = importlib.import_module("pred-occ-planner_amd.driver")
+    K, A = 4, 6
+    want = []
+    ok_l, _, _, _ = _lockstep_lag2(driver, "parity", A, K, maps=want)
+    sw = driver.SwarmTick("parity", A, moving_world=True, prestamp=False)
+    sw.fly(K)
+    torch.cuda.synchronize()
+    _, hdr = sw.planner.flight_stats()
+    pop_abi = importlib.import_module("pred-occ-planner_amd")._abi
+    assert hdr[pop_abi.FLIGHT_HDR_ERR] == 0 and hdr[pop_abi.FLIGHT_HDR_FINISHED] == A * K, hdr.tolist()
+    got = [sw.map.download(a) for a in range(A)]
+    sw.close()
+    assert ok_l[1].any()  # (table ver(1) holds records: tick 3's overlay had something to add)
+    for a in range(A):
+        assert np.count_nonzero(want[a]) > 0 and np.count_nonzero(got[a]) > 0, a
+        assert np.array_equal(got[a], want[a]), f"agent {a}: {np.count_nonzero(got[a] != want[a])} cells differ"
 
 
 def test_a_flight_continues_a_flight(pop):
