@@ -604,6 +604,11 @@ void sogm_planner_destroy(sogm_planner *p);
  * dev t_start   [n_agents]   fp64 absolute trajectory start time (traj_start_time_)
  * dev out_ret   [n_agents]   int32 ASTAR_RET (dyn_a_star.h:15)
  * dev out_route [n_agents*route_cap*6] fp64, dev out_route_len [n_agents] int32
+ *   A route longer than its row: out_route_len is the route's FULL count n (0 after NO_PATH), whatever route_cap
+ *   (>= 2) is; the agent's row holds the first min(n, route_cap) points counted from the start of the route, so its
+ *   first point is the same for every route_cap; points past them are left as they were.  Every consumer of (route,
+ *   route_len, route_cap) — sogm_corridor_generate, sogm_corridor_rules_batched, the replan — uses
+ *   min(route_len, route_cap) points and reads nothing past the agent's row.
  * dev out_stats [n_agents*4] int32 {use_node_num, iter_num, n_path_nodes, searches_run}
  * dev out_trace [n_agents*trace_cap] int32 or NULL: pool id of every popped node, in order.
  */
@@ -616,6 +621,8 @@ int sogm_astar_search(sogm_planner *p, const double *start_pva, const double *go
  * Corridor generation for given routes: baseline_fake.cpp:300-412 — per segment local box,
  * getObstaclePoints, firi::firi (sfc_gen/firi.hpp:238-365), ShrinkCorridor, validity LP;
  * adjacent-intersection LPs; goal reachability.  Polytopes are rows h0 x + h1 y + h2 z + h3 <= 0.
+ * dev route [n_agents*route_cap*6] fp64, dev route_len [n_agents] int32 as sogm_astar_search writes them: an agent
+ *   with route_len > route_cap is treated as one with route_len = route_cap (the points its row holds).
  * dev out_polys  [n_agents*SOGM_MAX_PIECES*max_faces*4] fp64
  * dev out_nfaces [n_agents*SOGM_MAX_PIECES] int32,  dev out_npoly [n_agents] int32
  * dev out_goal   [n_agents*6] fp64 local goal pos,vel

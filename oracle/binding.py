@@ -158,8 +158,17 @@ def astar_search(spec, ap, grid, pose, start_pva, goal, t_after_map, corridor_ta
                                  C.c_double(t_after_map), C.c_double(corridor_tau), dptr(route), C.byref(n),
                                  route_cap, stats, trace.ctypes.data_as(C.POINTER(C.c_int32)), trace_cap,
                                  C.byref(ntr))
-    return {"ret": ret, "route": route[:n.value].copy(), "stats": list(stats),
+    # route_len: the route's full count; "route" holds its first min(route_len, route_cap) points
+    return {"ret": ret, "route": route[:n.value].copy(), "route_len": n.value, "stats": list(stats),
             "trace": trace[:min(ntr.value, trace_cap)].copy(), "trace_len": ntr.value}
+
+
+def astar_debug_nodes(n):
+    """the first n pool nodes of the last astar_search: rows {state[6], input[3], duration, time, g, f, index[3], time_idx,
+    parent}"""
+    out = np.zeros((n, 18))
+    k = lib().orc_astar_debug_nodes(dptr(out), n)
+    return out[:k]
 
 
 # ---------------------------------------------------------------- LP

@@ -955,13 +955,41 @@ __device__ __forceinline__ bool astar_search_wg(
           t_sample = corridor_tau;
         }
       }
-      const int kept = n < io.route_cap ? n : io.route_cap;
-      for (int i = 0; i < kept / 2; ++i)
-        for (int q = 0; q < 6; ++q) {
-          const double tmp              = route[i * 6 + q];
-          route[i * 6 + q]              = route[(kept - 1 - i) * 6 + q];
-          route[(kept - 1 - i) * 6 + q] = tmp;
+      if (n <= io.route_cap) {
+        for (int i = 0; i < n / 2; ++i)
+          for (int q = 0; q < 6; ++q) {
+            const double tmp           = route[i * 6 + q];
+            route[i * 6 + q]           = route[(n - 1 - i) * 6 + q];
+            route[(n - 1 - i) * 6 + q] = tmp;
+          }
+      } else {
+        // a route longer than the row (sogm_abi.h: the row holds the FIRST route_cap points, counted from the route's
+        // start): the row now holds the walk's first points, the route's last ones.  n is known: walk again — the same
+        // subtractions, the same points — and store the j-th point of the walk at its place n - 1 - j if that is in the row
+        node     = terminal;
+        t_sample = corridor_tau;
+        int j    = 1;  // (the terminal state, j = 0, is past the row)
+        while (pool[node].parent >= 0) {
+          const Node &nd  = pool[node];
+          const Node &par = pool[nd.parent];
+          t_node          = nd.duration;
+          while (true) {
+            if (t_sample > t_node) {
+              node = nd.parent;
+              t_sample -= t_node;
+              break;
+            }
+            t_node -= t_sample;
+            if (n - 1 - j < io.route_cap) {
+              double xt[6];
+              state_transit(par.state, xt, nd.input, t_node);
+              for (int q = 0; q < 6; ++q) route[(n - 1 - j) * 6 + q] = xt[q];
+            }
+            ++j;
+            t_sample = corridor_tau;
+          }
         }
+      }
     }
     // number of nodes on the retrieved path (retrievePath :826-836)
     int n_path = 0;

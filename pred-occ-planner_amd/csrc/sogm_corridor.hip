@@ -789,7 +789,7 @@ __device__ __forceinline__ void corridor_points_body(const MapView &m, const Sog
                                                      const CorridorWorkspace &ws, const CorridorIO &io, int agent,
                                                      int seg) {
   const int tid   = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rl    = io.route_len[agent];
+  const int rl    = io.points(agent);
   const int slot  = agent * SOGM_MAX_PIECES + seg;
   if (seg >= rl - 1 || seg >= SOGM_MAX_PIECES) return;
   __shared__ double s_box[6], s_w[6];
@@ -935,7 +935,7 @@ __device__ __forceinline__ void corridor_segment_body(const MapView &m, const So
   const int lane  = threadIdx.x;
   const int slot  = DIRECT ? agent : agent * SOGM_MAX_PIECES + seg;
   if constexpr (!DIRECT) {
-    const int rl = io.route_len[agent];
+    const int rl = io.points(agent);
     if (seg >= rl - 1 || seg >= SOGM_MAX_PIECES) {
       if (lane == 0) ws.seg_state[slot] = -2;  // no such segment
       return;
@@ -1277,7 +1277,7 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
   const int    *state = ws.seg_state + agent * SOGM_MAX_PIECES;
   const double *rt    = io.route + (size_t)agent * io.route_cap * 6;
   const double *sp    = io.start_pva + agent * 9;
-  const int     rl    = io.route_len[agent];
+  const int     rl    = io.points(agent);
   int           npoly = 0;
   if (w0) {
     for (int i = 0; i < SOGM_MAX_PIECES; ++i) io.out_nfaces[agent * SOGM_MAX_PIECES + i] = 0;
@@ -1296,7 +1296,8 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
     }
     ++npoly;
   }
-  if (npoly == SOGM_MAX_PIECES && rl - 1 > SOGM_MAX_PIECES && w0 && ws.counters)
+  // (the route's full count: a route cut by its row AND by the 16 pieces is counted as before)
+  if (npoly == SOGM_MAX_PIECES && io.route_len[agent] - 1 > SOGM_MAX_PIECES && w0 && ws.counters)
     atomicAdd(&ws.counters[SOGM_CNT_PIECES_CAPACITY], 1ull);  // route longer than 16 pieces: truncated
   if (npoly == 0) return;
   for (int i = 0; i + 1 < npoly; ++i) {
@@ -1374,7 +1375,7 @@ __global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, Corrido
   const int               prob = blockIdx.x, lane = threadIdx.x;
   const SogmPlannerParams pp   = cr.pp[prob];
   const int               MF   = pp.max_faces;
-  const int               rl   = io.route_len[prob];
+  const int               rl   = io.points(prob);
   for (int seg = 0; seg < SOGM_MAX_PIECES; ++seg) {
     const int slot = prob * SOGM_MAX_PIECES + seg;
     if (seg >= rl - 1) {
@@ -1424,7 +1425,7 @@ __global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, Corrido
 __device__ __forceinline__ bool corridor_slot(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
                                               const CorridorIO &io, int agent, int seg, char *smem, int *seg_done,
                                               bool cumulative, long long *stamps) {
-  if (seg < io.route_len[agent] - 1) {
+  if (seg < io.points(agent) - 1) {
     corridor_points_body<1>(m, pp, ws, io, agent, seg);
     __threadfence_block();
     __syncthreads();

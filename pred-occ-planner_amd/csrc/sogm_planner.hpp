@@ -147,6 +147,11 @@ struct CorridorIO {  // corridors: the search's route in, polytopes and the loca
   double        *out_polys;
   int32_t       *out_nfaces, *out_npoly;
   double        *out_goal;
+  // way-points in the agent's row: route_len is the route's full count, the row keeps route_cap of them (sogm_abi.h)
+  __device__ __forceinline__ int points(int agent) const {
+    const int n = route_len[agent];
+    return n < route_cap ? n : route_cap;
+  }
 };
 struct QpIO {  // QP: the corridors' polytopes and goal in, control points / status / iterations out
   const double  *start_pva, *goal_pv, *polys;

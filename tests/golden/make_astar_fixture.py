@@ -10,6 +10,8 @@ Restated, statement by statement:
   FakeRiskHybridAstar::reset / search        path_searching/src/fake_risk_hybrid_a_star.cpp:84-100, 114-432
   estimateHeuristic, cubic, quartic          :434-469, 533-591
   computeShotTraj                            :470-531
+  getPathWithVel                             :671-701  (routes at five corridor_tau values, and searches labelled by the branch
+      they end in — NEAR_END, the root as terminal node, the node pool running out —> astar_route_independent.json)
   posToIndex, timeToIndex, stateTransit      :802-831
   NodeComparator, NodeHashTable              path_searching/include/path_searching/grid_node.h:46-51, path_node.h:70-97
   std::priority_queue = std::push_heap / std::pop_heap of libstdc++ (bits/stl_heap.h: __push_heap, __adjust_heap) — the
@@ -207,9 +209,10 @@ class Heap:
 
 
 class Search:
-    def __init__(self, fmap, pop_cap=200):
+    def __init__(self, fmap, pop_cap=200, allocate_num=ALLOCATE_NUM):
         self.map = fmap
-        self.pool = [Node(i) for i in range(ALLOCATE_NUM)]
+        self.allocate_num = allocate_num         # search/allocate_num (:71); init sizes the pool with it (:50)
+        self.pool = [Node(i) for i in range(allocate_num)]
         self.use_node_num = 0
         self.pop_cap = pop_cap
         self.reset()
@@ -225,6 +228,12 @@ class Search:
         self.iter_num = 0
         self.is_shot_succ = False
         self.pops = []
+        # bookkeeping of the fixture's labels (not part of the reference): nodes overwritten while open, the child at which
+        # the pool ran out (index, number of inputs of that expansion), the shot's blocking sample (position, time)
+        self.rewritten = set()
+        self.exhausted_at = None
+        self.shot_block = None
+        self.shot_samples = []
 
     def pos_to_index(self, pt):
         return tuple(int(math.floor((pt[i] - self.map_center[i]) * INV_RES)) for i in range(3))
@@ -250,10 +259,13 @@ class Search:
         b = [0.5 * (6.0 / (t_d * t_d) * (dp[i] - v0[i] * t_d) - 2 / t_d * dv[i]) for i in range(3)]
         t_delta = t_d / 10
         time = t_delta
+        self.shot_samples = []
         while time <= t_d:
             tp = [math.pow(time, j) for j in range(4)]
             coord = [((p0[i] * tp[0] + v0[i] * tp[1]) + b[i] * tp[2]) + a[i] * tp[3] for i in range(3)]
+            self.shot_samples.append((coord, time))
             if self.map.clear_occupancy_dt(coord, time) != 0:
+                self.shot_block = (coord, time)
                 return False
             time += t_delta
         self.is_shot_succ = True
@@ -325,7 +337,7 @@ class Search:
                         ay += MAX_ACC * res
                     ax += MAX_ACC * res
             durations = [TIME_RESOLUTION]
-            for um in inputs:
+            for i_um, um in enumerate(inputs):
                 for tau in durations:
                     pro_state = state_transit(cur_state, um, tau)
                     pro_t = cur.time + tau
@@ -380,7 +392,8 @@ class Search:
                             self.insert(pro_id, int(pro_node.time), pro_node)
                             tmp_expand.append(pro_node)
                             self.use_node_num += 1
-                            if self.use_node_num == ALLOCATE_NUM:
+                            if self.use_node_num == self.allocate_num:
+                                self.exhausted_at = (i_um, len(inputs))
                                 return NO_PATH
                         elif pro_node.node_state == IN_OPEN_SET:
                             if tmp_g < pro_node.g:
@@ -391,14 +404,16 @@ class Search:
                                 pro_node.duration = tau
                                 pro_node.parent = cur
                                 pro_node.time = cur.time + tau
+                                self.rewritten.add(pro_node.pid)
                         else:
                             return SEARCH_ERR
         return NO_PATH
 
 
-def replan_search(fmap, start_pva, goal, t_after_map, pop_cap=200):
-    """baseline_fake.cpp:280-291: reset, search(init = true); on NO_PATH reset and search(init = false)"""
-    s = Search(fmap, pop_cap)
+def replan_search_full(fmap, start_pva, goal, t_after_map, pop_cap=200, allocate_num=ALLOCATE_NUM):
+    """baseline_fake.cpp:280-291: reset, search(init = true); on NO_PATH reset and search(init = false).  Returns the
+    attempts and the Search as the last attempt left it (node_path_, is_shot_succ_: what getPathWithVel reads)"""
+    s = Search(fmap, pop_cap, allocate_num)
     attempts = []
     for init in (True, False):
         s.reset()
@@ -409,7 +424,35 @@ def replan_search(fmap, start_pva, goal, t_after_map, pop_cap=200):
                          "path_nodes": [n.pid for n in s.node_path]})
         if ret != NO_PATH:
             break
-    return attempts
+    return attempts, s
+
+
+def replan_search(fmap, start_pva, goal, t_after_map, pop_cap=200, allocate_num=ALLOCATE_NUM):
+    return replan_search_full(fmap, start_pva, goal, t_after_map, pop_cap, allocate_num)[0]
+
+
+def get_path_with_vel(search, delta_t):   # :671-701, from the reference's text alone
+    state_list = []
+    node = search.node_path[-1]
+    t_node = 0.0                          # time to next node
+    t_sample = delta_t                    # time to next sample
+    state_list.append(list(node.state))
+    while node.parent is not None:
+        ut = node.input
+        duration = node.duration
+        x0 = node.parent.state
+        t_node = duration
+        while True:
+            if t_sample > t_node:         # can't sample in this node, skip to next
+                node = node.parent
+                t_sample -= t_node
+                break
+            t_node -= t_sample
+            xt = state_transit(x0, ut, t_node)   # backward
+            state_list.append(xt)
+            t_sample = delta_t
+    state_list.reverse()
+    return state_list
 
 
 POCKETS = [(1.6, 1.4), (2.2, 1.8), (1.2, 2.4), (2.8, 1.2)]   # (half_width, depth) of the wall pockets
@@ -450,11 +493,147 @@ def build_cases():
     return seed, A, sc, cases
 
 
+CORRIDOR_TAUS = [0.3, 0.2, 0.1, 0.45, 0.7]   # the tie with time_resolution, sim_cfg.yaml's 0.2, several samples per node,
+#                                              a carry across nodes, nodes without a sample
+
+
+def route_record(att, s):
+    """what the route fixture keeps of one replan_search_full: per attempt the verdict and counts, of the last attempt the
+    path nodes after the root (the root's input / duration are never written) and getPathWithVel at every corridor_tau —
+    no route after NO_PATH (baseline_fake.cpp:293-297 returns before getPathWithVel)"""
+    last = att[-1]
+    rec = {"attempts": [{"init": x["init"], "ret": x["ret"], "iter_num": x["iter_num"], "use_node_num": x["use_node_num"],
+                         "path_nodes": x["path_nodes"]} for x in att],
+           "path": {"nodes": [n.pid for n in s.node_path], "input": [list(n.input) for n in s.node_path[1:]],
+                    "duration": [n.duration for n in s.node_path[1:]], "time": [n.time for n in s.node_path[1:]]},
+           "route_len": {}, "routes": {}}
+    for tau in CORRIDOR_TAUS:
+        route = get_path_with_vel(s, tau) if last["ret"] != NO_PATH else []
+        rec["route_len"][repr(tau)] = len(route)
+        rec["routes"][repr(tau)] = route
+    return rec
+
+
+def shot_probes(fmap, coord, time):
+    """the map's answers at a shot sample and at the 26 positions one cell (RESOLUTION) away from it, in the sample's slice"""
+    return [fmap.clear_occupancy_dt([coord[0] + dx * RESOLUTION, coord[1] + dy * RESOLUTION, coord[2] + dz * RESOLUTION], time)
+            for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1)]
+
+
+def shot_not_marginal(fmap, s):
+    """a failed shot: its blocking sample lies at least one cell inside the region that is not clear; a shot that
+    succeeded: every sample at least one cell inside the clear region"""
+    if s.is_shot_succ:
+        return all(all(v == 0 for v in shot_probes(fmap, c, t)) for (c, t) in s.shot_samples)
+    return s.shot_block is not None and all(v != 0 for v in shot_probes(fmap, *s.shot_block))
+
+
+def build_edge_cases(seed, sc, cyl, cases, searches):
+    """the labelled searches of tests/golden/astar_route_independent.json (see its `what`)"""
+    def record(branch, a, pose, pva, goal, t0, pocket, att, s, allocate_num=ALLOCATE_NUM, extra=None):
+        rec = {"branch": branch, "agent": a, "pose": [float(x) for x in pose], "start_pva": [float(x) for x in pva],
+               "goal": [float(x) for x in goal], "t_after_map": t0, "pocket": pocket, "extra_cloud": extra,
+               "allocate_num": allocate_num}
+        rec.update(route_record(att, s))
+        print(f"  {branch}: allocate_num {allocate_num} " +
+              " | ".join(f"ret={x['ret']} iters={x['iter_num']} nodes={x['use_node_num']}" for x in att) +
+              f" route_len {rec['route_len']}")
+        return rec
+
+    edge = {}
+    # ---- a seeded scan: goals 0 - 2.5 m (180) and 2.5 - 9 m (20) from the first open-field start of every agent ----
+    rng = np.random.default_rng(seed + 2)
+    rewritten = None
+    for i, ((a, m, pose, pva, goal, t0, pocket), (att, s)) in enumerate(zip(cases, searches)):
+        if rewritten is None and any(n.pid in s.rewritten for n in s.node_path):
+            rewritten = record("path_node_rewritten_while_open", a, pose, pva, goal, t0, pocket, att, s)
+    for k in range(200):
+        a, m, pose, pva, _, t0, _ = cases[(k % 3) * 8]
+        dist = rng.uniform(0.05, 2.5) if k < 180 else rng.uniform(2.5, 9.0)
+        ang = rng.uniform(0, 2 * math.pi)
+        goal = [pva[0] + dist * math.cos(ang), pva[1] + dist * math.sin(ang), pva[2] + rng.uniform(-0.3, 0.3)]
+        att, s = replan_search_full(m, pva, goal, t0)
+        last = att[-1]
+        if rewritten is None and last["ret"] != NO_PATH and any(n.pid in s.rewritten for n in s.node_path):
+            rewritten = record("path_node_rewritten_while_open", a, pose, pva, goal, t0, None, att, s)
+        if "near_end_shot_fails" not in edge and last["ret"] == NEAR_END and len(s.node_path) > 1 and shot_not_marginal(m, s):
+            edge["near_end_shot_fails"] = record("near_end_shot_fails", a, pose, pva, goal, t0, None, att, s)
+        if ("root_terminal_shot_ok" not in edge and len(att) == 1 and last["ret"] == REACH_END and last["iter_num"] == 0 and
+                len(s.node_path) == 1 and shot_not_marginal(m, s)):
+            rec = record("root_terminal_shot_ok", a, pose, pva, goal, t0, None, att, s)
+            assert all(n == 1 for n in rec["route_len"].values())
+            edge["root_terminal_shot_ok"] = rec
+    # NEAR_END with a shot that is blocked WELL inside: the shot's clock starts at 0 again (:521), so a goal where a moving
+    # cylinder still stands in slice 0 and has left by the time the search arrives.  Goals around the moving cylinders within
+    # 4 m of the open-field starts, until one qualifies
+    rng = np.random.default_rng(seed + 3)
+    for ci in [i for i in range(len(cases)) if cases[i][6] is None]:
+        a, m, pose, pva, _, t0, _ = cases[ci]
+        for r in sc["cylinders"]:
+            if math.hypot(r[0] - pva[0], r[1] - pva[1]) > 4.0 or math.hypot(r[3], r[4]) < 0.2:
+                continue
+            for k in range(12):
+                goal = [float(r[0]) + rng.uniform(-0.7, 0.7), float(r[1]) + rng.uniform(-0.7, 0.7), pva[2] + rng.uniform(-0.3, 0.3)]
+                if "near_end_shot_fails" in edge:
+                    continue
+                att, s = replan_search_full(m, pva, goal, t0)
+                if att[-1]["ret"] == NEAR_END and len(s.node_path) > 1 and shot_not_marginal(m, s):
+                    edge["near_end_shot_fails"] = record("near_end_shot_fails", a, pose, pva, goal, t0, None, att, s)
+    assert "near_end_shot_fails" in edge and "root_terminal_shot_ok" in edge, sorted(edge)
+
+    # ---- the root is the terminal node and its shot is blocked: NO_PATH in both attempts without an expansion ----
+    a, m, pose, pva, _, t0, _ = cases[0]
+    goal = [pva[0] + 0.1, pva[1] + 0.05, pva[2]]
+    g = np.arange(-3, 4) * 0.1
+    extra = np.round(np.array([[goal[0] + dx, goal[1] + dy, goal[2] + dz] for dx in g for dy in g for dz in g]), 2)
+    mb = FakeMap()
+    mb.update_map(np.concatenate([sc["cloud"], extra.astype(np.float32)]), cyl, pose)
+    att, s = replan_search_full(mb, pva, goal, t0)
+    assert [x["ret"] for x in att] == [NO_PATH, NO_PATH] and all(x["iter_num"] == 0 for x in att), att
+    assert all(abs(p - q) <= 1 for p, q in zip(s.pos_to_index(pva[0:3]), s.pos_to_index(goal)))
+    assert shot_not_marginal(mb, s)
+    edge["root_terminal_shot_blocked"] = record("root_terminal_shot_blocked", a, pose, pva, goal, t0, None, att, s,
+                                                extra=extra.tolist())
+
+    # ---- the pool runs out (:403-407): on the full search's last allocation, one node later, and inside an expansion ----
+    a, m, pose, pva, goal, t0, pocket = cases[10]
+    N = searches[10][0][-1]["use_node_num"]
+    assert len(searches[10][0]) == 1 and 130 <= N <= 300, N
+    att, s = replan_search_full(m, pva, goal, t0, allocate_num=N)
+    assert [x["ret"] for x in att] == [NO_PATH, NO_PATH] and all(x["use_node_num"] == N for x in att), att
+    edge["pool_exhausted_on_last_allocation"] = record("pool_exhausted_on_last_allocation", a, pose, pva, goal, t0, pocket,
+                                                       att, s, N)
+    att, s = replan_search_full(m, pva, goal, t0, allocate_num=N + 1)
+    assert [{k: v for k, v in x.items()} for x in att] == searches[10][0], "one spare node: the full search's result"
+    edge["pool_one_spare"] = record("pool_one_spare", a, pose, pva, goal, t0, pocket, att, s, N + 1)
+    for half in range(N // 2, N // 2 - 16, -1):
+        att, s = replan_search_full(m, pva, goal, t0, allocate_num=half)
+        if (len(att) == 2 and att[1]["ret"] == NO_PATH and att[1]["use_node_num"] == half and s.exhausted_at is not None and
+                s.exhausted_at[1] > 1 and 0 < s.exhausted_at[0] < s.exhausted_at[1] - 1):
+            break   # (the full primitive set: 5 x 5 x 3 = 75 inputs at max_acc 6, res 1/2 (:245-250))
+    else:
+        raise AssertionError("no pool size near N / 2 ends inside an expansion of the second attempt")
+    assert all(x["use_node_num"] == half for x in att)
+    edge["pool_exhausted_mid_expansion"] = record("pool_exhausted_mid_expansion", a, pose, pva, goal, t0, pocket, att, s, half)
+
+    a, m, pose, pva, goal, t0, pocket = cases[4]
+    att, s = searches[4]
+    assert len(att) == 2 and att[0]["ret"] == NO_PATH and att[1]["ret"] != NO_PATH
+    edge["first_attempt_fails"] = record("first_attempt_fails", a, pose, pva, goal, t0, pocket, att, s)
+    if rewritten is not None:
+        edge["path_node_rewritten_while_open"] = rewritten
+    return list(edge.values()), rewritten is not None
+
+
 def main():
     seed, A, sc, cases = build_cases()
+    cyl = [{"type": 3, "x": float(r[0]), "y": float(r[1]), "w": float(r[2]), "vx": float(r[3]), "vy": float(r[4])}
+           for r in sc["cylinders"]]
     out_cases = []
+    searches = []
     for (a, m, pose, pva, goal, t0, pocket) in cases:
-        att = replan_search(m, pva, goal, t0)
+        att, s = replan_search_full(m, pva, goal, t0)
+        searches.append((att, s))
         print(f"agent {a} pocket {pocket}: goal {np.round(goal, 2).tolist()} t0 {t0}: " +
               " | ".join(f"init={x['init']} ret={x['ret']} iters={x['iter_num']} nodes={x['use_node_num']}" for x in att))
         out_cases.append({"agent": a, "pose": [float(x) for x in pose], "start_pva": [float(x) for x in pva],
@@ -466,6 +645,32 @@ def main():
     with open(os.path.join(ROOT, "tests", "golden", "astar_independent.json"), "w") as f:
         json.dump(out, f)
     print("written tests/golden/astar_independent.json")
+
+    # ---- the routes: getPathWithVel of the same 24 searches, and the labelled edge cases ----
+    routes = []
+    for i, (att, s) in enumerate(searches):
+        rec = {"case": i}
+        rec.update(route_record(att, s))
+        for x in rec["attempts"]:
+            x["path_nodes"] = len(x["path_nodes"])
+        routes.append(rec)
+    edge, found_rewritten = build_edge_cases(seed, sc, cyl, cases, searches)
+    for rec in edge:
+        for x in rec["attempts"]:
+            x["path_nodes"] = len(x["path_nodes"])
+    what = ("FakeRiskHybridAstar::getPathWithVel(corridor_tau) (fake_risk_hybrid_a_star.cpp:671-701) restated independently "
+            "in Python (tests/golden/make_astar_fixture.py) for the 24 searches of astar_independent.json (`routes`, `case` = "
+            "index there) at every corridor_tau of `corridor_taus`: rows of 6 = position, velocity; `path` = pool ids of the "
+            "path nodes, and input, duration and time of those after the root; `route_len` 0 and no route after NO_PATH.  `edge_cases`: searches on "
+            "the same scene labelled by the branch they take (`branch`), with `allocate_num` the size of the node pool and "
+            "`extra_cloud` points added to the scene's cloud; attempts[*].path_nodes = number of nodes on the retrieved path.  ")
+    what += ("Every label was found." if found_rewritten else
+             "path_node_rewritten_while_open was NOT found: none of the 24 searches and of 200 seeded goals returns a path "
+             "through a node overwritten by the tmp_g < pro_node->g branch (:410-418); the tests do not claim it.")
+    out = {"what": what, "seed": seed, "agents": A, "corridor_taus": CORRIDOR_TAUS, "routes": routes, "edge_cases": edge}
+    with open(os.path.join(ROOT, "tests", "golden", "astar_route_independent.json"), "w") as f:
+        json.dump(out, f)
+    print("written tests/golden/astar_route_independent.json")
 
 
 if __name__ == "__main__":
