@@ -1,8 +1,10 @@
-// sogm_handover.hpp — device-side hand-overs between the persistent kernels: the control blocks, the tag arithmetic of their
-// slots, the failure codes, ONE bounded wait and ONE publish.  The arithmetic and the codes compile on the host too
-// (tests/handover_host_test.cpp); everything that runs on the device sits behind __HIPCC__.
+// sogm_handover.hpp — device-side hand-overs between the persistent kernels: the control blocks, their
+// layouts (FlowBlock, FlightBlock: what is carved where, what a call resets), the tag arithmetic of their slots, the failure
+// codes, ONE bounded wait and ONE publish.  The layouts, the arithmetic and the codes compile on the host too
+// (tests/planner_blocks_host_test.cpp, tests/handover_host_test.cpp); everything that runs on the device sits behind __HIPCC__.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -48,6 +50,31 @@ struct FlowCtl {
   int       *out_records;  // [A][rec_words]
   int        rec_words;
 };
+// The block's layout (sogm_planner::d_flow), word offsets from its base, the only place that knows it:
+//   hdr[FLOW_HDR] | seg_done[A] | stage[A] | a_ready[A] | q_ready[A] | f_ready[A] | p_ready[A] | gen
+// Tests and tools read peeked words by these offsets (sogm_debug_flow_peek copies the block in front of `gen`).
+struct FlowBlock {
+  int seg_done, stage, a_ready, q_ready, f_ready, p_ready;
+  int gen;  // the reset's generation word (FlowCtl::reset_gen), the block's last
+  constexpr explicit FlowBlock(int A)
+      : seg_done(FLOW_HDR), stage(seg_done + A), a_ready(stage + A), q_ready(a_ready + A), f_ready(q_ready + A),
+        p_ready(f_ready + A), gen(p_ready + A) {}
+  // what k_flow_reset puts back per replan: header, seg_done and stage to 0, the four ready lists to -1
+  constexpr int zero_words() const { return a_ready; }  // [0, zero_words)
+  constexpr int fill_first() const { return a_ready; }  // [fill_first, fill_first + fill_words)
+  constexpr int fill_words() const { return gen - a_ready; }
+  static constexpr size_t words(int A) { return (size_t)FlowBlock(A).gen + 1; }
+  static void carve(int *base, int A, FlowCtl *fc) {
+    const FlowBlock b(A);
+    fc->hdr      = base;
+    fc->seg_done = base + b.seg_done;
+    fc->stage    = base + b.stage;
+    fc->a_ready  = base + b.a_ready;
+    fc->q_ready  = base + b.q_ready;
+    fc->f_ready  = base + b.f_ready;
+    fc->p_ready  = base + b.p_ready;
+  }
+};
 // ---------------------------------------------------------------------------------------------------------------
 // Flight (sogm_flight_run): n_ticks replan ticks of every agent in ONE set of launches, every agent on its own clock.
 // The reference's drones replan asynchronously, each reading whatever trajectories arrived last
@@ -56,7 +83,7 @@ struct FlowCtl {
 // their tick k - 2 (table ver(k - 2)), and may start once every agent has finished tick k - 2 — and the SCHEDULE is free:
 // an agent whose chain is done goes straight on to its next tick while a straggler still solves its QP.
 // Four persistent kernels, each on a stream with its own compute units (a CU-masked stream; every mask balanced over
-// the shader engines it touches and every launch exactly as large as its mask holds — flight_layout in sogm_planner.hip: all
+// the shader engines it touches and every launch exactly as large as its mask holds — flight_partition in sogm_flight_layout.hpp: all
 // workgroups resident from the first microsecond, which is also what lets a flight survive the hardware scheduler's queue
 // save / restore; no residency gates, no dispatch-order assumptions, four hardware queues):
 //   k_flight_map     a few admitting waves + role-less one-wave workgroups over ONE work queue of ready map work (a descriptor
@@ -157,6 +184,51 @@ struct FlightCtl {
   int  n_agents, n_ticks, first_tick;
   int  lag;         // tick k reads the neighbours' records of tick k - lag: 2 (the flight's rule: the most overlap) or 1 (the
                     // reference's staleness — a record one broadcast old, particles.cpp:179-190; tuning key flight_neighbour_lag)
+};
+// The block's layout (sogm_planner::d_fl), word offsets from its base, the only place that knows it:
+//   hdr[FL_HDR] | s_ring | q_ring | m_ring | u_ring (ring(A) each) | mw | lw (2 FL_WQ_SLOTS each) | tick_done | parked_n |
+//   xready (FLIGHT_MAX_TICKS each) | tick_of | seg_done | stage | urgent (A each) | parked[FLIGHT_MAX_TICKS][A] | uw (2 FL_WQ_SLOTS)
+// Every call zeroes the words in front of `parked` (k_flight_reset; k_flight_seed fills the parked lists); the urgent queue
+// lies behind them because its slots and its head / tail words run on over the planner's life (k_flight_reset).
+struct FlightBlock {
+  int ring;  // slots of each ring: the smallest power of two >= 2 A
+  int s_ring, q_ring, m_ring, u_ring, mw, lw, tick_done, parked_n, xready, tick_of, seg_done, stage, urgent, parked, uw;
+  int end;   // == words(A)
+  static constexpr int ring_of(int A) {
+    int r = 1;
+    while (r < 2 * A) r <<= 1;
+    return r;
+  }
+  constexpr explicit FlightBlock(int A)
+      : ring(ring_of(A)), s_ring(FL_HDR), q_ring(s_ring + ring), m_ring(q_ring + ring), u_ring(m_ring + ring),
+        mw(u_ring + ring), lw(mw + 2 * FL_WQ_SLOTS), tick_done(lw + 2 * FL_WQ_SLOTS), parked_n(tick_done + FLIGHT_MAX_TICKS),
+        xready(parked_n + FLIGHT_MAX_TICKS), tick_of(xready + FLIGHT_MAX_TICKS), seg_done(tick_of + A), stage(seg_done + A),
+        urgent(stage + A), parked(urgent + A), uw(parked + parked_words(A)), end(uw + 2 * FL_WQ_SLOTS) {}
+  // the 64-bit queues start on 8 bytes: every term in front of them is even (a ring holds >= 2 slots, A >= 1)
+  static_assert(FL_HDR % 2 == 0 && FLIGHT_MAX_TICKS % 2 == 0, "mw, lw and uw must start on even word offsets");
+  static constexpr int    parked_words(int A) { return FLIGHT_MAX_TICKS * A; }
+  static constexpr int    reset_words(int A) { return FlightBlock(A).parked; }
+  static constexpr size_t words(int A) { return (size_t)FlightBlock(A).end; }
+  static void carve(int *base, int A, FlightCtl *fl, int **xready_out) {
+    const FlightBlock b(A);
+    fl->hdr       = base;
+    fl->s_ring    = base + b.s_ring;
+    fl->q_ring    = base + b.q_ring;
+    fl->m_ring    = base + b.m_ring;
+    fl->u_ring    = base + b.u_ring;
+    fl->mw        = reinterpret_cast<unsigned long long *>(base + b.mw);
+    fl->lw        = reinterpret_cast<unsigned long long *>(base + b.lw);
+    fl->uw        = reinterpret_cast<unsigned long long *>(base + b.uw);
+    fl->ring_mask = b.ring - 1;
+    fl->tick_done = base + b.tick_done;
+    fl->parked_n  = base + b.parked_n;
+    *xready_out   = base + b.xready;  // (FlightCtl::xready is set per call: null without the exchange behind it)
+    fl->tick_of   = base + b.tick_of;
+    fl->seg_done  = base + b.seg_done;
+    fl->stage     = base + b.stage;
+    fl->urgent    = base + b.urgent;
+    fl->parked    = base + b.parked;
+  }
 };
 
 // ---------------------------------------------------------------------------------------------------------------

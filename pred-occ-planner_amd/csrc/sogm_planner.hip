@@ -1,7 +1,7 @@
 // sogm_planner.hip — planner context and host side of the planner entry points: the per-stage calls (search,
 // corridors, QP, deconfliction) and sogm_replan in its two forms — the dataflow replan (replan_flow: five launches,
 // persistent corridor / QP / finish kernels chained per agent through ready lists) and the grouped-stream chain
-// (replan_impl).  SOGM_ERR_STATE from an entry point means a call-order error (no map update before planning).
+// (replan_impl).  The flight (sogm_flight_run) is in sogm_flight.hip.  SOGM_ERR_STATE from an entry point means a call-order error (no map update before planning).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -108,9 +108,87 @@ __global__ void k_flow_report(const int *__restrict__ hdr, int *__restrict__ hos
 
 extern "C" {
 
+// Everything sogm_planner_create acquires, all or nothing (Resources::Setup): an error return leaves nothing allocated.
+static int planner_acquire(sogm_planner *p) {
+  sogm_ctx                *map = p->map;
+  const SogmPlannerParams *pp  = &p->pp;
+  const int                A   = map->n_agents;
+  sogm::Resources::Setup   setup(p->res);
+  // two pools / hash tables per agent: the replan's second search attempt runs speculatively beside the first
+  SOGM_HIP_CHECK(p->res.device(&p->aw.pool, p->aw.pool_stride * A * 2));
+  SOGM_HIP_CHECK(p->res.device(&p->aw.hkeys, 8 * (size_t)p->aw.hash_cap * A * 2));
+  SOGM_HIP_CHECK(p->res.device(&p->aw.verdict, sizeof(int) * A));
+  SOGM_HIP_CHECK(p->res.device(&p->aw.dbg, sizeof(long long) * 8 * A, true));
+  SOGM_HIP_CHECK(p->res.device(&p->d_ret, sizeof(int32_t) * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_route_len, sizeof(int32_t) * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_stats, sizeof(int32_t) * 4 * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_route, sizeof(double) * 6 * p->route_cap * A));
+  const size_t slots = (size_t)A * SOGM_MAX_PIECES, cap = (size_t)pp->pc_capacity;
+  SOGM_HIP_CHECK(p->res.device(&p->cw.pc, sizeof(double) * slots * cap * 3));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.fpc, sizeof(double) * slots * cap * 3));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.tang, sizeof(double) * slots * cap * 4));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.distr, sizeof(double) * slots * cap));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.polys, sizeof(double) * slots * pp->max_faces * 4));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.seg_nfaces, sizeof(int32_t) * slots));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.seg_state, sizeof(int32_t) * slots));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.seg_npts, sizeof(int32_t) * slots));
+  // (slots no segment ever ran in are read by sogm_debug_corridor_stats as well: zero, not whatever the allocation held)
+  SOGM_HIP_CHECK(p->res.device(&p->cw.seg_dbg, sizeof(long long) * 16 * slots, true));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.counters, sizeof(unsigned long long) * SOGM_CNT_N, true));
+  // QP row storage fallback (rows normally live in LDS)
+  p->qw.scratch_stride = qp_scratch_bytes_per_agent(pp->max_faces);
+  p->qw.dyn_lds_bytes  = qp_kernel_setup();  // 160 KiB/CU minus the QP kernels' static LDS, granted on this device
+  SOGM_HIP_CHECK(p->res.device(&p->qw.scratch, p->qw.scratch_stride * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->qw.k1_scratch, qp_k1_scratch_bytes_per_agent() * (size_t)A));
+  SOGM_HIP_CHECK(p->res.device(&p->qw.dbg, sizeof(long long) * 16 * (size_t)A, true));
+  SOGM_HIP_CHECK(p->res.device(&p->d_polys, sizeof(double) * slots * pp->max_faces * 4));
+  SOGM_HIP_CHECK(p->res.device(&p->d_goal, sizeof(double) * 6 * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_cpts, sizeof(double) * slots * 15));
+  SOGM_HIP_CHECK(p->res.device(&p->d_nfaces, sizeof(int32_t) * slots));
+  SOGM_HIP_CHECK(p->res.device(&p->d_npoly, sizeof(int32_t) * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_status, sizeof(int32_t) * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_iters, sizeof(int32_t) * A));
+  SOGM_HIP_CHECK(p->res.device(&p->d_safe, sizeof(int32_t) * A));
+  // (the group streams themselves are created by the grouped path's first replan: the dataflow path never uses them,
+  // and every stream is a hardware queue the process holds — INTEGRATION.md section 2 on sharing a GPU)
+  for (int g = 0; g < p->n_groups; ++g) {
+    SOGM_HIP_CHECK(p->res.event(&p->ev_corr[g]));
+    SOGM_HIP_CHECK(p->res.event(&p->ev_pts[g]));
+    SOGM_HIP_CHECK(p->res.event(&p->ev_done[g]));
+  }
+  SOGM_HIP_CHECK(p->res.event(&p->ev_in));
+  // dataflow replan: control block + four streams (needs >= 5 hardware queues to overlap with the clear)
+  SOGM_HIP_CHECK(p->res.device(&p->d_flow, sizeof(int) * FlowBlock::words(A), true));
+  FlowBlock::carve(p->d_flow, A, &p->fc);
+  SOGM_HIP_CHECK(p->res.event(&p->ev_pdone));
+  // [A][8] chain stamps, then [A][4] pre-stamp stamps (record seen, cull done, bits done, marks done)
+  SOGM_HIP_CHECK(p->res.device(&p->d_flow_ts, sizeof(long long) * 12 * (size_t)A, true));
+  p->fc.ts = p->d_flow_ts;
+  for (int k = 0; k < 4; ++k) {
+    SOGM_HIP_CHECK(p->res.stream(&p->fstream[k]));
+    SOGM_HIP_CHECK(p->res.event(&p->ev_fdone[k]));
+  }
+  SOGM_HIP_CHECK(p->res.event(&p->ev_gate));
+  SOGM_HIP_CHECK(p->res.device(&p->d_epoch, sizeof(int), true));
+  SOGM_HIP_CHECK(p->res.pinned(&p->h_flow_fail, sizeof(int) * 2, hipHostMallocMapped));
+  p->h_flow_fail[0] = p->h_flow_fail[1] = 0;
+  // (the memsets above are null-stream operations: complete before any kernel on the planner's non-blocking streams)
+  SOGM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  return setup.done();
+}
+
 int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmPlannerParams *pp,
                         const SogmQpSettings *qp, sogm_planner **out) {
   if (!map || !astar || !pp || !qp || !out) return SOGM_ERR_INVALID_ARG;
+  // The QP's register-resident path assumes every velocity / acceleration row is two-sided (rho = rho_cur or 1000 rho_cur):
+  // "unbounded" limits (OSQP_INFTY-like values) would give those rows RHO_MIN and a K that does not match (ADVICE r4)
+  if (!(pp->opt_max_vel > 0 && pp->opt_max_vel < 1e20) || !(pp->opt_max_acc > 0 && pp->opt_max_acc < 1e20))
+    return SOGM_ERR_INVALID_ARG;
+  if (astar->allocate_num < 2 || astar->allocate_num > astar_pool_max() || astar->check_num < 1 || !(astar->resolution > 0) ||
+      !(astar->time_resolution > 0))
+    return SOGM_ERR_INVALID_ARG;
+  if (pp->max_faces < 6 || pp->max_faces > 64 || pp->pc_capacity < 1 || pp->pc_capacity > 16384 || pp->firi_iterations < 1)
+    return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(map->device));
   sogm_planner *p = new (std::nothrow) sogm_planner();  // (value-initialised: every field without an initialiser is zero)
   if (!p) return SOGM_ERR_INVALID_ARG;
@@ -121,66 +199,13 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
   // differ in the shot check only (risk_hybrid_a_star.cpp:514 vs fake_risk_hybrid_a_star.cpp:521)
   p->ap.shot_ignores_time = pp->fake_planner ? 0 : 1;
   p->qs  = *qp;
-  // The QP's register-resident path assumes every velocity / acceleration row is two-sided (rho = rho_cur or 1000 rho_cur):
-  // "unbounded" limits (OSQP_INFTY-like values) would give those rows RHO_MIN and a K that does not match (ADVICE r4)
-  if (!(pp->opt_max_vel > 0 && pp->opt_max_vel < 1e20) || !(pp->opt_max_acc > 0 && pp->opt_max_acc < 1e20)) {
-    delete p;
-    return SOGM_ERR_INVALID_ARG;
-  }
-  if (astar->allocate_num < 2 || astar->allocate_num > astar_pool_max() || astar->check_num < 1 || !(astar->resolution > 0) ||
-      !(astar->time_resolution > 0)) {
-    delete p;
-    return SOGM_ERR_INVALID_ARG;
-  }
   const int A = map->n_agents;
   int       hc = 1;
   while (hc < 2 * astar->allocate_num) hc <<= 1;
   p->aw.hash_cap    = hc;
   p->aw.pool_stride = astar_node_bytes() * (size_t)astar->allocate_num;
   p->route_cap      = 64;
-  // two pools / hash tables per agent: the replan's second search attempt runs speculatively beside the first
-  hipError_t e      = p->res.device(&p->aw.pool, p->aw.pool_stride * A * 2);
-  if (e == hipSuccess) e = p->res.device(&p->aw.hkeys, 8 * (size_t)hc * A * 2);
-  if (e == hipSuccess) e = p->res.device(&p->aw.verdict, sizeof(int) * A);
-  if (e == hipSuccess) e = p->res.device(&p->aw.dbg, sizeof(long long) * 8 * A, true);
-  if (e == hipSuccess) e = p->res.device(&p->d_ret, sizeof(int32_t) * A);
-  if (e == hipSuccess) e = p->res.device(&p->d_route_len, sizeof(int32_t) * A);
-  if (e == hipSuccess) e = p->res.device(&p->d_stats, sizeof(int32_t) * 4 * A);
-  if (e == hipSuccess) e = p->res.device(&p->d_route, sizeof(double) * 6 * p->route_cap * A);
-  {
-    if (pp->max_faces < 6 || pp->max_faces > 64 || pp->pc_capacity < 1 || pp->pc_capacity > 16384 ||
-        pp->firi_iterations < 1) {
-      sogm_planner_destroy(p);
-      return SOGM_ERR_INVALID_ARG;
-    }
-    const size_t slots = (size_t)A * SOGM_MAX_PIECES, cap = (size_t)pp->pc_capacity;
-    if (e == hipSuccess) e = p->res.device(&p->cw.pc, sizeof(double) * slots * cap * 3);
-    if (e == hipSuccess) e = p->res.device(&p->cw.fpc, sizeof(double) * slots * cap * 3);
-    if (e == hipSuccess) e = p->res.device(&p->cw.tang, sizeof(double) * slots * cap * 4);
-    if (e == hipSuccess) e = p->res.device(&p->cw.distr, sizeof(double) * slots * cap);
-    if (e == hipSuccess) e = p->res.device(&p->cw.polys, sizeof(double) * slots * pp->max_faces * 4);
-    if (e == hipSuccess) e = p->res.device(&p->cw.seg_nfaces, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = p->res.device(&p->cw.seg_state, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = p->res.device(&p->cw.seg_npts, sizeof(int32_t) * slots);
-    // (slots no segment ever ran in are read by sogm_debug_corridor_stats as well: zero, not whatever the allocation held)
-    if (e == hipSuccess) e = p->res.device(&p->cw.seg_dbg, sizeof(long long) * 16 * slots, true);
-    if (e == hipSuccess) e = p->res.device(&p->cw.counters, sizeof(unsigned long long) * SOGM_CNT_N, true);
-    // QP row storage fallback (rows normally live in LDS)
-    p->qw.scratch_stride = qp_scratch_bytes_per_agent(pp->max_faces);
-    p->qw.dyn_lds_bytes  = qp_kernel_setup();  // 160 KiB/CU minus the QP kernels' static LDS, granted on this device
-    if (e == hipSuccess) e = p->res.device(&p->qw.scratch, p->qw.scratch_stride * (size_t)A);
-    if (e == hipSuccess) e = p->res.device(&p->qw.k1_scratch, qp_k1_scratch_bytes_per_agent() * (size_t)A);
-    if (e == hipSuccess) e = p->res.device(&p->qw.dbg, sizeof(long long) * 16 * (size_t)A, true);
-    min_jerk_block(p->qc.QM);
-    if (e == hipSuccess) e = p->res.device(&p->d_polys, sizeof(double) * slots * pp->max_faces * 4);
-    if (e == hipSuccess) e = p->res.device(&p->d_goal, sizeof(double) * 6 * A);
-    if (e == hipSuccess) e = p->res.device(&p->d_cpts, sizeof(double) * slots * 15);
-    if (e == hipSuccess) e = p->res.device(&p->d_nfaces, sizeof(int32_t) * slots);
-    if (e == hipSuccess) e = p->res.device(&p->d_npoly, sizeof(int32_t) * A);
-    if (e == hipSuccess) e = p->res.device(&p->d_status, sizeof(int32_t) * A);
-    if (e == hipSuccess) e = p->res.device(&p->d_iters, sizeof(int32_t) * A);
-    if (e == hipSuccess) e = p->res.device(&p->d_safe, sizeof(int32_t) * A);
-  }
+  min_jerk_block(p->qc.QM);
   // Streams beyond the number of hardware queues (ROCm default GPU_MAX_HW_QUEUES = 4) share a queue
   // and serialise, so the default is 2 groups; the Python driver raises both (GPU_MAX_HW_QUEUES = 32 before HIP
   // initialises, sogm_set_tuning "groups" = 8 before it creates the planner).
@@ -198,47 +223,13 @@ int sogm_planner_create(sogm_ctx *map, const SogmAstarParams *astar, const SogmP
     // the second attempts wait on the first ones: only when every workgroup of both is resident at once
     if (p->spec_astar && 2 * A > sogm::astar_resident_workgroups(map->device)) p->spec_astar = 0;
   }
-  // (the group streams themselves are created by the grouped path's first replan: the dataflow path never uses them,
-  // and every stream is a hardware queue the process holds — INTEGRATION.md section 2 on sharing a GPU)
-  for (int g = 0; g < p->n_groups && e == hipSuccess; ++g) {
-    e = p->res.event(&p->ev_corr[g]);
-    if (e == hipSuccess) e = p->res.event(&p->ev_pts[g]);
-    if (e == hipSuccess) e = p->res.event(&p->ev_done[g]);
-  }
-  if (e == hipSuccess) e = p->res.event(&p->ev_in);
-  // dataflow replan: control block + four streams (needs >= 5 hardware queues to overlap with the clear)
   {
     const char *ef = getenv("SOGM_FLOW");  // (one of the library's three environment switches)
     p->flow        = ef ? atoi(ef) != 0 : 1;
-    // layout: header, seg_done[A], stage[A] (zeroed per replan), then the four ready lists (-1 per replan)
-    if (e == hipSuccess) e = p->res.device(&p->d_flow, sizeof(int) * (FLOW_HDR + 6 * (size_t)A + 1), true);  // (+ the reset's generation word)
-    p->fc.hdr      = p->d_flow;
-    p->fc.seg_done = p->d_flow + FLOW_HDR;
-    p->fc.stage    = p->fc.seg_done + A;
-    p->fc.a_ready  = p->fc.stage + A;
-    p->fc.q_ready  = p->fc.a_ready + A;
-    p->fc.f_ready  = p->fc.q_ready + A;
-    p->fc.p_ready  = p->fc.f_ready + A;
-    if (e == hipSuccess) e = p->res.event(&p->ev_pdone);
-    // [A][8] chain stamps, then [A][4] pre-stamp stamps (record seen, cull done, bits done, marks done)
-    if (e == hipSuccess) e = p->res.device(&p->d_flow_ts, sizeof(long long) * 12 * (size_t)A, true);
-    p->fc.ts = p->d_flow_ts;
-
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-      e = p->res.stream(&p->fstream[k]);
-      if (e == hipSuccess) e = p->res.event(&p->ev_fdone[k]);
-    }
-    if (e == hipSuccess) e = p->res.event(&p->ev_gate);
-    if (e == hipSuccess) e = p->res.device(&p->d_epoch, sizeof(int), true);
-    if (e == hipSuccess) e = p->res.pinned(&p->h_flow_fail, sizeof(int) * 2, hipHostMallocMapped);
-    if (e == hipSuccess) p->h_flow_fail[0] = p->h_flow_fail[1] = 0;
   }
-  // (the memsets above are null-stream operations: complete before any kernel on the planner's non-blocking streams)
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) {
-    sogm::set_error("sogm_planner_create", e);
-    sogm_planner_destroy(p);
-    return SOGM_ERR_HIP;
+  if (int rc = planner_acquire(p)) {
+    delete p;
+    return rc;
   }
   if (p->flow) {  // the map's pooled clear follows this planner's "corridors final" counter (sogm_device.hpp)
     map->clear_gate        = p->fc.hdr + FLOW_Q_READY_N;
@@ -269,48 +260,6 @@ void sogm_planner_destroy(sogm_planner *p) {
   }
   p->res.release_all();
   delete p;
-}
-
-// The search's per-phase clock statistics (sogm_debug_astar_stats, tools/diag_astar.py) are collected while the map's
-// profiling is on: five s_memrealtime reads per expansion are not free.
-static sogm::AstarWorkspace astar_ws(const sogm_planner *p) {
-  sogm::AstarWorkspace w = p->aw;
-  if (!((p->map->profiling >> SOGM_PROF_ASTAR) & 1)) w.dbg = nullptr;
-  return w;
-}
-
-// A launcher's error under the caller's label.  The launchers hand over what hipGetLastError() gave them: it clears the
-// error as it reads it, so a second call here would report "no error".
-static int launched(const char *what, hipError_t e) {
-  if (e == hipSuccess) return SOGM_OK;
-  sogm::set_error(what, e);
-  return SOGM_ERR_HIP;
-}
-
-// The stages' buffers of a replan or a flight: the planner's own between the stages, the caller's at both ends.
-static sogm::SearchIO search_io(const sogm_planner *p, const double *start_pva, const double *goal, const double *t_start) {
-  return sogm::SearchIO{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = p->d_ret,
-                        .out_route = p->d_route, .out_route_len = p->d_route_len, .route_cap = p->route_cap,
-                        .out_stats = p->d_stats, .due = p->due};
-}
-static sogm::CorridorIO corridor_io(const sogm_planner *p, const double *start_pva, const double *t_start) {
-  return sogm::CorridorIO{.start_pva = start_pva, .t_start = t_start, .route = p->d_route,
-                          .route_len = p->d_route_len, .route_cap = p->route_cap, .out_polys = p->d_polys,
-                          .out_nfaces = p->d_nfaces, .out_npoly = p->d_npoly, .out_goal = p->d_goal};
-}
-static sogm::QpIO qp_io(const sogm_planner *p, const double *start_pva) {
-  return sogm::QpIO{.start_pva = start_pva, .goal_pv = p->d_goal, .polys = p->d_polys, .nfaces = p->d_nfaces,
-                    .npoly = p->d_npoly, .out_cpts = p->d_cpts, .out_status = p->d_status, .out_iters = p->d_iters};
-}
-// a replan's: swarm and publication as sogm_planner_set_swarm / _set_publish left them (the flight fills its own)
-static sogm::FinishArgs finish_args(const sogm_planner *p, const double *t_start, const int32_t *drone_ids,
-                                    SogmTrajRecord *out, int32_t *out_ok) {
-  return sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
-                          .status = p->d_status, .cpts = p->d_cpts, .swarm = p->swarm, .n_swarm = p->n_swarm,
-                          .swarm_ego = p->swarm_ego, .swarm_now = p->swarm_now, .t_start = t_start,
-                          .drone_ids = drone_ids, .out = out, .out_ok = out_ok, .out_safe = p->d_safe,
-                          .counters = p->cw.counters, .pub_own = p->pub_own, .pub_table = p->pub_table,
-                          .due = p->due};
 }
 
 int sogm_astar_search(sogm_planner *p, const double *start_pva, const double *goal,
@@ -456,7 +405,7 @@ int sogm_debug_flow_peek(sogm_planner *p, int *out_host, int n) {
   if (!p || !out_host || n < 0) return SOGM_ERR_INVALID_ARG;
   if (!p->peek) SOGM_HIP_CHECK(p->res.stream(&p->peek));
   hipStream_t peek = p->peek;
-  const int nf = FLOW_HDR + 6 * p->map->n_agents;
+  const int nf = FlowBlock(p->map->n_agents).gen;  // (everything in front of the generation word)
   SOGM_HIP_CHECK(hipMemcpyAsync(out_host, p->d_flow, sizeof(int) * (size_t)(n < nf ? n : nf), hipMemcpyDeviceToHost, peek));
   if (n > nf)  // followed by d_safe (progress markers in debug builds)
     SOGM_HIP_CHECK(hipMemcpyAsync(out_host + nf, p->d_safe, sizeof(int) * (size_t)(n - nf), hipMemcpyDeviceToHost, peek));
@@ -659,22 +608,30 @@ __global__ void k_update_rank(const long long *__restrict__ ts, int *__restrict_
   }
 }
 
-static int replan_flow(sogm_planner *p, const double *start_pva, const double *goal, const double *t_start,
-                       const int32_t *drone_ids, SogmTrajRecord *out_records, int32_t *out_ok, void *stream) {
-  sogm_ctx     *c    = p->map;
-  hipStream_t   main = (hipStream_t)stream;
-  const int     A    = c->n_agents;
-  const MapView mv   = view_of(c);
-  if (p->swarm)
-    if (int rc = sogm::join_exchange(c, main)) return rc;
-  // (the searches run on the caller's stream: they are the first kernel of the chain, and a hop to another stream
-  //  costs an event round trip on the critical path)
-  hipStream_t sA = main, sC = p->fstream[1], sQ = p->fstream[2], sF = p->fstream[3];
-  // reset the control block in stream order: counters and seg_done to 0, ready lists to -1
-  // (one launch instead of five memset nodes: each cost a dispatch gap on the tick's critical path)
-  // k_finish_flow writes ok / the record of every agent whose chain completes; an agent whose chain does NOT (a wait
-  // timed out, FLOW_ERR) must report ok = 0 and an empty record, not the previous tick's
-  const bool spec = p->spec_astar != 0;
+// One sogm_replan through the dataflow path: the caller's arguments and what the steps below (each called once, in this
+// order, by replan_flow) hand on.
+struct FlowCall {
+  const double   *start_pva, *goal, *t_start;
+  const int32_t  *drone_ids;
+  SogmTrajRecord *out_records;
+  int32_t        *out_ok;
+  hipStream_t     main;
+  bool            spec;      // the second search attempts run beside the first
+  int            *gen_word;  // the reset's generation word
+  int             n_cu, wg_q, wg_f;
+  bool            prestamp;  // this replan stamps the next tick's map ...
+  hipStream_t     pst;       // ... on this stream (the tick's report follows it there)
+};
+
+// 1. reset the control block in stream order: counters and seg_done to 0, ready lists to -1
+// (one launch instead of five memset nodes: each cost a dispatch gap on the tick's critical path)
+// k_finish_flow writes ok / the record of every agent whose chain completes; an agent whose chain does NOT (a wait
+// timed out, FLOW_ERR) must report ok = 0 and an empty record, not the previous tick's
+static int flow_reset(sogm_planner *p, FlowCall &call) {
+  sogm_ctx         *c    = p->map;
+  const hipStream_t main = call.main, sC = p->fstream[1];
+  const int         A    = c->n_agents;
+  const bool        spec = call.spec;
   // The reset on the corridor stream: behind the previous replan's report (that stream's last kernel: below) and, in the
   // pre-stamping variant, behind the pre-stamp's end; the waiting kernels of THIS replan follow it on the same stream or
   // behind ev_gate.  The readers of the swarm table on those streams wait for an all-gather in flight themselves.
@@ -686,13 +643,30 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     SOGM_HIP_CHECK(hipEventRecord(p->ev_gate, main));
     SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_gate, 0));
   }
-  int *gen_word = p->d_flow + FLOW_HDR + 6 * (size_t)A;
+  const FlowBlock fb(A);
+  int *gen_word = p->d_flow + fb.gen;
   ++p->reset_epoch;
-  hipLaunchKernelGGL(k_flow_reset, dim3(1), dim3(1024), 0, sC, p->d_flow, FLOW_HDR + 2 * A, p->fc.a_ready, 4 * A,
-                     spec ? p->aw.verdict : nullptr, A,
+  hipLaunchKernelGGL(k_flow_reset, dim3(1), dim3(1024), 0, sC, p->d_flow, fb.zero_words(), p->d_flow + fb.fill_first(),
+                     fb.fill_words(), spec ? p->aw.verdict : nullptr, A,
                      c->overlap >= 2 && c->clear_gate ? c->clear_epoch_word : nullptr,
                      c->overlap >= 2 && c->clear_gate ? sogm::next_clear_epoch(c) : 0, gen_word, p->reset_epoch);
   SOGM_HIP_CHECK(hipGetLastError());
+  call.gen_word = gen_word;
+  return SOGM_OK;
+}
+// 2. the searches on the caller's stream, then the residency gate and the persistent corridor and QP kernels on theirs
+// (the searches run on the caller's stream: they are the first kernel of the chain, and a hop to another stream
+//  costs an event round trip on the critical path)
+static int flow_launch_chain(sogm_planner *p, FlowCall &call) {
+  sogm_ctx         *c    = p->map;
+  const hipStream_t main = call.main, sA = main, sC = p->fstream[1], sQ = p->fstream[2], sF = p->fstream[3];
+  const int         A    = c->n_agents;
+  const MapView     mv   = view_of(c);
+  const bool        spec = call.spec;
+  int              *gen_word = call.gen_word;
+  const double     *start_pva = call.start_pva, *goal = call.goal, *t_start = call.t_start;
+  SogmTrajRecord   *out_records = call.out_records;
+  int32_t          *out_ok      = call.out_ok;
   if (c->exchange_pending)
     for (int k = 1; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(p->fstream[k], c->ev_xdone, 0));
   prof_begin(c, SOGM_PROF_ASTAR, sA);
@@ -730,6 +704,7 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   if (wg_q > A) wg_q = A;
   if (wg_q < 1) wg_q = 1;
   int wg_f = A < 64 ? A : 64;
+  call.n_cu = n_cu, call.wg_q = wg_q, call.wg_f = wg_f;
   prof_begin(c, SOGM_PROF_CORRIDOR, sC);
   if (int rc = launched("sogm_replan: k_corridor_flow",
                         sogm::launch_corridor_flow(mv, p->pp, p->cw, p->fc, A, wg_c, corridor_io(p, start_pva, t_start), sC)))
@@ -758,6 +733,13 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
     int rc = sogm::queue_spare_clears(c, p->ev_in);  // grids still dirty (first ticks, pool changes)
     if (rc) return rc;
   }
+  return SOGM_OK;
+}
+// 3. the finishing kernel; decides whether this replan pre-stamps (call.prestamp)
+static int flow_finish(sogm_planner *p, FlowCall &call) {
+  sogm_ctx         *c  = p->map;
+  const hipStream_t sF = p->fstream[3];
+  const int         A  = c->n_agents;
   sogm::FlowCtl fcf = p->fc;
   // (only with the sparse reset: the pre-stamp runs behind the target grid's reset on the side stream, and with
   //  SOGM_SPARSE_RESET=0 a dense clear fills that stream for the whole tick.  On the first ticks of a flight — and
@@ -766,43 +748,49 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   //  (tests/test_pipelining_gpu.py::test_overlay_under_the_prestamp_tail_at_full_size flies exactly that).)
   const bool prestamp = p->ps_on && c->sparse && c->overlap >= 2 && c->pool.front_ready() >= 0 && p->pub_own && c->clear_gate;
   if (!prestamp) fcf.p_ready = nullptr;
-  if (int rc = launched("sogm_replan: k_finish_flow",
-                        sogm::launch_finish_flow(fcf, A, wg_f, finish_args(p, t_start, drone_ids, out_records, out_ok), sF)))
-    return rc;
-  // pre-stamp (sogm_planner_set_prestamp): the next tick's map, agent by agent as their records are published, into
-  // the pool's next grid — behind the gate that keeps store streams away from the searches and point scans, and
-  // behind that grid's reset
+  call.prestamp = prestamp;
+  return launched("sogm_replan: k_finish_flow",
+                  sogm::launch_finish_flow(fcf, A, call.wg_f, finish_args(p, call.t_start, call.drone_ids, call.out_records, call.out_ok), sF));
+}
+// 4. the pre-stamp's arguments from sogm_planner_set_prestamp's and the tuning: no HIP call (tgt and frame.cb: flow_prestamp)
+static sogm::PrestampDev prestamp_args(const sogm_planner *p) {
+  const sogm_ctx   *c = p->map;
+  const int         A = c->n_agents;
+  sogm::PrestampDev d = p->ps;
+  d.tick.own = p->pub_own;
+  d.n_agents = A;
+  {
+    const double f = c->tune[SOGM_TUNE_PRESTAMP_GATE_FRAC];
+    d.gate_agents  = f >= 1.0 ? A : f <= 0.0 ? 0 : (int)(f * A + 0.5);
+  }
+  // tickets per agent (tuning aids): too few and the last agents' stamps trail the replan, too many and the
+  // hand-overs cost more than the work (bits + marks 16+16 / 32+64 / 64+64 / 128+256 tickets: 13.1 / 12.1 / 12.2 /
+  // 14.1 ms per tick, 13.0 without the pre-stamp); finer tickets for the last agents to be published (none / 8 / 16
+  // late agents: 12.06 / 11.85 / 11.98 ms per tick)
+  const int nb = c->tune_i(SOGM_TUNE_PRESTAMP_BITS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_BITS) : 32;
+  const int nm = c->tune_i(SOGM_TUNE_PRESTAMP_MARKS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_MARKS) : 64;
+  d.n_bits       = nb;
+  d.n_marks      = nm;
+  d.n_late       = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_AGENTS) < 0 ? 0 : c->tune_i(SOGM_TUNE_PRESTAMP_LATE_AGENTS);
+  d.n_bits_late  = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_BITS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_BITS) : nb;
+  d.n_marks_late = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) : nm;
+  return d;
+}
+// 5. pre-stamp (sogm_planner_set_prestamp): the next tick's map, agent by agent as their records are published, into
+// the pool's next grid — behind the gate that keeps store streams away from the searches and point scans, and
+// behind that grid's reset
+static int flow_prestamp(sogm_planner *p, FlowCall &call) {
+  sogm_ctx *c = p->map;
+  const int A = c->n_agents;
   c->pool.clear_prestamp_target();
   // the pre-stamp's stream (why it has one of its own: below); the tick's report follows it there
   const bool        own_stream = c->tune_i(SOGM_TUNE_PRESTAMP_STREAM) != 0 && c->pstream != nullptr;
   const hipStream_t pst        = own_stream ? c->pstream : c->side;
-  const int         retire     = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);  // measured: tick -2 %, but the clear 14.5 -> 15.5 ms; off
-  auto report = [&](hipStream_t st) {
-    hipLaunchKernelGGL(k_flow_report, dim3(1), dim3(1), 0, st, (const int *)p->d_flow, p->h_flow_fail,
-                       retire ? p->d_epoch : (int *)nullptr, c->h_tick_clock);
-    return hipGetLastError();
-  };
-  if (prestamp) {
+  call.pst = pst;
+  if (call.prestamp) {
     const int nxt = c->pool.front_ready();
-    sogm::PrestampDev d = p->ps;
+    sogm::PrestampDev d = prestamp_args(p);
     if (int rc = sogm::map_target(c, nxt, true, nullptr, &d.tgt)) return rc;
-    d.tick.own = p->pub_own;
-    d.n_agents = A;
-    {
-      const double f = c->tune[SOGM_TUNE_PRESTAMP_GATE_FRAC];
-      d.gate_agents  = f >= 1.0 ? A : f <= 0.0 ? 0 : (int)(f * A + 0.5);
-    }
-    // tickets per agent (tuning aids): too few and the last agents' stamps trail the replan, too many and the
-    // hand-overs cost more than the work (bits + marks 16+16 / 32+64 / 64+64 / 128+256 tickets: 13.1 / 12.1 / 12.2 /
-    // 14.1 ms per tick, 13.0 without the pre-stamp); finer tickets for the last agents to be published (none / 8 / 16
-    // late agents: 12.06 / 11.85 / 11.98 ms per tick)
-    const int nb = c->tune_i(SOGM_TUNE_PRESTAMP_BITS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_BITS) : 32;
-    const int nm = c->tune_i(SOGM_TUNE_PRESTAMP_MARKS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_MARKS) : 64;
-    d.n_bits       = nb;
-    d.n_marks      = nm;
-    d.n_late       = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_AGENTS) < 0 ? 0 : c->tune_i(SOGM_TUNE_PRESTAMP_LATE_AGENTS);
-    d.n_bits_late  = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_BITS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_BITS) : nb;
-    d.n_marks_late = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) : nm;
     if (p->ps_world_on)  // the frame's blocks + the context's crop lists (built by each agent's first ticket)
       if (int rc = sogm::world_blocks(c, &p->ps_world, &d.frame.cb)) return rc;
     // The pre-stamp's target grid was reset by an EARLIER replan when the pool holds three grids (the front of the ready
@@ -827,18 +815,30 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
       else if (c->gate_open_valid && d.gate_agents >= A)
         SOGM_HIP_CHECK(hipStreamWaitEvent(pst, c->ev_gate_open, 0));
     }
-    int wg_p = 8 * n_cu;  // one-wave workgroups (512 / 1024 / 2048+: 14.0 / 12.3 / 12.1 ms per tick)
+    int wg_p = 8 * call.n_cu;  // one-wave workgroups (512 / 1024 / 2048+: 14.0 / 12.3 / 12.1 ms per tick)
     if (c->tune_i(SOGM_TUNE_PRESTAMP_WGS) > 0) wg_p = c->tune_i(SOGM_TUNE_PRESTAMP_WGS);
     if (int rc = launched("sogm_replan: k_prestamp_flow",
-                          sogm::launch_prestamp_flow(c->geom, p->fc, d, wg_p, wg_q, wg_f < A ? wg_f : A, pst)))
+                          sogm::launch_prestamp_flow(c->geom, p->fc, d, wg_p, call.wg_q, call.wg_f < A ? call.wg_f : A, pst)))
       return rc;
     c->pool.set_prestamp_target(nxt);
     c->n_stamps++;
     c->ps_fail_host = p->h_flow_fail;  // sogm_update_prestamped refuses the grid if this replan turns out to have failed
     c->ps_fail_seen = p->h_flow_fail ? p->h_flow_fail[1] : 0;
   }
-  // fan-in.  Without a pre-stamp the tick's report runs on the corridor stream behind the QP and finishing kernels, so that
-  // the NEXT replan's reset — same stream — is ordered behind it without an event on the caller's stream
+  return SOGM_OK;
+}
+// 6. fan-in.  Without a pre-stamp the tick's report runs on the corridor stream behind the QP and finishing kernels, so that
+// the NEXT replan's reset — same stream — is ordered behind it without an event on the caller's stream
+static int flow_fan_in(sogm_planner *p, const FlowCall &call) {
+  sogm_ctx         *c    = p->map;
+  const hipStream_t main = call.main, sC = p->fstream[1], pst = call.pst;
+  const int         A    = c->n_agents;
+  const int         retire     = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);  // measured: tick -2 %, but the clear 14.5 -> 15.5 ms; off
+  auto report = [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_flow_report, dim3(1), dim3(1), 0, st, (const int *)p->d_flow, p->h_flow_fail,
+                       retire ? p->d_epoch : (int *)nullptr, c->h_tick_clock);
+    return hipGetLastError();
+  };
   const bool report_on_sc = !c->pool.prestamp_pending();
   for (int k = 0; k < 4; ++k)
     if (k != 1) SOGM_HIP_CHECK(hipEventRecord(p->ev_fdone[k], p->fstream[k]));
@@ -885,6 +885,19 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
   }
   if (!reported) SOGM_HIP_CHECK(report(main));
   return SOGM_OK;
+}
+
+static int replan_flow(sogm_planner *p, const double *start_pva, const double *goal, const double *t_start,
+                       const int32_t *drone_ids, SogmTrajRecord *out_records, int32_t *out_ok, void *stream) {
+  FlowCall call{.start_pva = start_pva, .goal = goal, .t_start = t_start, .drone_ids = drone_ids, .out_records = out_records,
+                .out_ok = out_ok, .main = (hipStream_t)stream, .spec = p->spec_astar != 0};
+  if (p->swarm)
+    if (int rc = sogm::join_exchange(p->map, call.main)) return rc;
+  if (int rc = flow_reset(p, call)) return rc;
+  if (int rc = flow_launch_chain(p, call)) return rc;
+  if (int rc = flow_finish(p, call)) return rc;
+  if (int rc = flow_prestamp(p, call)) return rc;
+  return flow_fan_in(p, call);
 }
 
 static int replan_impl(sogm_planner *p, const double *start_pva, const double *goal,
@@ -967,610 +980,6 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
   return SOGM_OK;
 }
 
-
-}  // extern "C"
-// ---------------------------------------------------------------------------------------------------------------
-// sogm_flight_run (the flight is described in sogm_planner.hpp / sogm_abi.h)
-// ---------------------------------------------------------------------------------------------------------------
-// control block back to its start values: header / rings / counters 0, every agent's first map item published in agent
-// order, tick_of = first_tick, verdicts 0 (their tags are absolute tick numbers), the flight's log cleared (an agent-tick
-// that does not complete reports ok = 0 and an empty record)
-__global__ __launch_bounds__(256) void k_flight_reset(FlightCtl fl, int n_words, int *verdict, long long *acc, int *log_words,
-                                                      long long n_log_words) {
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
-  // header, rings, plain queues, tick_done, tick_of, seg_done, stage: one block.  NOT the head / tail words of the urgent
-  // queue: its consumers decide "a descriptor is there" by LOADING tail and head (every other hand-over of the flight is a
-  // read-modify-write or a generation-tagged slot), so the queue runs on over the planner's life instead of restarting
-  // with every call: positions only grow (modulo 2^32; a slot's generation tag follows its position), and a value a
-  // consumer reads late can only be LOWER than the true one — it then looks again — never claim a descriptor that
-  // does not exist yet.
-  for (long long i = i0; i < n_words; i += step)
-    if (i != FL_UW_TAIL && i != FL_UW_HEAD) fl.hdr[i] = 0;
-  if (i0 == 0) fl.hdr[FL_UW_HEAD] = fl.hdr[FL_UW_TAIL];  // (descriptors an aborted call left behind are skipped)
-  for (long long i = i0; i < n_log_words; i += step) log_words[i] = 0;
-  for (long long i = i0; i < fl.n_agents; i += step) verdict[i] = 0;
-  for (long long i = i0; i < 8ll * fl.n_agents; i += step) acc[i] = 0;
-  for (long long i = i0; i < 16; i += step) fl.prof[i] = 0ull;
-  for (long long i = i0; i < 8 * FL_WG_LOG; i += step) fl.wg_start[i] = 0;
-}
-__global__ __launch_bounds__(256) void k_flight_seed(FlightCtl fl) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a < fl.n_agents) {
-    fl.tick_of[a] = fl.first_tick;
-    fl.m_ring[a]  = ring_encode(a, fl.ring_mask + 1, a);               // position a, generation 1: every agent's first head, in agent order
-    fl.ts[(size_t)a * FL_TS + 7] = wall_clock64();  // the head's publication
-  }
-  if (a == 0) fl.hdr[FL_M_READY] = fl.n_agents;
-  for (int i = a; i < FLIGHT_MAX_TICKS * fl.n_agents; i += (int)(gridDim.x * blockDim.x)) fl.parked[i] = -1;
-}
-// the exchange behind a multi-rank flight (sogm_flight_run with SogmFlight::nccl_comm), on the exchange stream, per tick i of the
-// call: k_flight_xwait -> ncclAllGather(rows of ver(first_tick + i)) -> k_flight_xsignal
-__global__ void k_flight_xwait(FlightCtl fl, int i) {  // every local agent has finished tick i: its rows of the version are final
-  if (threadIdx.x != 0) return;
-  // (no limit of its own: every wait INSIDE the flight is bounded and sets the error word, which ends this one — the
-  //  collective behind it still runs, its peers are waiting in theirs)
-  wait_at_least<WaitUntimed, false>(&fl.hdr[FL_ERR], &fl.tick_done[i], fl.n_agents);
-}
-__global__ void k_flight_xsignal(FlightCtl fl, int i) {  // every rank's rows of ver(first_tick + i) are here
-  if (threadIdx.x != 0) return;
-  __threadfence();
-  __hip_atomic_store(&fl.xready[i], fl.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  if (i + fl.lag < fl.n_ticks) fl_gate_release(fl, i + fl.lag);
-}
-__global__ void k_flight_report(const int *__restrict__ hdr, int *__restrict__ host_words) {
-  const int e = hdr[FL_ERR];
-  if (e != 0) {
-    host_words[0] = 100 + e;
-    host_words[1] = host_words[1] + 1;
-  }
-}
-
-// the 16-CU unit of a mask bit: two CUs per XCD whether bit i names XCD i / 32 or XCD i % 8 (tools/micro/cumask.hip).
-// unit = 4 * shader engine + r: the compute units of one shader engine (of every XCD) whose index is congruent r mod 4.
-static int flight_unit_of(int i) { return ((i / 8) % 4) * 4 + ((i / 32 + i % 8) % 4); }
-
-// Which units each of the four kernels gets.  The workgroup dispatcher hands the workgroups of a launch to the shader
-// engines of its compute-unit mask in strict ROTATION: when one engine's units are full the dispatch stops, whatever room the
-// other engines have (measured, tools/diag_flight_residency.py: a mask with four units in one engine and eight in another
-// held 16 + 16 one-wave workgroups per XCD, not 16 + 32 — 120 of the round-5 corridor kernel's 384 workgroups sat in the
-// dispatcher for the whole flight).  A workgroup that is not running is harmless until the hardware scheduler saves and
-// restores the process's queues (any queue created or destroyed on the device, by any process, does that): the waiting
-// workgroups then start in the slots the save freed, one per XCD ahead of the restored waves, and the wave that lost its slot
-// stays saved until somebody leaves — the 3-second stalls of round 5.  So: every kernel's mask holds the SAME number of units
-// in every shader engine it touches, and a launch has exactly as many workgroups as that mask holds at once
-// (engines x smallest engine share): every workgroup is resident from the first microsecond, nothing waits in a dispatcher.
-// grid[se][r] = kernel that owns unit 4 se + r (-1 free).  Kernels 0, 1, 3 (QP, search, map) are placed by a small search —
-// fewest engines first — such that the rest (kernel 2, corridor + finish) is balanced too; if no such layout exists the most
-// balanced one is kept and the launch is cut to what is resident.
-struct FlightLayout {
-  int grid[4][4];
-  int resident_units[4];  // engines touched x smallest share, in units
-};
-static int layout_rest_score(const int grid[4][4]) {  // units of the rest that are resident under the rotation
-  int touched = 0, smallest = 5;
-  for (int se = 0; se < 4; ++se) {
-    int n = 0;
-    for (int r = 0; r < 4; ++r) n += grid[se][r] == -1;
-    if (n > 0) {
-      ++touched;
-      if (n < smallest) smallest = n;
-    }
-  }
-  return touched ? touched * smallest : 0;
-}
-static void layout_search(int grid[4][4], const int want[4], const int order[3], int depth, int rest_units, int *best_score,
-                          int best[4][4]) {
-  if (depth == 3) {
-    const int sc = layout_rest_score(grid);
-    if (sc > *best_score) {
-      *best_score = sc;
-      std::memcpy(best, grid, sizeof(int) * 16);
-    }
-    return;
-  }
-  const int k = order[depth], u = want[k];
-  for (int n_se = 1; n_se <= 4 && *best_score < rest_units; ++n_se) {
-    if (u % n_se != 0 || u / n_se > 4) continue;
-    const int per = u / n_se;
-    for (int set = 1; set < 16 && *best_score < rest_units; ++set) {
-      if (__builtin_popcount((unsigned)set) != n_se) continue;
-      int  saved[4][4];
-      bool ok = true;
-      std::memcpy(saved, grid, sizeof(saved));
-      for (int se = 0; se < 4 && ok; ++se) {
-        if (!((set >> se) & 1)) continue;
-        int got = 0;
-        for (int r = 0; r < 4 && got < per; ++r)
-          if (grid[se][r] == -1) grid[se][r] = k, ++got;
-        ok = got == per;
-      }
-      if (ok) layout_search(grid, want, order, depth + 1, rest_units, best_score, best);
-      std::memcpy(grid, saved, sizeof(saved));
-    }
-  }
-}
-// engines [se0, se0 + n_se) are the flight's (the others belong to nobody here: -2); `reserved` units of them stay free of any
-// kernel (-3), taken from the highest engine's highest classes first
-static FlightLayout flight_layout(const int want[4], int se0 = 0, int n_se = 4, int reserved = 0) {
-  FlightLayout L;
-  int          grid[4][4], best_score = -1;
-  for (int i = 0; i < 16; ++i) (&grid[0][0])[i] = -1, (&L.grid[0][0])[i] = -1;
-  for (int se = 0; se < 4; ++se)
-    if (se < se0 || se >= se0 + n_se)
-      for (int r = 0; r < 4; ++r) grid[se][r] = -2;
-  for (int se = se0 + n_se - 1, left = reserved; se >= se0 && left > 0; --se)
-    for (int r = 3; r >= 0 && left > 0; --r)
-      if (grid[se][r] == -1) grid[se][r] = -3, --left;
-  std::memcpy(L.grid, grid, sizeof(grid));
-  const int order[3] = {0, 3, 1};  // QP and map (whole engines when they can have them), then the search
-  layout_search(grid, want, order, 0, want[2], &best_score, L.grid);
-  for (int i = 0; i < 16; ++i)
-    if ((&L.grid[0][0])[i] == -1) (&L.grid[0][0])[i] = 2;
-  for (int k = 0; k < 4; ++k) {
-    int touched = 0, smallest = 5;
-    for (int se = 0; se < 4; ++se) {
-      int n = 0;
-      for (int r = 0; r < 4; ++r) n += L.grid[se][r] == k;
-      if (n > 0) {
-        ++touched;
-        if (n < smallest) smallest = n;
-      }
-    }
-    L.resident_units[k] = touched ? touched * smallest : 0;
-  }
-  return L;
-}
-
-static int flight_setup(sogm_planner *p) {
-  sogm_ctx *c = p->map;
-  const int A = c->n_agents;
-  if (p->d_fl) return SOGM_OK;
-  sogm::Resources::Setup setup(p->res);
-  int ring = 1;
-  while (ring < 2 * A) ring <<= 1;
-  if (A >= (1 << 16)) return SOGM_ERR_INVALID_ARG;
-  const size_t words = FL_HDR + 4 * (size_t)ring + 6 * (size_t)FL_WQ_SLOTS + 3 * FLIGHT_MAX_TICKS + 4 * (size_t)A +
-                       (size_t)FLIGHT_MAX_TICKS * A + 2;
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl, sizeof(int) * words, true));  // (once: the urgent / priority queues start empty at position 0)
-  int *q          = p->d_fl;
-  p->fl.hdr       = q;              q += FL_HDR;
-  p->fl.s_ring    = q;              q += ring;
-  p->fl.q_ring    = q;              q += ring;
-  p->fl.m_ring    = q;              q += ring;
-  p->fl.u_ring    = q;              q += ring;
-  p->fl.mw        = reinterpret_cast<unsigned long long *>(q);  q += 2 * FL_WQ_SLOTS;  // (FL_HDR and 4 x ring are even: 8-byte aligned)
-  p->fl.lw        = reinterpret_cast<unsigned long long *>(q);  q += 2 * FL_WQ_SLOTS;
-  p->fl.tick_done = q;              q += FLIGHT_MAX_TICKS;
-  p->fl.parked_n  = q;              q += FLIGHT_MAX_TICKS;
-  p->fl_xready    = q;              q += FLIGHT_MAX_TICKS;
-  p->fl.tick_of   = q;              q += A;
-  p->fl.seg_done  = q;              q += A;
-  p->fl.stage     = q;              q += A;
-  p->fl.urgent    = q;              q += A;
-  p->fl.parked    = q;              q += (size_t)FLIGHT_MAX_TICKS * A;
-  // (behind everything a call resets: the urgent / priority queues and their head / tail words are NOT reset — below)
-  if ((q - p->d_fl) & 1) q += 1;
-  p->fl.uw        = reinterpret_cast<unsigned long long *>(q);  q += 2 * FL_WQ_SLOTS;
-  p->fl.ring_mask = ring - 1;
-  p->fl.n_agents  = A;
-  SOGM_HIP_CHECK(p->res.device(&p->fl.ts, sizeof(long long) * FL_TS * (size_t)A, true));
-  SOGM_HIP_CHECK(p->res.device(&p->fl.acc, sizeof(long long) * 8 * (size_t)A, true));
-  SOGM_HIP_CHECK(p->res.device(&p->fl.ts_log, sizeof(long long) * FL_TS * (size_t)A * FLIGHT_MAX_TICKS));
-  SOGM_HIP_CHECK(p->res.device(&p->fl.wg_start, sizeof(long long) * 8 * FL_WG_LOG));
-  SOGM_HIP_CHECK(p->res.device(&p->fl.prof, sizeof(unsigned long long) * 16, true));
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_worlds, sizeof(FlightWorld) * FLIGHT_MAX_TICKS));
-  SOGM_HIP_CHECK(p->res.pinned(&p->h_fl_worlds, sizeof(FlightWorld) * FLIGHT_MAX_TICKS, hipHostMallocDefault));
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_pva, sizeof(double) * 9 * (size_t)A));
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_tstart, sizeof(double) * (size_t)A));
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_now, sizeof(double) * (size_t)A));
-  // the head's hand-over arrays of the FSM mode (sogm_planner_set_flight_fsm)
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_due, sizeof(int32_t) * (size_t)A));
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_reached, sizeof(int32_t) * (size_t)A));
-  SOGM_HIP_CHECK(p->res.device(&p->d_fl_posnow, sizeof(double) * 3 * (size_t)A));
-  // the four streams and their compute units: QP, search, map take flight_*_units units of 16 CUs, corridor + finish
-  // the rest; workgroups = what the partition holds at once (every workgroup of a flight kernel is resident from the
-  // start: nothing waits for a workgroup that is not running)
-  int n_cu = 256;
-  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-  int n_se = c->tune_i(SOGM_TUNE_FLIGHT_ENGINES), se0 = c->tune_i(SOGM_TUNE_FLIGHT_ENGINE_FIRST);
-  if (se0 + n_se > 4) n_se = 4 - se0;
-  const int reserved    = c->tune_i(SOGM_TUNE_FLIGHT_EXCHANGE_UNITS);
-  const int units_total = 4 * n_se - reserved;
-  int       u[4] = {c->tune_i(SOGM_TUNE_FLIGHT_QP_UNITS), c->tune_i(SOGM_TUNE_FLIGHT_SEARCH_UNITS), 0,
-                    c->tune_i(SOGM_TUNE_FLIGHT_MAP_UNITS)};
-  u[2] = units_total - u[0] - u[1] - u[3];
-  if (u[2] < 1) {
-    sogm::set_error_text("sogm_flight_run: flight_qp_units + flight_search_units + flight_map_units must leave a unit for the corridor kernel");
-    return SOGM_ERR_INVALID_ARG;
-  }
-  const bool         masks = c->tune_i(SOGM_TUNE_FLIGHT_MASKS) != 0;
-  const FlightLayout L     = flight_layout(u, se0, n_se, reserved);
-  for (int k = 0; k < 4; ++k) {
-    uint32_t mask[16] = {0};
-    int      cus = 0;
-    for (int i = 0; i < n_cu && i < 512; ++i) {
-      const int un = flight_unit_of(i);
-      if (L.grid[un / 4][un % 4] == k) {
-        mask[i / 32] |= 1u << (i % 32);
-        ++cus;
-      }
-    }
-    // compute units that hold workgroups from the start: the dispatcher's rotation over the mask's shader engines stops at
-    // the smallest engine share (flight_layout balances the shares; an unbalanced rest is cut here)
-    p->fl_cus[k] = masks ? cus * L.resident_units[k] / (u[k] > 0 ? u[k] : 1) : cus;
-    if (masks)
-      SOGM_HIP_CHECK(p->res.stream_masked(&p->fl_stream[k], (uint32_t)((n_cu + 31) / 32), mask));
-    else
-      SOGM_HIP_CHECK(p->res.stream(&p->fl_stream[k]));
-    SOGM_HIP_CHECK(p->res.event(&p->fl_ev_done[k]));
-  }
-  SOGM_HIP_CHECK(p->res.event(&p->fl_ev_in));
-  p->fl_wgs[0] = p->fl_cus[0];      // one QP workgroup per CU (a whole CU's LDS and registers)
-  p->fl_wgs[1] = p->fl_cus[1];      // one search workgroup per CU (124 KB of LDS)
-  p->fl_wgs[2] = c->tune_i(SOGM_TUNE_FLIGHT_LIGHT_PER_CU) * p->fl_cus[2];  // corridor / finish waves: 39.8 KB of LDS, one per SIMD
-  p->fl_wgs[3] = c->tune_i(SOGM_TUNE_FLIGHT_MAP_PER_CU) * p->fl_cus[3];    // map waves: two per SIMD
-  SOGM_HIP_CHECK(hipStreamSynchronize(nullptr));
-  return setup.done();
-}
-
-#ifdef SOGM_FLIGHT_TRACE
-#include <chrono>
-#define FL_TRACE(what) std::fprintf(stderr, "FLTRACE %p %s %.3f ms\n", (void *)p, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count())
-#else
-#define FL_TRACE(what) (void)0
-#endif
-extern "C" {
-int sogm_flight_run(sogm_planner *p, const SogmFlight *f, void *stream) {
-  if (!p || !f || f->n_ticks < 1 || f->n_ticks > FLIGHT_MAX_TICKS || f->first_tick < 0 || !f->worlds || !f->goals ||
-      !f->drone_ids || !f->hover_inout || !f->own_inout || !f->tables || !f->log_records || !f->log_ok || !(f->period > 0))
-    return SOGM_ERR_INVALID_ARG;
-  sogm_ctx *c = p->map;
-  const int A = c->n_agents;
-  if (f->n_total < A || f->agent0 < 0 || f->agent0 + A > f->n_total) return SOGM_ERR_INVALID_ARG;
-  if (p->fl_fsm_on && f->n_total != A) {
-    sogm::set_error_text("sogm_flight_run: under sogm_planner_set_flight_fsm a flight has n_total == n_agents (one process owns every row)");
-    return SOGM_ERR_INVALID_ARG;
-  }
-  const bool xchg = f->n_total != A && f->nccl_comm != nullptr;  // the exchange runs behind the call (k_flight_xwait / xsignal)
-  const int lag = c->tune_i(SOGM_TUNE_FLIGHT_NEIGHBOUR_LAG) == 1 ? 1 : 2;
-  if (f->n_total != A && !xchg && f->n_ticks > lag) {
-    // several ranks, no communicator: the rows of the OTHER ranks' agents in ver(k - 2) must be complete before tick k starts,
-    // and only the host can put them there (an all-gather of the finished versions between two calls): two ticks per call
-    sogm::set_error_text("sogm_flight_run: with n_total > n_agents (other ranks' rows in the tables) and no nccl_comm a call flies at most two ticks");
-    return SOGM_ERR_INVALID_ARG;
-  }
-  if (!p->flow || !c->sparse || !c->d_body || c->n_body <= 0) return SOGM_ERR_STATE;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  hipStream_t main = (hipStream_t)stream;
-  if (int rc = sogm::join_update(c, main)) return rc;
-  if (int rc = sogm::join_prestamp(c, main)) return rc;
-  if (int rc = sogm::join_exchange(c, main)) return rc;
-  if (int rc = flight_setup(p)) return rc;
-  {  // the work queues hold the descriptors of two ticks at most (an agent is at most one tick ahead of the slowest)
-    const long long per_tick = (long long)A * (1 + c->tune_i(SOGM_TUNE_FLIGHT_RESET) + c->tune_i(SOGM_TUNE_FLIGHT_BITS) +
-                                               c->tune_i(SOGM_TUNE_FLIGHT_MARKS) + c->tune_i(SOGM_TUNE_FLIGHT_SPLAT));
-    if (2 * per_tick > FL_WQ_SLOTS || 2ll * A * (SOGM_MAX_PIECES + 1) > FL_WQ_SLOTS) {
-      sogm::set_error_text("sogm_flight_run: agents x tickets per tick exceed the work queue (lower flight_marks / flight_bits)");
-      return SOGM_ERR_CAPACITY;
-    }
-  }
-  const size_t agent_bytes = (size_t)c->spec.T * (size_t)c->geom.V * c->cell_bytes();
-  if (agent_bytes % 32 != 0 || (reinterpret_cast<uintptr_t>(c->d_grid) & 31) != 0) {
-    sogm::set_error_text("sogm_flight_run: agent grids must be 32-byte aligned (V * T * cell bytes a multiple of 32)");
-    return SOGM_ERR_INVALID_ARG;
-  }
-  int max_blocks = 0;
-  for (int i = 0; i < f->n_ticks; ++i) {
-    const SogmWorld &w = f->worlds[i];
-    if (!w.cloud_xyz || !w.block_bounds || w.n_points < 0 || w.block_points < 64 || w.block_points > 4096 ||
-        w.n_blocks != (w.n_points + w.block_points - 1) / w.block_points || w.n_cyl < 0 || (w.n_cyl > 0 && !w.cylinders))
-      return SOGM_ERR_INVALID_ARG;
-    if (w.n_blocks > max_blocks) max_blocks = w.n_blocks;
-    p->h_fl_worlds[i] = FlightWorld{w.cloud_xyz, w.block_bounds, w.cylinders, w.n_points, w.n_blocks, w.block_points, w.n_cyl};
-  }
-  sogm::FlightMapDev md{};
-  {
-    SogmWorld big = f->worlds[0];  // (only its block count sizes the lists)
-    big.n_blocks  = max_blocks;
-    big.n_points  = max_blocks * big.block_points;
-    if (int rc = sogm::world_blocks(c, &big, &md.cb)) return rc;
-    md.cb.n_blocks = max_blocks;  // (per frame in the kernel; the lists' row length is md.cb.row = the context's capacity)
-  }
-  // the agent's single grid of the flight is the context's current one; it must be covered by its mark log
-  // (a pooled tick path may have left a spare grid queued: nothing to adopt here)
-  const int slot = c->pool.current();
-  if (!c->pool.loggable(slot)) {
-    if (int rc = sogm::launch_clear(c, main, c->d_grid, false)) return rc;  // dense, once; restarts the log
-    if (!c->pool.loggable(slot)) {
-      sogm::set_error_text("sogm_flight_run: the current grid has no mark log (sogm_set_sparse_reset)");
-      return SOGM_ERR_STATE;
-    }
-  }
-  if (int rc = sogm::map_target(c, slot, false, nullptr, &md.tgt)) return rc;
-  FlightCtl fl   = p->fl;
-  fl.xready      = xchg ? p->fl_xready : nullptr;
-  fl.lag         = lag;
-  fl.n_ticks     = f->n_ticks;
-  fl.first_tick  = f->first_tick;
-  md.worlds      = p->d_fl_worlds;
-  md.ov          = {.rec = nullptr, .n_rec = 0, .ego_ids = f->drone_ids, .body = c->d_body, .n_body = c->n_body};
-  md.tables      = f->tables;
-  md.n_total     = f->n_total;
-  md.tick        = {.own = f->own_inout, .hover = f->hover_inout, .now = p->d_fl_now, .t_start = p->d_fl_tstart,
-                    .pva = p->d_fl_pva, .start_offset = f->replan_start_offset};
-  md.t0          = f->t0;
-  md.period      = f->period;
-  md.n_reset     = c->tune_i(SOGM_TUNE_FLIGHT_RESET);
-  md.n_bits      = c->tune_i(SOGM_TUNE_FLIGHT_BITS);
-  md.n_marks     = c->tune_i(SOGM_TUNE_FLIGHT_MARKS);
-  md.n_splat     = c->tune_i(SOGM_TUNE_FLIGHT_SPLAT);
-  md.n_head_wgs  = c->tune_i(SOGM_TUNE_FLIGHT_HEADS) < p->fl_wgs[3] / 2 ? c->tune_i(SOGM_TUNE_FLIGHT_HEADS)
-                                                                        : (p->fl_wgs[3] / 2 > 0 ? p->fl_wgs[3] / 2 : 1);
-  // the urgent lane (sogm_planner.hpp): a few heads and a share of the workers, none with flight_urgent = 0
-  fl.n_urgent    = c->tune_i(SOGM_TUNE_FLIGHT_URGENT) < A ? c->tune_i(SOGM_TUNE_FLIGHT_URGENT) : A - 1;
-  if (fl.n_urgent < 0) fl.n_urgent = 0;
-  md.n_uhead_wgs = 0;
-  md.n_uwork_wgs = 0;
-  {
-    const int fine = c->tune_i(SOGM_TUNE_FLIGHT_URGENT_FINE);
-    auto      cut  = [fine](int n, int hi) { return n * fine < hi ? n * fine : hi; };
-    md.un_reset = cut(md.n_reset, 256);
-    md.un_bits  = cut(md.n_bits, 256) > 2 * md.n_bits ? 2 * md.n_bits : cut(md.n_bits, 256);  // (bits tickets are short already)
-    md.un_marks = cut(md.n_marks, 256);
-    md.un_splat = cut(md.n_splat, 64);
-  }
-  fl.gate_pace_ticks = (int)(c->tune[SOGM_TUNE_FLIGHT_GATE_PACE_US] * 100.0);
-  p->fl_epoch = p->fl_epoch >= 0x7ffffff0 ? 1 : p->fl_epoch + 1;  // (never 0: the zeroed word)
-  fl.epoch    = p->fl_epoch;
-  fl.n_splat  = md.n_splat;
-  fl.un_splat = md.un_splat;
-  if (fl.n_urgent > 0) {
-    const int workers = p->fl_wgs[3] - md.n_head_wgs;
-    md.n_uhead_wgs = md.n_head_wgs >= 8 ? 4 : md.n_head_wgs / 2;
-    md.n_uwork_wgs = c->tune_i(SOGM_TUNE_FLIGHT_URGENT_WAVES) < workers ? c->tune_i(SOGM_TUNE_FLIGHT_URGENT_WAVES) : workers;
-    if (md.n_uhead_wgs < 1 || md.n_uwork_wgs < 1) fl.n_urgent = 0, md.n_uhead_wgs = 0, md.n_uwork_wgs = 0;
-  }
-  md.n_admit     = c->tune_i(SOGM_TUNE_FLIGHT_ADMIT);
-  md.pace_ticks  = (int)(c->tune[SOGM_TUNE_FLIGHT_PACE_US] * 100.0);
-  md.agent_bytes = agent_bytes;
-  md.reset_stat  = c->d_reset_stat;
-  // the per-agent FSM (sogm_planner_set_flight_fsm); all null: off
-  sogm::FlightFsmDev fd{};
-  if (p->fl_fsm_on) {
-    const SogmFlightFsm &u = p->fl_fsm;
-    fd = sogm::FlightFsmDev{.prm = u.prm, .check_duration = u.check_duration, .state = u.state_inout, .goals = f->goals,
-                            .due = p->d_fl_due, .reached = p->d_fl_reached, .pos_now = p->d_fl_posnow,
-                            .log_state = u.log_state, .log_due = u.log_due, .log_safe = u.log_safe,
-                            .log_reached = u.log_reached, .log_pub = u.log_pub, .log_hover_start = u.log_hover_start,
-                            .log_own = u.log_own};
-  }
-  md.fsm = fd;
-  const MapView mv = view_of(c);
-  // frames + control block, in stream order on the caller's stream
-  SOGM_HIP_CHECK(hipMemcpyAsync(p->d_fl_worlds, p->h_fl_worlds, sizeof(FlightWorld) * (size_t)f->n_ticks, hipMemcpyHostToDevice, main));
-  const int       ring    = p->fl.ring_mask + 1;
-  const int       n_words = FL_HDR + 4 * ring + 4 * FL_WQ_SLOTS + 3 * FLIGHT_MAX_TICKS + 4 * A;  // (the parked lists: k_flight_seed)
-  const long long n_log   = (long long)f->n_ticks * A * (long long)(sizeof(SogmTrajRecord) / sizeof(int));
-  hipLaunchKernelGGL(k_flight_reset, dim3(256), dim3(256), 0, main, fl, n_words, p->aw.verdict, p->fl.acc,
-                     reinterpret_cast<int *>(f->log_records), n_log);
-  SOGM_HIP_CHECK(hipGetLastError());
-  SOGM_HIP_CHECK(hipMemsetAsync(f->log_ok, 0, sizeof(int32_t) * (size_t)f->n_ticks * A, main));
-  hipLaunchKernelGGL(k_flight_seed, dim3((A + 255) / 256), dim3(256), 0, main, fl);
-  SOGM_HIP_CHECK(hipGetLastError());
-  SOGM_HIP_CHECK(hipEventRecord(p->fl_ev_in, main));
-  for (int k = 0; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(p->fl_stream[k], p->fl_ev_in, 0));
-  FL_TRACE("waits queued");
-  // QP first, then search (each wants whole CUs), then the one-wave kernels: with masks the order is immaterial
-  const int spec = c->tune_i(SOGM_TUNE_FLIGHT_SPEC) != 0 ? 1 : 0;
-  hipError_t e = sogm::launch_flight_qp(p->pp, p->qs, p->qw, p->qc, fl, p->fl_wgs[0], qp_io(p, p->d_fl_pva), p->fl_stream[0]);
-  if (e == hipSuccess) {
-    sogm::SearchIO sio = search_io(p, p->d_fl_pva, f->goals, p->d_fl_tstart);
-    sio.due            = fd.state ? fd.due : nullptr;  // (never sogm_planner_set_due's mask)
-    e = sogm::launch_flight_search(mv, p->ap, p->pp.corridor_tau, astar_ws(p), fl, p->fl_wgs[1], sio, spec, p->fl_stream[1]);
-  }
-  if (int rc = launched("sogm_flight_run: launch", e)) {
-    (void)hipDeviceSynchronize();
-    return rc;
-  }
-  FL_TRACE("qp + search launched");
-  sogm::FlightLightDev ld{};
-  ld.cor = corridor_io(p, p->d_fl_pva, p->d_fl_tstart);
-  // (the flight's swarm is its ring of tables: the kernel sets swarm / pub_table / out / out_ok per tick, null here)
-  ld.fin = sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
-                            .status = p->d_status, .cpts = p->d_cpts, .n_swarm = f->n_total, .swarm_ego = f->drone_ids,
-                            .swarm_now = p->d_fl_now, .t_start = p->d_fl_tstart, .drone_ids = f->drone_ids,
-                            .out_safe = p->d_safe, .counters = p->cw.counters, .pub_own = f->own_inout,
-                            .due = fd.state ? fd.due : nullptr};
-  ld.fsm         = fd;
-  ld.tables      = f->tables;
-  ld.n_total     = f->n_total;
-  ld.agent0      = f->agent0;
-  ld.log_records = f->log_records;
-  ld.log_ok      = f->log_ok;
-  e = sogm::launch_flight_light(mv, p->pp, p->cw, fl, ld, p->fl_wgs[2], p->fl_stream[2]);
-  if (e == hipSuccess) e = sogm::launch_flight_map(c->geom, fl, md, p->fl_wgs[3], p->fl_stream[3]);
-  if (int rc = launched("sogm_flight_run: launch", e)) {
-    (void)hipDeviceSynchronize();
-    return rc;
-  }
-  FL_TRACE("light + map launched");
-  if (xchg) {
-    // The exchange behind the call: per tick [wait: every local agent has finished it] -> in-place all-gather of this rank's
-    // rows of its table version -> [mark the version complete, queue the overlays parked at its gate], all queued now, on the
-    // context's exchange stream, behind the control block's reset.  Every rank queues the same n_ticks collectives; a rank
-    // whose flight fails still runs them (the waiting kernel gives up on the error word), so no peer hangs in a collective.
-    hipStream_t xs = nullptr;
-    if (int rc = sogm::exchange_stream(c, &xs)) return rc;
-    SOGM_HIP_CHECK(hipStreamWaitEvent(xs, p->fl_ev_in, 0));
-    int rc_x = SOGM_OK;
-    for (int i = 0; i < f->n_ticks; ++i) {
-      const int       k   = f->first_tick + i;
-      SogmTrajRecord *tab = f->tables + (size_t)(k & 3) * f->n_total;
-      hipLaunchKernelGGL(k_flight_xwait, dim3(1), dim3(64), 0, xs, fl, i);
-      if (rc_x == SOGM_OK)  // (after a failed collective the remaining ones are not attempted: the communicator is broken)
-        rc_x = sogm::exchange_allgather_raw(c, f->nccl_comm, tab + f->agent0, tab, sizeof(SogmTrajRecord) * (size_t)A);
-      hipLaunchKernelGGL(k_flight_xsignal, dim3(1), dim3(64), 0, xs, fl, i);
-      if (i == 0) FL_TRACE("first collective queued");
-    }
-    FL_TRACE("collectives queued");
-    SOGM_HIP_CHECK(hipGetLastError());
-    if (int rc = sogm::exchange_mark_pending(c)) return rc;
-    if (int rc = sogm::join_exchange(c, main)) return rc;  // the call's last versions are complete when `stream` goes on
-    if (rc_x != SOGM_OK) {
-      (void)hipDeviceSynchronize();
-      return rc_x;
-    }
-  }
-  for (int k = 0; k < 4; ++k) {
-    SOGM_HIP_CHECK(hipEventRecord(p->fl_ev_done[k], p->fl_stream[k]));
-    SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->fl_ev_done[k], 0));
-  }
-  hipLaunchKernelGGL(k_flight_report, dim3(1), dim3(1), 0, main, (const int *)p->fl.hdr, p->h_flow_fail);
-  SOGM_HIP_CHECK(hipGetLastError());
-  c->updated             = 1;
-  c->pool.current_rebuilt();
-  c->records_final_valid = 0;
-  c->n_stamps += f->n_ticks;
-  return SOGM_OK;
-}
-
-}  // extern "C"
-__global__ void k_flight_touch(int *word) {
-  if (threadIdx.x == 0 && word) atomicAdd(word, 0);
-}
-extern "C" {
-// Creates what the first sogm_flight_run would create — control block, the four masked streams, the exchange stream — and
-// runs one empty kernel on each, so that their hardware queues EXIST before any flight is in the air, and allocates what the
-// first sogm_flight_run would allocate (crop lists for frames of up to max_cloud_points points, the stamp's scratch): that
-// first call otherwise synchronises the DEVICE while it grows them.  A host that flies several planners in one process (two
-// ranks on one device: tests) calls this for each of them before the first flight — the second rank's first call would
-// otherwise wait for the first rank's flight to end, which waits for the second rank's rows.  Optional otherwise.  Synchronises.
-int sogm_flight_prepare(sogm_planner *p, int max_cloud_points) {
-  if (!p || max_cloud_points < 0) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(p->map->device));
-  if (int rc = flight_setup(p)) return rc;
-  {  // everything a first sogm_flight_run would allocate — and synchronise the DEVICE for: the per-agent crop lists for
-     // frames of up to max_cloud_points points (blocks of 256), the stamp's scratch
-    SogmWorld big{};
-    big.block_points = 256;
-    big.n_points     = max_cloud_points;
-    big.n_blocks     = (max_cloud_points + 255) / 256;
-    sogm::CloudBlocks cb{};
-    if (int rc = sogm::world_blocks(p->map, &big, &cb)) return rc;
-    if (p->map->sparse) {
-      // the stamp's scratch, the current grid's mark log (its creation ends with a null-stream memset and synchronisation,
-      // which waits for every BLOCKING stream of the process — masked streams are — i.e. for another planner's flight) and the
-      // one dense clear that puts the grid under its log
-      sogm_ctx       *c = p->map;
-      sogm::MapTarget tgt{};
-      if (int rc = sogm::map_target(c, c->pool.current(), false, nullptr, &tgt)) return rc;
-      if (!c->pool.loggable(c->pool.current()))
-        if (int rc = sogm::launch_clear(c, nullptr, c->d_grid, false)) return rc;
-    }
-  }
-  hipStream_t xs = nullptr;
-  if (int rc = sogm::exchange_stream(p->map, &xs)) return rc;
-  for (int k = 0; k < 4; ++k) hipLaunchKernelGGL(k_flight_touch, dim3(1), dim3(64), 0, p->fl_stream[k], (int *)nullptr);
-  hipLaunchKernelGGL(k_flight_touch, dim3(1), dim3(64), 0, xs, (int *)nullptr);
-  SOGM_HIP_CHECK(hipGetLastError());
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  return SOGM_OK;
-}
-
-// diagnostics (tools/ only): every agent-tick's stamps of the last flight, [n_ticks][A][FL_TS] ticks of 10 ns
-int sogm_debug_flight_times(sogm_planner *p, long long *out_host, int n_ticks) {
-  if (!p || !p->d_fl || !out_host || n_ticks < 1 || n_ticks > FLIGHT_MAX_TICKS) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  SOGM_HIP_CHECK(hipMemcpy(out_host, p->fl.ts_log, sizeof(long long) * FL_TS * (size_t)p->map->n_agents * n_ticks, hipMemcpyDeviceToHost));
-  return SOGM_OK;
-}
-
-// diagnostics (tools/ only): the control block of the last flight as it stands — out_words = [FL_COUNTERS header counters]
-// [FLIGHT_MAX_TICKS tick_done][FLIGHT_MAX_TICKS parked_n][A tick_of][A seg_done][A stage][A urgent], out_ts = [A][FL_TS]
-// stamps of every agent's current tick.  What a stalled flight looked like when it was aborted.
-int sogm_debug_flight_dump(sogm_planner *p, int32_t *out_words, int cap_words, long long *out_ts) {
-  if (!p || !p->d_fl || !out_words) return SOGM_ERR_INVALID_ARG;
-  const int A = p->map->n_agents;
-  if (cap_words < FL_COUNTERS + 2 * FLIGHT_MAX_TICKS + 4 * A) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(p->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  for (int i = 0; i < FL_COUNTERS; ++i)
-    SOGM_HIP_CHECK(hipMemcpy(out_words + i, p->fl.hdr + (size_t)i * FL_STRIDE, sizeof(int), hipMemcpyDeviceToHost));
-  int32_t *o = out_words + FL_COUNTERS;
-  SOGM_HIP_CHECK(hipMemcpy(o, p->fl.tick_done, sizeof(int) * FLIGHT_MAX_TICKS, hipMemcpyDeviceToHost));
-  o += FLIGHT_MAX_TICKS;
-  SOGM_HIP_CHECK(hipMemcpy(o, p->fl.parked_n, sizeof(int) * FLIGHT_MAX_TICKS, hipMemcpyDeviceToHost));
-  o += FLIGHT_MAX_TICKS;
-  SOGM_HIP_CHECK(hipMemcpy(o, p->fl.tick_of, sizeof(int) * (size_t)A, hipMemcpyDeviceToHost));
-  o += A;
-  SOGM_HIP_CHECK(hipMemcpy(o, p->fl.seg_done, sizeof(int) * (size_t)A, hipMemcpyDeviceToHost));
-  o += A;
-  SOGM_HIP_CHECK(hipMemcpy(o, p->fl.stage, sizeof(int) * (size_t)A, hipMemcpyDeviceToHost));
-  o += A;
-  SOGM_HIP_CHECK(hipMemcpy(o, p->fl.urgent, sizeof(int) * (size_t)A, hipMemcpyDeviceToHost));
-  if (out_ts) SOGM_HIP_CHECK(hipMemcpy(out_ts, p->fl.ts, sizeof(long long) * FL_TS * (size_t)A, hipMemcpyDeviceToHost));
-  return SOGM_OK;
-}
-
-// diagnostics (tools/, tests/): when every workgroup of the last flight's four kernels started — out_host [8][4096]: [0..3] wall-clock
-// ticks (100 MHz; 0 = the workgroup never ran), [4..7] where it started (HW_ID | XCC_ID << 32), out_wgs_host[4] the launched counts (QP, search, corridor + finish, map)
-int sogm_debug_flight_wg_starts(sogm_planner *p, long long *out_host, int32_t *out_wgs_host) {
-  if (!p || !p->d_fl || !out_host) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(p->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  SOGM_HIP_CHECK(hipMemcpy(out_host, p->fl.wg_start, sizeof(long long) * 8 * FL_WG_LOG, hipMemcpyDeviceToHost));
-  if (out_wgs_host)
-    for (int k = 0; k < 4; ++k) out_wgs_host[k] = p->fl_wgs[k];
-  return SOGM_OK;
-}
-
-int sogm_flight_stats(sogm_planner *p, double *out_ms, int32_t *out_hdr) {
-  if (!p || !p->d_fl) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(p->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  const int A = p->map->n_agents;
-  if (out_ms) {
-    long long *tmp = new (std::nothrow) long long[8 * (size_t)A];
-    if (!tmp) return SOGM_ERR_INVALID_ARG;
-    const hipError_t e = hipMemcpy(tmp, p->fl.acc, sizeof(long long) * 8 * (size_t)A, hipMemcpyDeviceToHost);
-    for (int i = 0; i < 8 * A; ++i) out_ms[i] = (i % 8) == 7 ? (double)tmp[i] : (double)tmp[i] / 1.0e5;  // 100 MHz -> ms
-    delete[] tmp;
-    SOGM_HIP_CHECK(e);
-  }
-  if (out_hdr) {  // the counters, compacted (the device keeps them FL_STRIDE words apart)
-    int *tmp = new (std::nothrow) int[FL_HDR];
-    if (!tmp) return SOGM_ERR_INVALID_ARG;
-    const hipError_t e = hipMemcpy(tmp, p->fl.hdr, sizeof(int) * FL_HDR, hipMemcpyDeviceToHost);
-    for (int i = 0; i < 32; ++i) out_hdr[i] = i < 15 ? tmp[(size_t)i * FL_STRIDE] : 0;  // (the urgent lane's four: not reported)
-    delete[] tmp;
-    SOGM_HIP_CHECK(e);
-    {  // [15]: workgroups of the four kernels that were NOT resident from the start (first instruction > 1 ms after the
-       // flight's first workgroup): must be 0 — the liveness argument (flight_layout) and tests/test_flight_gpu.py hold it
-      long long *ws = new (std::nothrow) long long[4 * FL_WG_LOG];
-      if (!ws) return SOGM_ERR_INVALID_ARG;
-      const hipError_t e2 = hipMemcpy(ws, p->fl.wg_start, sizeof(long long) * 4 * FL_WG_LOG, hipMemcpyDeviceToHost);
-      int late = 0;
-      for (int k = 0; k < 4; ++k) {  // per kernel: against ITS first workgroup (the four launches may start a millisecond apart)
-        long long first = 0;
-        for (int b = 0; b < p->fl_wgs[k] && b < FL_WG_LOG; ++b) {
-          const long long v = ws[(size_t)k * FL_WG_LOG + b];
-          if (v > 0 && (first == 0 || v < first)) first = v;
-        }
-        for (int b = 0; b < p->fl_wgs[k] && b < FL_WG_LOG; ++b) {
-          const long long v = ws[(size_t)k * FL_WG_LOG + b];
-          if (v == 0 || v - first > 100000) ++late;
-        }
-      }
-      delete[] ws;
-      SOGM_HIP_CHECK(e2);
-      out_hdr[15] = late;
-    }
-    unsigned long long prof[16];  // [16..31]: wave time by activity in units of 10 us (0-8), descriptor counts (9-15)
-    SOGM_HIP_CHECK(hipMemcpy(prof, p->fl.prof, sizeof(prof), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 16; ++i) out_hdr[16 + i] = (int32_t)(i < 9 ? prof[i] / 1000ull : prof[i]);
-  }
-  return SOGM_OK;
-}
 
 int sogm_replan(sogm_planner *p, const double *start_pva, const double *goal,
                 const double *t_start, const int32_t *drone_ids, SogmTrajRecord *out_records,

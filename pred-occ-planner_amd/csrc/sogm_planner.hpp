@@ -306,7 +306,7 @@ struct sogm_planner {
   hipEvent_t  ev_pts[SOGM_MAX_GROUPS];  // after a group's obstacle-point kernel: its last read of the SOGM
   // dataflow replan (persistent kernels chained per agent through device-side ready lists)
   int            flow;        // 1 = use it (pipelining modes other than the in-place pre-clear)
-  int           *d_flow;      // FLOW_HDR + 4 A ints: header, seg_done, a_ready, q_ready, f_ready
+  int           *d_flow;      // the control block (layout: sogm::FlowBlock)
   long long     *d_flow_ts;   // [A][8]
   sogm::FlowCtl  fc;
   hipStream_t    fstream[4];  // A*, corridors, QP, finish
@@ -317,7 +317,7 @@ struct sogm_planner {
   SogmWorld      ps_world;
   hipEvent_t     ev_gate, ev_fdone[4];
   int           *d_epoch;      // device word: the clear epoch of the replan in flight (sogm_ctx::clear_epoch_word)
-  int            reset_epoch;  // generation of the control block's reset (k_flow_reset writes it into d_flow's last word)
+  int            reset_epoch;  // generation of the control block's reset (k_flow_reset writes it into the block's word FlowBlock::gen)
   int           *h_flow_fail;  // pinned, device-visible: {last FLOW_ERR code, ticks that failed} (k_flow_report)
   // per-object use of the per-stage entries (sogm_planner_select_agents / _set_search_mode)
   int sel_first, sel_count;  // agents the per-stage entries process; (0, A) by default
@@ -326,7 +326,7 @@ struct sogm_planner {
   hipStream_t peek;          // sogm_debug_flow_peek's private stream (created on first use)
   // flight (sogm_flight_run): control block, per-agent tick inputs, frames, masked streams (all created on first use)
   sogm::FlightCtl     fl;
-  int                *d_fl;          // header + rings + tick_done + tick_of + seg_done + stage
+  int                *d_fl;          // the control block (layout: sogm::FlightBlock)
   sogm::FlightWorld  *d_fl_worlds, *h_fl_worlds;  // [FLIGHT_MAX_TICKS] device / pinned staging
   double             *d_fl_pva, *d_fl_tstart, *d_fl_now;
   hipStream_t         fl_stream[4];  // QP, search, corridor + finish, map
@@ -341,3 +341,45 @@ struct sogm_planner {
   int32_t            *d_fl_due = nullptr, *d_fl_reached = nullptr;
   double             *d_fl_posnow = nullptr;
 };
+
+// The search's per-phase clock statistics (sogm_debug_astar_stats, tools/diag_astar.py) are collected while the map's
+// profiling is on: five s_memrealtime reads per expansion are not free.
+inline sogm::AstarWorkspace astar_ws(const sogm_planner *p) {
+  sogm::AstarWorkspace w = p->aw;
+  if (!((p->map->profiling >> SOGM_PROF_ASTAR) & 1)) w.dbg = nullptr;
+  return w;
+}
+
+// A launcher's error under the caller's label.  The launchers hand over what hipGetLastError() gave them: it clears the
+// error as it reads it, so a second call here would report "no error".
+inline int launched(const char *what, hipError_t e) {
+  if (e == hipSuccess) return SOGM_OK;
+  sogm::set_error(what, e);
+  return SOGM_ERR_HIP;
+}
+
+// The stages' buffers of a replan or a flight: the planner's own between the stages, the caller's at both ends.
+inline sogm::SearchIO search_io(const sogm_planner *p, const double *start_pva, const double *goal, const double *t_start) {
+  return sogm::SearchIO{.start_pva = start_pva, .goal = goal, .t_start = t_start, .out_ret = p->d_ret,
+                        .out_route = p->d_route, .out_route_len = p->d_route_len, .route_cap = p->route_cap,
+                        .out_stats = p->d_stats, .due = p->due};
+}
+inline sogm::CorridorIO corridor_io(const sogm_planner *p, const double *start_pva, const double *t_start) {
+  return sogm::CorridorIO{.start_pva = start_pva, .t_start = t_start, .route = p->d_route,
+                          .route_len = p->d_route_len, .route_cap = p->route_cap, .out_polys = p->d_polys,
+                          .out_nfaces = p->d_nfaces, .out_npoly = p->d_npoly, .out_goal = p->d_goal};
+}
+inline sogm::QpIO qp_io(const sogm_planner *p, const double *start_pva) {
+  return sogm::QpIO{.start_pva = start_pva, .goal_pv = p->d_goal, .polys = p->d_polys, .nfaces = p->d_nfaces,
+                    .npoly = p->d_npoly, .out_cpts = p->d_cpts, .out_status = p->d_status, .out_iters = p->d_iters};
+}
+// a replan's: swarm and publication as sogm_planner_set_swarm / _set_publish left them (the flight fills its own)
+inline sogm::FinishArgs finish_args(const sogm_planner *p, const double *t_start, const int32_t *drone_ids,
+                                    SogmTrajRecord *out, int32_t *out_ok) {
+  return sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
+                          .status = p->d_status, .cpts = p->d_cpts, .swarm = p->swarm, .n_swarm = p->n_swarm,
+                          .swarm_ego = p->swarm_ego, .swarm_now = p->swarm_now, .t_start = t_start,
+                          .drone_ids = drone_ids, .out = out, .out_ok = out_ok, .out_safe = p->d_safe,
+                          .counters = p->cw.counters, .pub_own = p->pub_own, .pub_table = p->pub_table,
+                          .due = p->due};
+}

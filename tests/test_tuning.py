@@ -16,7 +16,8 @@ def test_the_library_reads_three_environment_switches_only():
     assert names == {"SOGM_SPARSE_RESET", "SOGM_FLOW", "SOGM_RCCL_LIB"}, names
     # ... and keeps no function-static copies of tuning values
     for f in glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_map.hip")) + \
-            glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_planner.hip")):
+            glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_planner.hip")) + \
+            glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_flight.hip")):
         assert not re.findall(r"static (const )?(int|double)\s+\w+\s*=\s*-1", open(f).read()), f
 
 
