@@ -155,6 +155,25 @@ int sogm_corridor_rules_batched(sogm_planner *counters_of, const SogmPlannerPara
                                 const int32_t *nfaces, const int32_t *seg_state, int n, int max_faces, double *out_box,
                                 double *out_shrunk, int32_t *out_seg_nfaces, int32_t *out_seg_state, double *out_polys,
                                 int32_t *out_nfaces, int32_t *out_npoly, double *out_goal, void *stream);
+/* The same hook with flags.  SOGM_RULES_PARALLEL: the dataflow replan's form — SOGM_MAX_PIECES one-wave workgroups per
+ * problem, one per segment slot; the wave that finishes the later of two neighbouring segments solves their
+ * adjacent-intersection LP at once, the one that completes the problem's last slot does the bookkeeping from those
+ * verdicts.  Every output is the sequential form's, byte for byte.  counters_of then also takes the pair counters
+ * (sogm_debug_corridor_pairs).  flags = 0: sogm_corridor_rules_batched. */
+#define SOGM_RULES_PARALLEL 1
+int sogm_corridor_rules_batched_flags(sogm_planner *counters_of, const SogmPlannerParams *pp_host, const double *start_pva,
+                                      const double *route, const int32_t *route_len, int route_cap, const double *polys,
+                                      const int32_t *nfaces, const int32_t *seg_state, int n, int max_faces,
+                                      double *out_box, double *out_shrunk, int32_t *out_seg_nfaces, int32_t *out_seg_state,
+                                      double *out_polys, int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
+                                      int flags, void *stream);
+
+/* Diagnostics: the adjacent-pair LPs of the corridor bookkeeping (dataflow replan, flight, parallel rules hook).  out4, since
+ * the last call: [0] pair LPs solved by a segment's wave as its neighbour was done, [1] pair LPs solved inside the
+ * bookkeeping because no verdict was there, [2] pairs the bookkeeping took from a verdict, [3] the OR of every ready word
+ * and verdict of the planner now and of what a parallel rules hook left set (0: every finalising wave cleaned up).
+ * Synchronises the device. */
+int sogm_debug_corridor_pairs(sogm_planner *p, unsigned long long *out4);
 
 #ifdef __cplusplus
 }

@@ -164,6 +164,7 @@ FSM_STATE_BYTES = C.sizeof(SogmFsmState)  # 24
 FSM_PUB_NONE, FSM_PUB_NEW, FSM_PUB_HOVER = 0, 1, 2  # sogm_fsm_apply's out_pub
 
 FLIGHT_MAX_TICKS = 64
+RULES_PARALLEL = 1  # sogm_corridor_rules_batched_flags: SOGM_RULES_PARALLEL
 FLIGHT_HDR_ERR, FLIGHT_HDR_FINISHED, FLIGHT_HDR_LATE_WGS = 4, 5, 15  # sogm_flight_stats out_hdr indices
 FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "chain", "ticks")
 TRAJ_RECORD_BYTES = C.sizeof(SogmTrajRecord)  # 2064
@@ -228,6 +229,9 @@ PROTOTYPES = {
     "sogm_linprog_batched": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sogm_corridor_rules_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp]),
+    "sogm_corridor_rules_batched_flags": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _i, _vp]),
+    "sogm_debug_corridor_pairs": (_i, [_vp, _vp]),
     "sogm_replan": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_create": (_i, [C.POINTER(SogmGridMapParams), _i, _i, C.POINTER(_vp)]),
     "sogm_gridmap_destroy": (None, [_vp]),

@@ -1266,8 +1266,14 @@ __global__ __launch_bounds__(64) void k_firi_direct(MapView m, SogmPlannerParams
 // =================================================================================================
 // Kernel B: per agent bookkeeping (baseline_fake.cpp:364-414 / baseline.cpp:362-403)
 // =================================================================================================
+// PAIRS (the dataflow replan, the flight, the parallel rules hook): pair_row is the agent's row of CorridorWorkspace::pair_ok
+// or null — a verdict the segments' waves left there (corridor_pairs_eager) replaces the pair's LP; 0, or a null row, runs the
+// LP in place — and stamps the agent's row of CorridorWorkspace::fin_dbg or null.  Without PAIRS (k_corridor_finalize,
+// k_corridor_rules) neither exists in the code: these kernels compile to what they were.
+template <bool PAIRS = false>
 __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                                                       const CorridorIO &io, int agent, const LpScratch &sc) {
+                                                       const CorridorIO &io, int agent, const LpScratch &sc,
+                                                       const int32_t *pair_row = nullptr, long long *stamps = nullptr) {
   // The sequential bookkeeping below is executed by all 64 lanes with identical data (uniform control flow);
   // the LPs inside are solved by the whole wave, outputs are written by lane 0 / copied lane-parallel.
   const bool    w0    = threadIdx.x == 0;
@@ -1279,6 +1285,8 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
   const double *sp    = io.start_pva + agent * 9;
   const int     rl    = io.points(agent);
   int           npoly = 0;
+  if constexpr (PAIRS)
+    if (stamps && w0) stamps[0] = stamps[1] = stamps[2] = stamps[3] = wall_clock64();
   if (w0) {
     for (int i = 0; i < SOGM_MAX_PIECES; ++i) io.out_nfaces[agent * SOGM_MAX_PIECES + i] = 0;
     for (int i = 0; i < 6; ++i) io.out_goal[agent * 6 + i] = 0;
@@ -1300,12 +1308,31 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
   if (npoly == SOGM_MAX_PIECES && io.route_len[agent] - 1 > SOGM_MAX_PIECES && w0 && ws.counters)
     atomicAdd(&ws.counters[SOGM_CNT_PIECES_CAPACITY], 1ull);  // route longer than 16 pieces: truncated
   if (npoly == 0) return;
-  for (int i = 0; i + 1 < npoly; ++i) {
-    if (!corridorValidW(polys + (size_t)i * MF * 4, nfs[i], polys + (size_t)(i + 1) * MF * 4,
-                        nfs[i + 1], sc)) {
-      if (i < 2) return;
-      npoly = pp.fake_planner ? i + 1 : i;
-      break;
+  if constexpr (!PAIRS) {
+    for (int i = 0; i + 1 < npoly; ++i) {
+      if (!corridorValidW(polys + (size_t)i * MF * 4, nfs[i], polys + (size_t)(i + 1) * MF * 4,
+                          nfs[i + 1], sc)) {
+        if (i < 2) return;
+        npoly = pp.fake_planner ? i + 1 : i;
+        break;
+      }
+    }
+  } else {
+    // the same scan with the verdicts the segments' waves left: 1 / 2 replace the pair's LP, 0 (or no row) runs it here
+    int n_late = 0, n_used = 0;
+    for (int i = 0; i + 1 < npoly; ++i) {
+      const int v = pair_row ? pair_row[i] : 0;
+      ++(v ? n_used : n_late);
+      if (v == 2 || (v == 0 && !corridorValidW(polys + (size_t)i * MF * 4, nfs[i], polys + (size_t)(i + 1) * MF * 4,
+                                               nfs[i + 1], sc))) {
+        npoly = i < 2 ? 0 : pp.fake_planner ? i + 1 : i;  // (i < 2: no corridors — the exit below takes it)
+        break;
+      }
+    }
+    if (w0) {
+      if (pair_row && ws.pair_cnt && n_late) atomicAdd(&ws.pair_cnt[1], (unsigned long long)n_late);
+      if (pair_row && ws.pair_cnt && n_used) atomicAdd(&ws.pair_cnt[2], (unsigned long long)n_used);
+      if (stamps) stamps[1] = stamps[2] = stamps[3] = wall_clock64();
     }
   }
   if (pp.fake_planner ? npoly == 0 : npoly <= 1) return;
@@ -1331,6 +1358,8 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
       }
     }
   }
+  if constexpr (PAIRS)
+    if (stamps && w0) stamps[2] = stamps[3] = wall_clock64();
   for (int i = 0; i < npoly; ++i) {
     if (w0) io.out_nfaces[agent * SOGM_MAX_PIECES + i] = nfs[i];
     const double *src = polys + (size_t)i * MF * 4;
@@ -1343,6 +1372,8 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
       io.out_goal[agent * 6 + 3 + k] = gvel[k];
     }
     io.out_npoly[agent] = npoly;
+    if constexpr (PAIRS)
+      if (stamps) stamps[3] = wall_clock64();
   }
 }
 
@@ -1368,41 +1399,45 @@ struct CorridorRules {
   const int32_t           *state_in;   // [n][SOGM_MAX_PIECES] or null; -3 = "capacity exceeded" in this segment
   double                  *out_box;    // [n][SOGM_MAX_PIECES][6] llc, lhc
 };
-__global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, CorridorWorkspace ws, CorridorIO io) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// segment `seg` of problem `prob`: box, shrink, own validity, with the caller's polytope where FIRI's would be (whole wave)
+__device__ __forceinline__ void rules_segment(const CorridorRules &cr, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
+                                              const CorridorIO &io, int prob, int seg, char *smem) {
   double *base = (double *)smem, *s_poly = base + RulesLds::poly, *s_box = base + RulesLds::box, *s_w = base + RulesLds::w;
   const LpScratch sc{base + LpLds::work, base + LpLds::rows, (int *)(smem + RulesLds::perm)};
-  const int               prob = blockIdx.x, lane = threadIdx.x;
-  const SogmPlannerParams pp   = cr.pp[prob];
-  const int               MF   = pp.max_faces;
-  const int               rl   = io.points(prob);
-  for (int seg = 0; seg < SOGM_MAX_PIECES; ++seg) {
-    const int slot = prob * SOGM_MAX_PIECES + seg;
-    if (seg >= rl - 1) {
-      if (lane == 0) {
-        ws.seg_state[slot]  = -2;  // no such segment
-        ws.seg_nfaces[slot] = 0;
-        for (int k = 0; k < 6; ++k) cr.out_box[slot * 6 + k] = 0.0;
-      }
-      continue;
-    }
-    int nf = cr.nfaces_in[slot];
-    nf     = nf < 0 ? 0 : (nf > MF ? MF : nf);
-    if (lane == 0) segment_box(pp, io.start_pva + prob * 9, io.route + (size_t)prob * io.route_cap * 6, seg, s_box, s_w);
-    for (int i = lane; i < nf * 4; i += 64) s_poly[i] = cr.polys_in[(size_t)slot * MF * 4 + i];
-    wave_lds_sync();
-    shrink_corridor(pp, s_w, s_poly, nf);
-    wave_lds_sync();
-    const bool valid = corridorValidW(s_poly, nf, nullptr, 0, sc);
-    double    *out   = ws.polys + (size_t)slot * MF * 4;
-    for (int i = lane; i < nf * 4; i += 64) out[i] = s_poly[i];
+  const int lane = threadIdx.x, MF = pp.max_faces;
+  const int slot = prob * SOGM_MAX_PIECES + seg;
+  if (seg >= io.points(prob) - 1) {
     if (lane == 0) {
-      for (int k = 0; k < 6; ++k) cr.out_box[slot * 6 + k] = s_box[k];
-      ws.seg_nfaces[slot] = nf;
-      ws.seg_state[slot]  = cr.state_in && cr.state_in[slot] == -3 ? -3 : (valid ? 1 : 0);
+      ws.seg_state[slot]  = -2;  // no such segment
+      ws.seg_nfaces[slot] = 0;
+      for (int k = 0; k < 6; ++k) cr.out_box[slot * 6 + k] = 0.0;
     }
-    wave_lds_sync();
+    return;
   }
+  int nf = cr.nfaces_in[slot];
+  nf     = nf < 0 ? 0 : (nf > MF ? MF : nf);
+  if (lane == 0) segment_box(pp, io.start_pva + prob * 9, io.route + (size_t)prob * io.route_cap * 6, seg, s_box, s_w);
+  for (int i = lane; i < nf * 4; i += 64) s_poly[i] = cr.polys_in[(size_t)slot * MF * 4 + i];
+  wave_lds_sync();
+  shrink_corridor(pp, s_w, s_poly, nf);
+  wave_lds_sync();
+  const bool valid = corridorValidW(s_poly, nf, nullptr, 0, sc);
+  double    *out   = ws.polys + (size_t)slot * MF * 4;
+  for (int i = lane; i < nf * 4; i += 64) out[i] = s_poly[i];
+  if (lane == 0) {
+    for (int k = 0; k < 6; ++k) cr.out_box[slot * 6 + k] = s_box[k];
+    ws.seg_nfaces[slot] = nf;
+    ws.seg_state[slot]  = cr.state_in && cr.state_in[slot] == -3 ? -3 : (valid ? 1 : 0);
+  }
+  wave_lds_sync();
+}
+__global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, CorridorWorkspace ws, CorridorIO io) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double         *base = (double *)smem;
+  const LpScratch sc{base + LpLds::work, base + LpLds::rows, (int *)(smem + RulesLds::perm)};
+  const int               prob = blockIdx.x;
+  const SogmPlannerParams pp   = cr.pp[prob];
+  for (int seg = 0; seg < SOGM_MAX_PIECES; ++seg) rules_segment(cr, pp, ws, io, prob, seg, smem);
   __threadfence_block();  // the bookkeeping reads every lane's polytope rows back from memory
   __syncthreads();
   corridor_finalize_body(pp, ws, io, prob, sc);
@@ -1422,10 +1457,72 @@ __global__ __launch_bounds__(64) void k_corridor_rules(CorridorRules cr, Corrido
 // polytope, its completion counted in seg_done[agent] and — if that made it the agent's last slot (`cumulative`: the counter
 // runs on over the flight's ticks) — the per-agent bookkeeping, with the LP view laid over the segment layout's head
 // (SegmentLds).  True if this wave finalised the agent: publishing it is the caller's.  stamps: the flight's (null: none).
+//
+// The adjacent-pair LPs of the bookkeeping, corridorValidW(poly_i, poly_i+1), depend on their two polytopes only, so the wave
+// that finishes the LATER of two neighbouring segments solves the pair's LP at once, in its own LDS (free between two
+// segments), instead of leaving all M - 1 of them to the finalising wave behind the agent's slowest segment.  Who is later is
+// decided by one fetch-or on the agent's ready word: of two neighbours exactly one sees the other's bit, so every pair with two
+// valid states is evaluated exactly once, and before either segment's completion is counted in seg_done — when the last
+// ticket is drawn every verdict is visible.  The verdict is a pure function of the two polytopes (linprog_wave orders its
+// rows by a fixed permutation of the row count and keeps no call history); the bookkeeping consumes the same booleans in
+// the same order.  Nothing waits: no spin, no new row in the liveness table of DESIGN 3.1.
+// SOGM_PAIRS_EAGER=0 (a profiling build) leaves every pair LP to the bookkeeping, for before / after stamps of one source.
+#ifndef SOGM_PAIRS_EAGER
+#define SOGM_PAIRS_EAGER 1
+#endif
+// called by the whole wave behind the fence that makes segment `seg` (a real one: seg < points - 1) visible
+__device__ __forceinline__ void corridor_pairs_eager(const SogmPlannerParams &pp, const CorridorWorkspace &ws, int agent,
+                                                     int seg, const LpScratch &sc) {
+  unsigned old = 0;
+  if (threadIdx.x == 0) old = __hip_atomic_fetch_or(&ws.seg_ready[agent], 1u << seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  old = __builtin_amdgcn_readfirstlane(old);
+  if (!(old & ((1u << seg) >> 1 | 2u << seg))) return;  // neither neighbour is done: the pairs are theirs
+  __threadfence();  // the neighbours' polytopes, face counts and states (the fence the finalising wave takes behind its ticket)
+  const int     MF    = pp.max_faces;
+  const double *polys = ws.polys + (size_t)agent * SOGM_MAX_PIECES * MF * 4;
+  const int    *nfs   = ws.seg_nfaces + agent * SOGM_MAX_PIECES;
+  const int    *state = ws.seg_state + agent * SOGM_MAX_PIECES;
+  if (state[seg] == 1) {
+    for (int lo = seg - 1; lo <= seg; ++lo) {  // pair (lo, lo + 1): the lower segment is polyA, as in the bookkeeping
+      const int other = lo == seg ? seg + 1 : lo;
+      if (other < 0 || other >= SOGM_MAX_PIECES || !((old >> other) & 1u) || state[other] != 1) continue;
+      const bool meet = corridorValidW(polys + (size_t)lo * MF * 4, nfs[lo], polys + (size_t)(lo + 1) * MF * 4, nfs[lo + 1], sc);
+      if (threadIdx.x == 0) {
+        ws.pair_ok[agent * SOGM_MAX_PIECES + lo] = meet ? 1 : 2;
+        if (ws.pair_cnt) atomicAdd(&ws.pair_cnt[0], 1ull);
+      }
+    }
+  }
+  __threadfence();  // the verdicts are visible before this segment's completion is counted
+}
+
+// the slot's second half, behind the segment itself (k_corridor_rules_slots shares it): pairs, ticket, bookkeeping
+__device__ __forceinline__ bool corridor_slot_done(const SogmPlannerParams &pp, const CorridorWorkspace &ws, const CorridorIO &io,
+                                                   int agent, int seg, bool real, char *smem, int *seg_done, bool cumulative) {
+  __threadfence();  // this segment's polytope is visible before its completion is counted
+  const bool eager = SOGM_PAIRS_EAGER && ws.seg_ready;
+  if (eager && real) corridor_pairs_eager(pp, ws, agent, seg, LpLds::carve(smem));
+  const int done = flow_ticket(&seg_done[agent]);
+  if ((cumulative ? done & (SOGM_MAX_PIECES - 1) : done) != SOGM_MAX_PIECES - 1) return false;
+  __threadfence();  // the other segments' polytopes and verdicts (their completions were counted before ours)
+  corridor_finalize_body<true>(pp, ws, io, agent, LpLds::carve(smem), eager ? ws.pair_ok + agent * SOGM_MAX_PIECES : nullptr,
+                               ws.fin_dbg ? ws.fin_dbg + agent * 4 : nullptr);
+  // Back to zero for the agent's next tick, in front of the caller's publication.  Every other slot of this agent has drawn
+  // its seg_done ticket, which lies behind its fetch-or and its verdicts: nobody touches the word or the row any more.  In the
+  // flight the agent's next tick reaches a segment only through this publication (q_ring -> QP -> finish -> map head -> map
+  // -> search -> corridor descriptors), so its first fetch-or finds the zeroes.
+  if (eager) {
+    if (threadIdx.x < SOGM_MAX_PIECES) ws.pair_ok[agent * SOGM_MAX_PIECES + threadIdx.x] = 0;
+    if (threadIdx.x == 0) ws.seg_ready[agent] = 0u;
+  }
+  __syncthreads();
+  return true;
+}
 __device__ __forceinline__ bool corridor_slot(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
                                               const CorridorIO &io, int agent, int seg, char *smem, int *seg_done,
                                               bool cumulative, long long *stamps) {
-  if (seg < io.points(agent) - 1) {
+  const bool real = seg < io.points(agent) - 1;
+  if (real) {
     corridor_points_body<1>(m, pp, ws, io, agent, seg);
     __threadfence_block();
     __syncthreads();
@@ -1434,13 +1531,25 @@ __device__ __forceinline__ bool corridor_slot(const MapView &m, const SogmPlanne
   corridor_segment_body<6, false>(m, pp, ws, io, agent, seg, smem, FiriDirect{});
   __syncthreads();
   if (stamps && threadIdx.x == 0) stamps[14] = wall_clock64();
-  __threadfence();  // this segment's polytope is visible before its completion is counted
-  const int done = flow_ticket(&seg_done[agent]);
-  if ((cumulative ? done & (SOGM_MAX_PIECES - 1) : done) != SOGM_MAX_PIECES - 1) return false;
-  __threadfence();  // the other segments' polytopes (their completions were counted before ours)
-  corridor_finalize_body(pp, ws, io, agent, LpLds::carve(smem));
+  return corridor_slot_done(pp, ws, io, agent, seg, real, smem, seg_done, cumulative);
+}
+
+// The rules hook in the replan's parallel form (sogm_corridor_rules_batched_flags, SOGM_RULES_PARALLEL): SOGM_MAX_PIECES one-wave
+// workgroups per problem, each its segment as k_corridor_rules does it, then corridor_slot's second half — corridor_slot
+// with the caller's polytopes where FIRI's would be.  seg_done: [n] zeroes.
+__global__ __launch_bounds__(64) void k_corridor_rules_slots(CorridorRules cr, CorridorWorkspace ws, CorridorIO io, int *seg_done) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int               prob = blockIdx.x / SOGM_MAX_PIECES, seg = blockIdx.x % SOGM_MAX_PIECES;
+  const SogmPlannerParams pp   = cr.pp[prob];
+  rules_segment(cr, pp, ws, io, prob, seg, smem);
   __syncthreads();
-  return true;
+  corridor_slot_done(pp, ws, io, prob, seg, seg < io.points(prob) - 1, smem, seg_done, false);
+}
+// what the parallel hook left set in its ready words and verdict rows (nothing, if its finalising waves cleaned up)
+__global__ void k_pairs_residue(const unsigned *words, int n, unsigned long long *pair_cnt) {
+  unsigned v = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) v |= words[i];
+  if (v) atomicOr(&pair_cnt[3], (unsigned long long)v);
 }
 
 __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerParams pp, CorridorWorkspace ws,
@@ -2126,8 +2235,21 @@ extern "C" int sogm_corridor_rules_batched(sogm_planner *counters_of, const Sogm
                                            double *out_shrunk, int32_t *out_seg_nfaces, int32_t *out_seg_state,
                                            double *out_polys, int32_t *out_nfaces, int32_t *out_npoly,
                                            double *out_goal, void *stream) {
+  return sogm_corridor_rules_batched_flags(counters_of, pp_host, start_pva, route, route_len, route_cap, polys, nfaces, seg_state,
+                                           n, max_faces, out_box, out_shrunk, out_seg_nfaces, out_seg_state, out_polys,
+                                           out_nfaces, out_npoly, out_goal, 0, stream);
+}
+
+extern "C" int sogm_corridor_rules_batched_flags(sogm_planner *counters_of, const SogmPlannerParams *pp_host,
+                                                 const double *start_pva, const double *route, const int32_t *route_len,
+                                                 int route_cap, const double *polys, const int32_t *nfaces,
+                                                 const int32_t *seg_state, int n, int max_faces, double *out_box,
+                                                 double *out_shrunk, int32_t *out_seg_nfaces, int32_t *out_seg_state,
+                                                 double *out_polys, int32_t *out_nfaces, int32_t *out_npoly,
+                                                 double *out_goal, int flags, void *stream) {
   // route_cap > SOGM_MAX_PIECES: the rules read way-points 0 .. SOGM_MAX_PIECES at most, whatever route_len says
-  if (n < 0 || max_faces < 1 || max_faces > RULES_MAX_FACES || route_cap <= SOGM_MAX_PIECES ||
+  if ((flags & ~SOGM_RULES_PARALLEL) || ((flags & SOGM_RULES_PARALLEL) && n > (1 << 20)) ||
+      n < 0 || max_faces < 1 || max_faces > RULES_MAX_FACES || route_cap <= SOGM_MAX_PIECES ||
       (n > 0 && (!pp_host || !start_pva || !route || !route_len || !polys || !nfaces || !out_box || !out_shrunk ||
                  !out_seg_nfaces || !out_seg_state || !out_polys || !out_nfaces || !out_npoly || !out_goal)))
     return SOGM_ERR_INVALID_ARG;
@@ -2139,6 +2261,13 @@ extern "C" int sogm_corridor_rules_batched(sogm_planner *counters_of, const Sogm
   SOGM_HIP_CHECK(hipMallocAsync((void **)&d_pp, sizeof(SogmPlannerParams) * (size_t)n, st));
   hipError_t e = hipMemcpyAsync(d_pp, pp_host, sizeof(SogmPlannerParams) * (size_t)n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // pp_host is the caller's pageable memory
+  // the parallel form's control words, zeroed: seg_done [n] | seg_ready [n] | pair_ok [n][SOGM_MAX_PIECES]
+  int         *d_ctl = nullptr;
+  const size_t n_ctl = (size_t)n + sogm::corridor_pair_words(n);
+  if (e == hipSuccess && (flags & SOGM_RULES_PARALLEL)) {
+    e = hipMallocAsync((void **)&d_ctl, sizeof(int) * n_ctl, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_ctl, 0, sizeof(int) * n_ctl, st);
+  }
   if (e == hipSuccess) {
     sogm::CorridorWorkspace ws{};
     ws.polys      = out_shrunk;
@@ -2149,9 +2278,21 @@ extern "C" int sogm_corridor_rules_batched(sogm_planner *counters_of, const Sogm
                                  .out_polys = out_polys, .out_nfaces = out_nfaces, .out_npoly = out_npoly,
                                  .out_goal = out_goal};
     const sogm::CorridorRules cr{d_pp, polys, nfaces, seg_state, out_box};
-    hipLaunchKernelGGL(sogm::k_corridor_rules, dim3(n), dim3(64), sogm::RulesLds::bytes(), st, cr, ws, io);
+    if (flags & SOGM_RULES_PARALLEL) {
+      ws.seg_ready = reinterpret_cast<unsigned *>(d_ctl + n);
+      ws.pair_ok   = d_ctl + 2 * (size_t)n;
+      ws.pair_cnt  = counters_of ? counters_of->cw.pair_cnt : nullptr;
+      hipLaunchKernelGGL(sogm::k_corridor_rules_slots, dim3(n * SOGM_MAX_PIECES), dim3(64), sogm::RulesLds::bytes(), st, cr, ws,
+                         io, d_ctl);
+      if (ws.pair_cnt)
+        hipLaunchKernelGGL(sogm::k_pairs_residue, dim3(1), dim3(256), 0, st, ws.seg_ready, (int)sogm::corridor_pair_words(n),
+                           ws.pair_cnt);
+    } else {
+      hipLaunchKernelGGL(sogm::k_corridor_rules, dim3(n), dim3(64), sogm::RulesLds::bytes(), st, cr, ws, io);
+    }
     e = hipGetLastError();
   }
+  if (d_ctl) (void)hipFreeAsync(d_ctl, st);
   (void)hipFreeAsync(d_pp, st);
   SOGM_HIP_CHECK(e);
   return SOGM_OK;

@@ -16,8 +16,10 @@ using namespace sogm;
 // control block back to its start values: header / rings / counters 0, every agent's first map item published in agent
 // order, tick_of = first_tick, verdicts 0 (their tags are absolute tick numbers), the flight's log cleared (an agent-tick
 // that does not complete reports ok = 0 and an empty record)
+// pairs: the corridors' ready words and pair verdicts (CorridorWorkspace::seg_ready, one block with pair_ok), which an aborted
+// flight or a drained replan may have left set
 __global__ __launch_bounds__(256) void k_flight_reset(FlightCtl fl, int n_words, int *verdict, long long *acc, int *log_words,
-                                                      long long n_log_words) {
+                                                      long long n_log_words, unsigned *pairs, int n_pairs) {
   const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
   // header, rings, plain queues, tick_done, tick_of, seg_done, stage: one block (FlightBlock::reset_words).  NOT the head / tail words of the urgent
   // queue: its consumers decide "a descriptor is there" by LOADING tail and head (every other hand-over of the flight is a
@@ -30,6 +32,7 @@ __global__ __launch_bounds__(256) void k_flight_reset(FlightCtl fl, int n_words,
   if (i0 == 0) fl.hdr[FL_UW_HEAD] = fl.hdr[FL_UW_TAIL];  // (descriptors an aborted call left behind are skipped)
   for (long long i = i0; i < n_log_words; i += step) log_words[i] = 0;
   for (long long i = i0; i < fl.n_agents; i += step) verdict[i] = 0;
+  for (long long i = i0; i < n_pairs; i += step) pairs[i] = 0u;
   for (long long i = i0; i < 8ll * fl.n_agents; i += step) acc[i] = 0;
   for (long long i = i0; i < 16; i += step) fl.prof[i] = 0ull;
   for (long long i = i0; i < 8 * FL_WG_LOG; i += step) fl.wg_start[i] = 0;
@@ -279,7 +282,7 @@ static int flight_reset_and_seed(sogm_planner *p, const SogmFlight *f, const Fli
   const int       n_words = FlightBlock::reset_words(A);  // (the parked lists: k_flight_seed)
   const long long n_log  = (long long)f->n_ticks * A * (long long)(sizeof(SogmTrajRecord) / sizeof(int));
   hipLaunchKernelGGL(k_flight_reset, dim3(256), dim3(256), 0, main, fl, n_words, p->aw.verdict, p->fl.acc,
-                     reinterpret_cast<int *>(f->log_records), n_log);
+                     reinterpret_cast<int *>(f->log_records), n_log, p->cw.seg_ready, (int)corridor_pair_words(A));
   SOGM_HIP_CHECK(hipGetLastError());
   SOGM_HIP_CHECK(hipMemsetAsync(f->log_ok, 0, sizeof(int32_t) * (size_t)f->n_ticks * A, main));
   hipLaunchKernelGGL(k_flight_seed, dim3((A + 255) / 256), dim3(256), 0, main, fl);

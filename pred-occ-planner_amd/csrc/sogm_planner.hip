@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "sogm_planner.hpp"
 
@@ -135,6 +136,11 @@ static int planner_acquire(sogm_planner *p) {
   // (slots no segment ever ran in are read by sogm_debug_corridor_stats as well: zero, not whatever the allocation held)
   SOGM_HIP_CHECK(p->res.device(&p->cw.seg_dbg, sizeof(long long) * 16 * slots, true));
   SOGM_HIP_CHECK(p->res.device(&p->cw.counters, sizeof(unsigned long long) * SOGM_CNT_N, true));
+  // eager adjacent-pair LPs: ready words and verdict rows in one block (one reset range), their counters, the bookkeeping's stamps
+  SOGM_HIP_CHECK(p->res.device(&p->cw.seg_ready, sizeof(int32_t) * sogm::corridor_pair_words(A), true));
+  p->cw.pair_ok = reinterpret_cast<int32_t *>(p->cw.seg_ready) + A;
+  SOGM_HIP_CHECK(p->res.device(&p->cw.pair_cnt, sizeof(unsigned long long) * 4, true));
+  SOGM_HIP_CHECK(p->res.device(&p->cw.fin_dbg, sizeof(long long) * 4 * (size_t)A, true));
   // QP row storage fallback (rows normally live in LDS)
   p->qw.scratch_stride = qp_scratch_bytes_per_agent(pp->max_faces);
   p->qw.dyn_lds_bytes  = qp_kernel_setup();  // 160 KiB/CU minus the QP kernels' static LDS, granted on this device
@@ -335,6 +341,26 @@ int sogm_debug_corridor_stats(sogm_planner *p, long long *out_host) {
   SOGM_HIP_CHECK(hipMemcpy(out_host, p->cw.seg_dbg,
                            sizeof(long long) * 16 * (size_t)p->map->n_agents * SOGM_MAX_PIECES,
                            hipMemcpyDeviceToHost));
+  return SOGM_OK;
+}
+
+// diagnostics: the adjacent-pair LPs' counters since the last call and what is set in the ready words / verdict rows now
+int sogm_debug_corridor_pairs(sogm_planner *p, unsigned long long *out4) {
+  if (!p || !out4) return SOGM_ERR_INVALID_ARG;
+  SOGM_HIP_CHECK(hipDeviceSynchronize());
+  SOGM_HIP_CHECK(hipMemcpy(out4, p->cw.pair_cnt, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost));
+  SOGM_HIP_CHECK(hipMemset(p->cw.pair_cnt, 0, sizeof(unsigned long long) * 4));
+  std::vector<uint32_t> words(sogm::corridor_pair_words(p->map->n_agents));
+  SOGM_HIP_CHECK(hipMemcpy(words.data(), p->cw.seg_ready, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost));
+  for (const uint32_t w : words) out4[3] |= w;
+  return SOGM_OK;
+}
+// diagnostics (tools/ only): [A][4] wall_clock64 of every agent's last bookkeeping in the dataflow replan or the flight
+// (CorridorWorkspace::fin_dbg: start, adjacent pairs done, goal LPs done, copy done)
+int sogm_debug_corridor_finalize_times(sogm_planner *p, long long *out_host) {
+  if (!p || !out_host) return SOGM_ERR_INVALID_ARG;
+  SOGM_HIP_CHECK(hipDeviceSynchronize());
+  SOGM_HIP_CHECK(hipMemcpy(out_host, p->cw.fin_dbg, sizeof(long long) * 4 * (size_t)p->map->n_agents, hipMemcpyDeviceToHost));
   return SOGM_OK;
 }
 
@@ -575,11 +601,15 @@ int sogm_planner_set_swarm(sogm_planner *p, const SogmTrajRecord *records, int n
 // planner's own words): when everything is back to its start value the generation word gets this replan's number — the
 // search workgroups wait for it in their prologue (no event between the update's last kernel and k_astar on the caller's
 // stream: the record's marker cost 55 us there) and zero their agent's ok / record themselves.
+// pairs: the corridors' ready words and pair verdicts (CorridorWorkspace::seg_ready, one block with pair_ok) — the waves that
+// finalise an agent zero its own, a drained or timed-out tick leaves bits behind.
 __global__ __launch_bounds__(1024) void k_flow_reset(int *hdr, int n_hdr, int *ready, int n_ready, int *verdict,
-                                                     int n_verdict, int *epoch_word, int epoch, int *gen_word, int gen) {
+                                                     int n_verdict, unsigned *pairs, int n_pairs, int *epoch_word, int epoch,
+                                                     int *gen_word, int gen) {
   const int i0 = (int)threadIdx.x, step = (int)blockDim.x;
   for (int i = i0; i < n_hdr; i += step) hdr[i] = 0;
   for (int i = i0; i < n_ready; i += step) ready[i] = -1;
+  for (int i = i0; i < n_pairs; i += step) pairs[i] = 0u;
   if (verdict)
     for (int i = i0; i < n_verdict; i += step) verdict[i] = 0;
   __threadfence();
@@ -647,7 +677,7 @@ static int flow_reset(sogm_planner *p, FlowCall &call) {
   int *gen_word = p->d_flow + fb.gen;
   ++p->reset_epoch;
   hipLaunchKernelGGL(k_flow_reset, dim3(1), dim3(1024), 0, sC, p->d_flow, fb.zero_words(), p->d_flow + fb.fill_first(),
-                     fb.fill_words(), spec ? p->aw.verdict : nullptr, A,
+                     fb.fill_words(), spec ? p->aw.verdict : nullptr, A, p->cw.seg_ready, (int)sogm::corridor_pair_words(A),
                      c->overlap >= 2 && c->clear_gate ? c->clear_epoch_word : nullptr,
                      c->overlap >= 2 && c->clear_gate ? sogm::next_clear_epoch(c) : 0, gen_word, p->reset_epoch);
   SOGM_HIP_CHECK(hipGetLastError());

@@ -31,7 +31,18 @@ struct CorridorWorkspace {
   int32_t *seg_npts;    // [A*P]
   long long *seg_dbg;   // [A*P][16] diagnostics: counts and wall_clock64 ticks (100 MHz) per phase
   unsigned long long *counters;  // [SOGM_CNT_N] cumulative outcome / capacity counters (sogm_planner_counters)
+  // Adjacent-pair LPs run as their segments finish (corridor_slot); all null: every pair LP runs in the bookkeeping.
+  // seg_ready and pair_ok are ONE allocation (pair_ok = seg_ready + A): zero at creation, zeroed by the wave that finalises
+  // the agent, by k_flow_reset per replan and by k_flight_reset per flight (a drained tick leaves bits behind).
+  unsigned *seg_ready;           // [A] bit i: segment i's polytope, seg_nfaces and seg_state are stored and fenced
+  int32_t  *pair_ok;             // [A*P] pair (i, i + 1): 0 not evaluated, 1 the polytopes intersect, 2 they do not
+  unsigned long long *pair_cnt;  // [4] sogm_debug_corridor_pairs: pair LPs run eagerly, run in the bookkeeping behind a verdict
+                                 //     of 0, pairs consumed from a verdict, words the parallel rules hook left set
+  long long *fin_dbg;            // [A][4] wall_clock64 of the agent's last bookkeeping in the dataflow replan or the flight:
+                                 //     start, pair loop done, goal LPs done, copy done (diagnostics, always written)
 };
+// words of the seg_ready + pair_ok allocation
+constexpr size_t corridor_pair_words(int A) { return (size_t)A * (1 + SOGM_MAX_PIECES); }
 
 // The flight (sogm_flight_run): its control block FlightCtl and the hand-overs between its kernels are in sogm_handover.hpp.
 static_assert(SOGM_MAX_PIECES <= WK_MAX_SUB, "a search pushes one corridor descriptor per segment slot, sub = the slot");

@@ -45,11 +45,13 @@ def firi_batched(bd, pc, pc_range, a, b, r=None, iterations=2, epsilon=1.0e-6, m
     return hp, nf, st, r
 
 
-def corridor_rules_batched(pps, start_pva, route, route_len, polys, nfaces, seg_state=None, planner=None):
+def corridor_rules_batched(pps, start_pva, route, route_len, polys, nfaces, seg_state=None, planner=None, parallel=False):
     """The corridor rules around FIRI (box, ShrinkCorridor, validity, intersection and goal scans) for n problems with
     injected polytopes (sogm_corridor_rules_batched).  pps: n SogmPlannerParams with one max_faces; start_pva [n, 9],
     route [n, route_cap, 6], route_len [n] int32, polys [n, 16, max_faces, 4], nfaces [n, 16] int32, seg_state [n, 16]
     int32 or None — device tensors; planner: the SogmPlanner whose capacity counters are raised (or None).
+    parallel: the dataflow replan's form, one wave per segment slot and the adjacent-pair LPs run as the segments finish
+    (sogm_corridor_rules_batched_flags with SOGM_RULES_PARALLEL; the planner's corridor_pairs() counts them).
     Returns a dict of device tensors: box, shrunk, seg_nfaces, seg_state, polys, nfaces, npoly, goal."""
     n, P, MF = int(polys.shape[0]), SOGM_MAX_PIECES, int(polys.shape[2])
     dev = polys.device
@@ -58,12 +60,12 @@ def corridor_rules_batched(pps, start_pva, route, route_len, polys, nfaces, seg_
     i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
     out = {"box": f64(n, P, 6), "shrunk": f64(n, P, MF, 4), "seg_nfaces": i32(n, P), "seg_state": i32(n, P),
            "polys": f64(n, P, MF, 4), "nfaces": i32(n, P), "npoly": i32(n), "goal": f64(n, 6)}
-    check(lib().sogm_corridor_rules_batched(
+    check(lib().sogm_corridor_rules_batched_flags(
         planner._p if planner is not None else None, pp, start_pva.data_ptr(), route.data_ptr(), route_len.data_ptr(),
         int(route.shape[1]), polys.data_ptr(), nfaces.data_ptr(), seg_state.data_ptr() if seg_state is not None else None,
         n, MF, out["box"].data_ptr(), out["shrunk"].data_ptr(), out["seg_nfaces"].data_ptr(), out["seg_state"].data_ptr(),
-        out["polys"].data_ptr(), out["nfaces"].data_ptr(), out["npoly"].data_ptr(), out["goal"].data_ptr(), _stream()),
-        "sogm_corridor_rules_batched")
+        out["polys"].data_ptr(), out["nfaces"].data_ptr(), out["npoly"].data_ptr(), out["goal"].data_ptr(),
+        _abi.RULES_PARALLEL if parallel else 0, _stream()), "sogm_corridor_rules_batched_flags")
     return out
 
 
@@ -114,6 +116,14 @@ class SogmPlanner:
         out = (C.c_int64 * len(_abi.COUNTER_NAMES))()
         check(lib().sogm_planner_counters(self._p, out, 1 if reset else 0), "sogm_planner_counters")
         return dict(zip(_abi.COUNTER_NAMES, [int(v) for v in out]))
+
+    def corridor_pairs(self):
+        """The adjacent-pair LPs of the corridor bookkeeping since the last call (sogm_debug_corridor_pairs): a dict of
+        eager (run by a segment's wave), late (run inside the bookkeeping, no verdict there), consumed (taken from a
+        verdict), residue (OR of every ready word and verdict still set; 0 after complete ticks).  Synchronises."""
+        out = (C.c_uint64 * 4)()
+        check(lib().sogm_debug_corridor_pairs(self._p, out), "sogm_debug_corridor_pairs")
+        return dict(zip(("eager", "late", "consumed", "residue"), [int(v) for v in out]))
 
     # ---- FakeRiskHybridAstar::search + getPathWithVel ----
     def search(self, start_pva, goal, t_start, route_cap=64, trace_cap=0):
