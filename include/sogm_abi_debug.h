@@ -175,6 +175,36 @@ int sogm_corridor_rules_batched_flags(sogm_planner *counters_of, const SogmPlann
  * Synchronises the device. */
 int sogm_debug_corridor_pairs(sogm_planner *p, unsigned long long *out4);
 
+/* Diagnostics: every agent's last QP solve as its workgroup clocked it, host out[n_agents][SOGM_QP_STAT_N].  Times are
+ * ticks of the device's 100 MHz wall clock unless said otherwise.  Synchronises the device. */
+enum {
+  SOGM_QP_STAT_TOTAL = 0,      /* the whole solve */
+  SOGM_QP_STAT_SETUP = 1,      /* assembly, scaling, first factorisation */
+  SOGM_QP_STAT_REFAC = 2,      /* later refactorisations ... */
+  SOGM_QP_STAT_N_REFAC = 3,    /* ... and their count */
+  SOGM_QP_STAT_CHECK = 4,      /* termination checks: residual passes, tests, certificates ... */
+  SOGM_QP_STAT_N_CHECK = 5,    /* ... and their count */
+  SOGM_QP_STAT_ITERS = 6,      /* iterations run */
+  SOGM_QP_STAT_PATH = 7,       /* bit 0: register-resident iteration, bit 1: every row array in LDS (sogm_debug_qp_layout) */
+  SOGM_QP_STAT_FACTOR_ASM = 8, /* the factorisations, summed: block assembly | forward sweep | backward rows + K^-1 registers */
+  SOGM_QP_STAT_FACTOR_FWD = 9,
+  SOGM_QP_STAT_FACTOR_BWD = 10,
+  SOGM_QP_STAT_SHADER_CLOCKS = 11, /* the span of slot 0 in shader clocks */
+  SOGM_QP_STAT_CHECK_STAGE = 12,   /* of slot 4: staging the row state for the check | the residual pass */
+  SOGM_QP_STAT_CHECK_RESID = 13,
+  SOGM_QP_STAT_SETUP_SPLIT = 14, /* three 20-bit fields of ticks since the start: assembly + CSC done | Ruiz scaling done |
+                                    rho + K1 done (slot 1 minus the third: the first factorisation and the load of the row state) */
+  SOGM_QP_STAT_N = 16
+};
+int sogm_debug_qp_stats(sogm_planner *p, long long *out_host);
+/* What the QP kernels are expected to do with a problem of n_pieces polytopes with nfaces_host[n_pieces] faces: the host's
+ * description of their memory plan (csrc/sogm_qp_layout.hpp, which also sizes the planner's QP scratch) evaluated with the
+ * dynamic LDS this planner was granted.  The kernels compute their plan themselves, from the same constants and byte
+ * totals; tests/test_qp_gpu.py holds the path they report (SOGM_QP_STAT_PATH) to this one.  host out8: {register-resident iteration, every row array in LDS (the two bits of
+ * SOGM_QP_STAT_PATH), dynamic LDS granted, dynamic LDS used, bytes of the agent's HBM scratch used, K1 in LDS,
+ * general rows, safety rows}.  No GPU work. */
+int sogm_debug_qp_layout(sogm_planner *p, int n_pieces, const int32_t *nfaces_host, long long *out8);
+
 #ifdef __cplusplus
 }
 #endif

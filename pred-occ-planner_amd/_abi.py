@@ -174,6 +174,11 @@ _vp = C.c_void_p
 _i = C.c_int
 
 # name -> (restype, argtypes); every symbol include/sogm_abi.h declares
+# slots of the per-agent record of sogm_debug_qp_stats (the enum SOGM_QP_STAT_* of sogm_abi_debug.h)
+QP_STAT_TOTAL, QP_STAT_SETUP, QP_STAT_REFAC, QP_STAT_N_REFAC, QP_STAT_CHECK, QP_STAT_N_CHECK, QP_STAT_ITERS, QP_STAT_PATH = range(8)
+QP_STAT_FACTOR_ASM, QP_STAT_FACTOR_FWD, QP_STAT_FACTOR_BWD, QP_STAT_SHADER_CLOCKS = 8, 9, 10, 11
+QP_STAT_CHECK_STAGE, QP_STAT_CHECK_RESID, QP_STAT_SETUP_SPLIT, QP_STAT_N = 12, 13, 14, 16
+
 PROTOTYPES = {
     "sogm_abi_version": (_i, []),
     "sogm_last_error": (C.c_char_p, []),
@@ -232,6 +237,8 @@ PROTOTYPES = {
     "sogm_corridor_rules_batched_flags": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _i, _vp]),
     "sogm_debug_corridor_pairs": (_i, [_vp, _vp]),
+    "sogm_debug_qp_stats": (_i, [_vp, _vp]),  # [A][QP_STAT_N] int64
+    "sogm_debug_qp_layout": (_i, [_vp, _i, _vp, _vp]),
     "sogm_replan": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_create": (_i, [C.POINTER(SogmGridMapParams), _i, _i, C.POINTER(_vp)]),
     "sogm_gridmap_destroy": (None, [_vp]),

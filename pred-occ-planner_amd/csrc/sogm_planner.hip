@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "sogm_planner.hpp"
+#include "sogm_qp_layout.hpp"
 
 using namespace sogm;
 
@@ -146,7 +147,7 @@ static int planner_acquire(sogm_planner *p) {
   p->qw.dyn_lds_bytes  = qp_kernel_setup();  // 160 KiB/CU minus the QP kernels' static LDS, granted on this device
   SOGM_HIP_CHECK(p->res.device(&p->qw.scratch, p->qw.scratch_stride * (size_t)A));
   SOGM_HIP_CHECK(p->res.device(&p->qw.k1_scratch, qp_k1_scratch_bytes_per_agent() * (size_t)A));
-  SOGM_HIP_CHECK(p->res.device(&p->qw.dbg, sizeof(long long) * 16 * (size_t)A, true));
+  SOGM_HIP_CHECK(p->res.device(&p->qw.dbg, sizeof(long long) * SOGM_QP_STAT_N * (size_t)A, true));
   SOGM_HIP_CHECK(p->res.device(&p->d_polys, sizeof(double) * slots * pp->max_faces * 4));
   SOGM_HIP_CHECK(p->res.device(&p->d_goal, sizeof(double) * 6 * A));
   SOGM_HIP_CHECK(p->res.device(&p->d_cpts, sizeof(double) * slots * 15));
@@ -326,11 +327,26 @@ int sogm_debug_astar_nodes(sogm_planner *p, int agent, void *out_host, int n) {
   return SOGM_OK;
 }
 
-// diagnostics (tools/ only): per-agent clock split of the last QP solve (QpWorkspace::dbg), [A][16]
+// diagnostics: per-agent clock split of the last QP solve (QpWorkspace::dbg), [A][SOGM_QP_STAT_N]
 int sogm_debug_qp_stats(sogm_planner *p, long long *out_host) {
   if (!p || !out_host) return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipDeviceSynchronize());
-  SOGM_HIP_CHECK(hipMemcpy(out_host, p->qw.dbg, sizeof(long long) * 16 * (size_t)p->map->n_agents, hipMemcpyDeviceToHost));
+  SOGM_HIP_CHECK(hipMemcpy(out_host, p->qw.dbg, sizeof(long long) * SOGM_QP_STAT_N * (size_t)p->map->n_agents,
+                           hipMemcpyDeviceToHost));
+  return SOGM_OK;
+}
+// diagnostics: the QP kernels' memory plan for one problem as the host's description (sogm_qp_layout.hpp) gives it; no GPU work
+int sogm_debug_qp_layout(sogm_planner *p, int n_pieces, const int32_t *nfaces_host, long long *out8) {
+  if (!p || !nfaces_host || !out8 || n_pieces < 1 || n_pieces > SOGM_MAX_PIECES) return SOGM_ERR_INVALID_ARG;
+  int faces = 0;
+  for (int i = 0; i < n_pieces; ++i) {
+    if (nfaces_host[i] < 0 || nfaces_host[i] > p->pp.max_faces) return SOGM_ERR_INVALID_ARG;
+    faces += nfaces_host[i];
+  }
+  const sogm::QpLayout L(sogm::QpShape(n_pieces, faces), (size_t)p->qw.dyn_lds_bytes);
+  const long long      out[8] = {L.fast, L.rows_in_lds, p->qw.dyn_lds_bytes, (long long)L.lds_bytes(), (long long)L.scratch_bytes(),
+                                 L.fast && L.rows_in_lds, L.sh.G, L.sh.S};
+  std::memcpy(out8, out, sizeof(out));
   return SOGM_OK;
 }
 

@@ -242,7 +242,8 @@ hipError_t launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, c
                                 const FlowCtl &fc, int n_agents, int n_workgroups, const CorridorIO &io, hipStream_t st);
 hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st);
 
-// Per-agent QP row storage in HBM, used only when a problem's rows do not fit in LDS.
+// Per-agent QP row storage in HBM, used only when a problem's rows do not fit in LDS (what lives where: sogm_qp_layout.hpp,
+// which also sizes both buffers: qp_scratch_bytes_per_agent(max_faces), qp_k1_scratch_bytes_per_agent()).
 struct QpWorkspace {
   char  *scratch;         // [A][scratch_stride]
   size_t scratch_stride;  // bytes per agent (rows at M = SOGM_MAX_PIECES, max_faces faces)
@@ -253,14 +254,11 @@ struct QpWorkspace {
   // final acceleration 0 — what replan() asks for (baseline.cpp:411,423).
   const double *t_alloc;
   int           goal_stride;
-  // diagnostics (tools/): [A][16] wall_clock64 ticks (100 MHz) of the agent's last solve — 0 total, 1 set-up (assembly,
-  // scaling, first factorisation), 2 later refactorisations, 3 their count, 4 checks (residual passes + certificates),
-  // 5 their count, 6 iterations run, 8-10 the three phases of factor() summed over all factorisations; always written (a handful of clock reads per 25 iterations)
+  // diagnostics (tools/): [A][SOGM_QP_STAT_N] the clocks of the agent's last solve, slots SOGM_QP_STAT_* (sogm_abi_debug.h);
+  // always written (a handful of clock reads per 25 iterations)
   long long    *dbg;
   int           ablate;  // phase ablation mask of the staged k_qp launch (profiling builds only; tuning key qp_ablate)
 };
-size_t qp_scratch_bytes_per_agent(int max_faces);
-size_t qp_k1_scratch_bytes_per_agent();
 // Lets the three QP kernels use the CU's LDS beyond the default limit on the current device and returns the dynamic
 // LDS a workgroup of them may ask for (QpWorkspace::dyn_lds_bytes): once per planner, before its first launch.
 int    qp_kernel_setup();

@@ -38,17 +38,16 @@
 
 #include "../../include/sogm_detmath.h"
 #include "sogm_planner.hpp"
+#include "sogm_qp_layout.hpp"
 
 #include <type_traits>
 
 namespace sogm {
 namespace {
 
-#define QP_BW 17  // half bandwidth of K
 #define QP_NMAX (15 * SOGM_MAX_PIECES)
-#define QP_ELL 6
 #define QP_NT 512  // lanes per workgroup (8 waves: two per SIMD)
-#define QP_K1_DOUBLES (120 * (QP_BW + 1))  // K1 band of a register-resident problem (M <= 8)
+#define QP_K1_DOUBLES (15 * QP_FAST_MAX_PIECES * (QP_BW + 1))  // K1 band of the largest register-resident problem
 
 __device__ const double OSQP_INFTY  = 1e30;
 __device__ const double MIN_SCALING = 1e-04, MAX_SCALING = 1e+04;
@@ -123,28 +122,17 @@ __device__ inline double block_max(double v, double *s_red) {
               dmax(dmax(s_red[4], s_red[5]), dmax(s_red[6], s_red[7])));
 }
 
-// Row storage (LDS or HBM scratch).  The "hot" arrays are the only row data the register-resident ADMM
-// iteration touches; they always live in LDS on that path, the "cold" rest may sit in HBM scratch.
-struct Rows {
-  // general rows [0, G)
-  double *gval;  // [G][6]
-  double *gl, *gu, *grho, *gE, *gz, *gy, *gdy;
-  double *grinv;  // [G] 1 / rho (OSQP rho_inv_vec)
-  double *gw;     // [G] rho z - y                                                    (hot)
-  int    *gcol;  // [G][6]
-  int    *cidx;  // CSC entries over general rows: row * 8 + slot, row-sorted inside a column
-  // safety rows [0, S):  s = off_i + 5 * face + k ; columns i*15 + k*3 + {0,1,2}
-  double *sval;  // [S][3]                                                             (hot)
-  double *su, *sE, *sz, *sy, *sdy;
-  double *sw;   // [S] rho z - y (refreshed by the row update, consumed by the next A^T product)   (hot)
-  int    *sc0;  // [S] first column of the row's control point
-};
-
-__host__ __device__ inline size_t rows_hot_bytes(int G, int S) { return ((size_t)S * 4 + G) * 8; }
-__host__ __device__ inline size_t rows_cold_bytes(int G, int S) {
-  return (size_t)G * (QP_ELL * 8 + 8 * 8 + QP_ELL * 4 + QP_ELL * 4) + (size_t)S * (5 * 8 + 4) + 64;
-}
-__host__ __device__ inline size_t rows_bytes(int G, int S) { return rows_hot_bytes(G, S) + rows_cold_bytes(G, S); }
+// Row storage (LDS or HBM scratch): struct Rows, what "hot" means and the byte totals (rows_hot_bytes, rows_cold_bytes,
+// rows_bytes) come from the table in sogm_qp_layout.hpp.  carve_rows below still walks the arrays by hand, in the table's
+// order, and qp_solve_agent's prologue still computes QpLayout's offsets itself: with carve_rows generated from the table, or
+// with R1 .. G taken from QpShape, or with the pointers taken from QpLayout, the device code of the whole solve changed
+// (register allocation moves with the prologue's integer arithmetic) and every form timed ran 0.05 to 0.3 ms per tick
+// slower (profiles/EXPERIMENTS.md).  The walk is held to the table's totals here, the path a solve reports to QpLayout's
+// by tests/test_qp_gpu.py.
+static_assert(row_bytes('S', true) == (3 + 1) * sizeof(double) && row_bytes('G', true) == sizeof(double), "carve_rows: hot arrays");
+static_assert(row_bytes('G', false) == (QP_ELL + 8) * sizeof(double) + 2 * QP_ELL * sizeof(int) &&
+                  row_bytes('S', false) == 5 * sizeof(double) + sizeof(int),
+              "carve_rows: cold arrays");
 __device__ inline void carve_rows(Rows &R, char *hot, char *cold, int G, int S) {
   double *h = (double *)hot;
   R.sval = h;  h += (size_t)S * 3;
@@ -172,14 +160,7 @@ __device__ inline void carve_rows(Rows &R, char *hot, char *cold, int G, int S) 
 }
 
 // value of the lane selected by a DPP quad permute (0xB1: lane ^ 1, 0x4E: lane ^ 2)
-template <int CTRL>
-__device__ inline double dpp_quad_t(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo     = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  hi     = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-#define dpp_quad(v, ctrl) dpp_quad_t<ctrl>(v)
+#define dpp_quad(v, ctrl) dpp_ctrl_t<ctrl>(v)
 
 // Opaque copy of a lane index: addresses derived from it inside a loop are recomputed there (one VALU add)
 // instead of being hoisted into dozens of long-lived address registers that spill to scratch.
@@ -191,13 +172,6 @@ __device__ inline int launder(int v) {
 __device__ inline double &KB(double *Kb, int i, int j) { return Kb[i * (QP_BW + 1) + (i - j)]; }
 
 }  // namespace
-
-size_t qp_k1_scratch_bytes_per_agent() { return (size_t)QP_K1_DOUBLES * sizeof(double); }
-size_t qp_scratch_bytes_per_agent(int max_faces) {
-  const int G = 9 * (SOGM_MAX_PIECES + 1) + 21 * SOGM_MAX_PIECES;
-  const int S = 5 * max_faces * SOGM_MAX_PIECES;
-  return (rows_bytes(G, S) + 255) & ~(size_t)255;
-}
 
 // One agent's QP, executed by the whole workgroup (QP_NT lanes); called by k_qp (one workgroup per agent) and by
 // the dataflow kernel k_qp_flow (a workgroup solves agents one after the other as their corridors become final).
@@ -227,13 +201,8 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
   const int n  = 15 * M;
 
   extern __shared__ __attribute__((aligned(16))) char qp_smem[];
-  // Dynamic LDS, general path: s_Kb [n][18] K band / Cholesky factor | s_P [M][225] scaled cost blocks | rows.
-  // Register-resident path (M <= 8): K is block tridiagonal in 15 x 15 piece blocks (the profile of the continuity
-  // rows) and its inverse is built block by block (factor()):
-  //   s_P [M][225] | s_Dv [M][225] diagonal blocks of K, then inv(D_i) | s_V [M][225] K(i, i-1), then V_i |
-  //   s_Z [M][225] one block row of K^-1 | hot rows | cold rows | K1 [n][18] the band of A^T diag(rho / rho_cur) A
-  //   (the cold rows and K1 sit in LDS when everything fits, in the agent's HBM scratch otherwise)
-  const bool use_blocks = M <= 8;
+  // Dynamic LDS: the plan is QpLayout (sogm_qp_layout.hpp), restated by the predicates and pointers below
+  const bool use_blocks = M <= QP_FAST_MAX_PIECES;
   __shared__ double s_ginv[QP_NMAX];
   __shared__ __attribute__((aligned(16))) double s_xt[QP_NMAX];
   __shared__ double s_x[QP_NMAX], s_D[QP_NMAX], s_Dt[QP_NMAX];
@@ -266,8 +235,10 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
   const size_t head1 = ((size_t)n * (QP_BW + 1) + (size_t)M * 225) * sizeof(double);
   const size_t head4 = (size_t)M * 225 * 4 * sizeof(double);
   const size_t k1_bytes = (size_t)n * (QP_BW + 1) * sizeof(double);
-  // (the check of the register-resident path stages y through factor()'s block area: it must hold one double per row and 320 partial results)
-  const bool   fast  = use_blocks && G <= 256 && S <= 1024 && (size_t)(G + S) + 320 <= (size_t)M * 675 &&
+  // (the check of the register-resident path stages y through factor()'s block area Dv | V | Z: it must hold one double per
+  //  row and the QP_CHECK_RED partial results)
+  const bool   fast  = use_blocks && G <= QP_FAST_MAX_G && S <= QP_FAST_MAX_S &&
+                    (size_t)(G + S) + QP_CHECK_RED <= (size_t)M * (225 * 3) &&
                     head4 + rows_hot_bytes(G, S) <= (size_t)ws.dyn_lds_bytes;
   const size_t head        = fast ? head4 : head1;
   const size_t rows_al     = (rows_bytes(G, S) + 15) & ~(size_t)15;
@@ -1746,24 +1717,22 @@ __device__ __forceinline__ void qp_solve_agent(const SogmPlannerParams &pp, cons
     io.out_status[agent] = status;
     io.out_iters[agent]  = iter;
     if (ws.dbg) {
-      long long *o = ws.dbg + (size_t)agent * 16;
-      o[8]  = dbg_f1;  // factor(): block assembly | forward sweep | backward rows + K^-1 registers (all factorisations)
-      o[9]  = dbg_f2;
-      o[10] = dbg_f3;
-      o[11] = clock64() - dbg_clk0;
-      o[12] = dbg_k1;  // checks: the spill of the row state | the residual pass (the rest of o[4]: tests, certificate)
-      o[13] = dbg_k2;  // shader clocks of the whole solve (o[0]: the same span in 10 ns ticks)
-      o[0] = wall_clock64() - dbg_t0;
-      // set-up split, three 20-bit fields of 10 ns ticks since the start: assembly + CSC done | Ruiz scaling done | rho + K1 done
-      // (o[1] - the third: the first factorisation and the load of the row state)
-      o[14] = dbg_s1 | (dbg_s2 << 20) | (dbg_s3 << 40);
-      o[1] = dbg_setup;
-      o[2] = dbg_refac;
-      o[3] = dbg_nrefac;
-      o[4] = dbg_check;
-      o[5] = dbg_ncheck;
-      o[6] = iter;
-      o[7] = (FAST ? 1 : 0) | (rows_in_lds ? 2 : 0);  // bit 0: register-resident iteration, bit 1: every row array in LDS
+      long long *o = ws.dbg + (size_t)agent * SOGM_QP_STAT_N;  // (slots: sogm_abi_debug.h)
+      o[SOGM_QP_STAT_FACTOR_ASM]    = dbg_f1;
+      o[SOGM_QP_STAT_FACTOR_FWD]    = dbg_f2;
+      o[SOGM_QP_STAT_FACTOR_BWD]    = dbg_f3;
+      o[SOGM_QP_STAT_SHADER_CLOCKS] = clock64() - dbg_clk0;
+      o[SOGM_QP_STAT_CHECK_STAGE]   = dbg_k1;
+      o[SOGM_QP_STAT_CHECK_RESID]   = dbg_k2;
+      o[SOGM_QP_STAT_TOTAL]         = wall_clock64() - dbg_t0;
+      o[SOGM_QP_STAT_SETUP_SPLIT]   = dbg_s1 | (dbg_s2 << 20) | (dbg_s3 << 40);
+      o[SOGM_QP_STAT_SETUP]         = dbg_setup;
+      o[SOGM_QP_STAT_REFAC]         = dbg_refac;
+      o[SOGM_QP_STAT_N_REFAC]       = dbg_nrefac;
+      o[SOGM_QP_STAT_CHECK]         = dbg_check;
+      o[SOGM_QP_STAT_N_CHECK]       = dbg_ncheck;
+      o[SOGM_QP_STAT_ITERS]         = iter;
+      o[SOGM_QP_STAT_PATH]          = (FAST ? 1 : 0) | (rows_in_lds ? 2 : 0);
     }
   }
 #undef gv

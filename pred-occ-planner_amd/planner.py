@@ -125,6 +125,24 @@ class SogmPlanner:
         check(lib().sogm_debug_corridor_pairs(self._p, out), "sogm_debug_corridor_pairs")
         return dict(zip(("eager", "late", "consumed", "residue"), [int(v) for v in out]))
 
+    def qp_stats(self):
+        """Every agent's last QP solve as its workgroup clocked it (sogm_debug_qp_stats): int64 [A][_abi.QP_STAT_N],
+        slots _abi.QP_STAT_* — QP_STAT_PATH: bit 0 the register-resident iteration, bit 1 every row array in LDS;
+        QP_STAT_ITERS: the iterations run.  Synchronises."""
+        out = np.zeros((self.A, _abi.QP_STAT_N), np.int64)
+        check(lib().sogm_debug_qp_stats(self._p, out.ctypes.data_as(C.c_void_p)), "sogm_debug_qp_stats")
+        return out
+
+    def qp_layout(self, nfaces):
+        """What the QP kernels are expected to do with a problem of len(nfaces) pieces with these face counts
+        (sogm_debug_qp_layout: the host's description of their memory plan, no GPU work; the kernels compute theirs
+        themselves and report the path they took in qp_stats()), as a dict."""
+        nf = np.ascontiguousarray(nfaces, dtype=np.int32)
+        out = (C.c_longlong * 8)()
+        check(lib().sogm_debug_qp_layout(self._p, len(nf), nf.ctypes.data_as(C.c_void_p), out), "sogm_debug_qp_layout")
+        keys = ("fast", "rows_in_lds", "dyn_lds_bytes", "lds_bytes", "scratch_bytes", "k1_in_lds", "G", "S")
+        return dict(zip(keys, [int(v) for v in out]))
+
     # ---- FakeRiskHybridAstar::search + getPathWithVel ----
     def search(self, start_pva, goal, t_start, route_cap=64, trace_cap=0):
         A, dev = self.A, start_pva.device

@@ -106,13 +106,22 @@ def _box_chain(M, nf, max_faces, rng, tau_len=0.3):
     return polys, nfaces
 
 
-# (pieces, faces per polytope): 12 x 6 -> general path (no block factor), rows in LDS;
-# 8 x 30 -> S = 1200 rows: general path, row storage in HBM scratch;
-# 8 x 25 -> S = 1000: register-resident iteration with the cold row data in HBM scratch;
-# 5 x 40 -> S = 1000 with few pieces; 3 x 6 -> the common small case; 16 x 6 -> the most pieces the ABI takes (n = 240: the
-# set-up's column quads take two trips)
-@pytest.mark.parametrize("M,nf", [(12, 6), (8, 30), (8, 25), (5, 40), (3, 6), (16, 6)])
-def test_qp_solver_paths_match_oracle(pop, orc, M, nf):
+# (pieces, faces per polytope) and the path the solver must take for it, (register-resident iteration, every row array in
+# LDS) — what the layout description (csrc/sogm_qp_layout.hpp; on the host: tests/qp_layout_host_test.cpp) gives for the
+# shape at the dynamic LDS a planner is granted.  All four combinations occur:
+QP_PATH_SHAPES = [
+    (12, 6, (0, 1)),   # general iteration (no block factor), rows in LDS
+    (8, 30, (0, 0)),   # S = 1200 rows: general iteration, row storage in HBM scratch
+    (8, 25, (1, 0)),   # S = 1000: register-resident iteration with the cold row data in HBM scratch
+    (5, 40, (1, 0)),   # S = 1000 with few pieces: 149 584 bytes with everything in LDS, just beyond the grant
+    (3, 6, (1, 1)),    # the common small case
+    (16, 6, (0, 0)),   # the most pieces the ABI takes (n = 240: the set-up's column quads take two trips)
+]
+assert {p for _, _, p in QP_PATH_SHAPES} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+
+
+@pytest.mark.parametrize("M,nf,path", QP_PATH_SHAPES, ids=[f"{M}-{nf}" for M, nf, _ in QP_PATH_SHAPES])
+def test_qp_solver_paths_match_oracle(pop, orc, M, nf, path):
     import torch
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     planner = importlib.import_module("pred-occ-planner_amd.planner")
@@ -146,6 +155,16 @@ def test_qp_solver_paths_match_oracle(pop, orc, M, nf):
             assert np.allclose(got, x, atol=TOL, rtol=0), f"agent {a}: max diff {np.abs(got - x).max()}"
     print(f"M={M} faces={nf}: statuses {qn['status'].tolist()} iters {qn['iters'].tolist()} max diff {worst:.2e}")
     assert (qn["status"] == 1).any(), "the synthetic corridors are meant to be solvable"
+    # every agent's workgroup took the named path, which is also what the layout predicts for its (M, nfaces)
+    stats = P.qp_stats()
+    for a in range(A):
+        lay = P.qp_layout(nfaces[a, :M])
+        # the record is this solve's (a record nobody wrote would read path 0, which two of the shapes expect)
+        assert stats[a, pop._abi.QP_STAT_ITERS] == qn["iters"][a] > 0 and stats[a, pop._abi.QP_STAT_TOTAL] > 0, (a, stats[a])
+        took = int(stats[a, pop._abi.QP_STAT_PATH])
+        print(f"  agent {a}: path {took} layout {lay}")
+        assert (lay["fast"], lay["rows_in_lds"]) == path, (a, lay)
+        assert took == lay["fast"] | lay["rows_in_lds"] << 1, (a, took, lay)
     P.close()
     m.close()
 
