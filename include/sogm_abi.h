@@ -481,6 +481,71 @@ int sogm_gridmap_update(sogm_gridmap *g, const uint16_t *depth, const double *ca
 int sogm_gridmap_query_inflate(sogm_gridmap *g, const int32_t *agent_idx, const double *pos, int n,
                                int8_t *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* depth camera: the frames the two front ends above see of a SogmWorld                          */
+/*   The reference took them from its uav_simulator submodule, an empty directory in its tree:   */
+/*   this camera is the build's OWN (SURVEY section 8 d), as the intrinsics of the GridMap       */
+/*   parameters are.  There is nothing to be in parity with; what is held is the definition      */
+/*   below, by two independent implementations (csrc/sogm_depth.hip and the numpy restatement    */
+/*   tests/depth_render_reference.py), bit for bit.                                              */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Camera: pin-hole, x right, y down, z forward.  cam_rot is the row-major camera-to-world rotation R
+ * (scene.camera_pose; the same array sogm_gridmap_update takes), cam_pos the camera centre p.
+ * Obstacles: the SogmCylinder records of a SogmWorld, "of the same instant" — vx, vy are not used.  Geometry as the
+ * flight audit's: type 3 is a vertical cylinder of diameter w with its axis at (x, y), z extent [z - h/2, z + h/2],
+ * closed by two discs.  Optionally a ground plane z = ground_z.  Records of any other type (rings, type 2) are not
+ * rendered: they are counted per agent (out_unsupported) and the image is what it would be without them.
+ *
+ * All arithmetic is fp64, in exactly this order, without contraction (the library is built with -ffp-contract=off).
+ * Pixel (row v, column u) of agent a:
+ *
+ *   xc = (u - cx) / fx;  yc = (v - cy) / fy
+ *   d_i = (R[i][0]*xc + R[i][1]*yc) + R[i][2]     i = 0, 1, 2
+ *         (z-depth parametrisation: the point p + t d has camera z = t)
+ *
+ *   per type-3 cylinder:  r = 0.5*w;  z0 = z - 0.5*h;  z1 = z + 0.5*h;  ox = p.x - x;  oy = p.y - y
+ *     side:  a = d0*d0 + d1*d1;  if a > 0:  b = ox*d0 + oy*d1;  c = (ox*ox + oy*oy) - r*r;  disc = b*b - a*c
+ *            if disc >= 0:  s = sqrt(disc);  t = (-b - s)/a  and  t = (-b + s)/a,
+ *            each accepted if t > 0 and z0 <= p.z + t*d2 <= z1
+ *     caps:  if d2 != 0, for zp in (z0, z1):  t = (zp - p.z)/d2;  qx = ox + t*d0;  qy = oy + t*d1;
+ *            accepted if t > 0 and qx*qx + qy*qy <= r*r
+ *   ground:  if use_ground and d2 != 0:  t = (ground_z - p.z)/d2, accepted if t > 0
+ *
+ *   t*  = the smallest accepted t (a camera inside a cylinder sees its inner wall)
+ *   d16 = (uint16) floor(t* * depth_scale + 0.5)  if t* exists and t* <= max_depth, else 0      (0 = no return)
+ *   cloud point (camera frame: GridMap::projectDepthImage's back-projection of this image, grid_map.cpp:231-235):
+ *     zq = d16 / depth_scale;  ( (float)((u - cx)*zq/fx), (float)((v - cy)*zq/fy), (float)zq );
+ *     d16 == 0 -> three quiet NaNs (sogm_filter_point_cloud skips non-finite points: every agent hands over exactly
+ *     rows*cols points, raw_range[a] = {a*rows*cols, (a+1)*rows*cols}, no compaction)
+ *
+ * The result is a minimum over the cylinders: it depends neither on their order nor on any culling of cylinders
+ * that cannot be hit within max_depth.
+ */
+typedef struct SogmDepthCamera {
+  double  fx, fy, cx, cy;
+  double  max_depth;     /* metres along the optical axis */
+  double  depth_scale;   /* k_depth_scaling_factor, 1000 */
+  double  ground_z;
+  int32_t rows, cols;
+  int32_t use_ground;
+  int32_t reserved_;
+} SogmDepthCamera;       /* 72 bytes */
+/*
+ * Renders every agent's frame of `world` (only cylinders / n_cyl are read).  Context-free like sogm_traj_eval: the
+ * current device, stream-ordered, no allocation, no host synchronisation.
+ * dev cam_pos [n*3] fp64, dev cam_rot [n*9] fp64, dev out_depth [n*rows*cols] uint16 (what sogm_gridmap_update takes),
+ * dev out_cloud_xyz [n*rows*cols*3] fp32 or NULL (what sogm_filter_point_cloud takes as raw_xyz),
+ * dev out_unsupported [n] int32: obstacles of a type other than 3.
+ * SOGM_ERR_INVALID_ARG (checked first, as in sogm_create): rows, cols or n_agents < 1, n_cyl < 0, fx, fy, max_depth or
+ * depth_scale not positive, max_depth*depth_scale > 65535, intrinsics that are not finite, a null required pointer, an
+ * image of more than 2^31 - 1 pixels.  SOGM_ERR_NO_DEVICE without a GPU.
+ */
+int sogm_render_depth(const SogmWorld *world, const SogmDepthCamera *cam, int n_agents,
+                      const double *cam_pos /* dev [n*3] */, const double *cam_rot /* dev [n*9] */,
+                      uint16_t *out_depth /* dev [n*rows*cols] */, float *out_cloud_xyz /* dev [n*rows*cols*3] or NULL */,
+                      int32_t *out_unsupported /* dev [n]: obstacles of a type other than 3 */, void *stream);
+
 /*
  * Tick glue of a batched planner service, each ONE launch (the FSM bookkeeping around replan()):
  * sogm_tick_inputs — the replan start state of every agent: its executing trajectory own_records[a] sampled at

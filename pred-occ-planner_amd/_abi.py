@@ -66,6 +66,12 @@ class SogmGridMapParams(C.Structure):
                 ("local_map_margin", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
+class SogmDepthCamera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("max_depth", C.c_double), ("depth_scale", C.c_double), ("ground_z", C.c_double),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("use_ground", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class SogmCylinder(C.Structure):
     _fields_ = [("type", C.c_int32), ("_pad", C.c_int32)] + [
         (k, C.c_double) for k in ("x", "y", "z", "w", "h", "vx", "vy", "qw", "qx", "qy", "qz")]
@@ -169,6 +175,7 @@ FLIGHT_HDR_ERR, FLIGHT_HDR_FINISHED, FLIGHT_HDR_LATE_WGS = 4, 5, 15  # sogm_flig
 FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "chain", "ticks")
 TRAJ_RECORD_BYTES = C.sizeof(SogmTrajRecord)  # 2064
 CYLINDER_BYTES = C.sizeof(SogmCylinder)  # 96
+DEPTH_CAMERA_BYTES = C.sizeof(SogmDepthCamera)  # 72
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -244,6 +251,7 @@ PROTOTYPES = {
     "sogm_gridmap_destroy": (None, [_vp]),
     "sogm_gridmap_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_query_inflate": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "sogm_render_depth": (_i, [C.POINTER(SogmWorld), C.POINTER(SogmDepthCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_download": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_force_frame": (_i, [_vp, _i]),
     "sogm_traj_safe": (_i, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

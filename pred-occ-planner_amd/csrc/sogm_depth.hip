@@ -1,0 +1,302 @@
+// Depth camera (include/sogm_abi.h "depth camera"): every agent's depth image and camera-frame cloud of a SogmWorld's
+// cylinders (+ ground plane), rendered where sogm_gridmap_update and sogm_filter_point_cloud read them.  One launch:
+//   k_render_depth  a workgroup of 256 lanes owns 256 groups of 8 consecutive pixels of one agent (a band of rows).  It
+//                   first culls the world's cylinders against the camera's range — 256 per trip, one per lane, survivors
+//                   compacted into an LDS list with 64-wide ballots; a list that would overflow is rendered and emptied
+//                   first, so no cylinder is ever dropped — then every lane walks the list for its 8 pixels and keeps the
+//                   smallest accepted t of each, and stores 16 B of depth and 6 x 16 B of cloud (scalar stores for row
+//                   tails and for pieces that are not 16-byte aligned).
+// The header's arithmetic is evaluated as written (fp64, -ffp-contract=off).  What is NOT evaluated is skipped only where
+// the header's own expressions cannot yield an accepted t <= max_depth; each skip says why next to it.
+#include "sogm_device.hpp"
+
+#include <cmath>
+#include <cstdio>
+
+namespace sogm {
+namespace {
+
+constexpr int DEPTH_WG  = 256;  // lanes per workgroup = cylinders culled per trip
+constexpr int DEPTH_PX  = 8;    // consecutive pixels of a row per lane
+constexpr int DEPTH_CAP = 256;  // candidates in LDS; >= DEPTH_WG so that one trip's survivors always fit an empty list
+
+// what a pixel needs of one (camera, cylinder) pair: the header's ox, oy, c = (ox*ox + oy*oy) - r*r, r*r, z0, z1
+struct DepthCand {
+  double ox, oy, c, rr, z0, z1;
+};
+
+struct DepthArgs {
+  SogmDepthCamera     cam;
+  const SogmCylinder *cyl;
+  const double       *pos, *rot;
+  uint16_t           *depth;
+  float              *cloud;
+  int32_t            *unsupported;
+  int                 n_cyl;
+  int                 groups_per_row;    // ceil(cols / 8)
+  int                 groups_per_agent;  // rows * groups_per_row
+  int                 wgs_per_agent;     // ceil(groups_per_agent / 256)
+};
+
+struct Ray {
+  double d0, d1, d2, a;  // direction and a = d0*d0 + d1*d1
+};
+
+__device__ inline void keep_min(double t, double &best) {
+  if (t < best) best = t;
+}
+
+// one cylinder against one ray; t_reach = max_depth (1 + 1e-9)
+__device__ inline void hit_cylinder(const DepthCand &q, const Ray &r, double pz, double t_reach, double &best) {
+  if (r.a > 0) {
+    const double b = q.ox * r.d0 + q.oy * r.d1;
+    // Camera outside the cylinder (c > 0) and the ray's xy projection leaving the axis (b > 0): |q(t)|^2 - r^2 =
+    // a t^2 + 2 b t + c > c for every t > 0, so no cap is hit (the margin on c covers the rounding of qx, qy: 1e-14 of
+    // ox^2 + oy^2 = c + r^2), and a c >= 0 gives disc <= b b, s <= b, both roots <= 0: no side either.
+    if (b > 1e-100 && q.c > 1e-9 * q.rr) return;
+    const double disc = b * b - r.a * q.c;
+    if (disc >= 0) {
+      const double s = sqrt(disc);
+      // (-b - s) / a <= (-b + s) / a (a > 0, s >= 0, division is monotone): the far root is needed only when the near one
+      // is not accepted
+      double t = (-b - s) / r.a;
+      double z = pz + t * r.d2;
+      if (!(t > 0 && q.z0 <= z && z <= q.z1)) {
+        t = (-b + s) / r.a;
+        z = pz + t * r.d2;
+      }
+      if (t > 0 && q.z0 <= z && z <= q.z1) keep_min(t, best);
+    } else if (disc < -1e-9 * (b * b + r.a * (q.c + 2.0 * q.rr))) {
+      // min over t of |q(t)|^2 - r^2 is -disc / a: with disc this far below zero (rounding is 1e-15 of the same terms) the
+      // ray's xy projection stays outside the circle and no cap is hit
+      return;
+    }
+  }
+  if (r.d2 != 0) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const double num = (e ? q.z1 : q.z0) - pz;
+      // num / d2 > 0 needs both of one sign (IEEE division gives the exact sign); beyond t_reach the quotient is above
+      // max_depth and cannot be the image's t*
+      if (num == 0 || (num > 0) != (r.d2 > 0) || fabs(num) > fabs(r.d2) * t_reach) continue;
+      const double t  = num / r.d2;
+      const double qx = q.ox + t * r.d0, qy = q.oy + t * r.d1;
+      if (t > 0 && qx * qx + qy * qy <= q.rr) keep_min(t, best);
+    }
+  }
+}
+
+__device__ inline Ray make_ray(const double *R, double xc, double yc) {
+  Ray r;
+  r.d0 = (R[0] * xc + R[1] * yc) + R[2];
+  r.d1 = (R[3] * xc + R[4] * yc) + R[5];
+  r.d2 = (R[6] * xc + R[7] * yc) + R[8];
+  r.a  = r.d0 * r.d0 + r.d1 * r.d1;
+  return r;
+}
+
+__global__ __launch_bounds__(DEPTH_WG) void k_render_depth(DepthArgs g) {
+  __shared__ DepthCand s_list[DEPTH_CAP];
+  __shared__ int       s_wave_n[DEPTH_WG / 64];
+  __shared__ int       s_unsupported;
+
+  const SogmDepthCamera &cam = g.cam;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int agent = blockIdx.x / g.wgs_per_agent, wg = blockIdx.x - agent * g.wgs_per_agent;
+  const int grp   = wg * DEPTH_WG + tid;
+  const bool live = grp < g.groups_per_agent;
+  const int v = live ? grp / g.groups_per_row : 0, u0 = live ? (grp - v * g.groups_per_row) * DEPTH_PX : 0;
+  const int npx = live ? min(DEPTH_PX, cam.cols - u0) : 0;
+
+  double R[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = g.rot[(size_t)agent * 9 + i];
+  const double px = g.pos[(size_t)agent * 3], py = g.pos[(size_t)agent * 3 + 1], pz = g.pos[(size_t)agent * 3 + 2];
+  const double yc = ((double)v - cam.cy) / cam.fy;
+  const double t_reach = cam.max_depth * (1.0 + 1e-9);
+
+  // How far from the camera, in xy, a point with t <= max_depth can be: t |d_xy|, and |d_xy|^2 is convex in (xc, yc), so
+  // its maximum over the image is at a corner.  1e-6: rounding, and the caps' and t_reach's own margins.
+  double reach;
+  {
+    const double x_lo = (0.0 - cam.cx) / cam.fx, x_hi = ((double)(cam.cols - 1) - cam.cx) / cam.fx;
+    const double y_lo = (0.0 - cam.cy) / cam.fy, y_hi = ((double)(cam.rows - 1) - cam.cy) / cam.fy;
+    const double a_max = fmax(fmax(make_ray(R, x_lo, y_lo).a, make_ray(R, x_hi, y_lo).a),
+                              fmax(make_ray(R, x_lo, y_hi).a, make_ray(R, x_hi, y_hi).a));
+    reach = cam.max_depth * sqrt(a_max) * (1.0 + 1e-6);
+  }
+
+  double best[DEPTH_PX];
+#pragma unroll
+  for (int k = 0; k < DEPTH_PX; ++k) best[k] = INFINITY;
+
+  // every live lane: its pixels against the first n entries of the list
+  auto render_list = [&](int n) {
+    if (n == 0) return;
+#pragma unroll
+    for (int k = 0; k < DEPTH_PX; ++k) {
+      if (k >= npx) continue;
+      const Ray r = make_ray(R, ((double)(u0 + k) - cam.cx) / cam.fx, yc);
+      double    t = best[k];
+      for (int j = 0; j < n; ++j) hit_cylinder(s_list[j], r, pz, t_reach, t);
+      best[k] = t;
+    }
+  };
+
+  if (tid == 0) s_unsupported = 0;
+  int n_list = 0, n_other = 0;
+  for (int c0 = 0; c0 < g.n_cyl; c0 += DEPTH_WG) {
+    const int i    = c0 + tid;
+    bool      keep = false;
+    DepthCand q{};
+    if (i < g.n_cyl) {
+      const SogmCylinder &o = g.cyl[i];
+      if (o.type != 3) {
+        ++n_other;
+      } else {
+        const double r = 0.5 * o.w;
+        q.z0 = o.z - 0.5 * o.h;
+        q.z1 = o.z + 0.5 * o.h;
+        q.ox = px - o.x;
+        q.oy = py - o.y;
+        const double oo = q.ox * q.ox + q.oy * q.oy;
+        q.rr = r * r;
+        q.c  = oo - q.rr;
+        // a hit point lies within r of the axis (1e-6: the caps' rounded test) and within `reach` of the camera
+        const double far = reach + fabs(r) * (1.0 + 1e-6);
+        keep = oo <= far * far;
+      }
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) s_wave_n[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < DEPTH_WG / 64; ++w) {
+      before += w < wave ? s_wave_n[w] : 0;
+      total += s_wave_n[w];
+    }
+    if (n_list + total > DEPTH_CAP) {  // (uniform) render what is listed, start an empty list: total <= DEPTH_WG fits
+      render_list(n_list);
+      n_list = 0;
+      __syncthreads();
+    }
+    if (keep) s_list[n_list + before + __popcll(mask & ((1ull << lane) - 1ull))] = q;
+    n_list += total;
+    __syncthreads();
+  }
+  render_list(n_list);
+
+  if (wg == 0) {  // one workgroup per agent reports the records of another type
+    if (n_other) atomicAdd(&s_unsupported, n_other);
+    __syncthreads();
+    if (tid == 0) g.unsupported[agent] = s_unsupported;
+  }
+  if (!live) return;
+
+  // ground, quantisation, back-projection
+  uint16_t d16[DEPTH_PX];
+  float    xyz[DEPTH_PX * 3];
+  const double gnum = cam.ground_z - pz;
+#pragma unroll
+  for (int k = 0; k < DEPTH_PX; ++k) {
+    d16[k]         = 0;
+    xyz[k * 3]     = xyz[k * 3 + 1] = xyz[k * 3 + 2] = __uint_as_float(0x7FC00000u);
+    if (k >= npx) continue;
+    const double du = (double)(u0 + k) - cam.cx;
+    double       t  = best[k];
+    if (cam.use_ground) {
+      const double d2 = (R[6] * (du / cam.fx) + R[7] * yc) + R[8];
+      // (gnum / d2 > 0 needs both of one sign)
+      if (d2 != 0 && gnum != 0 && (gnum > 0) == (d2 > 0)) {
+        const double tg = gnum / d2;
+        if (tg > 0) keep_min(tg, t);
+      }
+    }
+    if (t <= cam.max_depth) d16[k] = (uint16_t)floor(t * cam.depth_scale + 0.5);
+    if (d16[k]) {
+      const double zq = (double)d16[k] / cam.depth_scale;
+      xyz[k * 3]      = (float)(du * zq / cam.fx);
+      xyz[k * 3 + 1]  = (float)(((double)v - cam.cy) * zq / cam.fy);
+      xyz[k * 3 + 2]  = (float)zq;
+    }
+  }
+
+  const size_t pix = ((size_t)agent * cam.rows + v) * (size_t)cam.cols + u0;
+  uint16_t    *dp  = g.depth + pix;
+  if (npx == DEPTH_PX && ((uintptr_t)dp & 15) == 0) {
+    uint4 w;
+    w.x = d16[0] | ((unsigned)d16[1] << 16);
+    w.y = d16[2] | ((unsigned)d16[3] << 16);
+    w.z = d16[4] | ((unsigned)d16[5] << 16);
+    w.w = d16[6] | ((unsigned)d16[7] << 16);
+    *reinterpret_cast<uint4 *>(dp) = w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < DEPTH_PX; ++k)
+      if (k < npx) dp[k] = d16[k];
+  }
+  if (g.cloud) {
+    float *cp = g.cloud + pix * 3;
+    if (npx == DEPTH_PX && ((uintptr_t)cp & 15) == 0) {
+#pragma unroll
+      for (int k = 0; k < DEPTH_PX * 3; k += 4) {
+        vfloat4 w = {xyz[k], xyz[k + 1], xyz[k + 2], xyz[k + 3]};
+        *reinterpret_cast<vfloat4 *>(cp + k) = w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < DEPTH_PX * 3; ++k)
+        if (k < npx * 3) cp[k] = xyz[k];
+    }
+  }
+}
+
+int depth_refuse(const char *what) {
+  char buf[256];
+  std::snprintf(buf, sizeof(buf), "sogm_render_depth: %s", what);
+  set_error_text(buf);
+  return SOGM_ERR_INVALID_ARG;
+}
+
+}  // namespace
+}  // namespace sogm
+
+extern "C" int sogm_render_depth(const SogmWorld *world, const SogmDepthCamera *cam, int n_agents, const double *cam_pos,
+                                 const double *cam_rot, uint16_t *out_depth, float *out_cloud_xyz,
+                                 int32_t *out_unsupported, void *stream) {
+  using namespace sogm;
+  if (!world || !cam || !cam_pos || !cam_rot || !out_depth || !out_unsupported) return depth_refuse("null pointer");
+  if (cam->rows < 1 || cam->cols < 1 || n_agents < 1) return depth_refuse("rows, cols and n_agents must be >= 1");
+  if (world->n_cyl < 0 || (world->n_cyl > 0 && !world->cylinders)) return depth_refuse("n_cyl < 0, or null cylinders with n_cyl > 0");
+  if (!(cam->fx > 0) || !(cam->fy > 0) || !(cam->max_depth > 0) || !(cam->depth_scale > 0))
+    return depth_refuse("fx, fy, max_depth and depth_scale must be positive");
+  if (!(cam->max_depth * cam->depth_scale <= 65535.0)) return depth_refuse("max_depth * depth_scale exceeds 65535");
+  if (!std::isfinite(cam->cx) || !std::isfinite(cam->cy) || !std::isfinite(cam->fx) || !std::isfinite(cam->fy) ||
+      (cam->use_ground && !std::isfinite(cam->ground_z)))
+    return depth_refuse("intrinsics and ground_z must be finite");
+  DepthArgs g{};
+  g.cam            = *cam;
+  g.groups_per_row = (cam->cols + DEPTH_PX - 1) / DEPTH_PX;
+  const long long groups = (long long)cam->rows * g.groups_per_row;
+  const long long wgs    = (groups + DEPTH_WG - 1) / DEPTH_WG;
+  if ((long long)cam->rows * cam->cols > 2147483647LL || wgs * n_agents > 2147483647LL)
+    return depth_refuse("image or batch too large for one launch");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+    set_error_text("sogm_render_depth: no HIP device");
+    return SOGM_ERR_NO_DEVICE;
+  }
+  g.groups_per_agent = (int)groups;
+  g.wgs_per_agent    = (int)wgs;
+  g.cyl              = world->cylinders;
+  g.n_cyl            = world->n_cyl;
+  g.pos              = cam_pos;
+  g.rot              = cam_rot;
+  g.depth            = out_depth;
+  g.cloud            = out_cloud_xyz;
+  g.unsupported      = out_unsupported;
+  hipLaunchKernelGGL(k_render_depth, dim3((unsigned)(wgs * n_agents)), dim3(DEPTH_WG), 0, (hipStream_t)stream, g);
+  SOGM_HIP_CHECK(hipGetLastError());
+  return SOGM_OK;
+}

@@ -309,6 +309,14 @@ class GridMap {
               hipStream_t st = nullptr) {
     check(sogm_gridmap_update(h_, depth, cam_pos, cam_rot, out_updated, st), "sogm_gridmap_update");
   }
+  // The build's own depth camera (sogm_abi.h "depth camera"): every agent's frame of `frame`'s cylinders (RiskMap::world
+  // makes the struct), device pointers, in the layouts update() above (depth) and DspMap::filterPointCloud (cloud, may be
+  // nullptr; raw_range[a] = {a rows cols, (a + 1) rows cols}) read.  unsupported [n]: records of a type other than 3.
+  static void renderDepth(const SogmWorld &frame, const SogmDepthCamera &cam, int n_agents, const double *cam_pos,
+                          const double *cam_rot, uint16_t *depth, float *cloud_xyz, int32_t *unsupported,
+                          hipStream_t st = nullptr) {
+    check(sogm_render_depth(&frame, &cam, n_agents, cam_pos, cam_rot, depth, cloud_xyz, unsupported, st), "sogm_render_depth");
+  }
   // int getInflateOccupancy(Eigen::Vector3d pos) for a batch of device-resident queries
   void getInflateOccupancy(const int32_t *agent_idx, const double *pos, int n, int8_t *out, hipStream_t st = nullptr) {
     check(sogm_gridmap_query_inflate(h_, agent_idx, pos, n, out, st), "sogm_gridmap_query_inflate");

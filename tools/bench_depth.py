@@ -1,0 +1,114 @@
+"""Timing of the depth camera (sogm_render_depth, include/sogm_abi.h "depth camera"): A cameras, 480 x 640, on the cfg2
+moving world (make_scene(A, 15 m, 0x5069) through WorldTimeline, one frame per tick), alone and back to back with its two
+consumers (sogm_gridmap_update; sogm_filter_point_cloud).  The cameras stand on a 12 m circle and look at its centre, so that
+every one is inside the GridMap's 40 x 40 m map.  HIP events on the launch stream around every timed call, all inputs
+resident before the first one.  Prints one JSON line.
+
+Three more renders of the same frames say what bounds the kernel: the image alone (the same arithmetic, 2 of the 14 bytes
+per pixel), an empty world with the ground (all 14 bytes, next to no arithmetic), and the full render."""
+import argparse, importlib, json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np, torch
+
+
+def candidates(cyl, cam, pos, rot):
+    """per camera: the type-3 records k_render_depth's cull keeps (csrc/sogm_depth.hip, restated: it is the same list for
+    every workgroup of an agent) — xy distance to the axis <= max_depth * max |d_xy| over the image corners + r"""
+    out = []
+    xs = [(0.0 - cam.cx) / cam.fx, (cam.cols - 1 - cam.cx) / cam.fx]
+    ys = [(0.0 - cam.cy) / cam.fy, (cam.rows - 1 - cam.cy) / cam.fy]
+    for p, R in zip(pos, rot.reshape(-1, 3, 3)):
+        a = max((R[0, 0] * x + R[0, 1] * y + R[0, 2]) ** 2 + (R[1, 0] * x + R[1, 1] * y + R[1, 2]) ** 2 for x in xs for y in ys)
+        far = cam.max_depth * np.sqrt(a) * (1.0 + 1e-6) + 0.5 * cyl[:, 2] * (1.0 + 1e-6)
+        out.append(int(((cyl[:, 0] - p[0]) ** 2 + (cyl[:, 1] - p[1]) ** 2 <= far * far).sum()))
+    return out
+
+
+def camera_ring(pop, A):
+    """A cameras on a 12 m circle looking roughly at its centre, in GENERAL position: no pose component is a round number.
+    The reference's RayCaster (raycast.cpp:242-335; the oracle's and k_gm_paths' walk alike) never reaches its end cell from a
+    ray end that lies exactly on a voxel boundary, and the clean frames of an axis-aligned camera at z = 1.0 have such ends
+    (ground returns at z = 0.0 exactly: row 330, depth 4300) — a real sensor's pose and noise never do."""
+    th = 2.0 * np.pi * np.arange(A) / A + 0.1
+    return [pop.scene.camera_pose(12.0 * np.cos(t), 12.0 * np.sin(t), 1.03 + 0.0111 * np.sin(a + 1.0), t + np.pi + 0.05 * np.sin(a))
+            for a, t in enumerate(th)]
+
+
+def run(A, steps=30, warmup=5):
+    pop = importlib.import_module("pred-occ-planner_amd")
+    sogm = importlib.import_module("pred-occ-planner_amd.sogm")
+    gm = importlib.import_module("pred-occ-planner_amd.gridmap")
+    depth = importlib.import_module("pred-occ-planner_amd.depth")
+    sc = pop.scene.make_scene(A, 15.0, seed=0x5069)
+    tl = pop.scene.WorldTimeline(sc, 0.1)
+    cam = depth.make_depth_camera()
+    poses = camera_ring(pop, A)
+    pos, rot = np.stack([p for p, _ in poses]), np.stack([R.reshape(9) for _, R in poses])
+    pos_d, rot_d = sogm._dev(pos, np.float64), sogm._dev(rot, np.float64)
+    n = warmup + steps
+    none = np.zeros((0, 3), np.float32)
+    worlds = [sogm.World(none, tl.cylinders(k)) for k in range(n)]
+    empty = sogm.World(none, np.zeros((0, 5)))
+    g = gm.GridMap(gm.make_gridmap_params(), A)
+    m = sogm.SogmMap(pop.config.make_spec("cfg1", map_kind=pop._abi.SOGM_MAP_RISKVOXEL), A)
+    n_cand = [candidates(tl.cylinders(k), cam, pos, rot) for k in (warmup, n - 1)]
+
+    def timed(fn):
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(steps)]
+        for k in range(n):
+            e = ev[k - warmup] if k >= warmup else None
+            if e: e[0].record()
+            fn(k)
+            if e: e[1].record()
+        torch.cuda.synchronize()
+        ms = np.array([e[0].elapsed_time(e[1]) for e in ev])
+        return {"mean": round(float(ms.mean()), 4), "min": round(float(ms.min()), 4), "max": round(float(ms.max()), 4)}
+
+    keep = {}
+
+    def render(k, want_cloud=True, world=None):
+        keep["out"] = depth.render_depth(world or worlds[k], cam, pos_d, rot_d, want_cloud)
+        return keep["out"]
+
+    def render_gridmap(k):
+        d = render(k, False)[0]
+        keep["upd"] = g.update(d, pos_d, rot_d)
+
+    def render_filter(k):
+        _, cl, rng, _ = render(k)
+        keep["flt"] = m.filterPointCloud(cl, rng, 0.15, 5000)
+
+    t_render = timed(render)
+    d16 = keep["out"][0]
+    returns = float((d16 != 0).float().mean().item())
+    t_image = timed(lambda k: render(k, False))
+    t_ground = timed(lambda k: render(k, True, empty))
+    t_gridmap = timed(lambda k: keep.__setitem__("upd", g.update(d16, pos_d, rot_d)))
+    t_rg = timed(render_gridmap)
+    _, cl, rng, _ = render(n - 1)
+    t_filter = timed(lambda k: keep.__setitem__("flt", m.filterPointCloud(cl, rng, 0.15, 5000)))
+    t_rf = timed(render_filter)
+    nbytes = A * cam.rows * cam.cols * 14
+    out = {"agents": A, "cylinders": int(len(sc["cylinders"])), "frames_timed": steps,
+           "render_ms": t_render, "render_GBps_algorithmic": round(nbytes / (t_render["mean"] * 1e-3) / 1e9, 1),
+           "algorithmic_bytes": nbytes, "pixels_with_return": round(returns, 3),
+           "candidates_per_workgroup_mean": round(float(np.mean(n_cand)), 2), "candidates_per_workgroup_max": int(np.max(n_cand)),
+           "render_image_only_ms": t_image, "render_empty_world_ground_ms": t_ground,
+           "gridmap_update_ms": t_gridmap, "render_then_gridmap_ms": t_rg,
+           "filter_ms": t_filter, "render_then_filter_ms": t_rf,
+           "gridmap_updated": int(keep["upd"].sum().item()), "filtered_points_agent0": int(keep["flt"][1][0].item())}
+    g.close()
+    m.close()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agents", type=int, nargs="+", default=[16, 128])
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    assert a.steps >= 20 and torch.cuda.is_available(), "needs a GPU and at least 20 timed frames"
+    print(json.dumps({"workload": "sogm_render_depth, 480x640 per camera, cfg2 moving world (seed 0x5069), cameras on a 12 m "
+                                  "circle; ms per frame: HIP events on the launch stream around each call",
+                      "runs": [run(A, a.steps, a.warmup) for A in a.agents]}))
