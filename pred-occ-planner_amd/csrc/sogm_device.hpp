@@ -468,7 +468,7 @@ __device__ __forceinline__ void copy_record(SogmTrajRecord *dst, const SogmTrajR
   uint4       *d = reinterpret_cast<uint4 *>(dst);
   for (int w = lane; w < (int)(sizeof(SogmTrajRecord) / 16); w += stride) d[w] = s[w];
 }
-// (shared by sogm_map.hip, sogm_audit.hip and sogm_fsm.hip)
+// (shared by sogm_traj.hip, sogm_planner.hpp's tick_inputs_agent, sogm_audit.hip and sogm_fsm.hip)
 // Bezier pos / vel / acc of a trajectory record at an absolute time (bernstein.cpp:25-59)
 // returns false (and zeros) for an empty record
 __device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, double out[9]) {
@@ -682,7 +682,8 @@ struct sogm_ctx {
   int            update_pending;
   int            map_epoch;
   int           *d_map_ready;      // [A]
-  int           *d_update_ctl;     // [8 + A]: {ticket, error, -...} + per-agent progress counters
+  int           *d_update_ctl;     // [UpdateBlock::words(A)] ticket, error and per-agent progress words, a 128-byte line each
+                                   // (layout: sogm::UpdateBlock, sogm_handover.hpp)
   long long     *d_update_ts;      // [A][4] diagnostics (sogm_debug_update_flow_times)
   int           *d_update_order;   // [A] agents in the order the flow takes them (identity until a replan ranks them)
   double         tune[SOGM_TUNE_N];  // sogm_set_tuning; defaults from SOGM_TUNING_TABLE at sogm_create

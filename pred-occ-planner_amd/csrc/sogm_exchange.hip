@@ -44,7 +44,7 @@ struct RcclApi {
 
 RcclApi *rccl() {
   static RcclApi        api;
-  static int            state = -1;  // 1 ok, -1 failed
+  static bool           loaded = false;  // the library and every entry point it needs were found
   static std::once_flag once;        // several contexts / host threads may reach the first collective together
   std::call_once(once, [] {
     // SOGM_RCCL_LIB names the library to load instead (tests substitute an in-process stand-in for RCCL whose
@@ -65,10 +65,10 @@ RcclApi *rccl() {
       api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.handle, "ncclGetErrorString");
       if (api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.CommCount && api.CommUserRank &&
           api.AllGather && api.GetErrorString)
-        state = 1;
+        loaded = true;
     }
   });
-  return state == 1 ? &api : nullptr;
+  return loaded ? &api : nullptr;
 }
 
 int rccl_fail(const char *what, ncclResult_t r) {

@@ -1,5 +1,5 @@
 // sogm_handover.hpp — device-side hand-overs between the persistent kernels: the control blocks, their
-// layouts (FlowBlock, FlightBlock: what is carved where, what a call resets), the tag arithmetic of their slots, the failure
+// layouts (FlowBlock, UpdateBlock, FlightBlock: what is carved where, what a call resets), the tag arithmetic of their slots, the failure
 // codes, ONE bounded wait and ONE publish.  The layouts, the arithmetic and the codes compile on the host too
 // (tests/planner_blocks_host_test.cpp, tests/handover_host_test.cpp); everything that runs on the device sits behind __HIPCC__.
 #pragma once
@@ -74,6 +74,20 @@ struct FlowBlock {
     fc->f_ready  = base + b.f_ready;
     fc->p_ready  = base + b.p_ready;
   }
+};
+// The update flow's control block (sogm_ctx::d_update_ctl; k_update_flow, csrc/sogm_map.hip), word offsets from its base, the
+// only place that knows it.  Thousands of waves claim tickets, bump and poll these words — in one 128-byte line that line's
+// memory channel is the bottleneck, as the flight's header showed —, so every word has a line of its own:
+//   ticket | (unused) | error at word 1024 | (unused) | from word 2048 one progress counter per agent, 32 words apart
+// Zeroed as a whole in front of every update flow.
+struct UpdateBlock {
+  static constexpr int    ticket() { return 0; }
+  static constexpr int    err() { return 1024; }
+  static constexpr int    stage(int agent) { return 2048 + 32 * agent; }
+  static constexpr size_t words(int A) { return (size_t)stage(A); }  // the last agent's line is whole
+  // base + stage(agent) for the kernel: the constant part first, so that it is folded into one address in front of the ticket
+  // loop and a ticket adds its agent's 32 words to it
+  static constexpr int *stage_word(int *base, int agent) { return base + stage(0) + (stage(1) - stage(0)) * agent; }
 };
 // ---------------------------------------------------------------------------------------------------------------
 // Flight (sogm_flight_run): n_ticks replan ticks of every agent in ONE set of launches, every agent on its own clock.

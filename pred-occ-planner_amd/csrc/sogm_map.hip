@@ -1,36 +1,32 @@
-// sogm_map.hip — batched SOGM build + queries for gfx950 (MI355X), behind include/sogm_abi.h.
+// sogm_map.hip — building an agent's SOGM on gfx950 (MI355X), behind include/sogm_abi.h.  (The library's root is
+// sogm_context.hip, the readers of a finished map sogm_query.hip, the record kernels sogm_traj.hip, the kernels that zero a
+// grid, the mark logs and the pool of grids sogm_clear.hip.)
 //
-// Kernels (all HBM-bound integer / fp32 work — no MFMA anywhere on this path):
-//   (the kernels that zero a grid, the mark logs and the pool of grids: sogm_clear.hip)
-//   k_stamp_cloud        per (agent, cloud point): crop, slice-0 mark, GT-velocity lookup (cylinders
-//                        staged in LDS), T-1 advected marks.   fake_particle_risk_voxel.cpp:88-161
-//   k_splat_neighbours   per (agent, record, slice): Bezier sample (fp64) + body particles,
-//                        float atomic add.                      risk_base.cpp:136-168,199-208
-//   k_query_clear        batched getClearOcccupancy.            fake_particle_risk_voxel.cpp:309-346
-//   k_obstacle_points    one workgroup per corridor box, order-preserving block-scan compaction.
-//                                                               map.cpp:480-518 / risk_base.cpp:295-337
-//   k_slabs_to_vt / k_vt_to_slabs   layout converters for parity I/O and futureRiskCallback.
+// An agent's map is built by one of four builders out of the same steps, each step written once as a ticket body:
+//   cull_ticket      candidate cylinders around the map centre + the agent's crop of a SogmWorld cloud.
+//   bits_ticket      per cloud point: crop, voxel index, one atomic OR into the occupancy bitmask of slice 0.
+//                                                               fake_particle_risk_voxel.cpp:88-114
+//   marks_ticket     per occupied voxel: slice-0 mark, GT velocity of the first matching record, T - 1 advected marks,
+//                    mark log.                                  fake_particle_risk_voxel.cpp:114-170
+//   overlay_ticket   per (record, slice): Bezier sample (fp64) + body particles, float atomic add, mark log.
+//                                                               risk_base.cpp:136-168,199-208
+// (all HBM-bound integer / fp32 work — no MFMA anywhere on this path).  The builders:
+//   the lock-step kernels   k_cull_cylinders, k_stamp_bits / _blocks, k_stamp_marks / _cached, k_splat_neighbours: one launch
+//                           per step over the whole swarm (sogm_update_gt / _gt_swarm / _world, sogm_project_neighbours)
+//   k_update_flow           one persistent launch, agent by agent (tuning key update_flow)
+//   k_prestamp_flow         the NEXT tick's map inside this tick's dataflow replan (sogm_update_prestamped adopts it)
+//   k_flight_map            the map role of sogm_flight_run
+// Behind them the host side: map_target / world_blocks, the lock-step update as named steps, the update entries.
 #include <hip/hip_runtime.h>
 
 #include <utility>
 #include <vector>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
 
 #include "sogm_device.hpp"
 #include "sogm_fsm.hpp"
 #include "sogm_planner.hpp"  // FlowCtl: the pre-stamp consumes the dataflow replan's list of finished agents
 
 namespace sogm {
-
-static thread_local char g_err[512] = {0};
-void set_error(const char *what, hipError_t e) {
-  std::snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-}
-void set_error_text(const char *text) { std::snprintf(g_err, sizeof(g_err), "%s", text); }
 
 // ------------------------------------------------------------------------------------------------
 // stamp: cloud -> slice 0, GT velocity -> slices 1..T-1
@@ -1013,202 +1009,6 @@ __global__ __launch_bounds__(256) void k_splat_neighbours(
 }
 
 // ------------------------------------------------------------------------------------------------
-// queries
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_query_clear(MapView m, const int32_t *__restrict__ agent,
-                                                     const double *__restrict__ pos,
-                                                     const double *__restrict__ t, int t_is_index,
-                                                     int n, int8_t *__restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int a = agent[i];
-  int       r;
-  if (t_is_index) {
-    r = query_clear_idx(m, a, pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2], (int)t[i]);
-  } else {
-    r = query_clear_time(m, a, pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2], t[i]);
-  }
-  out[i] = (int8_t)r;
-}
-
-// Order-preserving extraction.  Cells of the box are visited in the reference's z,y,x order, 256
-// cells per trip; each lane counts the slices of its cell that exceed the threshold, a block-wide
-// exclusive scan turns counts into output offsets, so the emitted sequence is exactly the
-// reference's (FIRI's greedy selection breaks ties by point order).
-__global__ __launch_bounds__(256) void k_obstacle_points(
-    MapView m, const int32_t *__restrict__ agent_idx, const double *__restrict__ box_lo,
-    const double *__restrict__ box_hi, const double *__restrict__ t0v,
-    const double *__restrict__ t1v, double *__restrict__ out_pts, int32_t *__restrict__ out_cnt,
-    int cap) {
-  __shared__ int s_wave[4];
-  __shared__ int s_base;
-  const GridGeom &g     = m.g;
-  const int       b     = blockIdx.x;
-  const int       agent = agent_idx[b];
-  const float    *pose  = m.poses + agent * 3;
-  const double    stamp = m.stamps[agent];
-  const double    tr    = (double)g.dt;
-  int             js    = (int)floor((t0v[b] - stamp) / tr);
-  int             je    = (int)ceil((t1v[b] - stamp) / tr);
-  js                    = js < 0 ? 0 : js;
-  js                    = js > g.T ? g.T : js;
-  je                    = je > g.T ? g.T : je;
-  je                    = je < 0 ? 0 : je;
-  if (je > g.T - 1) je = g.T - 1;  // slices >= T do not exist (reference reads one past the end)
-  int lx = (int)((box_lo[b * 3 + 0] - pose[0] + g.rx) / g.res);
-  int ly = (int)((box_lo[b * 3 + 1] - pose[1] + g.ry) / g.res);
-  int lz = (int)((box_lo[b * 3 + 2] - pose[2] + g.rz) / g.res);
-  int hx = (int)((box_hi[b * 3 + 0] - pose[0] + g.rx) / g.res);
-  int hy = (int)((box_hi[b * 3 + 1] - pose[1] + g.ry) / g.res);
-  int hz = (int)((box_hi[b * 3 + 2] - pose[2] + g.rz) / g.res);
-  hx     = min(hx, g.L - 1);
-  hy     = min(hy, g.W - 1);
-  hz     = min(hz, g.H - 1);
-  lx     = max(lx, 0);
-  ly     = max(ly, 0);
-  lz     = max(lz, 0);
-  const int nx = hx - lx + 1, ny = hy - ly + 1, nz = hz - lz + 1;
-  if (threadIdx.x == 0) s_base = 0;
-  __syncthreads();
-  if (nx <= 0 || ny <= 0 || nz <= 0 || js > je) {
-    if (threadIdx.x == 0) out_cnt[b] = 0;
-    return;
-  }
-  const int    cells = nx * ny * nz;
-  const void  *grid0 = m.slab(agent, 0);
-  double      *outp  = out_pts + (size_t)b * cap * 3;
-  const int    lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-
-  for (int c0 = 0; c0 < cells; c0 += blockDim.x) {
-    const int c    = c0 + threadIdx.x;
-    int       cnt  = 0;
-    unsigned  mask = 0;  // bit j-js set when slice j exceeds
-    int       vi   = 0;
-    if (c < cells) {
-      const int x = lx + c % nx;
-      const int y = ly + (c / nx) % ny;
-      const int z = lz + c / (nx * ny);
-      vi          = x + y * g.L + z * g.L * g.W;
-      const int pi = g.phys(x, y, z);
-      for (int j = js; j <= je; ++j) {
-        const float thr =
-            g.map_kind == SOGM_MAP_FAKE ? g.risk_threshold : g.risk_threshold - g.decay_voxel * (float)j;
-        if (cell_ld(grid0, (size_t)j * g.V + pi, g.half) > thr) {
-          ++cnt;
-          mask |= 1u << (j - js);
-        }
-      }
-    }
-    // wave-level inclusive scan (64 lanes), then 4-wave combine through LDS
-    int incl = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int wave_off = 0, total = 0;
-    for (int w = 0; w < 4; ++w) {
-      const int v = s_wave[w];
-      if (w < wave) wave_off += v;
-      total += v;
-    }
-    const int base = s_base;
-    int       off  = base + wave_off + incl - cnt;
-    if (cnt) {
-      float fx, fy, fz;
-      g.corner_of(vi, pose, fx, fy, fz);
-      for (int j = 0; j < 32 && (mask >> j); ++j) {
-        if ((mask >> j) & 1u) {
-          if (off < cap) {
-            outp[off * 3 + 0] = (double)fx;
-            outp[off * 3 + 1] = (double)fy;
-            outp[off * 3 + 2] = (double)fz;
-          }
-          ++off;
-        }
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = base + total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out_cnt[b] = s_base;
-}
-
-// ------------------------------------------------------------------------------------------------
-// layout converters ([T][V] slabs <-> reference [V][T])
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_slabs_to_vt(const void *__restrict__ slabs, GridGeom g, float *__restrict__ vt) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= g.V) return;
-  const int p = g.phys_of(v);
-  for (int t = 0; t < g.T; ++t) vt[(size_t)v * g.T + t] = cell_ld(slabs, (size_t)t * g.V + p, g.half);
-}
-__global__ __launch_bounds__(256) void k_vt_to_slabs(const float *__restrict__ vt, GridGeom g, void *__restrict__ slabs) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= g.V) return;
-  const int p = g.phys_of(v);
-  for (int t = 0; t < g.T; ++t) cell_st(slabs, (size_t)t * g.V + p, vt[(size_t)v * g.T + t], g.half);
-}
-
-__global__ __launch_bounds__(64) void k_traj_eval(const SogmTrajRecord *__restrict__ rec, int n,
-                                                  const double *__restrict__ t,
-                                                  double *__restrict__ out, int32_t *__restrict__ ok) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double o[9];
-  ok[i] = traj_eval_record(rec[i], t[i], o) ? 1 : 0;
-  for (int k = 0; k < 9; ++k) out[i * 9 + k] = o[k];
-}
-
-// Start of a replan tick for n agents in one launch (the tick driver's glue): the replan start state of every agent
-// from the trajectory it is executing — FiniteStateMachine samples traj_ at the planned start time
-// (plan_manager/src/plan_manager.cpp:169-175), an agent without a trajectory starts from where it hovers
-// (odom, :127-133) — plus the stamps the map update and the replan take.
-// One wave per agent: the 2064-byte record is fetched with ONE coalesced batch of loads into LDS (a lane walking
-// n_pieces -> durations -> control points through global memory needs four dependent round trips, which the tail
-// of the streaming clear beside this kernel stretches to a millisecond each), lane 0 evaluates it there.
-// One agent's tick inputs (plan_manager.cpp:169-175): the start state sampled from its executing trajectory at
-// stamp + start_offset, or where it hovers; the map centre of the tick is that position.
-__device__ inline void tick_inputs_agent(const SogmTrajRecord &rec, const double *hov, int i, double stamp,
-                                         const TickInputsIO &io, float *__restrict__ poses) {
-  const double ts = stamp + io.start_offset;
-  double       o[9];
-  if (!traj_eval_record(rec, ts, o))
-    for (int k = 0; k < 9; ++k) o[k] = hov[k];
-  for (int k = 0; k < 9; ++k) io.pva[i * 9 + k] = o[k];
-  for (int k = 0; k < 3; ++k) {
-    io.hover[i * 9 + k]     = o[k];
-    io.hover[i * 9 + 3 + k] = 0.0;
-    io.hover[i * 9 + 6 + k] = 0.0;
-    poses[i * 3 + k]        = (float)o[k];
-  }
-  io.now[i]     = stamp;
-  io.t_start[i] = ts;
-}
-// The agent's executed record and hover row into the workgroup's LDS (one wave), visible to every lane on return.
-__device__ __forceinline__ void stage_record_hover(SogmTrajRecord *s_rec, double *s_hov, const SogmTrajRecord *own,
-                                                   const double *hover, int agent, int lane) {
-  copy_record(s_rec, own + agent, lane);
-  if (lane < 9) s_hov[lane] = hover[agent * 9 + lane];
-  __syncthreads();
-}
-__global__ __launch_bounds__(64) void k_tick_inputs(const SogmTrajRecord *__restrict__ own, int n, double stamp,
-                                                    double start_offset, double *__restrict__ hover,
-                                                    double *__restrict__ now, double *__restrict__ t_start,
-                                                    double *__restrict__ pva, float *__restrict__ poses) {
-  __shared__ __attribute__((aligned(16))) SogmTrajRecord s_rec;
-  __shared__ double                                      s_hov[9];
-  const int i = blockIdx.x;
-  if (i >= n) return;
-  const TickInputsIO io{.own = own, .hover = hover, .now = now, .t_start = t_start, .pva = pva, .start_offset = start_offset};
-  stage_record_hover(&s_rec, s_hov, io.own, io.hover, i, threadIdx.x);
-  if (threadIdx.x != 0) return;
-  tick_inputs_agent(s_rec, s_hov, i, stamp, io, poses);
-}
-
-// ------------------------------------------------------------------------------------------------
 // Pre-stamp: the NEXT tick's map built inside this tick's replan (dataflow replan only).
 // The tick's critical path was "stamp (1.8 ms, nothing else running) -> chain of the slowest agent"; but an agent's
 // next map centre only depends on its OWN new record, which is final the moment k_finish_flow publishes it.  This
@@ -1553,35 +1353,6 @@ hipError_t launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const Pres
   hipLaunchKernelGGL(k_prestamp_flow, dim3(n_workgroups), dim3(64), 0, st, g, fc, ps);
   return hipGetLastError();
 }
-// End of a tick: latest-wins per drone (particles.cpp:179-190) — a successful replan replaces the agent's record,
-// a failed one keeps the trajectory being executed (plan_manager.cpp:176-196); `all` (optional) is the swarm table of
-// a single-process run, refreshed in the same pass.  One lane per 16 bytes of a record.
-__global__ __launch_bounds__(256) void k_merge_latest(const SogmTrajRecord *__restrict__ fresh,
-                                                      const int32_t *__restrict__ ok, SogmTrajRecord *__restrict__ own,
-                                                      SogmTrajRecord *__restrict__ all, int n) {
-  constexpr int W = (int)(sizeof(SogmTrajRecord) / 16);
-  static_assert(sizeof(SogmTrajRecord) % 16 == 0, "record size");
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (long long)n * W) return;
-  const int a = (int)(gid / W), w = (int)(gid % W);
-  // all three loads are issued together: this kernel often runs beside the tail of the streaming clear, where a
-  // dependent global round trip costs a millisecond
-  const int   good = ok[a];
-  const uint4 vf = reinterpret_cast<const uint4 *>(fresh + a)[w], vo = reinterpret_cast<const uint4 *>(own + a)[w];
-  const uint4 v  = good ? vf : vo;
-  if (good) reinterpret_cast<uint4 *>(own + a)[w] = v;
-  if (all) reinterpret_cast<uint4 *>(all + a)[w] = v;
-}
-
-// BaselinePlanner::isTrajSafe (plan_manager/src/baseline.cpp:45-68): sample the executed trajectory every
-// 0.1 s from "now" up to min(T, duration) and query the SOGM at the sample's time after the map stamp.
-__global__ __launch_bounds__(64) void k_traj_safe(MapView m, const SogmTrajRecord *__restrict__ rec,
-                                                  const double *__restrict__ t_now, double T,
-                                                  int32_t *__restrict__ out) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= m.n_agents) return;
-  out[a] = traj_safe_agent(m, a, rec[a], t_now[a], T, 0, 1);
-}
 
 // row length of the stamp's occupancy bitmask (one row per agent): k_stamp_marks reads 256 words per trip
 static int stamp_bits_words(const GridGeom &g) { return (((g.V + 31) / 32) + 255) & ~255; }
@@ -1632,320 +1403,6 @@ int world_blocks(sogm_ctx *c, const SogmWorld *w, CloudBlocks *out) {
   return SOGM_OK;
 }
 
-}  // namespace sogm
-
-using namespace sogm;
-
-// ================================================================================================
-// C ABI
-// ================================================================================================
-extern "C" {
-
-int sogm_abi_version(void) { return SOGM_ABI_VERSION; }
-const char *sogm_last_error(void) { return sogm::g_err; }
-
-int sogm_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) {
-  if (!spec || !out || n_agents <= 0) return SOGM_ERR_INVALID_ARG;
-  if (spec->L <= 0 || spec->W <= 0 || spec->H <= 0 || spec->T <= 0 || spec->T > 32 ||
-      !(spec->resolution > 0.f) || !(spec->time_resolution > 0.f))
-    return SOGM_ERR_INVALID_ARG;
-  if (spec->map_kind != SOGM_MAP_FAKE && spec->map_kind != SOGM_MAP_RISKBASE &&
-      spec->map_kind != SOGM_MAP_RISKVOXEL)
-    return SOGM_ERR_INVALID_ARG;
-  if ((spec->storage & ~(1 | SOGM_LAYOUT_TILED)) != 0) return SOGM_ERR_INVALID_ARG;
-  if ((spec->storage & SOGM_LAYOUT_TILED) && ((spec->L | spec->W | spec->H) & 1)) return SOGM_ERR_INVALID_ARG;  // whole tiles
-  // one time slice is addressed with 32-bit byte offsets (window_sum_hits) and V is an int
-  if ((unsigned long long)spec->L * spec->W * spec->H >= (1ull << 30)) {
-    sogm::set_error_text("sogm_create: L * W * H must stay below 2^30 cells per time slice");
-    return SOGM_ERR_INVALID_ARG;
-  }
-  *out = nullptr;
-  if (sogm_device_count() <= device || device < 0) {
-    std::snprintf(sogm::g_err, sizeof(sogm::g_err), "no HIP device %d", device);
-    return SOGM_ERR_NO_DEVICE;
-  }
-  if (hipSetDevice(device) != hipSuccess) return SOGM_ERR_NO_DEVICE;
-  sogm_ctx *c = new (std::nothrow) sogm_ctx();  // (value-initialised: every field is zero)
-  if (!c) return SOGM_ERR_INVALID_ARG;
-  c->spec          = *spec;
-  c->geom          = make_geom(*spec);
-  c->n_agents      = n_agents;
-  c->device        = device;
-  {
-#define X(id, name, dflt, lo, hi) c->tune[SOGM_TUNE_##id] = (double)(dflt);
-    SOGM_TUNING_TABLE(X)
-#undef X
-    const char *e = getenv("SOGM_SPARSE_RESET");  // (one of the library's three environment switches)
-    c->sparse     = e ? atoi(e) != 0 : 1;
-    // default capacity per agent: one entry per 80 cells, at least 2^20 (the bench scenes log ~0.3 M entries per
-    // agent and tick at 200^3 x 20); sogm_set_sparse_reset changes it
-    const long long dflt = (long long)spec->L * spec->W * spec->H * spec->T / 80;
-    c->log_cap    = (int)(dflt < (1 << 20) ? (1 << 20) : (dflt > (1 << 26) ? (1 << 26) : dflt));
-  }
-  const size_t n   = (size_t)n_agents * spec->T * (size_t)c->geom.V;
-  hipError_t   e   = c->res.device(&c->pool.slot[0].grid, (n * c->cell_bytes() + 15) & ~(size_t)15);
-  sogm::sync_grid(c);
-  if (e == hipSuccess) e = c->res.device(&c->d_poses, sizeof(float) * 3 * n_agents, true);
-  if (e == hipSuccess) e = c->res.device(&c->d_stamps, sizeof(double) * n_agents, true);
-  if (e == hipSuccess) e = c->res.device(&c->d_scratch_vt, sizeof(float) * (size_t)c->geom.V * spec->T);
-  if (e == hipSuccess) e = c->res.device(&c->clear_cursor, 2 * sizeof(unsigned long long), true);
-  if (e == hipSuccess) e = c->res.stream(&c->side);
-  if (e == hipSuccess) e = c->res.stream(&c->side2);
-  if (e == hipSuccess) e = c->res.stream(&c->pstream);
-  if (e == hipSuccess) e = c->res.event(&c->ev_side2_go);
-  if (e == hipSuccess) e = c->res.event(&c->ev_side2_done);
-  if (e == hipSuccess) e = c->res.event(&c->ev_grid_free);
-  if (e == hipSuccess) e = c->res.event(&c->ev_cleared);
-  if (e == hipSuccess) e = c->res.event(&c->ev_gate_open);
-  if (e == hipSuccess) e = c->res.event(&c->ev_gate_frac);
-  // the memsets above are null-stream operations, which the non-blocking streams every later call uses do not wait for
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) {
-    sogm::set_error("sogm_create", e);
-    sogm_destroy(c);
-    return SOGM_ERR_HIP;
-  }
-  *out = c;
-  return SOGM_OK;
-}
-
-void sogm_destroy(sogm_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  c->res.release_all();
-  delete c;
-}
-
-int64_t sogm_grid_bytes(const sogm_ctx *c) {
-  return c ? (int64_t)c->n_agents * c->spec.T * (int64_t)c->geom.V * (int64_t)c->cell_bytes() : 0;
-}
-float *sogm_grid_ptr(sogm_ctx *c) {
-  if (!c) return nullptr;
-  if (c->update_pending) {  // an update flow still building this grid: the pointer is handed out complete
-    (void)hipStreamSynchronize(c->ustream);
-    c->update_pending = 0;
-  }
-  c->pool.dense_write_current();  // the caller may write cells the mark log does not see
-  return c->d_grid;
-}
-
-static const char *const k_tune_names[SOGM_TUNE_N] = {
-#define X(id, name, dflt, lo, hi) name,
-    SOGM_TUNING_TABLE(X)
-#undef X
-};
-static const double k_tune_range[SOGM_TUNE_N][2] = {
-#define X(id, name, dflt, lo, hi) {(double)(lo), (double)(hi)},
-    SOGM_TUNING_TABLE(X)
-#undef X
-};
-static int tune_index(const char *key) {
-  if (!key) return -1;
-  for (int i = 0; i < SOGM_TUNE_N; ++i)
-    if (std::strcmp(key, k_tune_names[i]) == 0) return i;
-  return -1;
-}
-int sogm_set_tuning(sogm_ctx *c, const char *key, double value) {
-  const int i = tune_index(key);
-  if (!c) return SOGM_ERR_INVALID_ARG;
-  if (i < 0) {
-    char buf[160];
-    std::snprintf(buf, sizeof(buf), "sogm_set_tuning: unknown key '%s'", key ? key : "(null)");
-    sogm::set_error_text(buf);
-    return SOGM_ERR_INVALID_ARG;
-  }
-  // the values end up as launch dimensions and ticket counts: NaN, infinities and anything outside the key's range
-  // (SOGM_TUNING_TABLE) are refused here rather than cast to int later
-  if (!(value >= k_tune_range[i][0] && value <= k_tune_range[i][1])) {
-    char buf[200];
-    std::snprintf(buf, sizeof(buf), "sogm_set_tuning: '%s' = %g is outside [%g, %g]", key, value, k_tune_range[i][0],
-                  k_tune_range[i][1]);
-    sogm::set_error_text(buf);
-    return SOGM_ERR_INVALID_ARG;
-  }
-  c->tune[i] = value;
-  return SOGM_OK;
-}
-int sogm_get_tuning(const sogm_ctx *c, const char *key, double *out) {
-  const int i = tune_index(key);
-  if (!c || !out || i < 0) return SOGM_ERR_INVALID_ARG;
-  *out = c->tune[i];
-  return SOGM_OK;
-}
-const char *sogm_tuning_key(int index) { return index >= 0 && index < SOGM_TUNE_N ? k_tune_names[index] : nullptr; }
-
-int sogm_set_resample(sogm_ctx *c, float replan_risk_rate, int num_resample, const float *normal_table_dev, int n_table) {
-  if (!c || !(replan_risk_rate >= 0.0f) || num_resample < 0 || n_table < 0) return SOGM_ERR_INVALID_ARG;
-  const bool on = replan_risk_rate > 0.0f && num_resample > 0;
-  if (on) {
-    if (!normal_table_dev || c->n_body <= 0 || n_table < 3 * c->n_body * num_resample) {
-      sogm::set_error_text("sogm_set_resample: the table must hold 3 * body particles * num_resample standard normals "
-                           "(call sogm_set_body_particles first)");
-      return SOGM_ERR_INVALID_ARG;
-    }
-    if (c->geom.half) {
-      sogm::set_error_text("sogm_set_resample: fractional weights need SOGM_STORE_F32 cells");
-      return SOGM_ERR_INVALID_ARG;
-    }
-  }
-  c->geom.rs_rate = on ? replan_risk_rate : 0.0f;
-  c->geom.rs_n    = on ? num_resample : 0;
-  c->geom.rs_z    = on ? normal_table_dev : nullptr;
-  c->geom.rs_nz   = on ? n_table : 0;
-  return SOGM_OK;
-}
-
-// diagnostics (tools/ only): one agent's CURRENT grid ([T][V] cells, device layout) copied to a device buffer in stream
-// order — no device synchronisation, no effect on the mark logs (unlike sogm_grid_ptr)
-int sogm_debug_copy_grid(sogm_ctx *c, int agent, void *dst_dev, void *stream) {
-  if (!c || !dst_dev || agent < 0 || agent >= c->n_agents) return SOGM_ERR_INVALID_ARG;
-  const size_t bytes = (size_t)c->spec.T * (size_t)c->geom.V * c->cell_bytes();
-  if (int rc = sogm::join_update(c, (hipStream_t)stream)) return rc;
-  SOGM_HIP_CHECK(hipMemcpyAsync(dst_dev, (const char *)c->d_grid + (size_t)agent * bytes, bytes, hipMemcpyDeviceToDevice,
-                                (hipStream_t)stream));
-  return SOGM_OK;
-}
-
-}  // extern "C"
-// every float whose bit pattern lies in [bits_lo, bits_hi) and its negative: GridGeom::div_res against the IEEE division
-__global__ __launch_bounds__(256) void k_div_check(sogm::GridGeom g, unsigned bits_lo, unsigned bits_hi, unsigned long long *out) {
-  const unsigned long long n    = (unsigned long long)(bits_hi - bits_lo);
-  const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
-  unsigned                 bad = 0, first = 0xFFFFFFFFu;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const unsigned b = bits_lo + (unsigned)i;
-    const float    a = __uint_as_float(b);
-    const float    q = g.div_res(a), t = a / g.res, qn = g.div_res(-a), tn = (-a) / g.res;
-    if (__float_as_uint(q) != __float_as_uint(t) || __float_as_uint(qn) != __float_as_uint(tn)) {
-      ++bad;
-      if (b < first) first = b;
-    }
-  }
-  if (bad) {
-    atomicAdd(out, (unsigned long long)bad);
-    atomicMin(out + 1, (unsigned long long)first);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[2] = (unsigned long long)g.fast_div;
-}
-extern "C" {
-// diagnostics (tests/ only): GridGeom::div_res — the three-instruction fp32 division the stamp and the search use — against
-// the IEEE division, on the device, for EVERY float in [lo, hi) and its negative.  out3_host = {mismatches, bit pattern of the
-// first one (2^64 - 1 if none), whether the context uses the fast sequence at all (its resolution is 0.15f)}
-int sogm_debug_div_check(sogm_ctx *c, float lo, float hi, unsigned long long *out3_host) {
-  if (!c || !out3_host || !(lo > 0.0f) || !(hi > lo)) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  unsigned long long *d = nullptr;
-  SOGM_HIP_CHECK(hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
-  const unsigned long long init[3] = {0ull, ~0ull, 0ull};
-  SOGM_HIP_CHECK(hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice));
-  unsigned bl, bh;
-  std::memcpy(&bl, &lo, 4);
-  std::memcpy(&bh, &hi, 4);
-  hipLaunchKernelGGL(k_div_check, dim3(4096), dim3(256), 0, nullptr, c->geom, bl, bh, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out3_host, d, sizeof(init), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  SOGM_HIP_CHECK(e);
-  return SOGM_OK;
-}
-
-enum { UF_ERR = 1024, UF_STAGE = 2048, UF_STAGE_STRIDE = 32 };  // the update flow's control words (k_update_flow)
-// diagnostics (tools/ only): the update flow's control words after a device synchronisation —
-// out = {epoch, pending, ticket, error, ...ctl[2..7], stage[A], map_ready[A]}
-int sogm_debug_update_flow(sogm_ctx *c, int32_t *out, int cap) {
-  if (!c || !out || cap < 10 + 2 * c->n_agents) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  (void)hipDeviceSynchronize();
-  const int A = c->n_agents;
-  out[0]      = c->map_epoch;
-  out[1]      = c->update_pending;
-  if (!c->d_update_ctl) return SOGM_ERR_STATE;
-  {
-    std::vector<int> w((size_t)(UF_STAGE + UF_STAGE_STRIDE * A));
-    SOGM_HIP_CHECK(hipMemcpy(w.data(), c->d_update_ctl, sizeof(int) * w.size(), hipMemcpyDeviceToHost));
-    out[2] = w[0];
-    out[3] = w[UF_ERR];
-    for (int a = 0; a < A; ++a) out[10 + a] = w[(size_t)(UF_STAGE + UF_STAGE_STRIDE * a)];
-  }
-  SOGM_HIP_CHECK(hipMemcpy(out + 10 + A, c->d_map_ready, sizeof(int) * A, hipMemcpyDeviceToHost));
-  return SOGM_OK;
-}
-// ... and its per-agent stamps [A][4] (100 MHz wall clock) + the order it took the agents in [A]
-int sogm_debug_update_flow_times(sogm_ctx *c, int64_t *out_ts, int32_t *out_order) {
-  if (!c || !out_ts || !out_order || !c->d_update_ts) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  (void)hipDeviceSynchronize();
-  SOGM_HIP_CHECK(hipMemcpy(out_ts, c->d_update_ts, sizeof(long long) * 4 * c->n_agents, hipMemcpyDeviceToHost));
-  SOGM_HIP_CHECK(hipMemcpy(out_order, c->d_update_order, sizeof(int) * c->n_agents, hipMemcpyDeviceToHost));
-  return SOGM_OK;
-}
-int sogm_set_profiling(sogm_ctx *c, int enable) {
-  return sogm_set_profiling_slots(c, enable ? (1 << SOGM_PROF_N) - 1 : 0);
-}
-
-int sogm_set_profiling_slots(sogm_ctx *c, int slot_mask) {
-  if (!c || slot_mask < 0 || slot_mask >= (1 << SOGM_PROF_N)) return SOGM_ERR_INVALID_ARG;
-  c->profiling = slot_mask;
-  for (int k = 0; k < SOGM_PROF_N; ++k) c->ring_n[k] = 0;
-  return SOGM_OK;
-}
-
-int sogm_profile_read(sogm_ctx *c, double *out_ms) {
-  if (!c || !out_ms) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  for (int k = 0; k < SOGM_PROF_N; ++k) {
-    out_ms[k] = -1.0;
-    if (c->ring_n[k] <= 0 || c->ring[k].empty()) continue;
-    hipEvent_t *p  = c->ring[k].data() + 2 * ((c->ring_n[k] - 1) % SOGM_PROF_RING);
-    float       ms = 0.f;
-    if (hipEventElapsedTime(&ms, p[0], p[1]) == hipSuccess) out_ms[k] = (double)ms;
-  }
-  return SOGM_OK;
-}
-
-int sogm_profile_read_all(sogm_ctx *c, int slot, double *out_ms, int cap, int *out_n) {
-  if (!c || !out_ms || !out_n || slot < 0 || slot >= SOGM_PROF_N || cap < 0) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  long long n = c->ring_n[slot];
-  if (n > SOGM_PROF_RING) n = SOGM_PROF_RING;
-  if (n > cap) n = cap;
-  *out_n = 0;
-  if (c->ring[slot].empty()) return SOGM_OK;
-  for (long long i = c->ring_n[slot] - n; i < c->ring_n[slot]; ++i) {  // oldest kept launch first
-    hipEvent_t *p  = c->ring[slot].data() + 2 * (i % SOGM_PROF_RING);
-    float       ms = 0.f;
-    if (hipEventElapsedTime(&ms, p[0], p[1]) != hipSuccess) ms = -1.f;
-    out_ms[(*out_n)++] = (double)ms;
-  }
-  return SOGM_OK;
-}
-
-int sogm_set_body_particles(sogm_ctx *c, const double *xyz, int n) {
-  if (!c || !xyz || n <= 0) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  c->res.release(&c->d_body);
-  SOGM_HIP_CHECK(c->res.device(&c->d_body, sizeof(double) * 3 * n));
-  SOGM_HIP_CHECK(hipMemcpy(c->d_body, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
-  c->n_body = n;
-  for (int k = 0; k < 3; ++k) {
-    double m = 0.0;
-    for (int e = 0; e < n; ++e) m = std::fabs(xyz[e * 3 + k]) > m ? std::fabs(xyz[e * 3 + k]) : m;
-    c->geom.body_ext[k] = (float)m;
-  }
-  return SOGM_OK;
-}
-
-static int clear_grid(sogm_ctx *c, hipStream_t st) { return sogm::reset_slot(c, st, c->pool.current(), c->d_grid, false); }
-
 // ---- update flow (tuning key update_flow): the maps of a lock-step tick agent by agent ----
 // One persistent launch of one-wave workgroups over tickets; an agent's tickets are consecutive (bits, marks, overlay) and
 // agents are taken in `order` (the previous tick's longest chains first), so the first agents' maps are complete after the
@@ -1959,7 +1416,7 @@ struct UpdateFlowDev {
   MapFrame              frame;
   OverlayIO             ov;
   int                   n_agents, n_bits, n_marks, n_splat;
-  int                  *ctl;      // ticket, error and per-agent progress words (UF_* below)
+  int                  *ctl;      // ticket, error and per-agent progress words (layout: UpdateBlock, sogm_handover.hpp)
   int                   chunk;    // consecutive tickets per claim
   long long            *ts;       // [A][4] wall clock: first ticket claimed, bits complete, marks complete, map ready (diagnostics)
   int                  *map_ready;
@@ -1967,25 +1424,21 @@ struct UpdateFlowDev {
   const int            *order;
 };
 // (no LDS: the replan's corridor workgroups, resident beside this kernel and waiting for routes, hold every CU's LDS)
-// Control words, each on a line of its own (thousands of waves claim tickets, bump and poll them — in one 128-byte line that
-// line's memory channel is the bottleneck, as the flight's header showed): ticket at ctl[0], error at ctl[UF_ERR], the
-// per-agent progress counters at ctl[UF_STAGE + 32 agent].
-extern "C++" {
 template <bool CACHED>
 __global__ __launch_bounds__(64) void k_update_flow(GridGeom g, UpdateFlowDev u) {
   const int lane  = threadIdx.x;
   const int per   = u.n_bits + u.n_marks + u.n_splat;
   const int total = u.n_agents * per;
-  int      *err   = u.ctl + UF_ERR;
+  int      *err   = u.ctl + UpdateBlock::err();
   for (;;) {
     int t0 = 0;
-    if (lane == 0) t0 = atomicAdd(&u.ctl[0], u.chunk);  // a chunk of consecutive tickets per claim
+    if (lane == 0) t0 = atomicAdd(&u.ctl[UpdateBlock::ticket()], u.chunk);  // a chunk of consecutive tickets per claim
     t0 = __builtin_amdgcn_readfirstlane(t0);
     if (t0 >= total) break;
     for (int t = t0; t < t0 + u.chunk && t < total; ++t) {
       const int agent = u.order[t / per];
       const int s     = t % per;
-      int      *stage = u.ctl + UF_STAGE + UF_STAGE_STRIDE * agent;
+      int      *stage = UpdateBlock::stage_word(u.ctl, agent);
       bool      last  = false;
       if (s == 0 && lane == 0) u.ts[agent * 4] = wall_clock64();
       if (s < u.n_bits) {
@@ -2014,12 +1467,10 @@ __global__ __launch_bounds__(64) void k_update_flow(GridGeom g, UpdateFlowDev u)
     }
   }
 }
-}  // extern "C++"
 __global__ void k_iota(int *p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = i;
 }
-namespace sogm {
 // stream, events and words of the update flow (first use)
 static int update_flow_setup(sogm_ctx *c) {
   if (c->ustream) return SOGM_OK;
@@ -2029,7 +1480,7 @@ static int update_flow_setup(sogm_ctx *c) {
   SOGM_HIP_CHECK(c->res.event(&c->ev_uin));
   SOGM_HIP_CHECK(c->res.event(&c->ev_udone));
   SOGM_HIP_CHECK(c->res.device(&c->d_map_ready, sizeof(int) * A, true));
-  SOGM_HIP_CHECK(c->res.device(&c->d_update_ctl, sizeof(int) * (size_t)(UF_STAGE + UF_STAGE_STRIDE * A)));
+  SOGM_HIP_CHECK(c->res.device(&c->d_update_ctl, sizeof(int) * UpdateBlock::words(A)));
   SOGM_HIP_CHECK(c->res.device(&c->d_update_order, sizeof(int) * A));
   SOGM_HIP_CHECK(c->res.device(&c->d_update_ts, sizeof(long long) * 4 * A, true));
   hipLaunchKernelGGL(k_iota, dim3((A + 255) / 256), dim3(256), 0, nullptr, c->d_update_order, A);
@@ -2037,135 +1488,167 @@ static int update_flow_setup(sogm_ctx *c) {
   SOGM_HIP_CHECK(hipStreamSynchronize(nullptr));  // (null-stream work is not ordered with the non-blocking streams)
   return setup.done();
 }
-}  // namespace sogm
 
-// updateMap for every agent; with `records` (sogm_update_gt_swarm) the neighbour overlay follows in the same call
-static int update_gt_impl(sogm_ctx *c, const float *cloud_xyz, const int32_t *cloud_range,
-                          const SogmCylinder *cylinders, int n_cyl, const float *poses, const double *stamps,
-                          const SogmTrajRecord *records, int n_records, const int32_t *ego_ids, bool fused,
-                          hipStream_t st, const SogmWorld *world = nullptr) {
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  sogm::CloudBlocks cb{};
+// ------------------------------------------------------------------------------------------------
+// The lock-step update's host side (sogm_update_gt / _gt_swarm / _world): one function per step, in launch order.
+// ------------------------------------------------------------------------------------------------
+// The crop lists of a SogmWorld frame (they may grow, which drains the device: before anything of this tick is launched), then
+// the caller's stream behind whatever still builds or feeds what this update touches.
+static int update_joins(sogm_ctx *c, hipStream_t st, const SogmWorld *world, bool records, CloudBlocks *cb) {
   if (world)
-    if (int rc = sogm::world_blocks(c, world, &cb)) return rc;
-  const int A = c->n_agents;
-  if (int rc = sogm::join_update(c, st)) return rc;    // an update flow of the previous tick nobody joined
-  if (int rc = sogm::join_prestamp(c, st)) return rc;  // a pre-stamp of the last replan may still be running
-  if (fused)
-    if (int rc = sogm::join_exchange(c, st)) return rc;  // records may come from an all-gather in flight
-  // (poses / stamps are filed into the context by k_cull_cylinders below)
+    if (int rc = world_blocks(c, world, cb)) return rc;
+  if (int rc = join_update(c, st)) return rc;    // an update flow of the previous tick nobody joined
+  if (int rc = join_prestamp(c, st)) return rc;  // a pre-stamp of the last replan may still be running
+  if (records)
+    if (int rc = join_exchange(c, st)) return rc;  // records may come from an all-gather in flight
+  return SOGM_OK;
+}
+// The grid this update builds into, zero on `st`: the pool's pre-cleared one, or the current one cleared here.
+static int take_grid(sogm_ctx *c, hipStream_t st) {
   // A grid the previous replan pre-stamped is not what this call builds (other inputs): it is the front of the ready
   // queue, i.e. the grid adopted below — its marks are in its log, so it is reset again before the stamp.
   const int stale = c->pool.discard_prestamp();
   c->records_final_valid = 0;
   if (c->pool.precleared()) {
     // the grid was already cleared on the side stream during the previous tick
-    int rc = sogm::adopt_preclear(c, st);
-    if (rc) return rc;
-    if (stale >= 0 && c->pool.current() == stale) {
-      rc = sogm::reset_slot(c, st, stale, c->d_grid, false);
-      if (rc) return rc;
-    }
+    if (int rc = adopt_preclear(c, st)) return rc;
+    if (stale >= 0 && c->pool.current() == stale)
+      if (int rc = reset_slot(c, st, stale, c->d_grid, false)) return rc;
     if (stale >= 0 && c->d_stamp_bits) {
       // a pre-stamp that was cut short (a failed tick) may have left occupancy bits behind — only consumed words are
       // zeroed — and they are relative to ITS map centres: start this stamp from a clean mask
-      const int words = sogm::stamp_bits_words(c->geom);
-      SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * (size_t)words * A, st));
+      const size_t words = (size_t)stamp_bits_words(c->geom) * (size_t)c->n_agents;
+      SOGM_HIP_CHECK(hipMemsetAsync(c->d_stamp_bits, 0, sizeof(unsigned) * words, st));
     }
-  } else {
-    int rc = clear_grid(c, st);
-    if (rc) return rc;
-    if (c->overlap >= 2 && c->pool.first_dirty() >= 0 && c->clear_gate && c->tune_i(SOGM_TUNE_CLEAR_EARLY)) {
-      // tuning-aid mode: the pool's spare grids (dirty at the start, no readers) are cleared from here on as well,
-      // so that a run of updates alone exercises the pooled clear (tools/diag_clear_pmc.py)
-      rc = sogm::queue_spare_clears_ahead(c, st);
-      if (rc) return rc;
-    }
-  }
-  // candidate cylinders per agent, then one-wave workgroups stride over each agent's cloud range
-  sogm::MapTarget tgt{};
-  if (int rc = sogm::map_target(c, c->pool.current(), false, st, &tgt)) return rc;
-  const int words = tgt.words;
-  const int stamp_wgs = c->tune_i(SOGM_TUNE_STAMP_WGS) > 0 ? c->tune_i(SOGM_TUNE_STAMP_WGS) : 256;  // one-wave workgroups per agent
-  c->n_stamps++;
-  prof_begin(c, SOGM_PROF_STAMP, st);
-  hipLaunchKernelGGL(k_cull_cylinders, dim3(A), dim3(64), 0, st, c->geom, cylinders, n_cyl, poses,
-                     (CylCand *)c->d_cand, c->d_ncand, stamps, c->d_poses, c->d_stamps, cb, c->h_tick_clock);
-  if (world && c->tune_i(SOGM_TUNE_UPDATE_FLOW) != 0) {
-    // the maps agent by agent on the flow's stream; the caller's stream goes on (sogm_replan's searches wait per agent,
-    // everything else joins the flow's end: sogm::join_update)
-    if (int rc = sogm::update_flow_setup(c)) return rc;
-    const int           n_rec = fused ? n_records : 0;
-    const UpdateFlowDev u{
-        .tgt       = tgt,
-        .frame     = {.cloud = cloud_xyz, .cloud_range = nullptr, .cb = cb, .cyl = cylinders, .n_cyl = n_cyl},
-        .ov        = {.rec = records, .n_rec = n_rec, .ego_ids = ego_ids, .body = c->d_body, .n_body = c->n_body},
-        .n_agents  = A,
-        .n_bits    = c->tune_i(SOGM_TUNE_UPDATE_BITS),
-        .n_marks   = c->tune_i(SOGM_TUNE_UPDATE_MARKS),
-        .n_splat   = n_rec > 0 ? c->tune_i(SOGM_TUNE_UPDATE_SPLAT) : 0,
-        .ctl       = c->d_update_ctl,
-        .chunk     = c->tune_i(SOGM_TUNE_UPDATE_CHUNK) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_CHUNK) : 1,
-        .ts        = c->d_update_ts,
-        .map_ready = c->d_map_ready,
-        .epoch     = ++c->map_epoch,
-        .order     = c->d_update_order};
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    int wgs = c->tune_i(SOGM_TUNE_UPDATE_WGS) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_WGS) : 16 * n_cu;
-    const int total = A * (u.n_bits + u.n_marks + u.n_splat);
-    if (wgs > total) wgs = total;
-    SOGM_HIP_CHECK(hipEventRecord(c->ev_uin, st));
-    SOGM_HIP_CHECK(hipStreamWaitEvent(c->ustream, c->ev_uin, 0));
-    SOGM_HIP_CHECK(hipMemsetAsync(c->d_update_ctl, 0, sizeof(int) * (size_t)(UF_STAGE + UF_STAGE_STRIDE * A), c->ustream));
-    if (c->tune_i(SOGM_TUNE_UPDATE_CACHED))
-      hipLaunchKernelGGL(k_update_flow<true>, dim3(wgs), dim3(64), 0, c->ustream, c->geom, u);
-    else
-      hipLaunchKernelGGL(k_update_flow<false>, dim3(wgs), dim3(64), 0, c->ustream, c->geom, u);
-    SOGM_HIP_CHECK(hipGetLastError());
-    prof_end(c, SOGM_PROF_STAMP, c->ustream);
-    SOGM_HIP_CHECK(hipEventRecord(c->ev_udone, c->ustream));
-    c->update_pending = 1;
-    c->updated        = 1;
     return SOGM_OK;
   }
-  const int bits_wgs = c->tune_i(SOGM_TUNE_STAMP_BITS_WGS) > 0 ? c->tune_i(SOGM_TUNE_STAMP_BITS_WGS) : stamp_wgs;
-  if (world)
-    hipLaunchKernelGGL(k_stamp_bits_blocks, dim3(bits_wgs, A), dim3(64), 0, st, c->geom, cloud_xyz, cb, c->d_poses,
-                       c->d_stamp_bits, words);
+  if (int rc = reset_slot(c, st, c->pool.current(), c->d_grid, false)) return rc;
+  // tuning-aid mode: the pool's spare grids (dirty at the start, no readers) are cleared from here on as well,
+  // so that a run of updates alone exercises the pooled clear (tools/diag_clear_pmc.py)
+  if (c->overlap >= 2 && c->pool.first_dirty() >= 0 && c->clear_gate && c->tune_i(SOGM_TUNE_CLEAR_EARLY))
+    return queue_spare_clears_ahead(c, st);
+  return SOGM_OK;
+}
+// Candidate cylinders (and cloud blocks of a SogmWorld frame) per agent; the kernel also files the update's poses and stamps
+// into the target's arrays, where the later kernels of the update and the queries read them.
+static void launch_cull(sogm_ctx *c, hipStream_t st, const MapFrame &f, const MapTarget &tgt, const float *poses,
+                        const double *stamps) {
+  hipLaunchKernelGGL(k_cull_cylinders, dim3(c->n_agents), dim3(64), 0, st, c->geom, f.cyl, f.n_cyl, poses, (CylCand *)tgt.cand,
+                     tgt.n_cand, stamps, tgt.poses, tgt.stamps, f.cb, c->h_tick_clock);
+}
+// The maps agent by agent on the flow's stream, behind the cull on `st`; the caller's stream goes on (sogm_replan's searches
+// wait per agent, everything else joins the flow's end: join_update).  Closes the stamp's profiling pair on the flow's stream.
+static int launch_update_flow(sogm_ctx *c, hipStream_t st, const MapFrame &f, const MapTarget &tgt, const OverlayIO *ov) {
+  if (int rc = update_flow_setup(c)) return rc;
+  const int           A = c->n_agents;
+  const UpdateFlowDev u{.tgt       = tgt,
+                        .frame     = f,
+                        .ov        = ov ? *ov : OverlayIO{},
+                        .n_agents  = A,
+                        .n_bits    = c->tune_i(SOGM_TUNE_UPDATE_BITS),
+                        .n_marks   = c->tune_i(SOGM_TUNE_UPDATE_MARKS),
+                        .n_splat   = ov && ov->n_rec > 0 ? c->tune_i(SOGM_TUNE_UPDATE_SPLAT) : 0,
+                        .ctl       = c->d_update_ctl,
+                        .chunk     = c->tune_i(SOGM_TUNE_UPDATE_CHUNK) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_CHUNK) : 1,
+                        .ts        = c->d_update_ts,
+                        .map_ready = c->d_map_ready,
+                        .epoch     = ++c->map_epoch,
+                        .order     = c->d_update_order};
+  int n_cu = 256;
+  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
+  int       wgs   = c->tune_i(SOGM_TUNE_UPDATE_WGS) > 0 ? c->tune_i(SOGM_TUNE_UPDATE_WGS) : 16 * n_cu;
+  const int total = A * (u.n_bits + u.n_marks + u.n_splat);
+  if (wgs > total) wgs = total;
+  SOGM_HIP_CHECK(hipEventRecord(c->ev_uin, st));
+  SOGM_HIP_CHECK(hipStreamWaitEvent(c->ustream, c->ev_uin, 0));
+  SOGM_HIP_CHECK(hipMemsetAsync(c->d_update_ctl, 0, sizeof(int) * UpdateBlock::words(A), c->ustream));
+  if (c->tune_i(SOGM_TUNE_UPDATE_CACHED))
+    hipLaunchKernelGGL(k_update_flow<true>, dim3(wgs), dim3(64), 0, c->ustream, c->geom, u);
   else
-    hipLaunchKernelGGL(k_stamp_bits, dim3(bits_wgs, A), dim3(64), 0, st, c->geom, cloud_xyz, cloud_range, c->d_poses,
-                       c->d_stamp_bits, words, 0);
-  const sogm::MarkLog lg = tgt.lg;
+    hipLaunchKernelGGL(k_update_flow<false>, dim3(wgs), dim3(64), 0, c->ustream, c->geom, u);
+  SOGM_HIP_CHECK(hipGetLastError());
+  prof_end(c, SOGM_PROF_STAMP, c->ustream);
+  SOGM_HIP_CHECK(hipEventRecord(c->ev_udone, c->ustream));
+  c->update_pending = 1;
+  return SOGM_OK;
+}
+// The lock-step stamp: one-wave workgroups stride over each agent's listed blocks or cloud range and set the occupancy bits,
+// then over its mask words and write the marks.
+static void launch_stamp(sogm_ctx *c, hipStream_t st, const MapFrame &f, const MapTarget &tgt) {
+  const int A         = c->n_agents;
+  const int stamp_wgs = c->tune_i(SOGM_TUNE_STAMP_WGS) > 0 ? c->tune_i(SOGM_TUNE_STAMP_WGS) : 256;  // one-wave workgroups per agent
+  const int bits_wgs  = c->tune_i(SOGM_TUNE_STAMP_BITS_WGS) > 0 ? c->tune_i(SOGM_TUNE_STAMP_BITS_WGS) : stamp_wgs;
+  if (f.cb.bounds)
+    hipLaunchKernelGGL(k_stamp_bits_blocks, dim3(bits_wgs, A), dim3(64), 0, st, c->geom, f.cloud, f.cb, tgt.poses, tgt.bits,
+                       tgt.words);
+  else
+    hipLaunchKernelGGL(k_stamp_bits, dim3(bits_wgs, A), dim3(64), 0, st, c->geom, f.cloud, f.cloud_range, tgt.poses, tgt.bits,
+                       tgt.words, 0);
   // (dynamic LDS the kernel does not use bounds its waves per CU: the marks' scattered stores merge worse in L2 the more
   //  waves interleave theirs — tuning key stamp_lds_kb, 160 / kb workgroups per CU)
   const size_t marks_lds = (size_t)c->tune_i(SOGM_TUNE_STAMP_LDS_KB) * 1024;
-  if (c->tune_i(SOGM_TUNE_STAMP_CACHED))
-    hipLaunchKernelGGL(k_stamp_marks_cached, dim3(stamp_wgs, A), dim3(64), marks_lds, st, c->geom, (void *)c->d_grid,
-                       c->d_stamp_bits, words, cylinders, n_cyl, c->d_poses, (const CylCand *)c->d_cand,
-                       (const int *)c->d_ncand, 0, lg);
-  else
-  {
+  if (c->tune_i(SOGM_TUNE_STAMP_CACHED)) {
+    hipLaunchKernelGGL(k_stamp_marks_cached, dim3(stamp_wgs, A), dim3(64), marks_lds, st, c->geom, tgt.grid, tgt.bits,
+                       tgt.words, f.cyl, f.n_cyl, tgt.poses, (const CylCand *)tgt.cand, (const int *)tgt.n_cand, 0, tgt.lg);
+  } else {
     // the log pass's sector cache: T x 64 words of LDS per (one-wave) workgroup, in front of the tuning aid's padding
-    const int    lds_log = lg.entries && c->spec.T <= 64 && c->tune_i(SOGM_TUNE_STAMP_LDS_LOG) ? 1 : 0;
+    const int    lds_log = tgt.lg.entries && c->spec.T <= 64 && c->tune_i(SOGM_TUNE_STAMP_LDS_LOG) ? 1 : 0;
     const size_t lds     = marks_lds + (lds_log ? sizeof(unsigned) * 64 * (size_t)c->spec.T : 0);
-    hipLaunchKernelGGL(k_stamp_marks, dim3(stamp_wgs, A), dim3(64), lds, st, c->geom, (void *)c->d_grid, c->d_stamp_bits,
-                       words, cylinders, n_cyl, c->d_poses, (const CylCand *)c->d_cand, (const int *)c->d_ncand, 0, lg, lds_log);
+    hipLaunchKernelGGL(k_stamp_marks, dim3(stamp_wgs, A), dim3(64), lds, st, c->geom, tgt.grid, tgt.bits, tgt.words, f.cyl,
+                       f.n_cyl, tgt.poses, (const CylCand *)tgt.cand, (const int *)tgt.n_cand, 0, tgt.lg, lds_log);
   }
-  prof_end(c, SOGM_PROF_STAMP, st);
+}
+// The neighbours' records of `ov` into the CURRENT grid of every agent: one lane per (agent, record, slice) item, unless
+// max_workgroups > 0 narrows the launch (its lanes then stride over the items).  wait_stage / wait_err (or null): the launch
+// runs under the tail of the pre-stamp that builds this grid, and every lane waits for its agent's completion word
+// (k_splat_neighbours).  The caller has joined whatever writes the grid or the records.
+static int launch_overlay(sogm_ctx *c, hipStream_t st, const OverlayIO &ov, const int *wait_stage, int *wait_err,
+                          int max_workgroups) {
+  const long long total = (long long)c->n_agents * ov.n_rec * c->spec.T;
+  long long       nblk  = (total + 255) / 256;
+  if (max_workgroups > 0 && nblk > max_workgroups) nblk = max_workgroups;
+  prof_begin(c, SOGM_PROF_SPLAT, st);
+  hipLaunchKernelGGL(k_splat_neighbours, dim3((unsigned)nblk), dim3(256), 0, st, c->geom, (void *)c->d_grid, ov.rec, ov.n_rec,
+                     ov.ego_ids, c->d_poses, c->d_stamps, ov.body, ov.n_body, c->n_agents, 0, mark_log(c, c->pool.current()),
+                     wait_stage, wait_err);
+  prof_end(c, SOGM_PROF_SPLAT, st);
   SOGM_HIP_CHECK(hipGetLastError());
-  if (fused && n_records > 0) {
-    const long long total = (long long)A * n_records * c->spec.T;
-    prof_begin(c, SOGM_PROF_SPLAT, st);
-    hipLaunchKernelGGL(k_splat_neighbours, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, c->geom,
-                       (void *)c->d_grid, records, n_records, ego_ids, c->d_poses, c->d_stamps, c->d_body, c->n_body,
-                       A, 0, lg, nullptr, nullptr);
-    prof_end(c, SOGM_PROF_SPLAT, st);
+  return SOGM_OK;
+}
+static OverlayIO overlay_io(const sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids) {
+  return OverlayIO{.rec = records, .n_rec = n_records, .ego_ids = ego_ids, .body = c->d_body, .n_body = c->n_body};
+}
+
+// updateMap for every agent; with `ov` the neighbour overlay follows in the same call.  `world` (or null): the frame is a
+// SogmWorld's — its crop lists are the context's (frame.cb is filled here) and the tuning key update_flow applies.
+static int update_maps(sogm_ctx *c, hipStream_t st, MapFrame frame, const SogmWorld *world, const float *poses,
+                       const double *stamps, const OverlayIO *ov) {
+  SOGM_HIP_CHECK(hipSetDevice(c->device));
+  if (int rc = update_joins(c, st, world, ov != nullptr, &frame.cb)) return rc;
+  if (int rc = take_grid(c, st)) return rc;
+  MapTarget tgt{};
+  if (int rc = map_target(c, c->pool.current(), false, st, &tgt)) return rc;
+  c->n_stamps++;
+  prof_begin(c, SOGM_PROF_STAMP, st);
+  launch_cull(c, st, frame, tgt, poses, stamps);
+  if (world && c->tune_i(SOGM_TUNE_UPDATE_FLOW) != 0) {
+    if (int rc = launch_update_flow(c, st, frame, tgt, ov)) return rc;
+  } else {
+    launch_stamp(c, st, frame, tgt);
+    prof_end(c, SOGM_PROF_STAMP, st);
     SOGM_HIP_CHECK(hipGetLastError());
+    if (ov && ov->n_rec > 0)
+      if (int rc = launch_overlay(c, st, *ov, nullptr, nullptr, 0)) return rc;
   }
   c->updated = 1;
   return SOGM_OK;
 }
+
+}  // namespace sogm
+
+using namespace sogm;
+
+extern "C" {
 
 int sogm_update_gt(sogm_ctx *c, const float *cloud_xyz, const int32_t *cloud_range,
                    const SogmCylinder *cylinders, int n_cyl, const float *poses,
@@ -2173,8 +1656,8 @@ int sogm_update_gt(sogm_ctx *c, const float *cloud_xyz, const int32_t *cloud_ran
   if (!c || !cloud_xyz || !cloud_range || !poses || !stamps || n_cyl < 0 ||
       (n_cyl > 0 && !cylinders))
     return SOGM_ERR_INVALID_ARG;
-  return update_gt_impl(c, cloud_xyz, cloud_range, cylinders, n_cyl, poses, stamps, nullptr, 0, nullptr, false,
-                        (hipStream_t)stream);
+  const MapFrame frame{.cloud = cloud_xyz, .cloud_range = cloud_range, .cb = {}, .cyl = cylinders, .n_cyl = n_cyl};
+  return update_maps(c, (hipStream_t)stream, frame, nullptr, poses, stamps, nullptr);
 }
 
 int sogm_update_gt_swarm(sogm_ctx *c, const float *cloud_xyz, const int32_t *cloud_range,
@@ -2184,39 +1667,9 @@ int sogm_update_gt_swarm(sogm_ctx *c, const float *cloud_xyz, const int32_t *clo
       n_records < 0 || (n_records > 0 && !records) || !ego_ids)
     return SOGM_ERR_INVALID_ARG;
   if (!c->d_body || c->n_body <= 0) return SOGM_ERR_STATE;
-  return update_gt_impl(c, cloud_xyz, cloud_range, cylinders, n_cyl, poses, stamps, records, n_records, ego_ids,
-                        true, (hipStream_t)stream);
-}
-
-__global__ void k_device_clock(long long *out) { *out = wall_clock64(); }
-int sogm_device_clock(sogm_ctx *c, int64_t *out_ticks, void *stream) {
-  if (!c || !out_ticks) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (!c->h_tick_clock) {
-    SOGM_HIP_CHECK(c->res.pinned(&c->h_tick_clock, sizeof(long long) * 4, hipHostMallocMapped));
-    for (int i = 0; i < 4; ++i) c->h_tick_clock[i] = 0;
-  }
-  hipLaunchKernelGGL(k_device_clock, dim3(1), dim3(1), 0, (hipStream_t)stream, c->h_tick_clock + 2);
-  SOGM_HIP_CHECK(hipGetLastError());
-  SOGM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  *out_ticks = (int64_t) * (volatile long long *)(c->h_tick_clock + 2);
-  return SOGM_OK;
-}
-int sogm_tick_clock(sogm_ctx *c, int64_t *out2) {
-  if (!c || !out2) return SOGM_ERR_INVALID_ARG;
-  volatile long long *h = c->h_tick_clock;
-  out2[0] = h ? (int64_t)h[0] : 0;
-  out2[1] = h ? (int64_t)h[1] : 0;
-  return SOGM_OK;
-}
-
-int sogm_cloud_block_bounds(const float *cloud_xyz, int n_points, int block_points, float *out_bounds, void *stream) {
-  if (!cloud_xyz || !out_bounds || n_points < 0 || block_points < 64 || block_points > 4096) return SOGM_ERR_INVALID_ARG;
-  const int nb = (n_points + block_points - 1) / block_points;
-  if (nb == 0) return SOGM_OK;
-  hipLaunchKernelGGL(k_block_bounds, dim3(nb), dim3(64), 0, (hipStream_t)stream, cloud_xyz, n_points, block_points, out_bounds);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
+  const MapFrame  frame{.cloud = cloud_xyz, .cloud_range = cloud_range, .cb = {}, .cyl = cylinders, .n_cyl = n_cyl};
+  const OverlayIO ov = overlay_io(c, records, n_records, ego_ids);
+  return update_maps(c, (hipStream_t)stream, frame, nullptr, poses, stamps, &ov);
 }
 
 int sogm_update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const double *stamps,
@@ -2226,8 +1679,10 @@ int sogm_update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const
       (w->n_cyl > 0 && !w->cylinders) || n_records < 0 || (n_records > 0 && (!records || !ego_ids)))
     return SOGM_ERR_INVALID_ARG;
   if (n_records > 0 && (!c->d_body || c->n_body <= 0)) return SOGM_ERR_STATE;
-  return update_gt_impl(c, w->cloud_xyz, nullptr, w->cylinders, w->n_cyl, poses, stamps, records, n_records, ego_ids,
-                        n_records > 0, (hipStream_t)stream, w);
+  // (cb: the context's crop lists, sized for this frame inside the update)
+  const MapFrame  frame{.cloud = w->cloud_xyz, .cloud_range = nullptr, .cb = {}, .cyl = w->cylinders, .n_cyl = w->n_cyl};
+  const OverlayIO ov = overlay_io(c, records, n_records, ego_ids);
+  return update_maps(c, (hipStream_t)stream, frame, w, poses, stamps, n_records > 0 ? &ov : nullptr);
 }
 
 int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
@@ -2261,30 +1716,15 @@ int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_rec
     if (c->pdone_pending && hipEventQuery(c->ev_pdone) == hipSuccess)
       if (int rc = sogm::join_prestamp(c, st)) return rc;
     (void)hipGetLastError();  // (hipErrorNotReady is not an error here)
-    const int      *stage = c->pdone_pending ? c->ps_stage : nullptr;
-    const long long total = (long long)c->n_agents * n_records * c->spec.T;
-    long long       nblk  = (total + 255) / 256;
+    const int *stage = c->pdone_pending ? c->ps_stage : nullptr;
     // workgroups of the waiting launch (128 / 256 / 512 / 2048: 11.22 / 11.25 / 11.31 / 11.26 ms per tick)
     const int cap = c->tune_i(SOGM_TUNE_SPLAT_WGS) > 0 ? c->tune_i(SOGM_TUNE_SPLAT_WGS) : 256;
-    if (stage && nblk > cap) nblk = cap;
-    prof_begin(c, SOGM_PROF_SPLAT, st);
-    hipLaunchKernelGGL(k_splat_neighbours, dim3((unsigned)nblk), dim3(256), 0, st, c->geom, (void *)c->d_grid, records,
-                       n_records, ego_ids, c->d_poses, c->d_stamps, c->d_body, c->n_body, c->n_agents, 0,
-                       sogm::mark_log(c, c->pool.current()), stage, c->ps_err);
-    prof_end(c, SOGM_PROF_SPLAT, st);
-    SOGM_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_overlay(c, st, overlay_io(c, records, n_records, ego_ids), stage, c->ps_err, stage ? cap : 0)) return rc;
   }
   if (int rc = sogm::join_prestamp(c, st)) return rc;  // whatever follows is behind the pre-stamp's end
   if (int rc = sogm::retire_wide_clear(c, st)) return rc;
   c->updated = 1;
   return SOGM_OK;
-}
-
-int sogm_prestamp_pending(const sogm_ctx *c) { return c && c->pool.prestamp_pending() ? 1 : 0; }
-int sogm_prestamp_join(sogm_ctx *c, void *stream) {
-  if (!c) return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  return sogm::join_prestamp(c, (hipStream_t)stream);
 }
 
 int sogm_project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_records,
@@ -2296,141 +1736,52 @@ int sogm_project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_re
   SOGM_HIP_CHECK(hipSetDevice(c->device));
   if (int rc = sogm::join_update(c, (hipStream_t)stream)) return rc;
   if (int rc = sogm::join_exchange(c, (hipStream_t)stream)) return rc;  // records may come from an all-gather in flight
-  const long long total = (long long)c->n_agents * n_records * c->spec.T;
-  const int       nblk  = (int)((total + 255) / 256);
-  prof_begin(c, SOGM_PROF_SPLAT, (hipStream_t)stream);
-  hipLaunchKernelGGL(k_splat_neighbours, dim3(nblk), dim3(256), 0, (hipStream_t)stream, c->geom,
-                     (void *)c->d_grid, records, n_records, ego_ids, c->d_poses, c->d_stamps, c->d_body,
-                     c->n_body, c->n_agents, 0, sogm::mark_log(c, c->pool.current()), nullptr, nullptr);
-  prof_end(c, SOGM_PROF_SPLAT, (hipStream_t)stream);
+  return launch_overlay(c, (hipStream_t)stream, overlay_io(c, records, n_records, ego_ids), nullptr, nullptr, 0);
+}
+
+int sogm_cloud_block_bounds(const float *cloud_xyz, int n_points, int block_points, float *out_bounds, void *stream) {
+  if (!cloud_xyz || !out_bounds || n_points < 0 || block_points < 64 || block_points > 4096) return SOGM_ERR_INVALID_ARG;
+  const int nb = (n_points + block_points - 1) / block_points;
+  if (nb == 0) return SOGM_OK;
+  hipLaunchKernelGGL(k_block_bounds, dim3(nb), dim3(64), 0, (hipStream_t)stream, cloud_xyz, n_points, block_points, out_bounds);
   SOGM_HIP_CHECK(hipGetLastError());
   return SOGM_OK;
 }
 
-int sogm_set_future_risk(sogm_ctx *c, const float *grid_vt, const float *poses,
-                         const double *stamps, void *stream) {
-  if (!c || !grid_vt || !poses || !stamps) return SOGM_ERR_INVALID_ARG;
+int sogm_prestamp_pending(const sogm_ctx *c) { return c && c->pool.prestamp_pending() ? 1 : 0; }
+int sogm_prestamp_join(sogm_ctx *c, void *stream) {
+  if (!c) return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = sogm::join_update(c, st)) return rc;
-  SOGM_HIP_CHECK(hipMemcpyAsync(c->d_poses, poses, sizeof(float) * 3 * c->n_agents,
-                                hipMemcpyDeviceToDevice, st));
-  SOGM_HIP_CHECK(hipMemcpyAsync(c->d_stamps, stamps, sizeof(double) * c->n_agents,
-                                hipMemcpyDeviceToDevice, st));
-  if (c->pool.precleared()) {
-    int rc = sogm::adopt_preclear(c, st);
-    if (rc) return rc;
+  return sogm::join_prestamp(c, (hipStream_t)stream);
+}
+
+// diagnostics (tools/ only): the update flow's control words after a device synchronisation —
+// out = {epoch, pending, ticket, error, ...ctl[2..7], stage[A], map_ready[A]}
+int sogm_debug_update_flow(sogm_ctx *c, int32_t *out, int cap) {
+  if (!c || !out || cap < 10 + 2 * c->n_agents) return SOGM_ERR_INVALID_ARG;
+  SOGM_HIP_CHECK(hipSetDevice(c->device));
+  (void)hipDeviceSynchronize();
+  const int A = c->n_agents;
+  out[0]      = c->map_epoch;
+  out[1]      = c->update_pending;
+  if (!c->d_update_ctl) return SOGM_ERR_STATE;
+  {
+    std::vector<int> w(UpdateBlock::words(A));
+    SOGM_HIP_CHECK(hipMemcpy(w.data(), c->d_update_ctl, sizeof(int) * w.size(), hipMemcpyDeviceToHost));
+    out[2] = w[UpdateBlock::ticket()];
+    out[3] = w[UpdateBlock::err()];
+    for (int a = 0; a < A; ++a) out[10 + a] = w[(size_t)UpdateBlock::stage(a)];
   }
-  const int    V = c->geom.V, T = c->spec.T;
-  const size_t per = (size_t)V * T;
-  c->pool.dense_write_current();  // every cell is written: the next reset of this grid is the dense clear
-  for (int a = 0; a < c->n_agents; ++a) {
-    hipLaunchKernelGGL(k_vt_to_slabs, dim3((V + 255) / 256), dim3(256), 0, st, grid_vt + a * per, c->geom,
-                       (void *)((char *)c->d_grid + a * per * c->cell_bytes()));
-  }
-  SOGM_HIP_CHECK(hipGetLastError());
-  c->updated = 1;
+  SOGM_HIP_CHECK(hipMemcpy(out + 10 + A, c->d_map_ready, sizeof(int) * A, hipMemcpyDeviceToHost));
   return SOGM_OK;
 }
-
-int sogm_download_reference_layout(sogm_ctx *c, int agent, float *out) {
-  if (!c || !out || agent < 0 || agent >= c->n_agents) return SOGM_ERR_INVALID_ARG;
+// ... and its per-agent stamps [A][4] (100 MHz wall clock) + the order it took the agents in [A]
+int sogm_debug_update_flow_times(sogm_ctx *c, int64_t *out_ts, int32_t *out_order) {
+  if (!c || !out_ts || !out_order || !c->d_update_ts) return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(c->device));
-  const int    V = c->geom.V, T = c->spec.T;
-  const size_t per = (size_t)V * T;
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  hipLaunchKernelGGL(k_slabs_to_vt, dim3((V + 255) / 256), dim3(256), 0, 0,
-                     (const void *)((const char *)c->d_grid + (size_t)agent * per * c->cell_bytes()), c->geom,
-                     c->d_scratch_vt);
-  SOGM_HIP_CHECK(hipGetLastError());
-  SOGM_HIP_CHECK(hipMemcpy(out, c->d_scratch_vt, per * sizeof(float), hipMemcpyDeviceToHost));
-  return SOGM_OK;
-}
-
-int sogm_map_state(sogm_ctx *c, int agent, double *out_time, float *out_center, void *stream) {
-  if (!c || agent < 0 || agent >= c->n_agents || (!out_time && !out_center)) return SOGM_ERR_INVALID_ARG;
-  if (!c->updated) return SOGM_ERR_STATE;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (out_time)
-    SOGM_HIP_CHECK(hipMemcpyAsync(out_time, c->d_stamps + agent, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out_center)
-    SOGM_HIP_CHECK(hipMemcpyAsync(out_center, c->d_poses + 3 * agent, 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-  SOGM_HIP_CHECK(hipStreamSynchronize(st));
-  return SOGM_OK;
-}
-
-int sogm_traj_eval(const SogmTrajRecord *records, int n, const double *t, double *out_pva,
-                   int32_t *out_valid, void *stream) {
-  if (!records || !t || !out_pva || !out_valid || n < 0) return SOGM_ERR_INVALID_ARG;
-  if (n == 0) return SOGM_OK;
-  hipLaunchKernelGGL(k_traj_eval, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, records, n,
-                     t, out_pva, out_valid);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
-int sogm_tick_inputs(const SogmTrajRecord *own_records, int n, double stamp, double replan_start_offset,
-                     double *hover_inout, double *out_now, double *out_t_start, double *out_pva, float *out_poses,
-                     void *stream) {
-  if (!own_records || !hover_inout || !out_now || !out_t_start || !out_pva || !out_poses || n < 0)
-    return SOGM_ERR_INVALID_ARG;
-  if (n == 0) return SOGM_OK;
-  hipLaunchKernelGGL(k_tick_inputs, dim3(n), dim3(64), 0, (hipStream_t)stream, own_records, n, stamp,
-                     replan_start_offset, hover_inout, out_now, out_t_start, out_pva, out_poses);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
-int sogm_merge_latest(const SogmTrajRecord *new_records, const int32_t *ok, SogmTrajRecord *own_inout,
-                      SogmTrajRecord *all_or_null, int n, void *stream) {
-  if (!new_records || !ok || !own_inout || n < 0) return SOGM_ERR_INVALID_ARG;
-  if (n == 0) return SOGM_OK;
-  const long long lanes = (long long)n * (long long)(sizeof(SogmTrajRecord) / 16);
-  hipLaunchKernelGGL(k_merge_latest, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     new_records, ok, own_inout, all_or_null, n);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
-int sogm_traj_safe(sogm_ctx *c, const SogmTrajRecord *records, const double *t_now, double check_duration,
-                   int32_t *out_safe, void *stream) {
-  if (!c || !records || !t_now || !out_safe) return SOGM_ERR_INVALID_ARG;
-  if (!c->updated) return SOGM_ERR_STATE;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = sogm::join_update(c, (hipStream_t)stream)) return rc;
-  hipLaunchKernelGGL(k_traj_safe, dim3((c->n_agents + 63) / 64), dim3(64), 0, (hipStream_t)stream, view_of(c),
-                     records, t_now, check_duration, out_safe);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
-int sogm_query_clear(sogm_ctx *c, const int32_t *agent_idx, const double *pos_xyz, const double *t,
-                     int t_is_index, int n_q, int8_t *out, void *stream) {
-  if (!c || !agent_idx || !pos_xyz || !t || !out || n_q < 0) return SOGM_ERR_INVALID_ARG;
-  if (!c->updated) return SOGM_ERR_STATE;
-  if (n_q == 0) return SOGM_OK;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = sogm::join_update(c, (hipStream_t)stream)) return rc;
-  hipLaunchKernelGGL(k_query_clear, dim3((n_q + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                     view_of(c), agent_idx, pos_xyz, t, t_is_index, n_q, out);
-  SOGM_HIP_CHECK(hipGetLastError());
-  return SOGM_OK;
-}
-
-int sogm_obstacle_points(sogm_ctx *c, const int32_t *agent_idx, const double *box_lo,
-                         const double *box_hi, const double *t0, const double *t1, int n_b,
-                         double *out_pts, int32_t *out_counts, int cap, void *stream) {
-  if (!c || !agent_idx || !box_lo || !box_hi || !t0 || !t1 || !out_pts || !out_counts ||
-      n_b < 0 || cap <= 0)
-    return SOGM_ERR_INVALID_ARG;
-  if (!c->updated) return SOGM_ERR_STATE;
-  if (n_b == 0) return SOGM_OK;
-  SOGM_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = sogm::join_update(c, (hipStream_t)stream)) return rc;
-  hipLaunchKernelGGL(k_obstacle_points, dim3(n_b), dim3(256), 0, (hipStream_t)stream, view_of(c),
-                     agent_idx, box_lo, box_hi, t0, t1, out_pts, out_counts, cap);
-  SOGM_HIP_CHECK(hipGetLastError());
+  (void)hipDeviceSynchronize();
+  SOGM_HIP_CHECK(hipMemcpy(out_ts, c->d_update_ts, sizeof(long long) * 4 * c->n_agents, hipMemcpyDeviceToHost));
+  SOGM_HIP_CHECK(hipMemcpy(out_order, c->d_update_order, sizeof(int) * c->n_agents, hipMemcpyDeviceToHost));
   return SOGM_OK;
 }
 

@@ -112,6 +112,32 @@ struct TickInputsIO {  // sogm_tick_inputs' arguments: the executed records in, 
   double               *hover, *now, *t_start, *pva;
   double                start_offset;
 };
+// One agent's tick inputs (plan_manager.cpp:169-175): the start state sampled from its executing trajectory at
+// stamp + start_offset, or where it hovers; the map centre of the tick is that position.
+// (k_tick_inputs in csrc/sogm_traj.hip, and the heads of k_prestamp_flow and k_flight_map in csrc/sogm_map.hip)
+__device__ inline void tick_inputs_agent(const SogmTrajRecord &rec, const double *hov, int i, double stamp,
+                                         const TickInputsIO &io, float *__restrict__ poses) {
+  const double ts = stamp + io.start_offset;
+  double       o[9];
+  if (!traj_eval_record(rec, ts, o))
+    for (int k = 0; k < 9; ++k) o[k] = hov[k];
+  for (int k = 0; k < 9; ++k) io.pva[i * 9 + k] = o[k];
+  for (int k = 0; k < 3; ++k) {
+    io.hover[i * 9 + k]     = o[k];
+    io.hover[i * 9 + 3 + k] = 0.0;
+    io.hover[i * 9 + 6 + k] = 0.0;
+    poses[i * 3 + k]        = (float)o[k];
+  }
+  io.now[i]     = stamp;
+  io.t_start[i] = ts;
+}
+// The agent's executed record and hover row into the workgroup's LDS (one wave), visible to every lane on return.
+__device__ __forceinline__ void stage_record_hover(SogmTrajRecord *s_rec, double *s_hov, const SogmTrajRecord *own,
+                                                   const double *hover, int agent, int lane) {
+  copy_record(s_rec, own + agent, lane);
+  if (lane < 9) s_hov[lane] = hover[agent * 9 + lane];
+  __syncthreads();
+}
 // the map role's arguments (csrc/sogm_map.hip, k_flight_map)
 struct FlightMapDev {
   MapTarget             tgt;           // the context's current grid, centres and stamps
@@ -172,7 +198,7 @@ struct QpIO {  // QP: the corridors' polytopes and goal in, control points / sta
 };
 // `__restrict__` lives on the `__global__` parameters of the per-stage entries' kernels (k_astar, k_flight_search,
 // k_qp, k_corridor_points / _segment / _finalize) and of the map stage's lock-step kernels (k_cull_cylinders, k_stamp_bits /
-// _blocks, k_stamp_marks / _cached, k_splat_neighbours, k_tick_inputs), which fill the struct in their first lines: a struct
+// _blocks, k_stamp_marks / _cached, k_splat_neighbours; k_tick_inputs in csrc/sogm_traj.hip), which fill the struct in their first lines: a struct
 // member cannot carry it.
 // what finish_agent (csrc/sogm_corridor.hip) reads and writes for one agent
 struct FinishArgs {

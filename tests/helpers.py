@@ -109,7 +109,7 @@ class OracleCompute:
         return (self.abi.SogmTrajRecord * n).from_buffer_copy(t.numpy().tobytes())
 
     def tick_inputs(self, own, stamp, hover, now, t_start, pva, poses):
-        """k_tick_inputs (csrc/sogm_map.hip) restated: start state = the executed trajectory at stamp + 0.02, or
+        """k_tick_inputs (csrc/sogm_traj.hip) restated: start state = the executed trajectory at stamp + 0.02, or
         the hover state; hover <- position with zero velocity / acceleration."""
         import importlib
         drv = importlib.import_module("pred-occ-planner_amd.driver")

@@ -1,8 +1,10 @@
-// Host test of the two device-side control blocks' layouts (csrc/sogm_handover.hpp: FlowBlock, FlightBlock), compiled with the
+// Host test of the device-side control blocks' layouts (csrc/sogm_handover.hpp: FlowBlock, FlightBlock, UpdateBlock), compiled with the
 // host compiler: the regions in offset order without gap or overlap, carve() handing out exactly those offsets, the ranges a
-// call resets, the 8-byte alignment of the 64-bit work queues, and the offsets tests and tools read peeked words by as literals.
+// call resets, the 8-byte alignment of the 64-bit work queues, and the offsets tests and tools read peeked words by as literals;
+// the update flow's block: every word on a 128-byte line of its own.
 #include "sogm_handover.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
@@ -73,6 +75,24 @@ static int flight_block(int A, const int *base) {
   return 0;
 }
 
+// The update flow's block (the base is 128-byte aligned: a device allocation): the ticket, the error word and every agent's
+// progress word lie on distinct 128-byte lines inside words(A), at the offsets tools read them by.
+static int update_block(int A, int *base) {
+  EXPECT(UpdateBlock::words(A) == 2048 + 32 * (size_t)A);
+  EXPECT(UpdateBlock::ticket() == 0 && UpdateBlock::err() == 1024);
+  std::vector<long> lines = {UpdateBlock::ticket() * 4L / 128, UpdateBlock::err() * 4L / 128};
+  for (int a = 0; a < A; ++a) {
+    EXPECT(UpdateBlock::stage(a) == 2048 + 32 * a);
+    EXPECT(UpdateBlock::stage_word(base, a) == base + UpdateBlock::stage(a));
+    lines.push_back(UpdateBlock::stage(a) * 4L / 128);
+  }
+  std::sort(lines.begin(), lines.end());
+  EXPECT(std::adjacent_find(lines.begin(), lines.end()) == lines.end());
+  EXPECT(UpdateBlock::stage(A - 1) >= 0 && (size_t)UpdateBlock::stage(A - 1) < UpdateBlock::words(A));
+  EXPECT((size_t)UpdateBlock::err() < UpdateBlock::words(A) && (size_t)(lines.back() + 1) * 32 <= UpdateBlock::words(A));
+  return 0;
+}
+
 int main() {
   const int sizes[] = {1, 2, 3, 127, 128, 129, 1000, 65535};
   std::vector<int> mem(FlightBlock::words(65535));  // (carve only computes addresses: one buffer for every size of both blocks)
@@ -80,6 +100,8 @@ int main() {
     if (flow_block(A, mem.data())) return 1;
     if (flight_block(A, mem.data())) return 1;
   }
+  for (int A : {1, 2, 128})
+    if (update_block(A, mem.data())) return 1;
   EXPECT(FlowBlock::words(128) == 780 && FlowBlock::words(1) == 18);
   EXPECT(FlightBlock::ring_of(1) == 2 && FlightBlock::ring_of(3) == 8 && FlightBlock::ring_of(128) == 256 &&
          FlightBlock::ring_of(129) == 512);

@@ -1,11 +1,13 @@
-"""The layouts of the two device-side control blocks (csrc/sogm_handover.hpp: FlowBlock of the dataflow replan, FlightBlock
-of the flight) on the host, no GPU: compiled with the host compiler (tests/planner_blocks_host_test.cpp).
+"""The layouts of the device-side control blocks (csrc/sogm_handover.hpp: FlowBlock of the dataflow replan, FlightBlock
+of the flight, UpdateBlock of the update flow) on the host, no GPU: compiled with the host compiler (tests/planner_blocks_host_test.cpp).
 
 Checked there, for 1, 2, 3, 127, 128, 129, 1000 and 65535 agents: the regions lie in offset order without gap or overlap and
 end within words(A), and carve() hands out exactly those offsets; the replan zeroes [0, FLOW_HDR + 2A), fills
 [FLOW_HDR + 2A, FLOW_HDR + 6A) with -1 and keeps its generation word at FLOW_HDR + 6A; the flight's rings hold the smallest
 power of two >= 2A slots, its three 64-bit queues start on even words, and a call zeroes exactly the words in front of the
-parked lists — the exchange's ready words among them, the urgent queue behind them; the offsets at 128 agents as literals."""
+parked lists — the exchange's ready words among them, the urgent queue behind them; the offsets at 128 agents as literals.
+For 1, 2 and 128 agents the update flow's block holds 2048 + 32 A words, and its ticket, its error word and every agent's
+progress word lie on distinct 128-byte lines inside it."""
 import os
 import shutil
 import subprocess

@@ -15,9 +15,9 @@ def test_the_library_reads_three_environment_switches_only():
         names |= set(re.findall(r'getenv\("([A-Z_0-9]+)"\)', open(f).read()))
     assert names == {"SOGM_SPARSE_RESET", "SOGM_FLOW", "SOGM_RCCL_LIB"}, names
     # ... and keeps no function-static copies of tuning values
-    for f in glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_map.hip")) + \
-            glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_planner.hip")) + \
-            glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "sogm_flight.hip")):
+    sources = glob.glob(os.path.join(ROOT, "pred-occ-planner_amd", "csrc", "*.hip"))
+    assert len(sources) >= 16, sources  # (every translation unit, the map's four among them)
+    for f in sources:
         assert not re.findall(r"static (const )?(int|double)\s+\w+\s*=\s*-1", open(f).read()), f
 
 
