@@ -337,7 +337,7 @@ int linfracprog(int d, const double *halves, int max_size, int m, const double *
   return status;
 }
 
-// mode-0 insertion order: LCG Fisher-Yates, a function of n only (identical in sogm_corridor.hip)
+// mode-0 insertion order: LCG Fisher-Yates, a function of n only (identical in csrc/sogm_lp.hpp)
 void fixed_permutation(int n, int *p) {
   for (int i = 0; i < n; ++i) p[i] = i;
   unsigned long long s = 0x9E3779B97F4A7C15ULL;

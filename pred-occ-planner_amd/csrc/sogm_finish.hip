@@ -1,0 +1,104 @@
+// sogm_finish.hip — the end of a replan in all its forms: isSafeAfterOpt and the record / outcome count of every agent.
+// Grouped path (sogm_replan, pipelining mode 1, and the per-stage entry sogm_safe_after_opt): k_fill_i32 + k_safe_after_opt
+// (launch_deconflict), then k_pack_records.  Dataflow replan: k_finish_flow, one persistent launch that does both per agent
+// as its QP finishes.  The flight's finish is the WK_FINISH branch of k_flight_light (sogm_flight_light.hip).  All of them
+// share the device bodies and the outcome rule of sogm_finish.hpp.
+#include <hip/hip_runtime.h>
+
+#include "sogm_finish.hpp"
+
+namespace sogm {
+
+// grouped path: one workgroup per (other agent's record, ego agent), see deconflict_pair_unsafe
+__global__ __launch_bounds__(64) void k_safe_after_opt(const double *__restrict__ cpts,
+                                                       const int32_t *__restrict__ npoly,
+                                                       const SogmTrajRecord *__restrict__ rec, int n_rec,
+                                                       const int32_t *__restrict__ ego_ids,
+                                                       const double *__restrict__ t_now,
+                                                       int32_t *__restrict__ out_safe, int agent0,
+                                                       unsigned long long *counters) {
+  extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+  const int a = blockIdx.y + agent0, i = blockIdx.x;
+  if (deconflict_pair_unsafe(cpts + (size_t)a * SOGM_MAX_PIECES * 15, npoly[a], rec[i], ego_ids[a], t_now[a],
+                             LpLds::carve(s_dyn), counters) &&
+      threadIdx.x == 0)
+    out_safe[a] = 0;  // every writer writes 0
+}
+
+__global__ void k_fill_i32(int32_t *p, int n, int32_t v, int agent0) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[agent0 + i] = v;
+}
+
+// Dataflow kernel F (sogm_replan): ONE persistent launch; a wave takes the agent whose QP finished ticket-th, runs
+// finish_agent (what k_safe_after_opt + k_pack_records do in the grouped path) and hands the agent to the pre-stamp.
+__global__ __launch_bounds__(64) void k_finish_flow(FlowCtl fc, FinishArgs f, int n_agents) {
+  extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+  const int lane = threadIdx.x;
+  for (;;) {
+    const int k = flow_ticket(&fc.hdr[FLOW_F_TICKET]);
+    if (k >= n_agents) break;
+    const int a = flow_wait_slot(fc.f_ready + k, &fc.hdr[FLOW_ERR]);
+    if (a < 0) break;
+    __threadfence();
+    const int  code = finish_agent(f, a, LpLds::carve(s_dyn), lane);
+    const bool safe = (code & 1) != 0;
+    if (fc.p_ready) {  // the agent's record is final: hand it to the pre-stamp
+      __threadfence();
+      if (lane == 0) publish_next(fc.p_ready, &fc.hdr[FLOW_P_READY_N], a);
+    }
+    if (lane == 0) {
+      fc.ts[a * 8 + 6] = wall_clock64();
+      finish_count(f, a, safe);
+    }
+  }
+}
+
+// The grouped path's end of a replan, behind launch_qp and (with a swarm) launch_deconflict, one thread per agent: the count
+// of where it ended and the BezierTraj record of a successful replan (plan_manager/src/plan_manager.cpp:364-399 publishes
+// duration[] and cpts[]); n_pieces = 0 marks "replan() returned false".
+__global__ void k_pack_records(int A, FinishArgs f, int agent0) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x + agent0;
+  if (a >= A) return;
+  const int  npoly = f.npoly[a];
+  const bool safe  = f.swarm ? f.out_safe[a] != 0 : true;  // (launch_deconflict ran in front of this kernel only with a swarm)
+  // isSafeAfterOpt false -> replan() returns false (baseline_fake.cpp:455-460)
+  const int  outcome = replan_outcome(f.ret[a], npoly, f.status[a], safe);
+  const bool good    = outcome == SOGM_CNT_REPLAN_OK;
+  // (an agent sogm_planner_set_due's mask left out was not asked to plan: it is not counted)
+  if (f.counters && !(f.due && f.due[a] == 0)) atomicAdd(&f.counters[outcome], 1ull);
+  SogmTrajRecord &r = f.out[a];
+  r.drone_id        = f.drone_ids[a];
+  r.time_start      = f.t_start[a];
+  r.n_pieces        = good ? npoly : 0;
+  for (int i = 0; i < SOGM_MAX_PIECES; ++i) r.duration[i] = (good && i < npoly) ? f.corridor_tau : 0.0;
+  for (int i = 0; i < SOGM_MAX_PIECES * 15; ++i)
+    r.cpts[i] = (good && i < npoly * 15) ? f.cpts[(size_t)a * SOGM_MAX_PIECES * 15 + i] : 0.0;
+  f.out_ok[a] = good ? 1 : 0;
+  if (f.pub_own) {  // publication, as k_finish_flow does it (sogm_planner_set_publish)
+    if (good) f.pub_own[a] = r;
+    if (f.pub_table) f.pub_table[a] = f.pub_own[a];
+  }
+}
+
+hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
+                             int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
+                             hipStream_t st, int agent0, unsigned long long *counters) {
+  hipLaunchKernelGGL(k_fill_i32, dim3((n_agents + 63) / 64), dim3(64), 0, st, out_safe, n_agents, 1, agent0);
+  if (n_rec > 0)
+    hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), LpLds::bytes(), st, cpts, npoly, rec, n_rec,
+                       ego_ids, t_now, out_safe, agent0, counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st) {
+  hipLaunchKernelGGL(k_finish_flow, dim3(n_workgroups), dim3(64), LpLds::bytes(), st, fc, f, n_agents);
+  return hipGetLastError();
+}
+
+hipError_t launch_pack_records(int n_agents, const FinishArgs &f, hipStream_t st, int agent0) {
+  hipLaunchKernelGGL(k_pack_records, dim3((n_agents + 63) / 64), dim3(64), 0, st, agent0 + n_agents, f, agent0);
+  return hipGetLastError();
+}
+
+}  // namespace sogm

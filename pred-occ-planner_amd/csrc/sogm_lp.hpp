@@ -1,4 +1,4 @@
-// sogm_lp.hpp (included by sogm_corridor.hip only) — the wave LP (sdlp's projective Seidel LP) and the dynamic LDS of the
+// sogm_lp.hpp (included by sogm_corridor.hpp, sogm_finish.hpp and sogm_lp.hip) — the wave LP (sdlp's projective Seidel LP) and the dynamic LDS of the
 // kernels that run it, each layout described ONCE: the kernels carve their pointers from it, the launchers take their byte
 // count from it, tests/corridor_lds_host_test.cpp reads it with the host compiler (the device's code sits behind __HIPCC__).
 #pragma once

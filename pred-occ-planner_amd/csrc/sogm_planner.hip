@@ -1,7 +1,9 @@
 // sogm_planner.hip — planner context and host side of the planner entry points: the per-stage calls (search,
 // corridors, QP, deconfliction) and sogm_replan in its two forms — the dataflow replan (replan_flow: five launches,
 // persistent corridor / QP / finish kernels chained per agent through ready lists) and the grouped-stream chain
-// (replan_impl).  The flight (sogm_flight_run) is in sogm_flight.hip.  SOGM_ERR_STATE from an entry point means a call-order error (no map update before planning).
+// (replan_impl) — with the flow's one-lane glue kernels (k_flow_gate, k_flow_reset, k_flow_report).  The stages' kernels are
+// in their own units: sogm_astar.hip, sogm_corridor.hip, sogm_qp.hip, and the end of a replan (isSafeAfterOpt, records,
+// outcome counters) in sogm_finish.hip.  The flight (sogm_flight_run) is in sogm_flight.hip.  SOGM_ERR_STATE from an entry point means a call-order error (no map update before planning).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -58,38 +60,18 @@ static void min_jerk_block(double *QM /*15x15*/) {
     }
 }
 
-// BezierTraj record of a successful replan (plan_manager/src/plan_manager.cpp:364-399 publishes
-// duration[] and cpts[]); n_pieces = 0 marks "replan() returned false".
-__global__ void k_pack_records(int A, FinishArgs f, int agent0) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x + agent0;
-  if (a >= A) return;
-  const int32_t *ret = f.ret, *npoly = f.npoly, *status = f.status;
-  const int32_t *safe = f.swarm ? f.out_safe : nullptr;  // (launch_deconflict ran in front of this kernel only with a swarm)
-  // (an agent sogm_planner_set_due's mask left out was not asked to plan: it is not counted)
-  if (unsigned long long *counters = (f.due && f.due[a] == 0) ? nullptr : f.counters) {  // where this replan ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe)
-    int k = SOGM_CNT_REPLAN_OK;
-    if (ret[a] == 0) k = SOGM_CNT_FAIL_SEARCH;
-    else if (npoly[a] <= 0) k = SOGM_CNT_FAIL_CORRIDOR;
-    else if (!(status[a] == 1 || status[a] == 2)) k = SOGM_CNT_FAIL_QP;
-    else if (safe != nullptr && safe[a] == 0) k = SOGM_CNT_FAIL_UNSAFE;
-    atomicAdd(&counters[k], 1ull);
-  }
-  SogmTrajRecord &r = f.out[a];
-  // isSafeAfterOpt false -> replan() returns false (baseline_fake.cpp:455-460)
-  const bool good = ret[a] != 0 && npoly[a] > 0 && (status[a] == 1 || status[a] == 2) &&
-                    (safe == nullptr || safe[a] != 0);
-  r.drone_id        = f.drone_ids[a];
-  r.time_start      = f.t_start[a];
-  r.n_pieces        = good ? npoly[a] : 0;
-  for (int i = 0; i < SOGM_MAX_PIECES; ++i) r.duration[i] = (good && i < npoly[a]) ? f.corridor_tau : 0.0;
-  for (int i = 0; i < SOGM_MAX_PIECES * 15; ++i)
-    r.cpts[i] = (good && i < npoly[a] * 15) ? f.cpts[(size_t)a * SOGM_MAX_PIECES * 15 + i] : 0.0;
-  f.out_ok[a] = good ? 1 : 0;
-  if (f.pub_own) {  // publication, as k_finish_flow does it (sogm_planner_set_publish)
-    if (good) f.pub_own[a] = r;
-    if (f.pub_table) f.pub_table[a] = f.pub_own[a];
-  }
+namespace sogm {
+// residency gate of the dataflow replan: returns when every A* workgroup has started (see k_astar)
+__global__ void k_flow_gate(FlowCtl fc, int expected) {
+  if (threadIdx.x != 0) return;
+  wait_at_least<WaitResidencyGate, false>(&fc.hdr[FLOW_ERR], &fc.hdr[FLOW_A_RESIDENT], expected);
 }
+
+hipError_t launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st) {
+  hipLaunchKernelGGL(k_flow_gate, dim3(1), dim3(64), 0, st, fc, expected);
+  return hipGetLastError();
+}
+}  // namespace sogm
 
 // End of a dataflow replan (one lane, on the caller's stream after the fan-in): a wait of this tick timed out ->
 // remember the code and count the tick in pinned host memory, so the host can see failed ticks without a device
@@ -1017,9 +999,7 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
                             sogm::launch_deconflict(n, p->d_cpts, p->d_npoly, p->swarm, p->n_swarm, p->swarm_ego,
                                                     p->swarm_now, p->d_safe, st, a0, p->cw.counters)))
         return rc;
-    hipLaunchKernelGGL(k_pack_records, dim3((n + 63) / 64), dim3(64), 0, st, a1,
-                       finish_args(p, t_start, drone_ids, out_records, out_ok), a0);
-    SOGM_HIP_CHECK(hipGetLastError());
+    SOGM_HIP_CHECK(sogm::launch_pack_records(n, finish_args(p, t_start, drone_ids, out_records, out_ok), st, a0));
     SOGM_HIP_CHECK(hipEventRecord(p->ev_done[g], st));
     SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->ev_done[g], 0));  // fan in
   }

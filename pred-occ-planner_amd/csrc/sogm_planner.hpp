@@ -200,7 +200,7 @@ struct QpIO {  // QP: the corridors' polytopes and goal in, control points / sta
 // k_qp, k_corridor_points / _segment / _finalize) and of the map stage's lock-step kernels (k_cull_cylinders, k_stamp_bits /
 // _blocks, k_stamp_marks / _cached, k_splat_neighbours; k_tick_inputs in csrc/sogm_traj.hip), which fill the struct in their first lines: a struct
 // member cannot carry it.
-// what finish_agent (csrc/sogm_corridor.hip) reads and writes for one agent
+// what finish_agent (csrc/sogm_finish.hpp) and k_pack_records (csrc/sogm_finish.hip) read and write for one agent
 struct FinishArgs {
   double                corridor_tau;
   const int32_t        *ret, *npoly, *status;
@@ -259,6 +259,8 @@ hipError_t launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const Pres
 hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
                              int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
                              hipStream_t st, int agent0, unsigned long long *counters = nullptr);
+// the grouped path's records, ok flags and outcome counts for agents [agent0, agent0 + n_agents) (k_pack_records)
+hipError_t launch_pack_records(int n_agents, const FinishArgs &f, hipStream_t st, int agent0);
 hipError_t launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, int n_agents,
                            const CorridorIO &io, hipStream_t st, int agent0 = 0, hipEvent_t ev_map_read = nullptr);
 

@@ -367,7 +367,7 @@ def linprog(c, A, b, perm):
 
 def library_permutation(n):
     """NOT from the reference: the insertion order the LIBRARY uses in place of sdlp's process-global mt19937_64 (DESIGN.md
-    section 4, deviation 2; `fixed_permutation` in csrc/sogm_corridor.hip) — an LCG Fisher-Yates, a function of n only"""
+    section 4, deviation 2; `fixed_permutation` in csrc/sogm_lp.hpp) — an LCG Fisher-Yates, a function of n only"""
     p = list(range(n))
     s = 0x9E3779B97F4A7C15
     for i in range(n - 1, 0, -1):
