@@ -124,7 +124,14 @@ int sogm_download_reference_layout(sogm_ctx *ctx, int agent, float *out_vt_host)
 int sogm_dsp_download_state(sogm_dsp *d, int agent, float *store_host, float *objnum_host,
                             int32_t *counters_host);
 /* input_cloud_with_velocity of the last update (the new-born list, rows {x,y,z,vx,vy,vz,intensity}, at most `cap`
- * rows), its length, and counters4 = {clusters, possibly dynamic, matched, error code of the velocity estimation}. */
+ * rows), its length, and counters4 = {clusters, possibly dynamic, matched, error code of the velocity estimation}.
+ * The error code is 0 or the capacity that was exceeded: 2 = a point with more than 128 neighbours within the cluster
+ * tolerance (neighbours dropped), 3 = more than 256 accepted clusters (the rest dropped), 4 = more than 64 possibly-dynamic
+ * clusters (the rest treated as static), 5 = new x previous possibly-dynamic clusters > max_points (no association in that
+ * frame).  The update itself still returns SOGM_OK and the other agents of the batch are unaffected.  The code is STICKY:
+ * a later frame within the capacities does not clear it (the latest non-zero code stays until the handle is destroyed).
+ * A cloud longer than max_points is clamped to its first max_points points and counted in counters[12] of
+ * sogm_dsp_download_state (once per clamped update), not here. */
 int sogm_dsp_download_born(sogm_dsp *d, int agent, float *born_host, int cap, int32_t *n_born, int32_t *counters4);
 /* Observation tables of the last update: nobs[n_pyramids], pc[n_pyramids*obs_max*5], maxlen[n_pyramids] */
 int sogm_dsp_download_observations(sogm_dsp *d, int agent, int32_t *nobs_host, float *pc_host,

@@ -599,6 +599,7 @@ void velocityEstimation(Dsp &d) {
   const int n = (int)d.rotated.size() / 3;
   if (n == 0) return;  // :1488
   d.born.clear();
+  d.dbg_clusters = d.dbg_dynamic = d.dbg_matched = 0;  // a frame without non-ground points has no clusters (not the last frame's)
   const float vres = 0.15f;  // voxel_filtered_resolution (:105)
   std::vector<float> stat;   // static_points xyz
   std::vector<float> ng;     // non_ground_points xyz
