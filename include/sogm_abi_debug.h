@@ -175,6 +175,27 @@ int sogm_corridor_rules_batched_flags(sogm_planner *counters_of, const SogmPlann
                                       double *out_polys, int32_t *out_nfaces, int32_t *out_npoly, double *out_goal,
                                       int flags, void *stream);
 
+/* Test hook: the end of a replan — ParticleATC::isSafeAfterOpt against a swarm table, the outcome count, the SogmTrajRecord and
+ * its publication — for n independent agents whose search / corridor / QP results the caller injects, in either of the two
+ * forms the library has (csrc/sogm_finish.hip).  flags = 0: the grouped form, one wave per (record, agent) pair and the
+ * records packed behind it (sogm_replan in pipelining mode 1, sogm_safe_after_opt).  SOGM_FINISH_WAVE: the finishing wave,
+ * one wave per agent — the device body the dataflow sogm_replan and sogm_flight_run inline, without their hand-over
+ * control: one lane per record pre-tests 64 records at a time, the pairs left over take the LP in record order, the first
+ * unsafe one ends the check, and an agent that was not solved skips it (its out_safe is 1 there).
+ * Device memory: ret, npoly (<= SOGM_MAX_PIECES), status [n] (the search's return, the corridor count, the QP's status:
+ * 1 / 2 = solved), cpts [n][SOGM_MAX_PIECES * 15], swarm [n_swarm] (NULL: no check, n_swarm is taken as 0; every n_pieces
+ * <= SOGM_MAX_PIECES) with swarm_ego, swarm_now [n], t_start, drone_ids [n], due [n] or NULL (an agent with due 0 is not
+ * counted).  Outputs: out [n], out_ok [n], out_safe [n] (the grouped form writes it only when a swarm is given, and for
+ * unsolved agents too; the two forms agree on it for solved agents); pub_own [n] and pub_table [n], each or NULL, are read and
+ * written as sogm_planner_set_publish describes (with pub_own NULL nothing is published).  counters_of (may be NULL):
+ * the planner whose outcome and deconflict_capacity counters are raised.  Asynchronous on `stream`. */
+#define SOGM_FINISH_WAVE 1
+int sogm_finish_batched(sogm_planner *counters_of, double corridor_tau, const int32_t *ret, const int32_t *npoly,
+                        const int32_t *status, const double *cpts, const SogmTrajRecord *swarm, int n_swarm,
+                        const int32_t *swarm_ego, const double *swarm_now, const double *t_start, const int32_t *drone_ids,
+                        const int32_t *due, int n, SogmTrajRecord *out, int32_t *out_ok, int32_t *out_safe,
+                        SogmTrajRecord *pub_own, SogmTrajRecord *pub_table, int flags, void *stream);
+
 /* Diagnostics: the adjacent-pair LPs of the corridor bookkeeping (dataflow replan, flight, parallel rules hook).  out4, since
  * the last call: [0] pair LPs solved by a segment's wave as its neighbour was done, [1] pair LPs solved inside the
  * bookkeeping because no verdict was there, [2] pairs the bookkeeping took from a verdict, [3] the OR of every ready word

@@ -171,6 +171,7 @@ FSM_PUB_NONE, FSM_PUB_NEW, FSM_PUB_HOVER = 0, 1, 2  # sogm_fsm_apply's out_pub
 
 FLIGHT_MAX_TICKS = 64
 RULES_PARALLEL = 1  # sogm_corridor_rules_batched_flags: SOGM_RULES_PARALLEL
+FINISH_WAVE = 1  # sogm_finish_batched: SOGM_FINISH_WAVE
 FLIGHT_HDR_ERR, FLIGHT_HDR_FINISHED, FLIGHT_HDR_LATE_WGS = 4, 5, 15  # sogm_flight_stats out_hdr indices
 FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "chain", "ticks")
 TRAJ_RECORD_BYTES = C.sizeof(SogmTrajRecord)  # 2064
@@ -243,6 +244,8 @@ PROTOTYPES = {
                                          _vp, _vp, _vp]),
     "sogm_corridor_rules_batched_flags": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _i, _vp]),
+    "sogm_finish_batched": (_i, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
+                                 _vp, _vp, _i, _vp]),
     "sogm_debug_corridor_pairs": (_i, [_vp, _vp]),
     "sogm_debug_qp_stats": (_i, [_vp, _vp]),  # [A][QP_STAT_N] int64
     "sogm_debug_qp_layout": (_i, [_vp, _i, _vp, _vp]),

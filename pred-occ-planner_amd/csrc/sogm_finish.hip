@@ -3,6 +3,8 @@
 // (launch_deconflict), then k_pack_records.  Dataflow replan: k_finish_flow, one persistent launch that does both per agent
 // as its QP finishes.  The flight's finish is the WK_FINISH branch of k_flight_light (sogm_flight_light.hip).  All of them
 // share the device bodies and the outcome rule of sogm_finish.hpp.
+// Test hook (sogm_finish_batched, include/sogm_abi_debug.h): both forms on a FinishArgs the caller injects — the grouped
+// launchers as they are, or k_finish_wave, finish_agent + finish_count per agent without the dataflow's hand-over control.
 #include <hip/hip_runtime.h>
 
 #include "sogm_finish.hpp"
@@ -54,6 +56,15 @@ __global__ __launch_bounds__(64) void k_finish_flow(FlowCtl fc, FinishArgs f, in
   }
 }
 
+// The finishing wave alone (sogm_finish_batched with SOGM_FINISH_WAVE): one one-wave workgroup per agent runs what
+// k_finish_flow and k_flight_light inline for an agent, with no ticket, ready list or hand-over around it.
+__global__ __launch_bounds__(64) void k_finish_wave(FinishArgs f) {
+  extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+  const int a = blockIdx.x, lane = threadIdx.x;
+  const int code = finish_agent(f, a, LpLds::carve(s_dyn), lane);
+  if (lane == 0) finish_count(f, a, (code & 1) != 0);
+}
+
 // The grouped path's end of a replan, behind launch_qp and (with a swarm) launch_deconflict, one thread per agent: the count
 // of where it ended and the BezierTraj record of a successful replan (plan_manager/src/plan_manager.cpp:364-399 publishes
 // duration[] and cpts[]); n_pieces = 0 marks "replan() returned false".
@@ -102,3 +113,33 @@ hipError_t launch_pack_records(int n_agents, const FinishArgs &f, hipStream_t st
 }
 
 }  // namespace sogm
+
+extern "C" int sogm_finish_batched(sogm_planner *counters_of, double corridor_tau, const int32_t *ret, const int32_t *npoly,
+                                   const int32_t *status, const double *cpts, const SogmTrajRecord *swarm, int n_swarm,
+                                   const int32_t *swarm_ego, const double *swarm_now, const double *t_start,
+                                   const int32_t *drone_ids, const int32_t *due, int n, SogmTrajRecord *out, int32_t *out_ok,
+                                   int32_t *out_safe, SogmTrajRecord *pub_own, SogmTrajRecord *pub_table, int flags,
+                                   void *stream) {
+  if ((flags & ~SOGM_FINISH_WAVE) || n < 0 || n > (1 << 20) || n_swarm < 0 ||
+      (n > 0 && (!ret || !npoly || !status || !cpts || !t_start || !drone_ids || !out || !out_ok || !out_safe)) ||
+      (n > 0 && swarm && (!swarm_ego || !swarm_now)))
+    return SOGM_ERR_INVALID_ARG;
+  if (n == 0) return SOGM_OK;
+  if (!swarm) n_swarm = 0;
+  hipStream_t            st = (hipStream_t)stream;
+  const sogm::FinishArgs f{.corridor_tau = corridor_tau, .ret = ret, .npoly = npoly, .status = status, .cpts = cpts,
+                           .swarm = swarm, .n_swarm = n_swarm, .swarm_ego = swarm_ego, .swarm_now = swarm_now,
+                           .t_start = t_start, .drone_ids = drone_ids, .out = out, .out_ok = out_ok, .out_safe = out_safe,
+                           .counters = counters_of ? counters_of->cw.counters : nullptr, .pub_own = pub_own,
+                           .pub_table = pub_table, .due = due};
+  if (flags & SOGM_FINISH_WAVE) {
+    hipLaunchKernelGGL(sogm::k_finish_wave, dim3(n), dim3(64), sogm::LpLds::bytes(), st, f);
+    return launched("sogm_finish_batched k_finish_wave", hipGetLastError());
+  }
+  if (swarm)
+    if (int rc = launched("sogm_finish_batched launch_deconflict",
+                          sogm::launch_deconflict(n, cpts, npoly, swarm, n_swarm, swarm_ego, swarm_now, out_safe, st, 0,
+                                                  f.counters)))
+      return rc;
+  return launched("sogm_finish_batched launch_pack_records", sogm::launch_pack_records(n, f, st, 0));
+}

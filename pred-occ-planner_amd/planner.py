@@ -69,6 +69,22 @@ def corridor_rules_batched(pps, start_pva, route, route_len, polys, nfaces, seg_
     return out
 
 
+def finish_batched(corridor_tau, ret, npoly, status, cpts, t_start, drone_ids, out, out_ok, out_safe, swarm=None, n_swarm=0,
+                   swarm_ego=None, swarm_now=None, due=None, pub_own=None, pub_table=None, planner=None, wave=False):
+    """The end of a replan for n = len(ret) agents with injected stage results (sogm_finish_batched): isSafeAfterOpt against
+    `swarm` (uint8 [n_swarm, 2064] or None), the outcome count, the record and its publication.  ret / npoly / status /
+    swarm_ego / drone_ids / due int32 [n], cpts [n, 240], swarm_now / t_start float64 [n]; out / pub_own / pub_table uint8
+    [n, 2064], out_ok / out_safe int32 [n] are written in place — device tensors.  planner: the SogmPlanner whose outcome and
+    deconflict_capacity counters are raised (or None).  wave: the finishing wave of the dataflow replan and the flight
+    (SOGM_FINISH_WAVE) instead of the grouped kernels."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    check(lib().sogm_finish_batched(
+        planner._p if planner is not None else None, float(corridor_tau), ptr(ret), ptr(npoly), ptr(status), ptr(cpts),
+        ptr(swarm), int(n_swarm), ptr(swarm_ego), ptr(swarm_now), ptr(t_start), ptr(drone_ids), ptr(due), int(ret.numel()),
+        ptr(out), ptr(out_ok), ptr(out_safe), ptr(pub_own), ptr(pub_table), _abi.FINISH_WAVE if wave else 0, _stream()),
+        "sogm_finish_batched")
+
+
 class SogmPlanner:
     def __init__(self, sogm_map, astar_params, planner_params, qp_settings):
         self.map = sogm_map

@@ -1,4 +1,10 @@
-"""ParticleATC::isSafeAfterOpt (row f3): separating-plane LP, oracle on CPU, HIP vs oracle on the GPU."""
+"""ParticleATC::isSafeAfterOpt (row f3): separating-plane LP, oracle on CPU, HIP vs oracle on the GPU.
+
+Which device form each GPU test drives (csrc/sogm_finish.hip has two): test_safe_after_opt_gpu_matches_oracle and
+test_safe_after_opt_random_lp_cases call sogm_safe_after_opt, the GROUPED form (k_safe_after_opt, one wave per (record,
+agent) pair); test_replan_with_swarm_applies_deconfliction goes through sogm_replan, whose default dataflow ends in the
+FINISHING WAVE (finish_agent, one wave per agent) on the 8 records its scene has.  The finishing wave on injected inputs —
+tables longer than its 64-record chunks, the capacity rule, records and publication — is tests/test_finish_independent.py."""
 import importlib
 import json
 import os
