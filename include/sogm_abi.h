@@ -1113,6 +1113,118 @@ int sogm_swarm_audit(const SogmAuditParams *prm, const SogmTrajRecord *tables, i
                      SogmAuditAgent *acc, SogmAuditEvent *events, int32_t *n_events, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* trajectory server: the 100 Hz position commands (with yaw) a vehicle consumes                  */
+/*   (traj_server/src/bezier_traj_server.cpp, bezier_traj_server_rotors.cpp)                      */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Semantics (one definition: csrc/sogm_trajserver.hpp, compiled for the host and the device;
+ * tests/golden/make_traj_server_fixture.py restates it in plain Python).  One server per agent: a state record and a ring
+ * of queued samples.  Line numbers are bezier_traj_server.cpp's unless a file is named.
+ *   - State after the preamble: odometry received, yaw initialised, triggered at t_trigger (main :527-529,
+ *     triggerCallback :361-371): ts = te = t_trigger, duration = 0, last_yaw = init_yaw, last_yawdot = 0, traj_id = 0
+ *     (:531), nothing received, empty queue.
+ *   - Receiving a trajectory at `now` (bezierCallback :283-355): tns = time_start, duration = the sum of the piece
+ *     durations in order (:293-299).
+ *       te <= tns (:343): resetTrajQueue (:233-244): the queue is emptied; for (t = 0; t < replan_threshold; t += sample_dt)
+ *         a sample at t is pushed (t is that ACCUMULATED sum).
+ *       otherwise mergeTrajQueue (:246-277): int k = (now + replan_threshold - tns) / sample_dt, the truncated IEEE
+ *         quotient (a quotient outside int's range counts as a k larger than the queue).  k < 0 or k > size (:248 compares
+ *         the int with a size_t, so a negative k is "larger"): "next traj starts earlier than current buffer" — nothing
+ *         is erased and for (i = 0; i < replan_threshold / sample_dt; i++) a sample at i * sample_dt + (now - tns) is
+ *         pushed (:252-261).  Otherwise the last k samples are erased and samples at i * sample_dt, i < k, pushed
+ *         (:264-276).
+ *     Then traj = the record, ts = tns, te = ts + duration, traj_id += 1 (:351-354).  A sample pushed at trajectory time t
+ *     carries the time ts + t with the ts of BEFORE that assignment (pushToTrajQueue :202).
+ *   - The timer at `now` (PubCallback :415-485): nothing received or an empty queue publishes nothing (:452-462).  A
+ *     queue of one sample is held: that sample with zero velocity and acceleration, yaw = last_yaw, yaw_dot = 0
+ *     (:463-468).  Otherwise the front sample is popped and published, then fillTrajQueue (:211-228): tq = now +
+ *     replan_threshold; nothing is pushed when tq < ts or when t = tq - ts > duration; otherwise a sample of the current
+ *     trajectory at t.
+ *   - Yaw.  yaw_mode 0 (the launched bezier_traj_server: the getYaw call of pushToTrajQueue is commented out, :201):
+ *     every sample is pushed with yaw = yaw_dot = 0.  yaw_mode 1 (bezier_traj_server_rotors.cpp:212-223): getYaw
+ *     (:79-140; rotors :77-140) runs at every push, in push order, on the sample's velocity, and updates last_yaw /
+ *     last_yawdot.  PI = yaw_pi and YAW_DOT_MAX_PER_SEC = yaw_dot_max are parameters (3.14159265358979323846 and that
+ *     same value per second, :35-36; 3.1415926 and 0.05, rotors :36, :78); MAX_YAW_CHANGE = yaw_dot_max * 0.01 and the
+ *     literal 0.01 of yaw_dot = (yaw_temp - last_yaw) / 0.01 stay literals.  dir = v.normalized() is Eigen's: v / |v| when
+ *     the squared norm is > 0, v itself otherwise, so dir.norm() > 0.1 fails exactly for a zero velocity (the hover
+ *     records), where yaw_temp = last_yaw.  atan2 is sogm_det::atan2 (sogm_detmath.h): host, device and the Python
+ *     reading agree bit for bit.
+ *   - Times are built from integers as the audit builds them: tick k of a call has the stamp t_k = t0 + (first_tick + k) *
+ *     period; the timer fires at t_k + j * sample_dt, j = 0 .. m - 1, m = period / sample_dt whole to 1e-9.  Tick k's
+ *     record tables[k][a] is received at t_k + receive_delay (0 <= receive_delay < period), before the timer of the first
+ *     instant that is not earlier.  It is received if received[k][i] != 0, or with received == NULL if its time_start
+ *     differs from the previous table's record (tables[k - 1][a]; prev_table for k = 0) or that record has no pieces
+ *     (or is absent) — in both cases only if it has n_pieces > 0.
+ * Deviations, all stated here:
+ *   - Evaluation outside [0, duration] (the "earlier" branch and a reset with replan_threshold > duration ask for it) is
+ *     sogm_traj_eval's: t clamped to [0, duration].  Bezier::getPos (traj_utils/include/traj_utils/bernstein.hpp:164-177,
+ *     src/bernstein.cpp:25-59) extrapolates the first piece's polynomial below 0 and the last piece's above the duration.
+ *   - The ring holds SOGM_TRAJSRV_QUEUE samples; replan_threshold / sample_dt <= 127 (replan_threshold in (0, 1.27] at
+ *     100 Hz; the launch files use 0.02, 0.3, 0.5, 1.2).  A push into a full ring is dropped (it does not run getYaw) and
+ *     sets the sticky `overflow`; the reference's deque grows without bound when "earlier" arrivals repeat.
+ *   - Sample times stay doubles (ros::Time::fromSec rounds to nanoseconds, :202); a flagged record without pieces is
+ *     ignored (:307-311 would drop is_traj_received_).
+ *   - Out of scope: the yaw-alignment preamble (is_init_yaw, :429-450), the tracking error (:399-408), the trigger topic
+ *     and the visualiser.
+ */
+#define SOGM_TRAJSRV_QUEUE 256
+typedef struct SogmTrajServerParams {
+  double  replan_threshold;   /* seconds of trajectory kept queued, (0, 127 * sample_dt] */
+  double  sample_dt;          /* DELTA_T, 0.01 */
+  double  yaw_pi, yaw_dot_max;
+  int32_t yaw_mode;           /* 0: yaw 0 is pushed; 1: getYaw at every push */
+  int32_t reserved_;
+} SogmTrajServerParams;       /* 40 bytes */
+typedef struct SogmTrajPoint {   /* a queued sample */
+  double t, pos[3], vel[3], acc[3], yaw, yaw_dot;
+} SogmTrajPoint;              /* 96 bytes */
+enum { SOGM_CMD_PUBLISHED = 1, SOGM_CMD_HELD = 2 };
+typedef struct SogmPositionCommand {   /* quadrotor_msgs/PositionCommand as publishCmd fills it (:163-187) */
+  double  t_pub, t_sample;    /* the timer instant (header.stamp); the popped sample's time */
+  double  pos[3], vel[3], acc[3], yaw, yaw_dot;
+  int32_t traj_id;
+  int32_t flags;              /* SOGM_CMD_PUBLISHED (0: PubCallback returned without publishing: pos = init_pos, the rest
+                                 0) | SOGM_CMD_HELD (the queue's last sample, held) */
+} SogmPositionCommand;        /* 112 bytes */
+typedef struct SogmTrajServerCore {   /* one server's scalars */
+  double  ts, te, duration, last_yaw, last_yawdot, init_pos[3];
+  int32_t head, size;         /* the queue: ring slots head, head + 1, ... (mod SOGM_TRAJSRV_QUEUE), `size` of them */
+  int32_t traj_id, received, overflow, reserved_[3];
+} SogmTrajServerCore;         /* 96 bytes */
+typedef struct SogmTrajServerState {
+  SogmTrajServerCore core;
+  SogmTrajRecord     traj;    /* traj_: the trajectory fillTrajQueue samples */
+} SogmTrajServerState;        /* 96 + 2064 bytes */
+
+/*
+ * The three entries are context-free and stateless like sogm_swarm_audit: the caller's buffers, the caller's stream, no
+ * allocation, no host synchronisation.  SOGM_ERR_INVALID_ARG (with sogm_last_error text, checked first) for null pointers,
+ * counts out of range (n_ticks 1 .. 64, n_total >= 1, 0 <= agent0, 1 <= n_local <= n_total - agent0, first_tick >= 0),
+ * replan_threshold outside (0, 127 * sample_dt], period / sample_dt not whole (1 .. 4096), receive_delay outside
+ * [0, period), yaw_mode not 0 or 1, times or yaw constants that are not finite.
+ *
+ * sogm_traj_server_init: dev state [n], dev queue [n][SOGM_TRAJSRV_QUEUE] (zeroed), dev init_pos [n][3], dev init_yaw [n]
+ * or NULL (0).
+ * sogm_traj_server_run: n_ticks ticks of agents [agent0, agent0 + n_local): dev state [n_local] in/out, dev queue
+ * [n_local][SOGM_TRAJSRV_QUEUE] in/out, dev tables [n_ticks][n_total] (the executed tables the audit takes), dev prev_table
+ * [n_total] or NULL, dev received int32 [n_ticks][n_local] or NULL, dev out_cmd [n_local][n_ticks * m].
+ * sogm_camera_poses: commands cmd[i * cmd_stride], i < n (any command: an unpublished one stands at init_pos with yaw 0) ->
+ * the layouts sogm_render_depth takes: out_rot[i] = Rz(yaw) * cam2body (row-major; Rz from sogm_det::cos / sogm_det::sin, each
+ * entry (a * b + c * d) + e * f in column order), out_pos[i] = pos + Rz(yaw) * cam_offset.  cam2body [9] and cam_offset [3]
+ * are HOST arrays.  scene.camera_pose is the host expression of the same convention.
+ */
+int sogm_traj_server_init(SogmTrajServerState *state, SogmTrajPoint *queue, int n, double t_trigger,
+                          const double *init_pos /* dev [n][3] */, const double *init_yaw /* dev [n] or NULL */,
+                          void *stream);
+int sogm_traj_server_run(const SogmTrajServerParams *prm, SogmTrajServerState *state, SogmTrajPoint *queue,
+                         const SogmTrajRecord *tables, const SogmTrajRecord *prev_table, const int32_t *received,
+                         int n_ticks, int n_total, int agent0, int n_local, double t0, int first_tick, double period,
+                         double receive_delay, SogmPositionCommand *out_cmd, void *stream);
+int sogm_camera_poses(const SogmPositionCommand *cmd, int n, int cmd_stride, const double *cam2body /* host [9] */,
+                      const double *cam_offset /* host [3] */, double *out_pos /* dev [n][3] */,
+                      double *out_rot /* dev [n][9] */, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory exchange: the /broadcast_traj topic as ONE RCCL all-gather per replan tick          */
 /*   (plan_manager/src/plan_manager.cpp:364-399 publish, traj_coordinator/src/particles.cpp:131-191 receive)  */
 /* ------------------------------------------------------------------------------------------ */

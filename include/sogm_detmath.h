@@ -1,5 +1,5 @@
 /*
- * sogm_detmath.h — deterministic fp64 cbrt / cos / acos built only from IEEE-754 correctly rounded
+ * sogm_detmath.h — deterministic fp64 cbrt / cos / sin / acos / atan2 built only from IEEE-754 correctly rounded
  * operations (+ - * / sqrt) and exact exponent manipulation.
  *
  * Why: the hybrid A* heuristic (path_searching/src/fake_risk_hybrid_a_star.cpp:525-587) calls
@@ -129,6 +129,87 @@ SOGM_HD double cos(double x) {
     case 2: return -cos_k(r);
     default: return sin_k(r);
   }
+}
+
+/* sin for |x| < ~1e5: cos's reduction; sin(-x) = -sin(x) exactly */
+SOGM_HD double sin(double x) {
+  const double a       = fabs_(x);
+  const double kf      = (double)(long long)(a * 0.63661977236758134308 + 0.5);
+  const double PIO2_HI = 1.57079632673412561417e+00;
+  const double PIO2_LO = 6.07710050650619224932e-11;
+  const double PIO2_LL = 2.02226624879595063154e-21;
+  double       r       = a - kf * PIO2_HI;
+  r                    = r - kf * PIO2_LO;
+  r                    = r - kf * PIO2_LL;
+  const int k          = (int)((long long)kf & 3);
+  double    s;
+  switch (k) {
+    case 0: s = sin_k(r); break;
+    case 1: s = cos_k(r); break;
+    case 2: s = -sin_k(r); break;
+    default: s = -cos_k(r); break;
+  }
+  return x < 0 ? -s : s;
+}
+
+/* atan2 for finite arguments, signs and axes as C's atan2 (atan2(+-0, +0) = +-0, atan2(+-0, -0) = +-pi, atan2(+-y, 0) =
+ * +-pi/2).  t = min(|y|, |x|) / max(|y|, |x|) in [0, 1]; c = k / 8 the nearest eighth; atan t = atan c + atan r with
+ * r = (t - c) / (1 + t c), |r| <= 1/16 (odd Taylor series to r^17: remainder < 2^-80); atan c from a table in two parts;
+ * then the octant: pi/2 -+ . when |y| > |x|, pi - . when x < 0, the sign of y last (so atan2(-y, x) = -atan2(y, x) bit for
+ * bit).  tests/test_detmath_atan2.py bounds the error against libm (4 ulp) and checks the axes. */
+SOGM_HD double atan2(double y, double x) {
+  const double PI_HI   = 3.14159265358979311600e+00;
+  const double PI_LO   = 1.22464679914735320717e-16;
+  const double PIO2_HI = 1.57079632679489655800e+00;
+  const double PIO2_LO = 6.12323399573676603587e-17;
+  const double AT_HI[9] = {0.0,
+                           0.12435499454676144,
+                           0.24497866312686414,
+                           0.35877067027057225,
+                           0.4636476090008061,
+                           0.5585993153435624,
+                           0.6435011087932844,
+                           0.7188299996216245,
+                           0.7853981633974483};
+  const double AT_LO[9] = {0.0,
+                           -3.1253241424539383e-18,
+                           1.0698755618734451e-17,
+                           -2.4623815582638635e-17,
+                           2.2698777452961687e-17,
+                           -5.4556305485916264e-18,
+                           1.5834785051444286e-17,
+                           -2.1478388444456983e-17,
+                           3.061616997868383e-17};
+  if (x != x || y != y) return x + y;
+  const bool   yneg = (bits_of(y) >> 63) != 0, xneg = (bits_of(x) >> 63) != 0;
+  const double ay = fabs_(y), ax = fabs_(x);
+  double       a;
+  if (ay == 0.0) {
+    a = xneg ? PI_HI : 0.0;
+  } else if (ax == 0.0) {
+    a = PIO2_HI;
+  } else {
+    const bool   steep = ay > ax;
+    const double t     = steep ? ax / ay : ay / ax;
+    const int    k     = (int)(t * 8.0 + 0.5);
+    const double c     = (double)k * 0.125;
+    const double r     = (t - c) / (1.0 + t * c);
+    const double z     = r * r;
+    double       p     = 1.0 / 17.0;
+    p                  = p * z + -1.0 / 15.0;
+    p                  = p * z + 1.0 / 13.0;
+    p                  = p * z + -1.0 / 11.0;
+    p                  = p * z + 1.0 / 9.0;
+    p                  = p * z + -1.0 / 7.0;
+    p                  = p * z + 1.0 / 5.0;
+    p                  = p * z + -1.0 / 3.0;
+    const double a0    = AT_HI[k] + ((r + r * (z * p)) + AT_LO[k]);
+    if (steep)
+      a = x < 0 ? PIO2_HI + (a0 + PIO2_LO) : PIO2_HI - (a0 - PIO2_LO);
+    else
+      a = x < 0 ? PI_HI - (a0 - PI_LO) : a0;
+  }
+  return yneg ? -a : a;
 }
 
 /* asin on [0, ~0.51]: odd Taylor series, 26 terms, Horner in z = x^2 */

@@ -169,6 +169,33 @@ class SogmFlightFsm(C.Structure):
 FSM_STATE_BYTES = C.sizeof(SogmFsmState)  # 24
 FSM_PUB_NONE, FSM_PUB_NEW, FSM_PUB_HOVER = 0, 1, 2  # sogm_fsm_apply's out_pub
 
+# trajectory server (include/sogm_abi.h "trajectory server")
+SOGM_TRAJSRV_QUEUE = 256
+SOGM_CMD_PUBLISHED, SOGM_CMD_HELD = 1, 2
+
+
+class SogmTrajServerParams(C.Structure):
+    _fields_ = [("replan_threshold", C.c_double), ("sample_dt", C.c_double), ("yaw_pi", C.c_double),
+                ("yaw_dot_max", C.c_double), ("yaw_mode", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SogmTrajPoint(C.Structure):
+    _fields_ = [("t", C.c_double), ("pos", C.c_double * 3), ("vel", C.c_double * 3), ("acc", C.c_double * 3),
+                ("yaw", C.c_double), ("yaw_dot", C.c_double)]
+
+
+class SogmPositionCommand(C.Structure):
+    _fields_ = [("t_pub", C.c_double), ("t_sample", C.c_double), ("pos", C.c_double * 3), ("vel", C.c_double * 3),
+                ("acc", C.c_double * 3), ("yaw", C.c_double), ("yaw_dot", C.c_double), ("traj_id", C.c_int32),
+                ("flags", C.c_int32)]
+
+
+class SogmTrajServerCore(C.Structure):
+    _fields_ = [("ts", C.c_double), ("te", C.c_double), ("duration", C.c_double), ("last_yaw", C.c_double),
+                ("last_yawdot", C.c_double), ("init_pos", C.c_double * 3), ("head", C.c_int32), ("size", C.c_int32),
+                ("traj_id", C.c_int32), ("received", C.c_int32), ("overflow", C.c_int32), ("reserved_", C.c_int32 * 3)]
+
+
 FLIGHT_MAX_TICKS = 64
 RULES_PARALLEL = 1  # sogm_corridor_rules_batched_flags: SOGM_RULES_PARALLEL
 FINISH_WAVE = 1  # sogm_finish_batched: SOGM_FINISH_WAVE
@@ -177,6 +204,15 @@ FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "
 TRAJ_RECORD_BYTES = C.sizeof(SogmTrajRecord)  # 2064
 CYLINDER_BYTES = C.sizeof(SogmCylinder)  # 96
 DEPTH_CAMERA_BYTES = C.sizeof(SogmDepthCamera)  # 72
+
+
+class SogmTrajServerState(C.Structure):
+    _fields_ = [("core", SogmTrajServerCore), ("traj", SogmTrajRecord)]
+
+
+TRAJ_POINT_BYTES = C.sizeof(SogmTrajPoint)  # 96
+POSITION_COMMAND_BYTES = C.sizeof(SogmPositionCommand)  # 112
+TRAJSRV_STATE_BYTES = C.sizeof(SogmTrajServerState)  # 96 + 2064
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -276,6 +312,10 @@ PROTOTYPES = {
     "sogm_audit_init_agents": (_i, [_vp, _i, _vp]),
     "sogm_swarm_audit": (_i, [C.POINTER(SogmAuditParams), _vp, _i, _i, _vp, C.c_double, _i, C.c_double, _i, _i, _vp, _vp,
                               _vp, _i, _vp, _vp, _vp, _vp]),
+    "sogm_traj_server_init": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp]),
+    "sogm_traj_server_run": (_i, [C.POINTER(SogmTrajServerParams), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i,
+                                  C.c_double, C.c_double, _vp, _vp]),
+    "sogm_camera_poses": (_i, [_vp, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp]),
     "sogm_traj_allgather": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "sogm_exchange_wait": (_i, [_vp, _vp]),
     "sogm_comm_unique_id": (_i, [C.c_char_p]),

@@ -469,17 +469,16 @@ __device__ __forceinline__ void copy_record(SogmTrajRecord *dst, const SogmTrajR
   for (int w = lane; w < (int)(sizeof(SogmTrajRecord) / 16); w += stride) d[w] = s[w];
 }
 // (shared by sogm_traj.hip, sogm_planner.hpp's tick_inputs_agent, sogm_audit.hip and sogm_fsm.hip)
-// Bezier pos / vel / acc of a trajectory record at an absolute time (bernstein.cpp:25-59)
-// returns false (and zeros) for an empty record
-__device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, double out[9]) {
+// Bezier pos / vel / acc of a trajectory record (bernstein.cpp:25-59) at a time RELATIVE to its start, clamped to
+// [0, total] (sogm_trajserver.hip samples trajectory times); returns false (and zeros) for an empty record
+__device__ inline bool traj_eval_relative(const SogmTrajRecord &r, double tt, double out[9]) {
   if (r.n_pieces <= 0) {
     for (int k = 0; k < 9; ++k) out[k] = 0.0;
     return false;
   }
   double total = 0;
   for (int k = 0; k < r.n_pieces; ++k) total += r.duration[k];
-  double tt = t_abs - r.time_start;
-  tt        = tt < 0 ? 0 : (tt > total ? total : tt);
+  tt = tt < 0 ? 0 : (tt > total ? total : tt);
   // locatePiece (bernstein.hpp:164-172)
   int    piece = r.n_pieces - 1;
   double rem   = tt;
@@ -513,6 +512,10 @@ __device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, d
     out[6 + d] = a / (dur * dur);
   }
   return true;
+}
+// ... at an absolute time
+__device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, double out[9]) {
+  return traj_eval_relative(r, t_abs - r.time_start, out);
 }
 }  // namespace sogm
 

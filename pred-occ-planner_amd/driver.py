@@ -365,7 +365,7 @@ class SwarmTick:
     def __init__(self, grid="cfg2", agents_per_rank=None, rank=0, world=1, device=0, seed=0x5069,
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
-                 moving_world=None, neighbour_lag=1, audit=False, device_fsm=False):
+                 moving_world=None, neighbour_lag=1, audit=False, device_fsm=False, traj_server=None):
         self.rank, self.world, self.dist = rank, world, dist
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
@@ -456,6 +456,25 @@ class SwarmTick:
             self.auditor = SwarmAudit(self.A_tot, self.scene["goals"][lo:hi], self.scene["starts"], tl.cylinders(0),
                                       self.t0, agent0=lo, n_local=self.A_loc, moving=tl.moving, device=d)
 
+        # trajectory server (trajserver.py): the same executed tables -> every agent's 100 Hz position commands with yaw.
+        # traj_server: None / False (off), True (the launched server's parameters) or a SogmTrajServerParams
+        self.server = None
+        if traj_server is not None and traj_server is not False:
+            from . import trajserver
+            self.server = trajserver.TrajServer(self.A_tot, self.scene["starts"][lo:hi], self.t0, agent0=lo, n_local=self.A_loc,
+                                                prm=None if traj_server is True else traj_server, device=d)
+
+    def _serve_tick(self, table, received=None):
+        """feed the trajectory server the table every agent executes after tick self.tick (stream-ordered); received: which
+        agents published in this tick (the FSM's), None: an agent whose record's start time changed"""
+        if self.server is not None:
+            self.server.run(table, self.t0, self.tick, TICK_PERIOD, received=received)
+
+    def commands(self):
+        """the position commands of the last step() / fly() as a numpy structured array [A_loc][ticks * 10] (synchronises);
+        None when the SwarmTick was made without traj_server"""
+        return self.server.commands if self.server is not None else None
+
     def _audit_tick(self, table):
         """audit the table every agent executes after tick self.tick (stream-ordered)"""
         if self.auditor is not None:
@@ -540,8 +559,10 @@ class SwarmTick:
         self.last_fsm = {"now": stamp, "ok": ok, "safe": safe, "reached": reached, "pub_new": pub_new,
                          "pub_hover": pub_hover, "hover_start": hover_start, "t_start": t_start, "pos": pva_now[:, :3]}
         self._exchange()
-        if self.auditor is not None:
-            self._audit_tick(self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all())
+        if self.auditor is not None or self.server is not None:
+            table = self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all()
+            self._audit_tick(table)
+            self._serve_tick(table, pub_new | pub_hover)
         self.tick += 1
         return ok.to(torch.int32)
 
@@ -574,8 +595,10 @@ class SwarmTick:
                          "pub_new": f.pub == _abi.FSM_PUB_NEW, "pub_hover": f.pub == _abi.FSM_PUB_HOVER,
                          "hover_start": f.hover_start, "t_start": self.t_start, "pos": f.pos_now}
         self._exchange()
-        if self.auditor is not None:
-            self._audit_tick(self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all())
+        if self.auditor is not None or self.server is not None:
+            table = self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all()
+            self._audit_tick(table)
+            self._serve_tick(table, f.pub != _abi.FSM_PUB_NONE)
         self.tick += 1
         return ok
 
@@ -617,13 +640,14 @@ class SwarmTick:
                                                           else torch.zeros_like(self.all))
             if self.deconflict:
                 c.set_swarm(self.all, self.A_tot, self.now)
-            if self.auditor is not None:
-                self._audit_tick(self.own)     # ver(k); self.all is the stale table the readers see
+            self._audit_tick(self.own)     # ver(k); self.all is the stale table the readers see
+            self._serve_tick(self.own)
         else:
             c.replan(self.pva, self.goals, self.t_start, self.new, self.ok)
             self._publish()
-        if self.auditor is not None and self.neighbour_lag == 1:
+        if (self.auditor is not None or self.server is not None) and self.neighbour_lag == 1:
             self._audit_tick(self.records_all())
+            self._serve_tick(self.records_all())
         self.tick += 1
         return self.ok.clone()  # self.ok is rewritten by the next tick
 
@@ -651,6 +675,8 @@ class SwarmTick:
             if self.auditor is not None:
                 # log_r holds this rank's rows only and the four-table ring does not keep the other ranks' versions
                 raise NotImplementedError("fly() with audit=True over several ranks: audit step() ticks instead")
+            if self.server is not None:
+                raise NotImplementedError("fly() with traj_server over several ranks: serve step() ticks instead")
             return self._fly_ranks(n_ticks)
         if not hasattr(self, "_fl_tables"):
             assert self.tick == 0, "a flight starts at tick 0 (or continues a flight)"
@@ -661,7 +687,8 @@ class SwarmTick:
         log_r = torch.zeros((n_ticks, self.A_loc, _abi.TRAJ_RECORD_BYTES), dtype=torch.uint8, device="cuda")
         log_ok = torch.zeros((n_ticks, self.A_loc), dtype=torch.int32, device="cuda")
         worlds = [c.world(self.tick + i) for i in range(n_ticks)]
-        executed = self.own.clone() if self.auditor is not None else None   # the table before the call
+        sided = self.auditor is not None or self.server is not None
+        executed = self.own.clone() if sided else None   # the table before the call
         fsm_log = None
         if self.device_fsm:
             # every agent's tick is one FSMCallback: the machines' records are read and left in place (self.status / fail /
@@ -685,12 +712,15 @@ class SwarmTick:
                              "hover_start": fsm_log["hover_start"][-1]}
             if self.auditor is not None:
                 self.auditor.add(fsm_log["own"], self.t0, self.tick, TICK_PERIOD)   # the executed tables themselves
-        elif self.auditor is not None:
+            self._serve_tick(fsm_log["own"], fsm_log["pub"] != _abi.FSM_PUB_NONE)
+        elif sided:
             # the flight's executed tables: latest-wins merges of its log, one launch per tick, then one audit call
             tables = torch.empty((n_ticks, self.A_tot, _abi.TRAJ_RECORD_BYTES), dtype=torch.uint8, device="cuda")
             for i in range(n_ticks):
                 c.merge_latest(log_r[i], log_ok[i], executed, tables[i])
-            self.auditor.add(tables, self.t0, self.tick, TICK_PERIOD)
+            if self.auditor is not None:
+                self.auditor.add(tables, self.t0, self.tick, TICK_PERIOD)
+            self._serve_tick(tables)
         self.tick += n_ticks
         self._fl_next = self.tick
         self.all = self._fl_tables[(self.tick - 1) & 3]   # ver(last tick): what every agent executes now

@@ -512,4 +512,86 @@ class Audit {
   DevBuf<int32_t>        n_ev_;
 };
 
+// quadrotor_msgs/PositionCommand as publishCmd fills it (traj_server/src/bezier_traj_server.cpp:163-187): the fields a
+// host copies into the message it publishes on position_cmd.  header.frame_id is "world", trajectory_flag
+// TRAJECTORY_STATUS_READY (1); `publish` is false where PubCallback returned without publishing.
+struct PositionCommandFields {
+  bool    publish = false;
+  double  stamp = 0.0;  // header.stamp (ros::Time::now() of the timer)
+  Vec3    position{}, velocity{}, acceleration{};
+  double  yaw = 0.0, yaw_dot = 0.0;
+  int32_t trajectory_id = 0;
+  uint8_t trajectory_flag = 1;
+};
+inline PositionCommandFields positionCommandFields(const SogmPositionCommand &c) {
+  PositionCommandFields f;
+  f.publish = (c.flags & SOGM_CMD_PUBLISHED) != 0;
+  f.stamp   = c.t_pub;
+  for (int d = 0; d < 3; ++d) {
+    f.position[d]     = c.pos[d];
+    f.velocity[d]     = c.vel[d];
+    f.acceleration[d] = c.acc[d];
+  }
+  f.yaw           = c.yaw;
+  f.yaw_dot       = c.yaw_dot;
+  f.trajectory_id = c.traj_id;
+  return f;
+}
+
+// Trajectory server (sogm_abi.h "trajectory server"): owns the states and rings of n_local agents on the device; run()
+// serves a batch of executed tables on the caller's stream (no synchronisation) into a command buffer it owns,
+// commands() reads the last call's commands back, cameraPoses() hands one command per agent to sogm_render_depth's layouts.
+class TrajServer {
+ public:
+  // dev init_pos [n_local][3], dev init_yaw [n_local] or null
+  TrajServer(const SogmTrajServerParams &prm, int n_local, double t_trigger, const double *init_pos, const double *init_yaw,
+             void *stream = nullptr)
+      : prm_(prm), n_(n_local), state_((size_t)(n_local > 0 ? n_local : 1)),
+        queue_((size_t)(n_local > 0 ? n_local : 1) * SOGM_TRAJSRV_QUEUE) {
+    check_abi();
+    check(sogm_traj_server_init(state_.data(), queue_.data(), n_local, t_trigger, init_pos, init_yaw, stream),
+          "sogm_traj_server_init");
+  }
+  // dev tables [n_ticks][n_total], prev_table [n_total] or null, received int32 [n_ticks][n_local] or null; samples_per_tick
+  // = period / sample_dt.  Returns the device commands [n_local][n_ticks * samples_per_tick].
+  const SogmPositionCommand *run(const SogmTrajRecord *tables, int n_ticks, int n_total, const SogmTrajRecord *prev_table,
+                                 const int32_t *received, double t0, int first_tick, double period, int agent0,
+                                 int samples_per_tick, double receive_delay = 0.0, void *stream = nullptr) {
+    per_agent_ = n_ticks > 0 && samples_per_tick > 0 ? n_ticks * samples_per_tick : 0;
+    cmd_.resize((size_t)(n_ > 0 ? n_ : 1) * (size_t)(per_agent_ > 0 ? per_agent_ : 1));
+    check(sogm_traj_server_run(&prm_, state_.data(), queue_.data(), tables, prev_table, received, n_ticks, n_total, agent0,
+                               n_, t0, first_tick, period, receive_delay, cmd_.data(), stream),
+          "sogm_traj_server_run");
+    return cmd_.data();
+  }
+  int commandsPerAgent() const { return per_agent_; }
+  // the camera poses at command `sample` of the last run: dev out_pos [n_local][3], out_rot [n_local][9]
+  void cameraPoses(int sample, const double cam2body[9], const double cam_offset[3], double *out_pos, double *out_rot,
+                   void *stream = nullptr) {
+    if (sample < 0 || sample >= per_agent_) throw std::out_of_range("sogm_host::TrajServer::cameraPoses: no such command");
+    check(sogm_camera_poses(cmd_.data() + sample, n_, per_agent_, cam2body, cam_offset, out_pos, out_rot, stream),
+          "sogm_camera_poses");
+  }
+  // synchronous read-backs
+  std::vector<SogmPositionCommand> commands() {
+    std::vector<SogmPositionCommand> out((size_t)n_ * (size_t)per_agent_);
+    (void)hipDeviceSynchronize();
+    if (!out.empty()) cmd_.get(out.data(), out.size());
+    return out;
+  }
+  std::vector<SogmTrajServerState> states() {
+    std::vector<SogmTrajServerState> out((size_t)n_);
+    (void)hipDeviceSynchronize();
+    state_.get(out.data(), out.size());
+    return out;
+  }
+
+ private:
+  SogmTrajServerParams         prm_;
+  int                          n_, per_agent_ = 0;
+  DevBuf<SogmTrajServerState>  state_;
+  DevBuf<SogmTrajPoint>        queue_;
+  DevBuf<SogmPositionCommand>  cmd_;
+};
+
 }  // namespace sogm_host
