@@ -123,6 +123,22 @@ int sogm_download_reference_layout(sogm_ctx *ctx, int agent, float *out_vt_host)
  * pool_overflow, ...}.  Any pointer may be NULL. */
 int sogm_dsp_download_state(sogm_dsp *d, int agent, float *store_host, float *objnum_host,
                             int32_t *counters_host);
+/* Test hook, the inverse of sogm_dsp_download_state (synchronous): makes store_host [V][2*max][9] (reference layout) agent
+ * `agent`'s particle store as it stands BETWEEN two updates, so that a test can start from a hand-built store.  Rules:
+ *   - every slot's flag (entry 0) is exactly 0, 0.6f or 1.0f (empty / a resampler's copy / a particle: what
+ *     mapOccupancyCalculationAndResample leaves) and a non-empty slot's vz (entry 3) is 0; entry 8 (the update time) is
+ *     ignored; entries 1, 2 and 4-7 of an empty slot are stored as given (nothing reads them), its entry 3 is not kept
+ *     (the device stores no vz): sogm_dsp_download_state gives 0 for every slot's entries 3 and 8;
+ *   - last_pos3_host / last_stamp become the pose and stamp of the "previous update" (the next sogm_update_dsp is not a first
+ *     call: its deltas are taken against them); cursors3_host = {p_seq, v_seq, rand_seq}, each within its table;
+ *   - the agent's voxels_objects_number (weight sums, mean velocities, future status) is zeroed, its debug and error
+ *     counters (counters 0-3 and 10-12 of sogm_dsp_download_state) are cleared, and the velocity estimation forgets its
+ *     previous frame's clusters (its sticky error code stays).  The observation tables and the new-born list of the last
+ *     update stay as they are.
+ * Anything else — a NULL pointer, an agent out of range, another flag value, a NaN flag, vz != 0 on a non-empty slot, a
+ * cursor outside its table — returns SOGM_ERR_INVALID_ARG and changes nothing.  Other agents are never touched. */
+int sogm_dsp_upload_state(sogm_dsp *d, int agent, const float *store_host, const float *last_pos3_host, double last_stamp,
+                          const int32_t *cursors3_host);
 /* input_cloud_with_velocity of the last update (the new-born list, rows {x,y,z,vx,vy,vz,intensity}, at most `cap`
  * rows), its length, and counters4 = {clusters, possibly dynamic, matched, error code of the velocity estimation}.
  * The error code is 0 or the capacity that was exceeded: 2 = a point with more than 128 neighbours within the cluster

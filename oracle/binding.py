@@ -371,6 +371,15 @@ class DspOracle:
         lib().orc_dsp_state(self.h, fptr(store), fptr(objnum), counters.ctypes.data_as(C.c_void_p))
         return store, objnum, counters
 
+    def set_state(self, store, last_pos, last_stamp, cursors):
+        """orc_dsp_set_state: the meaning of sogm_dsp_upload_state.  Returns 0, or -1 (refused, nothing changed)."""
+        st = np.ascontiguousarray(store, np.float32)
+        assert st.shape == (self.V, self.S, 9), st.shape
+        lp = np.ascontiguousarray(last_pos, np.float32)
+        cu = np.ascontiguousarray(cursors, np.int32)
+        assert lp.shape == (3,) and cu.shape == (3,)
+        return lib().orc_dsp_set_state(self.h, fptr(st), fptr(lp), C.c_double(last_stamp), cu.ctypes.data_as(C.c_void_p))
+
     def observations(self, NP):
         OM = self.params.obs_max_per_pyramid
         nobs = np.zeros(NP, np.int32)

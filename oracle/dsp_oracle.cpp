@@ -860,6 +860,34 @@ void orc_dsp_state(void *h, float *store, float *objnum, int *counters) {
     counters[9] = d.NP;
   }
 }
+// Test hook with the meaning of sogm_dsp_upload_state: a between-updates store replaces the particle store.
+int orc_dsp_set_state(void *h, const float *store, const float *last_pos3, double last_stamp, const int32_t *cursors3) {
+  Dsp &d = *(Dsp *)h;
+  if (!store || !last_pos3 || !cursors3) return -1;
+  if (cursors3[0] < 0 || cursors3[0] >= (int)d.pg.size() || cursors3[1] < 0 || cursors3[1] >= (int)d.vg.size() ||
+      cursors3[2] < 0 || cursors3[2] >= (int)d.rnd.size())
+    return -1;
+  const size_t n = (size_t)d.V * d.S;
+  for (size_t i = 0; i < n; ++i) {
+    const float *o = store + i * 9;
+    if (!(o[0] == 0.f || o[0] == 0.6f || o[0] == 1.f)) return -1;
+    if (o[0] != 0.f && !(o[3] == 0.f)) return -1;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    for (int k = 0; k < 8; ++k) d.store[i * 9 + k] = store[i * 9 + k];
+    d.store[i * 9 + 8] = 0.f;
+  }
+  std::fill(d.objnum.begin(), d.objnum.end(), 0.f);
+  for (int k = 0; k < 3; ++k) d.last_p[k] = last_pos3[k];
+  d.last_t = last_stamp;
+  d.first  = false;
+  d.pseq   = cursors3[0];
+  d.vseq   = cursors3[1];
+  d.rseq   = cursors3[2];
+  d.dbg_voxel_full = d.dbg_pyr_full = d.dbg_out = d.dbg_vel_draws = 0;
+  d.clusters_last.clear();
+  return 0;
+}
 // per-pyramid observation table of the last update: nobs[NP], pc [NP][OM][5]
 // input_cloud_with_velocity of the last update: rows {x, y, z, vx, vy, vz, intensity}; returns the row count;
 // counters3 = {clusters, possibly dynamic, matched}

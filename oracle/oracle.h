@@ -148,6 +148,11 @@ int   orc_dsp_update(void *h, int n, const float *pts, const float *labels, floa
 int   orc_dsp_publish(void *h, float *out_vt, float threshold, int inf_step);
 void  orc_dsp_state(void *h, float *store, float *objnum, int *counters);
 void  orc_dsp_observations(void *h, int *nobs, float *pc, float *maxlen);
+/* the meaning of sogm_dsp_upload_state (include/sogm_abi_debug.h): store [V][2*max][9] with flags exactly 0 / 0.6f / 1.0f and
+ * vz == 0 on non-empty slots (entry 8 ignored) becomes the particle store, last_pos3 / last_stamp the previous update's pose,
+ * cursors3 = {p_seq, v_seq, rand_seq}; the object numbers, the debug counters and the previous frame's clusters are cleared.
+ * Returns 0, or -1 when the store or a cursor is refused (nothing changed). */
+int   orc_dsp_set_state(void *h, const float *store, const float *last_pos3, double last_stamp, const int32_t *cursors3);
 /* orc_dsp_update with labels == NULL runs velocityEstimationThread (dsp_dynamic.h:1487-1678) itself.
  * orc_dsp_born: input_cloud_with_velocity of the last update, rows {x,y,z,vx,vy,vz,intensity} */
 int   orc_dsp_born(void *h, float *out, int cap, int *counters3);

@@ -330,6 +330,7 @@ PROTOTYPES = {
     "sogm_update_dsp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_dsp_publish": (_i, [_vp, _vp, _vp]),
     "sogm_dsp_download_state": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "sogm_dsp_upload_state": (_i, [_vp, _i, _vp, _vp, C.c_double, _vp]),
     "sogm_dsp_download_born": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     "sogm_dsp_download_observations": (_i, [_vp, _i, _vp, _vp, _vp]),
 }

@@ -1866,6 +1866,61 @@ int sogm_dsp_download_state(sogm_dsp *h, int agent, float *store, float *objnum,
   return SOGM_OK;
 }
 
+// Test hook (sogm_abi_debug.h): the inverse of sogm_dsp_download_state for a between-updates store.  Validated on the
+// host before anything is written; plain copies, no kernel.
+int sogm_dsp_upload_state(sogm_dsp *h, int agent, const float *store, const float *last_pos3, double last_stamp,
+                          const int32_t *cursors3) {
+  if (!h || agent < 0 || agent >= h->d.A || !store || !last_pos3 || !cursors3) return SOGM_ERR_INVALID_ARG;
+  DspDev &d = h->d;
+  if (cursors3[0] < 0 || cursors3[0] >= d.n_gauss || cursors3[1] < 0 || cursors3[1] >= d.n_gauss || cursors3[2] < 0 ||
+      cursors3[2] >= d.n_rand)
+    return SOGM_ERR_INVALID_ARG;
+  const size_t V = d.V, VS = V * DSP_SLOTS;
+  std::vector<uint8_t> fl(VS, (uint8_t)F_EMPTY);
+  std::vector<float>   f[6];
+  for (int k = 0; k < 6; ++k) f[k].assign(VS, 0.f);
+  static const int src[6] = {1, 2, 4, 5, 6, 7};  // vx vy px py pz w
+  for (size_t v = 0; v < V; ++v)
+    for (int p = 0; p < d.S; ++p) {
+      const float *o  = store + (v * d.S + p) * 9;
+      const size_t at = v * DSP_SLOTS + p;
+      uint8_t      c;
+      if (o[0] == 0.f)
+        c = F_EMPTY;
+      else if (o[0] == 1.f)
+        c = F_VALID;
+      else if (o[0] == 0.6f)
+        c = F_RESAMP;
+      else
+        return SOGM_ERR_INVALID_ARG;  // (a NaN flag compares unequal to all three)
+      if (c != F_EMPTY && !(o[3] == 0.f)) return SOGM_ERR_INVALID_ARG;
+      fl[at] = c;
+      for (int k = 0; k < 6; ++k) f[k][at] = o[src[k]];
+    }
+  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
+  SOGM_HIP_CHECK(hipDeviceSynchronize());
+  DspAgent s;
+  SOGM_HIP_CHECK(hipMemcpy(&s, d.ag + agent, sizeof(s), hipMemcpyDeviceToHost));
+  SOGM_HIP_CHECK(hipMemcpy(d.flag + (size_t)agent * VS, fl.data(), VS, hipMemcpyHostToDevice));
+  for (int k = 0; k < 6; ++k)
+    SOGM_HIP_CHECK(hipMemcpy(d.f[k] + (size_t)agent * VS, f[k].data(), VS * sizeof(float), hipMemcpyHostToDevice));
+  SOGM_HIP_CHECK(hipMemset(d.occ + (size_t)agent * 4 * V, 0, 4 * V * sizeof(float)));
+  SOGM_HIP_CHECK(hipMemset(d.fut + (size_t)agent * d.T * V, 0, (size_t)d.T * V * sizeof(float)));
+  for (int k = 0; k < 3; ++k) s.last_p[k] = last_pos3[k];
+  s.last_t = last_stamp;
+  s.first  = 0;
+  s.pseq   = cursors3[0];
+  s.vseq   = cursors3[1];
+  s.rseq   = cursors3[2];
+  s.cand_cnt = 0;
+  s.dbg_voxel_full = s.dbg_pyr_full = s.dbg_out = 0;
+  s.err_unconverged = s.err_pool = s.err_points = 0;
+  s.vel_n_last = 0;
+  SOGM_HIP_CHECK(hipMemcpy(d.ag + agent, &s, sizeof(s), hipMemcpyHostToDevice));
+  SOGM_HIP_CHECK(hipDeviceSynchronize());
+  return SOGM_OK;
+}
+
 int sogm_dsp_download_observations(sogm_dsp *h, int agent, int32_t *nobs, float *pc, float *maxlen) {
   if (!h || agent < 0 || agent >= h->d.A) return SOGM_ERR_INVALID_ARG;
   DspDev &d = h->d;

@@ -99,6 +99,18 @@ class DspMap:
                                             counters.ctypes.data_as(C.c_void_p)), "sogm_dsp_download_state")
         return store, objnum, counters
 
+    def upload_state(self, agent, store, last_pos, last_stamp, cursors):
+        """Test hook (sogm_dsp_upload_state): a between-updates store [V, 2*max, 9] (flags 0 / 0.6 / 1, vz 0) becomes the
+        agent's; last_pos / last_stamp the previous update's pose; cursors = (p_seq, v_seq, rand_seq).  Returns the status
+        (SOGM_OK or SOGM_ERR_INVALID_ARG: nothing changed) instead of raising: tests assert both."""
+        st = np.ascontiguousarray(store, np.float32)
+        assert st.shape == (self.map.V, self.S, 9), st.shape
+        lp = np.ascontiguousarray(last_pos, np.float32)
+        cu = np.ascontiguousarray(cursors, np.int32)
+        assert lp.shape == (3,) and cu.shape == (3,)
+        return lib().sogm_dsp_upload_state(self._h, agent, st.ctypes.data_as(C.c_void_p), lp.ctypes.data_as(C.c_void_p),
+                                           C.c_double(last_stamp), cu.ctypes.data_as(C.c_void_p))
+
     def download_observations(self, agent):
         OM = self.params.obs_max_per_pyramid
         nobs = np.zeros(self.NP, np.int32)

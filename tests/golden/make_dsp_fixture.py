@@ -35,13 +35,21 @@ Restated, block by block (dsp_dynamic.h):
                                          addAParticle (:1268-1286: first slot with flag < 0.1 gets flag 15)
   mapOccupancyCalculationAndResample :994-1130  weights < 1e-3 removed, object numbers, the future status per prediction time,
                                          flags back to 1, the systematic resample with copies into the first empty slots (0.6)
-Run from the repo root:   python tests/golden/make_dsp_fixture.py      (a few minutes: the sweeps are Python loops)
+The class takes the grid as a constructor parameter (the defaults are the flight's 66 x 66 x 20 x 6), has set_state — the contract
+of the sogm_dsp_upload_state test hook — and, with trace=True, records what happened for LABELLING only: one event per sweep step
+(stay / move / out, the slot taken, voxel-full, pyramid-full and whose slot a vanish frees), a count per branch taken, and the
+smallest margin of every decision a tolerance could touch.  tests/golden/make_dsp_cases_fixture.py runs it branch by branch on
+hand-built stores.  Every non-zero entry of voxels_objects_number, per voxel and update, goes to dsp_independent_objnum.json;
+dsp_independent.json itself is byte for byte the file of before the class was parametrised.
+Run from the repo root:   python tests/golden/make_dsp_fixture.py      (a quarter of a minute: the sweeps are Python loops)
 """
+import base64
 import hashlib
 import json
 import math
 import os
 import sys
+import zlib
 
 import numpy as np
 
@@ -72,31 +80,46 @@ def fl(x):
 
 
 class DSP:
-    def __init__(self, tables, sigma_obs=0.05, p_det=0.95, kappa=0.01, nb_weight=0.0001, nb_num=20):
+    def __init__(self, tables, sigma_obs=0.05, p_det=0.95, kappa=0.01, nb_weight=0.0001, nb_num=20, grid=(NX, NY, NZ, T),
+                 trace=False):
+        """grid = (NX, NY, NZ, T).  trace: keep an event trace of the sweep, the branches taken and the margins of every
+        decision a tolerance could touch (self.trace / self.marks / self.margins: LABELLING ONLY, nothing reads them back)."""
+        self.NX, self.NY, self.NZ, self.T = grid
+        self.RES, self.MAXP, self.OMAX = RES, MAXP, OMAX
+        self.S = 2 * self.MAXP                                                    # SAFE_PARTICLE_NUM_VOXEL
+        self.V = self.NX * self.NY * self.NZ
+        self.NPH, self.NPV = NPH, NPV
+        self.NP = self.NPH * self.NPV
+        self.SP = (int(self.V * self.MAXP + 1e5) // (360 * 180 // ARES // ARES)) * 2     # SAFE_PARTICLE_NUM_PYRAMID
+        self.PRED = PRED[:self.T]
+        self.tracing = trace
+        self.trace, self.marks, self.margins, self.zero_dots, self.trunc_hits = [], {}, {}, [], []
         self.pg, self.vg, self.rnd = tables
         self.pseq = self.vseq = self.rseq = 0
         self.sigma = f32(sigma_obs)
         self.pdet, self.kappa, self.nbw, self.nbn = f32(p_det), f32(kappa), f32(nb_weight), nb_num
-        self.hx = fl(fl(RES * f32(NX)) * f32(0.5))
-        self.hy = fl(fl(RES * f32(NY)) * f32(0.5))
-        self.hz = fl(fl(RES * f32(NZ)) * f32(0.5))
+        self.hx = fl(fl(self.RES * f32(self.NX)) * f32(0.5))
+        self.hy = fl(fl(self.RES * f32(self.NY)) * f32(0.5))
+        self.hz = fl(fl(self.RES * f32(self.NZ)) * f32(0.5))
         ang = f32(float(f32(ARES) / f32(180.0)) * 3.14159265358979323846)     # (float / float) x a double literal, stored as float
         self.bh0 = [(f32(-math.sin(float(f32(i) * ang))), f32(math.cos(float(f32(i) * ang))), f32(0)) for i in range(-HFH, HFH + 1)]
         self.bv0 = [(f32(math.sin(float(f32(i) * ang))), f32(0), f32(math.cos(float(f32(i) * ang)))) for i in range(-HFV, HFV + 1)]
         self.nei = []
-        for i in range(NP):
-            h0, v0 = i // NPV, i % NPV
-            self.nei.append([h * NPV + v for h in (h0 - 1, h0, h0 + 1) for v in (v0 - 1, v0, v0 + 1) if 0 <= h < NPH and 0 <= v < NPV])
+        for i in range(self.NP):
+            h0, v0 = i // self.NPV, i % self.NPV
+            self.nei.append([h * self.NPV + v for h in (h0 - 1, h0, h0 + 1) for v in (v0 - 1, v0, v0 + 1) if 0 <= h < self.NPH and 0 <= v < self.NPV])
         c = f32(1.0) / f32(math.sqrt(float(f32(2.0 * 1.57079632679489661923))))
         vals = (np.arange(20000, dtype=np.int64) - 10000).astype(f32) * f32(0.001)
         self.pdf = (c * np.exp(-(vals.astype(np.float64) ** 2).astype(f32).astype(np.float64) / 2.0).astype(f32)).astype(f32)
-        self.store = np.zeros((V, S, 9), f32)
-        self.obj = np.zeros((V, 4 + T), f32)
-        self.pyr = np.zeros((NP, SP, 3), np.int32)
-        self.pc = np.zeros((NP, OMAX, 5), f32)
-        self.nobs = np.zeros(NP, np.int32)
-        self.maxlen = np.full(NP, -1.0, f32)
+        self.store = np.zeros((self.V, self.S, 9), f32)
+        self.obj = np.zeros((self.V, 4 + self.T), f32)
+        self.pyr = np.zeros((self.NP, self.SP, 3), np.int32)
+        self.pc = np.zeros((self.NP, self.OMAX, 5), f32)
+        self.nobs = np.zeros(self.NP, np.int32)
+        self.maxlen = np.full(self.NP, -1.0, f32)
         self.last = None
+        self.born = []
+        self.weights_exact = False      # (trace only) set by set_state, lost at the first update that lists a particle
         self.update_time = f32(0)
         self.cur = [f32(0)] * 3
 
@@ -116,17 +139,54 @@ class DSP:
         r = mul(mul((w, x, y, z), (f32(0), f32(v[0]), f32(v[1]), f32(v[2]))), inv)
         return (f32(r[1]), f32(r[2]), f32(r[3]))
 
-    @staticmethod
-    def dot(x, y, z, n):
-        return fl(fl(fl(x * n[0]) + fl(y * n[1])) + fl(z * n[2]))
+    def note(self, name, n=1):
+        if self.tracing:
+            self.marks[name] = self.marks.get(name, 0) + n
+
+    def margin(self, name, value):
+        # while weights_exact holds, every weight is plain IEEE arithmetic on injected values (no normal-PDF entry has entered
+        # any): all readings agree on it bit for bit, the tests then compare it with no tolerance, and it needs no margin
+        if self.tracing and not (self.weights_exact and name in ("removal", "resample", "split_truncation")):
+            self.margins[name] = min(self.margins.get(name, float("inf")), float(value))
+
+    def dot(self, x, y, z, n):
+        t = fl(fl(fl(x * n[0]) + fl(y * n[1])) + fl(z * n[2]))
+        if self.tracing:
+            size = math.sqrt(float(x) ** 2 + float(y) ** 2 + float(z) ** 2)
+            if t == 0:
+                self.zero_dots.append((float(x), float(y), float(z)))
+            elif size > 0:
+                self.margin("dot", abs(float(t)) / size)
+        return t
+
+    def set_state(self, store, last_pos, last_stamp, cursors):
+        """The contract of sogm_dsp_upload_state (include/sogm_abi_debug.h): a between-updates store — flags exactly 0 / 0.6 / 1,
+        vz == 0 on non-empty slots, entry 8 ignored — the previous update's pose and stamp, the three table cursors; the object
+        numbers are zeroed.  Returns 0, or -1 (refused: nothing changed)."""
+        st = np.asarray(store, f32)
+        if st.shape != (self.V, self.S, 9):
+            return -1
+        fl_ = st[:, :, 0]
+        ok = (fl_ == f32(0)) | (fl_ == f32(0.6)) | (fl_ == f32(1.0))
+        if not ok.all() or ((fl_ != 0) & ~(st[:, :, 3] == 0)).any():
+            return -1
+        if not (0 <= cursors[0] < len(self.pg) and 0 <= cursors[1] < len(self.vg) and 0 <= cursors[2] < len(self.rnd)):
+            return -1
+        self.store = st.copy()
+        self.store[:, :, 8] = 0
+        self.obj[:] = 0
+        self.last = (f32(last_pos[0]), f32(last_pos[1]), f32(last_pos[2]), float(last_stamp))
+        self.pseq, self.vseq, self.rseq = int(cursors[0]), int(cursors[1]), int(cursors[2])
+        self.weights_exact = True
+        return 0
 
     def in_fov(self, x, y, z):
-        return (self.dot(x, y, z, self.bh[0]) >= 0 and self.dot(x, y, z, self.bh[NPH]) <= 0 and
-                self.dot(x, y, z, self.bv[0]) <= 0 and self.dot(x, y, z, self.bv[NPV]) >= 0)
+        return (self.dot(x, y, z, self.bh[0]) >= 0 and self.dot(x, y, z, self.bh[self.NPH]) <= 0 and
+                self.dot(x, y, z, self.bv[0]) <= 0 and self.dot(x, y, z, self.bv[self.NPV]) >= 0)
 
     def pyr_h(self, x, y, z):
         last = f32(1.0)
-        for i in range(NPH):
+        for i in range(self.NPH):
             t = self.dot(x, y, z, self.bh[i + 1])
             if fl(last * t) <= 0:
                 return i
@@ -135,7 +195,7 @@ class DSP:
 
     def pyr_v(self, x, y, z):
         last = f32(-1.0)
-        for j in range(NPV):
+        for j in range(self.NPV):
             t = self.dot(x, y, z, self.bv[j + 1])
             if fl(last * t) <= 0:
                 return j
@@ -145,11 +205,21 @@ class DSP:
     def voxel_index(self, px, py, pz):
         if px >= self.hx or px <= -self.hx or py >= self.hy or py <= -self.hy or pz >= self.hz or pz <= -self.hz:
             return -1
-        x = int(fl(fl(px + self.hx) / RES))
-        y = int(fl(fl(py + self.hy) / RES))
-        z = int(fl(fl(pz + self.hz) / RES))
-        idx = z * NY * NX + y * NX + x
-        return idx if 0 <= idx < V else -1
+        x = int(fl(fl(px + self.hx) / self.RES))
+        y = int(fl(fl(py + self.hy) / self.RES))
+        z = int(fl(fl(pz + self.hz) / self.RES))
+        if self.tracing:
+            for ax, (p_, h_, i_, n_) in enumerate(((px, self.hx, x, self.NX), (py, self.hy, y, self.NY), (pz, self.hz, z, self.NZ))):
+                c = float(fl(fl(p_ + h_) / self.RES))
+                dist = abs(c - round(c))
+                if dist < 1e-4:
+                    self.trunc_hits.append((ax, float(p_), i_))
+                else:
+                    self.margin("trunc", dist)
+                if i_ == n_:
+                    self.note("axis_index_equals_size_" + "xyz"[ax])
+        idx = z * self.NY * self.NX + y * self.NX + x
+        return idx if 0 <= idx < self.V else -1
 
     def gauss_p(self):
         v = self.pg[self.pseq]
@@ -168,6 +238,11 @@ class DSP:
 
     def pdf_q(self, x, mu):
         c = fl(fl(x - mu) / self.sigma)
+        if self.tracing:
+            if (c > f32(9.9)).any():
+                self.note("pdf_clamp_high")
+            if (c < f32(-9.9)).any():
+                self.note("pdf_clamp_low")
         c = np.where(c > f32(9.9), f32(9.9), np.where(c < f32(-9.9), f32(-9.9), c)).astype(f32)
         return self.pdf[(c * f32(1000) + f32(10000)).astype(f32).astype(np.int64)]
 
@@ -189,23 +264,33 @@ class DSP:
         self.nobs[:] = 0
         self.maxlen[:] = -1.0
         rot, valid = [], 0
+        self.point_pyr = []      # (trace only: the pyramid of every input point, -1 outside the FOV)
         for p in np.asarray(points, f32).reshape(-1, 3):
             r = self.rotate(p, quat)
             rot.append(r)
+            if self.tracing:
+                self.point_pyr.append(-1)
             if self.in_fov(*r):
-                pi = self.pyr_h(*r) * NPV + self.pyr_v(*r)
+                pi = self.pyr_h(*r) * self.NPV + self.pyr_v(*r)
+                if self.tracing:
+                    self.point_pyr[-1] = pi
                 k = self.nobs[pi]
                 ln = f32(math.sqrt(float(fl(fl(fl(r[0] * r[0]) + fl(r[1] * r[1])) + fl(r[2] * r[2])))))
                 self.pc[pi, k] = (r[0], r[1], r[2], f32(0), ln)
                 if self.maxlen[pi] < ln:
                     self.maxlen[pi] = ln
                 self.nobs[pi] += 1
-                if self.nobs[pi] >= OMAX:
-                    self.nobs[pi] = OMAX - 1
+                if self.nobs[pi] >= self.OMAX:
+                    self.nobs[pi] = self.OMAX - 1
                 valid += 1
         self.expected = fl(fl(self.nbw * f32(valid)) * f32(self.nbn))
         # the new-born list as velocityEstimationThread leaves it: the rotated point + the sensor position, the label
-        born = [((fl(r[0] + self.cur[0]), fl(r[1] + self.cur[1]), fl(r[2] + self.cur[2])), lab) for r, lab in zip(rot, np.asarray(labels, f32).reshape(-1, 4))]
+        # (an empty cloud leaves the list of the previous update in place: velocityEstimationThread returns at once, :1488-1490)
+        if len(rot) > 0:
+            self.born = [((fl(r[0] + self.cur[0]), fl(r[1] + self.cur[1]), fl(r[2] + self.cur[2])), lab) for r, lab in zip(rot, np.asarray(labels, f32).reshape(-1, 4))]
+        elif self.tracing:
+            self.note("empty_cloud_reuses_born_list" if self.born else "empty_cloud")
+        born = self.born
         self.predict(fl(-d[0]), fl(-d[1]), fl(-d[2]), dt)
         self.map_update()
         self.add_new_born(born)
@@ -221,6 +306,7 @@ class DSP:
             q = st[v, p]
             if not (q[0] > f32(0.1) and q[0] < f32(6.0)):
                 continue
+            was_copy = bool(q[0] < f32(0.7))      # (trace only: a resampler's copy, flag 0.6)
             q[0] = 1.0
             if abs(float(fl(fl(q[1] * q[2]) * q[3]))) < 1e-6:
                 pass
@@ -233,34 +319,57 @@ class DSP:
             q[5] = fl(q[5] + fl(fl(dt * q[2]) + oy))
             q[6] = fl(q[6] + fl(fl(dt * q[3]) + oz))
             nv = self.voxel_index(q[4], q[5], q[6])
+            ev = None
+            if self.tracing:      # one event per sweep step (labelling only)
+                ev = {"src": (v, p), "kind": "out" if nv < 0 else ("stay" if nv == v else "move"), "dst_voxel": nv, "slot": None,
+                      "voxel_full": False, "pyramid_full": False, "pyramid": -1, "listed": False, "frees": None,
+                      "pos": (float(q[4]), float(q[5]), float(q[6])), "w_before": float(q[7]), "was_copy": was_copy}
+                self.trace.append(ev)
             if nv >= 0:
-                self.move(nv, v, p)
+                self.move(nv, v, p, ev)
             else:
                 q[0] = 0.0
+                if ev is not None:
+                    ev["frees"] = (v, p)
+        if self.tracing:      # what the sweep passed over: arrivals (flag 7) are not moved a second time
+            self.skipped_arrivals = [(v_, p_) for v_, p_ in zip(*[a.tolist() for a in np.nonzero(st[:, :, 0] > f32(6.0))])]
 
-    def move(self, nv, v, p):
+    def move(self, nv, v, p, ev=None):
         st = self.store
         ni = p
         if nv != v:
             src = st[v, p].copy()
             st[v, p, 0] = 0.0
-            for i in range(S):
+            if ev is not None:
+                ev["dst_occupied"] = [i for i in range(self.S) if not st[nv, i, 0] < f32(0.1)]
+            for i in range(self.S):
                 if st[nv, i, 0] < f32(0.1):
                     ni = i
                     st[nv, i, 0] = 7.0
                     st[nv, i, 1:9] = src[1:9]
                     break
             else:
+                if ev is not None:
+                    ev["voxel_full"] = True
                 return -1
+        if ev is not None:
+            ev["slot"] = ni
         q = st[nv, ni]
         if self.in_fov(q[4], q[5], q[6]):
-            pi = self.pyr_h(q[4], q[5], q[6]) * NPV + self.pyr_v(q[4], q[5], q[6])
-            for j in range(SP):
+            pi = self.pyr_h(q[4], q[5], q[6]) * self.NPV + self.pyr_v(q[4], q[5], q[6])
+            if ev is not None:
+                ev["pyramid"] = pi
+            for j in range(self.SP):
                 if self.pyr[pi, j, 0] == 0:
                     self.pyr[pi, j] = (1, nv, ni)
+                    if ev is not None:
+                        ev["listed"] = True
                     break
             else:
                 q[0] = 0.0
+                if ev is not None:
+                    ev["pyramid_full"], ev["frees"] = True, (nv, ni)
+                    ev["list_at_vanish"] = [(int(a), int(b)) for _, a, b in self.pyr[pi]]
                 return -2
             if abs(float(fl(fl(q[1] * q[2]) * q[3]))) < 1e-6:
                 pass
@@ -272,26 +381,37 @@ class DSP:
 
     def map_update(self):
         st, pc = self.store, self.pc
+        if (self.pyr[:, :, 0] & 1).any():      # a listed particle brings normal-PDF entries into C_k and into its own weight
+            self.weights_exact = False
         # C_k: per observation, the neighbour pyramids in list order, their listed particles in slot order — one float sum each
         for i in np.nonzero(self.nobs > 0)[0].tolist():
             n = int(self.nobs[i])
             acc = pc[i, :n, 3].copy()
+            if self.tracing and sum(1 for pi in self.nei[i] if (self.pyr[pi, :, 0] & 1).any()) >= 2:
+                self.note("ck_over_two_lists")
             for pi in self.nei[i]:
-                for s in range(SP):
+                for s in range(self.SP):
                     if self.pyr[pi, s, 0] & 1:
                         q = st[self.pyr[pi, s, 1], self.pyr[pi, s, 2]]
                         gk = (self.pdf_q(q[4], pc[i, :n, 0]) * self.pdf_q(q[5], pc[i, :n, 1])).astype(f32)
                         gk = (gk * self.pdf_q(q[6], pc[i, :n, 2])).astype(f32)
                         acc = (acc + ((self.pdet * q[7]).astype(f32) * gk).astype(f32)).astype(f32)
             pc[i, :n, 3] = (acc + fl(self.expected + self.kappa)).astype(f32)
-        for i in range(NP):
-            for s in range(SP):
+        for i in range(self.NP):
+            for s in range(self.SP):
                 if not (self.pyr[i, s, 0] & 1):
                     continue
                 q = st[self.pyr[i, s, 1], self.pyr[i, s, 2]]
                 px, py, pz = q[4], q[5], q[6]
                 dist = f32(math.sqrt(float(fl(fl(fl(px * px) + fl(py * py)) + fl(pz * pz)))))
+                if self.tracing:
+                    self.note("listed_in_pyramid_with_%d_neighbours" % len(self.nei[i]))
+                    if self.maxlen[i] > 0:
+                        self.margin("occlusion", abs(float(dist) - float(fl(self.maxlen[i] + THICK))) / float(dist))
+                    else:
+                        self.note("max_length_unset")
                 if self.maxlen[i] > 0 and dist > fl(self.maxlen[i] + THICK):
+                    self.note("occluded")
                     continue
                 tot = f32(0)
                 for ni in self.nei[i]:
@@ -319,10 +439,15 @@ class DSP:
                 pcx, pcy, pcz = fl(pt[0] - self.cur[0]), fl(pt[1] - self.cur[1]), fl(pt[2] - self.cur[2])
                 vi = self.voxel_index(pcx, pcy, pcz)
                 if vi < 0:
+                    self.note("point_outside_map")
                     continue
                 ws = wd = wsd = f32(0)
-                for k in range(S):
+                for k in range(self.S):
                     q = st[vi, k]
+                    if self.tracing and q[0] > f32(14.0):
+                        self.note("split_passes_over_flag_15")
+                    if self.tracing and q[0] > f32(6.0) and q[0] < f32(14.0):
+                        self.note("split_counts_flag_7")
                     if q[0] > f32(0.9) and q[0] < f32(14.0):
                         vabs = fl(fl(abs(q[1]) + abs(q[2])) + abs(q[3]))
                         if vabs < f32(0.1):
@@ -338,12 +463,28 @@ class DSP:
                 p_s_n = fl(p_s / fl(p_s + p_d))
                 x = fl(f32(n_model) * p_s_n)
                 n_static = -2147483648 if not np.isfinite(x) else int(x)      # (int)NaN on x86-64
+                if self.tracing:
+                    if not np.isfinite(x):
+                        self.note("split_nan")
+                    else:
+                        self.note("split_all_static" if wd == 0 and wsd == 0 else "split_all_dynamic" if ws == 0 and wsd == 0 else
+                                  "split_mixed_band" if wsd > 0 else "split_static_and_dynamic")
+                        if p_s_n == 0 or p_s_n == 1 or ws == wd:
+                            self.note("split_exact")      # one class only (m = 1), or p_s == p_d bit for bit (1/2): no rounding takes part
+                        else:      # the truncation (int)(16 p_static): relative distance to the nearest integer
+                            self.margin("split_truncation", min(float(x) - int(x), int(x) + 1 - float(x)) / float(x))
                 n_static = max(n_min, n_static)
                 for p in range(self.nbn):
                     ppx, ppy, ppz = fl(pcx + self.gauss_p()), fl(pcy + self.gauss_p()), fl(pcz + self.gauss_p())
                     nv = self.voxel_index(ppx, ppy, ppz)
                     if nv < 0:
+                        self.note("newborn_outside_map")
                         continue
+                    if self.tracing:
+                        self.note("born_static" if p < n_static else
+                                  ("born_labelled" if lab[3] > f32(0.01) else "born_labelled_low_intensity") if lab[0] > f32(-100.0) and p < n_model
+                                  else ("born_random_unmatched" if not lab[0] > f32(-100.0) else "born_random_p_ge_16") if lab[3] > f32(0.01)
+                                  else "born_random_low_intensity")
                     if p < n_static:
                         vx = vy = vz = f32(0)
                     elif lab[0] > f32(-100.0) and p < n_model:
@@ -359,10 +500,14 @@ class DSP:
                         else:
                             vx = vy = vz = f32(0)
                     vz = f32(0)
-                    for i in range(S):
+                    for i in range(self.S):
                         if st[nv, i, 0] < f32(0.1):
                             st[nv, i] = (15.0, vx, vy, vz, ppx, ppy, ppz, w_new, self.update_time)
                             break
+                    else:
+                        self.note("newborn_dropped_voxel_full")
+                        if (st[nv, :, 0] > f32(14.0)).all():      # the voxel was empty before this cloud
+                            self.note("newborn_dropped_voxel_of_newborns_only")
 
     def occupancy_and_resample(self):
         st, obj = self.store, self.obj
@@ -370,49 +515,72 @@ class DSP:
         for v in np.nonzero((st[:, :, 0] > f32(0.1)).any(axis=1))[0].tolist():
             wsum = vxs = vys = vzs = f32(0)
             n = old = 0
-            for p in range(S):
+            for p in range(self.S):
                 q = st[v, p]
                 if q[0] > f32(0.1):
+                    if self.tracing:
+                        if float(q[7]) == float(f32(0.001)) or float(q[7]) == float(np.nextafter(f32(0.001), f32(0))):
+                            self.note("weight_at_removal_edge")      # an injected weight no arithmetic touched: exact
+                        else:
+                            self.margin("removal", abs(float(q[7]) - 1e-3) / 1e-3)
                     if float(q[7]) < 1e-3:
                         q[0] = 0.0
+                        self.note("weight_removed")
                     else:
                         if q[0] < f32(10.0):
                             old += 1
                             vxs, vys, vzs = fl(vxs + q[1]), fl(vys + q[2]), fl(vzs + q[3])
-                            for t in range(T):
-                                fv = self.voxel_index(fl(q[4] + fl(q[1] * PRED[t])), fl(q[5] + fl(q[2] * PRED[t])), fl(q[6] + fl(q[3] * PRED[t])))
+                            n_out = 0      # (trace only)
+                            for t in range(self.T):
+                                fv = self.voxel_index(fl(q[4] + fl(q[1] * self.PRED[t])), fl(q[5] + fl(q[2] * self.PRED[t])), fl(q[6] + fl(q[3] * self.PRED[t])))
                                 if fv >= 0:
                                     obj[fv, 4 + t] = fl(obj[fv, 4 + t] + q[7])
+                                else:
+                                    n_out += 1
+                            if 0 < n_out < self.T:
+                                self.note("future_outside_for_some_slices_only")
                         q[0] = 1.0
                         n += 1
                         wsum = fl(wsum + q[7])
             obj[v, 0] = wsum
             if old > 0:
                 obj[v, 1], obj[v, 2], obj[v, 3] = fl(vxs / f32(old)), fl(vys / f32(old)), fl(vzs / f32(old))
+            if self.tracing:
+                self.note("voxel_with_%d_particles" % n)
+                if n > old:
+                    self.note("mean_velocity_excludes_newborns" if old > 0 else "mean_velocity_no_old_particles")
             if n < 5:
                 continue
-            n_after = MAXP if n > MAXP else n
+            n_after = self.MAXP if n > self.MAXP else n
             w_after = fl(wsum / f32(n_after))
             acc_o, acc_n = f32(0), fl(w_after * f32(0.5))
-            for p in range(S):
+            for p in range(self.S):
                 q = st[v, p]
                 if q[0] > f32(0.7):
                     acc_o = fl(acc_o + q[7])
+                    self.margin("resample", abs(float(acc_o) - float(acc_n)) / max(float(acc_o), float(acc_n)))
                     if acc_o > acc_n:
                         q[7] = w_after
                         acc_n = fl(acc_n + w_after)
                         full, pi = False, 0
-                        while acc_o > acc_n:
+                        while True:
+                            self.margin("resample", abs(float(acc_o) - float(acc_n)) / max(float(acc_o), float(acc_n)))
+                            if not acc_o > acc_n:
+                                break
                             found = False
                             if not full:
-                                while pi < S:
+                                while pi < self.S:
                                     if st[v, pi, 0] < f32(0.1):
+                                        self.note("resample_copy")
+                                        if pi < p:
+                                            self.note("resample_copy_into_slot_freed_in_this_pass_or_below")
                                         st[v, pi, 0] = 0.6
                                         st[v, pi, 1:9] = q[1:9]
                                         found = True
                                         break
                                     pi += 1
                             if not found:
+                                self.note("resample_no_empty_slot_adds_weight")
                                 q[7] = fl(q[7] + w_after)
                                 full = True
                             acc_n = fl(acc_n + w_after)
@@ -424,10 +592,14 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def pack(a):
+    return base64.b85encode(zlib.compress(np.ascontiguousarray(a).tobytes(), 9)).decode("ascii")
+
+
 def main():
     tables, seq = dsp_fixture_inputs()
     g = DSP(tables)
-    out = []
+    out, objnum = [], []
     for k, s in enumerate(seq):
         ok = g.update(s["points"], s["labels"], s["pos"], s["quat"], s["stamp"])
         st = g.store
@@ -445,11 +617,18 @@ def main():
                "ck_sum": float(np.where(np.arange(OMAX)[None, :] < g.nobs[:, None], g.pc[:, :, 3], 0).astype(np.float64).sum()),
                "obj0_sum": float(g.obj[:, 0].astype(np.float64).sum()), "future_sum": g.obj[:, 4:].astype(np.float64).sum(axis=0).tolist(),
                "occupied_voxels": int((g.obj[:, 0] > 0).sum())}
+        # every non-zero entry of voxels_objects_number [V][4 + T] (weight sum, mean velocity, future status per slice): the
+        # gaps between their flat indices (int32) and their float bits, base85(zlib(little-endian bytes))
+        nz = np.flatnonzero(g.obj.ravel())
+        objnum.append({"index_gaps": pack(np.diff(nz, prepend=0).astype(np.int32)), "values": pack(g.obj.ravel()[nz])})
         g.obj[:, 4:] = 0      # the consumer (getOccupancyMapWithFutureStatus, :454-476) clears the future status after reading it
         out.append(rec)
         print({k_: v for k_, v in rec.items() if k_ not in ("weight_samples",)}, flush=True)
+    # the per-voxel object numbers go to a file of their own: dsp_independent.json is written exactly as it always was
     with open(os.path.join(HERE, "dsp_independent.json"), "w") as f:
         json.dump({"grid": [NX, NY, NZ, T], "updates": out}, f)
+    with open(os.path.join(HERE, "dsp_independent_objnum.json"), "w") as f:
+        json.dump({"grid": [NX, NY, NZ, T], "updates": objnum}, f)
 
 
 if __name__ == "__main__":

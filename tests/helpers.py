@@ -620,3 +620,454 @@ def velocity_capacity_inputs():
         out.append(("points_%d" % n, [_vel_frame([B(30, 2 + 0.25 * k, 0), B(216, 4, 0, w=6), B(40, 2, 3), G(n - 286)], T(k),
                                                  shuffle=530 + n + k) for k in range(2)], 1024))
     return out
+
+
+# ---- DSPMap::update branch by branch: the INPUTS of tests/golden/make_dsp_cases_fixture.py and tests/test_dsp_cases_independent.py.
+# Hand-built particle stores (injected through the state hook), clouds, poses, cursors and small tables on two tiny grids.  The
+# sensor sits at the origin with the identity attitude unless a case says otherwise, so positions are sensor-relative and the
+# FOV opens along +x (|y| < x tan 43 deg, |z| < x tan 29 deg): everything at x < 0 is outside it and keeps its weight.  dt = 0.25 s
+# and a speed of 0.6 m/s carry a particle exactly one 0.15 m cell.  Nothing here decides anything about the expected output.
+
+DSP_CASE_GRIDS = {"g16": (16, 16, 8, 6), "g24": (24, 24, 8, 6)}
+DSP_CASE_T0, DSP_CASE_DT = 10.0, 0.25
+_F = np.float32
+
+
+def dsp_case_tables():
+    """4096 position / velocity noise values and 512 rand() values: small, so that every cursor can wrap inside one update"""
+    rng = _vel_rng(0xD5B1)
+    # position noise in whole 64ths of a metre, |n| <= 12/64: a new-born of a point at a cell centre then lies at (24 + 5 m) / 48 of a
+    # cell, never closer than 1/48 of a cell to a cell boundary — no float truncation in voxel_index is ever a close call
+    pg = np.asarray([(int(rng.next_u64() % 25) - 12) / 64.0 for _ in range(4096)], np.float32)
+    vg = np.asarray([rng.uniform(-0.1, 0.1) for _ in range(4096)], np.float32)
+    rnd = np.asarray([rng.next_u64() >> 33 for _ in range(512)], np.int64).astype(np.int32)
+    return pg, vg, rnd
+
+
+def _ulp_below(x):
+    return np.nextafter(_F(x), _F(0))
+
+
+class _DspCase:
+    def __init__(self, name, grid, seed=1):
+        self.name, self.grid = name, grid
+        self.NX, self.NY, self.NZ, self.T = DSP_CASE_GRIDS[grid]
+        self.V = self.NX * self.NY * self.NZ
+        self.res = _F(0.15)
+        self.h = [_F(_F(self.res * _F(n)) * _F(0.5)) for n in (self.NX, self.NY, self.NZ)]
+        self.store = np.zeros((self.V, 14, 9), np.float32)
+        self.rng = _vel_rng(0xCA5E0000 + seed)
+        self.last_pos, self.last_stamp, self.cursors = (0.0, 0.0, 0.0), DSP_CASE_T0, (0, 0, 0)
+        self.updates = []
+        self.allow = []        # what the generator's margin assertions let this case do on purpose
+        self.compare = True    # False: only the counters are held (an over-capacity agent)
+
+    def vox(self, ix, iy, iz):
+        return (iz * self.NY + iy) * self.NX + ix
+
+    def centre(self, ix, iy, iz, off=(0.0, 0.0, 0.0)):
+        return tuple(float(_F((i + 0.5) * 0.15 - float(h) + o)) for i, h, o in zip((ix, iy, iz), self.h, off))
+
+    def weight(self, lo=0.1, hi=0.5):
+        return self.rng.uniform(lo, hi)
+
+    def put(self, v, slot, pos, vel=(0.0, 0.0), w=None, flag=1.0):
+        assert self.store[v, slot, 0] == 0, (self.name, v, slot)
+        self.store[v, slot] = (flag, vel[0], vel[1], 0.0, pos[0], pos[1], pos[2], self.weight() if w is None else w, 0.0)
+
+    def put_at(self, pos, slot=0, **kw):
+        """a particle in the voxel its position lies in"""
+        self.put(self.vox(*[int((a + float(h)) / 0.15) for a, h in zip(pos, self.h)]), slot, pos, **kw)
+
+    def fill(self, cell, slots, vel=(0.0, 0.0), spread=0.004, **kw):
+        """particles in `cell` at the centre plus a small per-slot offset (told apart by position)"""
+        for s in slots:
+            self.put(self.vox(*cell), s, self.centre(*cell, off=((s - 6.5) * spread, (s % 3 - 1) * spread, 0.0)), vel, **kw)
+
+    def update(self, points=(), labels=None, pos=(0.0, 0.0, 0.0), quat=(1.0, 0.0, 0.0, 0.0), stamp=None):
+        pts = np.asarray(points, np.float32).reshape(-1, 3)
+        lab = np.zeros((len(pts), 4), np.float32) if labels is None else np.asarray(labels, np.float32).reshape(-1, 4)
+        assert len(lab) == len(pts)
+        stamp = DSP_CASE_T0 + DSP_CASE_DT * (len(self.updates) + 1) if stamp is None else stamp
+        self.updates.append({"points": pts, "labels": lab, "pos": tuple(pos), "quat": tuple(quat), "stamp": float(stamp)})
+        return self
+
+
+def _dsp_dir(az_deg, el_deg, r):
+    """a point at range r whose horizontal / vertical plane angles (atan y/x, atan z/x) are az / el degrees"""
+    d = np.array([1.0, np.tan(np.radians(az_deg)), np.tan(np.radians(el_deg))])
+    return tuple((d / np.linalg.norm(d) * r).tolist())
+
+
+FAR = [0.0, 0.0, 0.0, 0.0]                     # label of a static point
+DYN = [0.3, 0.1, 0.0, 0.55]                    # a matched cluster's label
+UNMATCHED = [-10000.0, -10000.0, -10000.0, 0.55]
+X, MX, Y, MY = (0.6, 0.0), (-0.6, 0.0), (0.0, 0.6), (0.0, -0.6)      # one cell per update along +x, -x, +y, -y
+
+
+def _dsp_search_index_equals_size(h, n):
+    """the floats below the upper bound h for which (int)((p + h) / res) == n (the axis size): the largest, or None"""
+    res, p = _F(0.15), _ulp_below(h)
+    for _ in range(64):
+        if int(_F(_F(p + h) / res)) == n:
+            return float(p)
+        p = _ulp_below(p)
+    return None
+
+
+def _dsp_search_zero_dot(normal, x):
+    """a float y with fl(fl(x n0) + fl(y n1)) == 0 exactly (z = 0 term adds +0), near -x n0 / n1; or None"""
+    n0, n1 = _F(normal[0]), _F(normal[1])
+    y = _F(-float(_F(_F(x) * n0)) / float(n1))
+    for cand in [y] + [np.nextafter(y, _F(s)) for s in (-10, 10)]:
+        if _F(_F(_F(x) * n0) + _F(cand * n1)) == 0:
+            return float(cand)
+    return None
+
+
+# every branch of DSPMap::update that DESIGN section 4 (row a6) lists: each is claimed by a case through the reading's own trace, or the
+# fixture lists it as unclaimed with the reason
+DSP_CASE_LABELS = """stay_in_fov stay_outside_fov mover_into_unswept_voxel mover_into_swept_voxel
+arrivals_before_turn_see_departing_occupants lowest_empty_slot_with_holes arrivals_in_key_order_from_three_sources
+fifteen_arrivals_one_phase twenty_eight_arrivals_two_phases leaves_through_each_face leaving_slot_frees_at_own_turn
+exactly_on_the_bound one_ulp_below_the_upper_bound_x one_ulp_below_the_upper_bound_y one_ulp_below_the_upper_bound_z
+pyramid_full_stay pyramid_full_mover on_a_boundary_plane on_the_fov_edge
+cascade_1 cascade_2 cascade_3 cascade_at_the_limit cascade_one_over_the_limit
+candidate_pool_exactly_2V candidate_pool_one_over
+observations_98_in_one_pyramid observations_99_in_one_pyramid observations_100_in_one_pyramid observations_150_in_one_pyramid
+observations_across_trip_boundaries observations_in_shuffled_input_order empty_cloud_reuses_born_list
+rejected_quaternion rejected_negative_dt rejected_dt_above_10 rejected_jump_above_10m
+occluded_particle_keeps_weight max_length_unset neighbourhood_of_4 neighbourhood_of_6 pdf_clamp_low pdf_clamp_high
+ck_over_two_lists split_nan split_all_static split_all_dynamic split_mixed_band split_counts_flag_7 split_passes_over_flag_15
+labelled_dynamic unmatched_label low_intensity_zero_velocity random_from_particle_16 newborn_outside_the_map
+point_outside_the_map position_table_wraps_inside_one_particle velocity_table_wraps rand_table_wraps
+newborn_scan_1024_points newborn_scan_1025_points newborn_scan_2100_points addAParticle_into_13_of_14
+more_than_14_newborns_into_an_empty_voxel weight_one_float_below_removal weight_exactly_at_removal
+no_resampling_below_5 resampling_5 resampling_7 resampling_8 resampling_14 resample_no_empty_slot_adds_weight
+resample_copies_into_slots_freed_in_the_pass flag_0_6_processed_by_next_prediction future_outside_for_some_slices
+mean_velocity_excludes_newborns mean_velocity_no_old_particles""".split()
+
+# the seed of a case's generic weights where seed 1 left a resampler comparison closer than the generator's 1e-3 margin
+DSP_CASE_SEEDS = {"resampling_counts": 2, "addAParticle_into_13_of_14": 2, "cascade_3": 3, "cascade_at_the_limit": 4,
+                  "cascade_one_over_the_limit": 3}
+
+
+def dsp_case_inputs(seeds=None):
+    """{grid: [case, ...]}: every case is one agent of its grid's handle; the branches are DSP_CASE_LABELS"""
+    seeds = DSP_CASE_SEEDS if seeds is None else seeds
+    cases = []
+
+    def new(name, grid="g16"):
+        c = _DspCase(name, grid, seed=seeds.get(name, 1))
+        cases.append(c)
+        return c
+
+    obs_far = [_dsp_dir(20.5, -10.5, 3.0)]       # one observation inside the FOV and outside both maps: C_k > 0, no new-born
+
+    # ---------------- prediction and placement
+    c = new("sweep_basics")
+    c.put(c.vox(13, 9, 4), 0, c.centre(13, 9, 4))                    # stays, inside the FOV
+    c.put(c.vox(2, 8, 4), 0, c.centre(2, 8, 4))                      # stays, outside
+    c.put(c.vox(11, 6, 4), 0, c.centre(11, 6, 4), X)                 # to a higher voxel index
+    c.put(c.vox(13, 10, 3), 0, c.centre(13, 10, 3), MX)              # to a lower one
+    c.update()
+
+    c = new("arrivals_before_turn_see_departing_occupants")
+    c.fill((4, 8, 4), range(14), X)
+    c.fill((3, 8, 4), (0, 1), X)
+    c.fill((4, 9, 4), (0, 1), MY)
+    c.update()
+
+    c = new("lowest_empty_slot_with_holes")
+    c.fill((4, 4, 4), (0, 1, 3, 4, 7))
+    c.fill((3, 4, 4), (2, 5, 9), X)
+    c.update()
+
+    c = new("arrivals_in_key_order_from_three_sources")
+    c.fill((4, 7, 4), (2, 9), Y)
+    c.fill((3, 8, 4), (0, 5), X)
+    c.fill((5, 8, 4), (1, 3), MX)
+    c.update()
+
+    c = new("fifteen_arrivals_one_phase")
+    c.fill((3, 8, 4), range(14), X)
+    c.fill((4, 7, 4), (4,), Y)
+    c.update()
+
+    c = new("twenty_eight_arrivals_two_phases")
+    c.fill((4, 8, 4), range(7), Y)
+    c.fill((3, 8, 4), range(14), X)
+    c.fill((5, 8, 4), range(14), MX)
+    c.update()
+
+    c = new("leaves_through_each_face")
+    c.put(c.vox(15, 14, 4), 0, c.centre(15, 14, 4), X)
+    c.put(c.vox(0, 9, 5), 0, c.centre(0, 9, 5), MX)
+    c.put(c.vox(3, 15, 4), 0, c.centre(3, 15, 4), Y)
+    c.put(c.vox(3, 0, 4), 0, c.centre(3, 0, 4), MY)
+    c.put(c.vox(2, 5, 7), 0, c.centre(2, 5, 7))                       # leaves through +z when the sensor sinks one cell
+    c.put(c.vox(2, 3, 0), 0, c.centre(2, 3, 0))                       # is at iz = 1 after that and leaves through -z when it climbs two
+    c.put(c.vox(2, 9, 4), 0, c.centre(2, 9, 4))                       # stays inside throughout
+    c.update(pos=(0.0, 0.0, -0.15))
+    c.update(pos=(0.0, 0.0, 0.15))
+
+    c = new("slot_of_a_leaving_particle_frees_at_its_turn")
+    c.fill((0, 8, 2), range(14))                                      # a full voxel on the -x face; slot 3 leaves the map
+    c.store[c.vox(0, 8, 2), 3, 1] = -0.6
+    c.fill((0, 7, 2), (0,), Y)                                        # smaller key: finds the slot still taken
+    c.fill((1, 8, 2), (0,), MX)                                       # larger key: finds it free
+    c.update()
+
+    c = new("exactly_on_the_bound")
+    c.allow.append("searched_truncation")      # (the particle one ulp inside the lower bound: (p + h) / res is a denormal-sized 0+)
+    px = c.centre(15, 13, 3)
+    c.put(c.vox(15, 13, 3), 0, (float(c.h[0]), px[1], px[2]))
+    c.put(c.vox(0, 13, 3), 0, (-float(c.h[0]), px[1], px[2]))
+    c.put(c.vox(0, 12, 3), 0, (float(np.nextafter(-c.h[0], _F(0))), c.centre(0, 12, 3)[1], px[2]))     # one ulp inside: stays
+    c.update()
+
+    c = new("one_ulp_below_the_upper_bound")
+    c.allow.append("searched_truncation")
+    c.searched = {}
+    for ax, (n, cell) in enumerate(((16, (15, 4, 3)), (16, (3, 15, 3)), (8, (3, 4, 7)))):
+        p = _dsp_search_index_equals_size(c.h[ax], n)
+        c.searched["xyz"[ax]] = p
+        if p is not None:
+            pos = list(c.centre(*cell))
+            pos[ax] = p
+            c.put(c.vox(*cell), 0, tuple(pos))
+    c.update()
+
+    c = new("pyramid_full_stay")
+    base = np.asarray(c.centre(13, 9, 4))
+    for s, k in enumerate((1.0, 1.02, 1.04)):
+        c.put(c.vox(13, 9, 4), s, tuple((base * k).tolist()))
+    c.update()
+
+    c = new("pyramid_full_mover")
+    base = np.asarray(c.centre(13, 7, 4))
+    for s, k in enumerate((1.0, 1.02)):
+        c.put(c.vox(13, 7, 4), s, tuple((base * k).tolist()))
+    land = base * 1.04
+    c.put(c.vox(14, 7, 4), 0, (land[0] + 0.15, land[1], land[2]), MX)               # lands in the full pyramid: takes slot 2, vanishes
+    c.put(c.vox(13, 8, 4), 0, c.centre(13, 8, 4, off=(0.03, 0.0, 0.03)), MY)       # a later arrival takes slot 2 again
+    c.update()
+
+    c = new("on_a_boundary_plane")
+    c.allow += ["zero_dot", "exact_cell_boundary"]
+    c.put(c.vox(11, 8, 4), 0, (0.525, 0.0, 0.075))        # on y = 0
+    c.put(c.vox(11, 8, 4), 1, (0.525, 0.075, 0.0))        # on z = 0
+    c.put(c.vox(11, 8, 4), 2, (0.525, 0.0, 0.0))          # on the optical axis
+    c.update(points=[(3.0, 0.0, 0.25), (3.0, 0.25, 0.0), (3.0, 0.0, 0.0)])
+
+    c = new("on_the_fov_edge")
+    c.allow += ["zero_dot"]
+    ang = _F(float(_F(1) / _F(180.0)) * 3.14159265358979323846)
+    c.searched = {}
+    for sign in (-1, 1):
+        nrm = (_F(-np.sin(float(_F(sign * 43) * ang))), _F(np.cos(float(_F(sign * 43) * ang))))
+        for x in (0.525, 0.53125, 0.5625, 0.59375, 0.515625):
+            y = _dsp_search_zero_dot(nrm, x)
+            if y is not None:
+                break
+        c.searched[sign] = None if y is None else (x, y)
+        if y is not None:
+            z = 0.075
+            ix, iy, iz = int((x + 1.2) / 0.15), int((y + 1.2) / 0.15), int((z + 0.6) / 0.15)
+            c.put(c.vox(ix, iy, iz), 0, (x, y, z))                                       # exactly on the edge plane: inside
+            c.put(c.vox(ix, iy, iz), 1, (x, float(_F(y) * _F(1.001)), z))                 # just outside it
+            c.put(c.vox(ix, iy, iz), 2, (x, float(_F(y) * _F(0.999)), z))                 # just inside it
+    c.update(points=obs_far)
+
+    # ---------------- the cascade: a pyramid-full vanish frees the only slot of a full voxel, the arrival that takes it fills the
+    # next pyramid, whose later particle vanishes ...  The voxels (14, iy, 7) straddle the upper edge of the FOV: their 12-13
+    # fillers sit above it (z > x tan 29 deg: never listed), the chain's particles below it, all in the 26-27 deg row of pyramids.
+    # Link k's pyramid crosses the face between voxel iy and iy + 1 (y < 0): its near point (x = 0.95) lies in the upper voxel, the
+    # same direction at x = 1.04 in the lower one.
+    def cascade(c, depth):
+        xn, xf = 0.95, 1.04
+        near = lambda y: np.array([xn, y, xn * np.tan(np.radians(26.5))])
+        for k in range(1, depth + 1):
+            iy = 1 + k
+            lower = -1.2 + 0.15 * iy
+            v, taken = c.vox(14, iy, 7), {13}
+            x_k = near(-0.80) if k == 1 else near(0.96 * lower)
+            c.put(v, 13, tuple(x_k.tolist()))                                     # X_k: the last slot, vanishes at depth k
+            if k == 1:
+                for s, f in ((0, 1.005), (1, 1.01)):                               # the two entries that fill pyramid 1 before X_1
+                    c.put(v, s, tuple((x_k * f).tolist()))
+                    taken.add(s)
+            if k < depth:
+                far = near(0.96 * (lower + 0.15)) * (xf / xn)                      # the direction of X_k+1, inside this voxel
+                s = 2 if k == 1 else 0
+                c.put(v, s, tuple((far * 0.995).tolist()))                          # L_k+1: the first entry of pyramid k + 1
+                taken.add(s)
+                c.put(c.vox(15, iy, 7), 0, (far[0] + 0.15, far[1], far[2]), MX)    # Y_k: arrives after X_k's turn, second entry
+            for s in range(14):
+                if s not in taken:
+                    c.put(v, s, (0.91, c.centre(14, iy, 7)[1] + (s - 6.5) * 0.008, 0.59))
+    for depth, name in ((1, "cascade_1"), (2, "cascade_2"), (3, "cascade_3"), (5, "cascade_at_the_limit"), (6, "cascade_one_over_the_limit")):
+        c = new(name)
+        cascade(c, depth)
+        c.compare = depth <= 5       # DSP_ROUNDS = 6 place / pyramid rounds settle a chain of 5 (round r finds the vanish of depth r + 1, the
+        c.update()                   # sixth round confirms that nothing changed); a chain of 6 raises counters[10] and is not compared
+
+    # ---------------- the candidate pool: cand_cap = 2 V
+    for extra in (0, 1):
+        c = new("candidate_pool_2V" if not extra else "candidate_pool_2V_plus_1")
+        wts = [0.125, 0.1875, 0.25, 0.3125, 0.375, 0.4375, 0.28125, 0.21875]
+        for iz in range(c.NZ):
+            for iy in range(c.NY):
+                for ix in range(c.NX):
+                    for s in range(2):
+                        o = 0.03 if s else -0.03
+                        c.put(c.vox(ix, iy, iz), s, c.centre(ix, iy, iz, off=(0.0, o, o)), MX if ix % 2 else X,
+                              w=wts[(ix + 3 * iy + 5 * iz + 4 * s) % 8])      # neighbours differ; periodic, so the fixture stays small
+        if extra:
+            c.put(c.vox(2, 3, 4), 2, c.centre(2, 3, 4), X, w=0.25)
+            c.compare = False
+        c.update()
+    c = new("neighbour_of_the_over_full_pool")
+    c.fill((4, 8, 4), range(3), X)
+    c.fill((12, 8, 4), range(3))
+    c.update(points=obs_far)
+
+    # ---------------- observation binning (g24; the points lie outside the map: no new-born particles)
+    for n in (98, 99, 100, 150):
+        c = new("observations_%d_in_one_pyramid" % n, "g24")
+        c.put_at(_dsp_dir(10.5, 5.5, 0.6))
+        c.put_at(_dsp_dir(-30.5, -10.5, 0.6))
+        # past the cap the LAST point is the longest: max_length comes from all points, the dropped ones included
+        c.update(points=[_dsp_dir(10.5, 5.5, 4.0 if n > 99 and k == n - 1 else 2.5 + 0.01 * ((k * 37) % n)) for k in range(n)] +
+                 [_dsp_dir(-30.5, -10.5, 2.75)])
+
+    def trip_cloud():
+        pts = [_dsp_dir(-40.5 + (k % 82), -25.5 + (k // 82), 3.0) for k in range(600)]
+        for j, k in enumerate((255, 256, 257, 511, 512)):
+            pts[k] = _dsp_dir(12.5, 26.5, 3.0 + 0.125 * (5 - j))      # one pyramid (above the filler's rows), decreasing length
+        return pts
+    c = new("observations_across_trip_boundaries", "g24")
+    c.put_at(_dsp_dir(12.5, 26.5, 0.5))
+    c.update(points=trip_cloud())
+    c = new("observations_in_shuffled_input_order", "g24")
+    c.put_at(_dsp_dir(12.5, 26.5, 0.5))
+    pts = trip_cloud()
+    c.update(points=[pts[i] for i in _vel_shuffle(77, len(pts))])
+
+    c = new("empty_cloud_after_a_cloud", "g24")
+    c.fill((4, 8, 4), (0, 1))
+    pts = [c.centre(5, 5, 3), c.centre(8, 17, 5), c.centre(3, 12, 2)] + obs_far
+    c.update(points=pts, labels=[FAR, DYN, UNMATCHED, FAR])
+    c.update()
+
+    for name, kw in (("rejected_quaternion", {"quat": (1.002, 0.0, 0.0, 0.0)}), ("rejected_negative_dt", {"stamp": 9.5}),
+                     ("rejected_dt_above_10", {"stamp": 20.5}), ("rejected_jump_above_10m", {"pos": (10.5, 0.0, 0.0)})):
+        c = new(name, "g24")
+        c.fill((4, 8, 4), range(6), X)
+        c.fill((16, 13, 4), (0, 2))
+        c.store[c.vox(16, 13, 4), 2, 0] = 0.6
+        c.update(points=obs_far, **kw)
+        c.update(points=obs_far, stamp=10.5)
+
+    # ---------------- mapUpdate
+    c = new("occluded_particle_keeps_weight", "g24")
+    c.put_at(_dsp_dir(10.5, 5.5, 1.5))
+    c.update(points=[_dsp_dir(10.5, 5.5, 0.9)])
+
+    c = new("neighbourhood_of_4_and_6")
+    for az, el in ((-42.5, 28.5), (-42.5, 0.5), (10.5, 5.5)):
+        c.put_at(_dsp_dir(az, el, 0.8))
+    c.update(points=[_dsp_dir(-42.5, 28.5, 3.0), _dsp_dir(-42.5, 0.5, 3.0), _dsp_dir(10.5, 5.5, 3.0)])
+
+    c = new("pdf_clamp_and_ck_over_two_lists")
+    for k, (az, el) in enumerate(((10.5, 5.5), (11.5, 5.5), (-30.5, -10.5))):
+        c.put_at(_dsp_dir(az, el, 0.8), slot=k)
+    # an observation 0.02 m behind the first particle (inside the map: it also breeds), and far ones on both sides of the clamp
+    c.update(points=[_dsp_dir(10.5, 5.5, 0.82), _dsp_dir(10.5, 5.5, 3.0), _dsp_dir(-30.5, -10.5, 3.0)])
+
+    # ---------------- new-born (behind the sensor: the old particles there keep their weights)
+    c = new("dempster_shafer_split")
+    cells = [(2, 3, 2), (2, 6, 2), (2, 9, 2), (2, 12, 2), (5, 3, 5), (5, 7, 5)]
+    c.put(c.vox(*cells[1]), 0, c.centre(*cells[1]))                                           # all static
+    c.put(c.vox(*cells[1]), 1, c.centre(*cells[1], off=(0.01, 0.0, 0.0)))
+    c.put(c.vox(*cells[2]), 0, c.centre(*cells[2], off=(-0.04, -0.04, 0.0)), (0.3, 0.3))      # all dynamic: |v|_1 = 0.6
+    c.put(c.vox(*cells[3]), 0, c.centre(*cells[3], off=(-0.02, 0.0, 0.0)), (0.2, 0.0))        # the mixed band ...
+    c.put(c.vox(*cells[3]), 1, c.centre(*cells[3]))                                           # ... beside a static one
+    c.put(c.vox(cells[4][0] - 1, cells[4][1], cells[4][2]), 0, c.centre(cells[4][0] - 1, cells[4][1], cells[4][2]), X)   # arrives: flag 7
+    pts = [c.centre(*cl) for cl in cells[:5]] + [c.centre(*cells[5], off=(0.0002 * k, 0.0, 0.0)) for k in range(3)] + obs_far
+    c.update(points=pts, labels=[FAR, DYN, DYN, DYN, DYN] + [FAR, DYN, DYN] + [FAR])      # (cell 5: the first point breeds static new-borns, flag 15, that the next two pass over)
+
+    c = new("class_branches")
+    pts = [c.centre(3, 4, 3), c.centre(3, 8, 3), c.centre(3, 12, 3), c.centre(6, 4, 5)] + obs_far
+    c.update(points=pts, labels=[DYN, UNMATCHED, [0.3, 0.1, 0.0, 0.005], [-10000.0, 0.0, 0.0, 0.005], FAR])
+
+    c = new("newborn_and_point_outside_the_map")
+    c.update(points=[(-1.125, 0.075, 0.075), (-1.5, 0.075, 0.075), (0.075, -1.125, -0.525)] + obs_far, labels=[DYN, DYN, UNMATCHED, FAR])
+
+    c = new("table_cursors_wrap")
+    c.cursors = (4096 - 4, 4096 - 2, 512 - 2)
+    c.update(points=[c.centre(3, 4, 3), c.centre(3, 8, 3)] + obs_far, labels=[DYN, UNMATCHED, FAR])
+
+    for n in (1024, 1025, 2100):
+        c = new("newborn_scan_%d_points" % n, "g24")
+        c.cursors = (4000, 4090, 500)
+        # Every point breeds (one observation inside the FOV gives the new-born weight 1e-4 / 0.012; nothing is listed, so every weight
+        # is plain float arithmetic).  Most points pile into one cell, whose neighbourhood fills from the first of them: every lane of
+        # the scan carries draws, few particles survive.  The points at the scan's lane, wave, chunk and trip boundaries have a cell
+        # of their own (three cells apart), so their new-borns survive, and carry the table offsets of everything before them.
+        own = [k for k in (0, 1, 63, 64, 65, 127, 128, 255, 256, 511, 512, 513, 767, 768, 1023, 1024, 1535, 1536, 2047, 2048, n - 2, n - 1)
+               if k < n]
+        cells = [(ix, iy, iz) for iz in (2, 5) for iy in range(0, 24, 3) for ix in (1, 4, 7)]      # (iy = 0: some new-borns leave the map)
+        spot = {k: cells[(7 * i) % len(cells)] for i, k in enumerate(sorted(set(own)))}
+        pts = [c.centre(*spot.get(k, (10, 12, 4))) for k in range(n)]
+        pts[2] = obs_far[0]      # the observation is point 2 of the n: outside the map, it breeds nothing and has no rank
+        c.update(points=pts, labels=[FAR if k == 2 else (DYN, UNMATCHED, FAR)[k % 3] for k in range(n)])
+
+    c = new("addAParticle_into_13_of_14")
+    c.fill((3, 8, 3), [s for s in range(14) if s != 9])
+    pg = dsp_case_tables()[0]      # a cursor at which the first two new-borns (six draws) stay within the point's own cell
+    c.cursors = (next(k for k in range(4000) if np.all(np.abs(pg[k:k + 6]) <= 4.0 / 64.0)), 0, 0)
+    c.update(points=[c.centre(3, 8, 3, off=(0.0002 * k, 0.0, 0.0)) for k in range(3)] + obs_far, labels=[DYN] * 3 + [FAR])
+
+    # ---------------- occupancy and resample (behind the sensor, no cloud: injected weights only)
+    c = new("weight_removal_edge")
+    c.put(c.vox(3, 8, 3), 0, c.centre(3, 8, 3), w=float(_F(0.001)))
+    c.put(c.vox(3, 8, 3), 1, c.centre(3, 8, 3, off=(0.01, 0.0, 0.0)), w=float(_ulp_below(0.001)))
+    c.update()
+
+    c = new("resampling_counts")
+    for k, n in enumerate((4, 5, 7, 8, 14)):
+        c.fill((2 + k, 5, 3), range(n))
+    c.update()
+
+    c = new("resample_no_empty_slot_adds_weight")
+    c.fill((3, 8, 3), (0,), w=10.0)
+    c.fill((3, 8, 3), range(1, 14), w=0.01)
+    c.update()
+
+    c = new("resample_copies_and_flag_0_6")
+    c.fill((3, 8, 3), range(6), w=0.01)
+    c.fill((3, 8, 3), (6,), w=3.0)
+    c.fill((3, 8, 3), range(7, 14), w=0.0125)
+    c.update()
+    c.update()
+
+    c = new("future_status_outside_for_some_slices")
+    c.put(c.vox(1, 8, 3), 0, (-1.0, 0.075, -0.075), (-0.3, 0.0))
+    c.put(c.vox(3, 1, 3), 0, (-0.7, -1.02, -0.075), (0.0, -0.2))
+    c.update()
+
+    out = {g: [c for c in cases if c.grid == g] for g in DSP_CASE_GRIDS}
+    return out
+
+
+def dsp_case_sha256(case):
+    """what the fixture records of a case's inputs"""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(case.store.tobytes())
+    h.update(np.asarray(case.last_pos + (case.last_stamp,) + tuple(case.cursors), np.float64).tobytes())
+    for u in case.updates:
+        h.update(u["points"].tobytes() + u["labels"].tobytes())
+        h.update(np.asarray(u["pos"] + u["quat"] + (u["stamp"],), np.float64).tobytes())
+    return h.hexdigest()

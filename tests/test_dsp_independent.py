@@ -4,10 +4,12 @@ updates.  Identical, bit for bit: which slots hold particles and their flags, ev
 table cursors, the observation tables.  To a tolerance (the normal-PDF table and the FOV plane normals are computed by the
 fixture's interpreter, not by glibc's expf / sinf): weights, C_k, object numbers, future status.  The C++ oracle on the CPU,
 sogm_update_dsp directly on the GPU."""
+import base64
 import hashlib
 import importlib
 import json
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -25,8 +27,12 @@ def _sha(a):
 def _fixture():
     with open(os.path.join(HERE, "golden", "dsp_independent.json")) as f:
         fx = json.load(f)
+    with open(os.path.join(HERE, "golden", "dsp_independent_objnum.json")) as f:      # the same four updates, per voxel
+        objnum = json.load(f)["updates"]
     tables, seq = dsp_fixture_inputs()
-    assert len(seq) == len(fx["updates"])
+    assert len(seq) == len(fx["updates"]) == len(objnum)
+    for u, o in zip(fx["updates"], objnum):
+        u["objnum"] = o
     for s, u in zip(seq, fx["updates"]):
         blob = np.concatenate([s["points"].ravel(), s["labels"].ravel(), np.asarray(s["pos"], np.float32), np.asarray(s["quat"], np.float32)])
         assert _sha(blob) == u["in_sha256"]
@@ -54,6 +60,16 @@ def _check(u, ok, store, objnum, cursors, nobs, pc, maxlen):
     np.testing.assert_allclose(objnum[:, 0].astype(np.float64).sum(), u["obj0_sum"], rtol=2e-5)
     np.testing.assert_allclose(objnum[:, 4:].astype(np.float64).sum(axis=0), u["future_sum"], rtol=1e-4, atol=1e-6)
     assert int((objnum[:, 0] > 0).sum()) == u["occupied_voxels"]
+    # per voxel: the weight sum, the three mean velocities and every future slice (the sums above let a weight land in the wrong voxel
+    # of the right slice); the tolerances of tests/test_dsp_gpu.py's future status
+    unz = lambda s, t: np.frombuffer(zlib.decompress(base64.b85decode(s)), t)
+    want = np.zeros(objnum.size, np.float32)
+    want[np.cumsum(unz(u["objnum"]["index_gaps"], np.int32))] = unz(u["objnum"]["values"], np.float32)
+    want = want.reshape(objnum.shape)
+    bad = ~(np.abs(objnum.astype(np.float64) - want) <= 1e-6 + 1e-4 * np.abs(want.astype(np.float64)))
+    if bad.any():
+        v, k = (int(i) for i in np.argwhere(bad)[0])
+        raise AssertionError("update %d: objnum differs first at voxel %d entry %d: got %r, want %r" % (u["update"], v, k, objnum[v, k], want[v, k]))
 
 
 def test_oracle_against_the_independent_restatement(pop, orc):
