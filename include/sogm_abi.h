@@ -299,6 +299,58 @@ int sogm_cloud_block_bounds(const float *cloud_xyz, int n_points, int block_poin
 int sogm_update_world(sogm_ctx *ctx, const SogmWorld *world, const float *poses, const double *stamps,
                       const SogmTrajRecord *records, int n_records, const int32_t *ego_ids, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* world timeline: the SogmWorld frames of any range of ticks, written on the device           */
+/*   The reference's counterpart is the map_generator dynamic_forest_seq node of its            */
+/*   uav_simulator submodule (simulator_fake.launch:41), an empty directory in its tree: like    */
+/*   the depth camera this is the build's OWN simulator piece.        */
+/*   What is held is the definition below, by two independent implementations                    */
+/*   (csrc/sogm_world.hpp + csrc/sogm_world.hip and the numpy restatement                        */
+/*   tests/world_frames_reference.py), bit for bit.                                              */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * The world at tick 0 and how it moves: every obstacle record keeps its constant planar velocity (vx, vy), every
+ * cloud point moves with the record that owns it.  Frame i of a call is tick k = first_tick + i and is written
+ * through the pointers of frames[i], buffers the caller allocated: cloud_xyz [n_points*3], block_bounds [n_blocks*4],
+ * cylinders [n_cyl].
+ *
+ * The arithmetic, in exactly this order, without contraction (the library is built with -ffp-contract=off):
+ *
+ *   t = (double)k * dt
+ *   k == 0 or moving == 0:  the cloud and the records of tick 0 are copied bit for bit (a -0.0f stays -0.0f)
+ *   otherwise, record c:    x = x0 + vx*t;  y = y0 + vy*t   (fp64);  every other field is copied
+ *   otherwise, point p with c = owner[p] in [0, n_cyl):
+ *                           offx = (float)(vx_c * t)        the product in fp64, then rounded ONCE
+ *                           X    = x_p + offx               an fp32 add, performed even when offx is zero
+ *                                                           (-0.0f + 0.0f = +0.0f, as numpy gives)
+ *                           y likewise; z is copied
+ *   a point whose owner is outside [0, n_cyl) is copied; no read ever depends on an out-of-range owner
+ *
+ *   block_bounds of the written cloud = what sogm_cloud_block_bounds(cloud_xyz, n_points, block_points, ...) gives,
+ *   bit for bit, the tail block included (min and max are exact: the order of the reduction is free).
+ *   Non-finite points are the caller's problem: they are treated as that entry treats them.
+ */
+typedef struct SogmWorldTimeline {
+  const float        *cloud0;      /* dev [n_points*3] fp32, the cloud at tick 0                                  */
+  const int32_t      *owner;       /* dev [n_points]: the record a point moves with; outside [0, n_cyl): static   */
+  const SogmCylinder *cylinders0;  /* dev [n_cyl] states at tick 0 (NULL if n_cyl == 0)                           */
+  int32_t n_points, n_cyl, block_points /* 64..4096 */, moving /* 0: every frame is tick 0 */;
+  double  dt;                      /* seconds per tick */
+} SogmWorldTimeline;
+/*
+ * Writes the frames of ticks first_tick .. first_tick + n_ticks - 1.  Context-free like sogm_render_depth: the current
+ * device, stream-ordered, no allocation, no host synchronisation; the structs are read on the host at call time.
+ * SOGM_ERR_INVALID_ARG (checked first, as in sogm_render_depth; sogm_last_error() names the rule): a null tl or frames;
+ * a null cloud0 or owner with n_points > 0; a null cylinders0 with n_cyl > 0; n_points < 0 or n_cyl < 0; block_points
+ * outside 64..4096; dt not finite or not positive; first_tick < 0, n_ticks < 1 or first_tick + n_ticks overflowing int;
+ * a frame whose n_points, n_blocks, block_points or n_cyl differs from the timeline's (n_blocks = ceil(n_points /
+ * block_points)); a frame with a null buffer it needs (cloud_xyz and block_bounds with n_points > 0, cylinders with
+ * n_cyl > 0); a frame buffer equal to one of the timeline's inputs or to another frame's buffer of the same call.
+ * SOGM_ERR_NO_DEVICE without a GPU.
+ */
+int sogm_world_frames(const SogmWorldTimeline *tl, int first_tick, int n_ticks,
+                      const SogmWorld *frames /* host [n_ticks]; their device buffers are WRITTEN */, void *stream);
+
 /*
  * Neighbour overlay: RiskBase::addOtherAgents (risk_base.cpp:136-168) ==
  * fake_particle_risk_voxel.cpp:178-218, through ParticleATC::getParticlesWithRisk

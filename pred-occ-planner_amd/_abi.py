@@ -111,6 +111,12 @@ class SogmWorld(C.Structure):
                 ("n_points", C.c_int32), ("n_blocks", C.c_int32), ("block_points", C.c_int32), ("n_cyl", C.c_int32)]
 
 
+class SogmWorldTimeline(C.Structure):
+    _fields_ = [("cloud0", C.c_void_p), ("owner", C.c_void_p), ("cylinders0", C.c_void_p),
+                ("n_points", C.c_int32), ("n_cyl", C.c_int32), ("block_points", C.c_int32), ("moving", C.c_int32),
+                ("dt", C.c_double)]
+
+
 class SogmPrestamp(C.Structure):
     _fields_ = [("cloud_xyz", C.c_void_p), ("cloud_range", C.c_void_p), ("cylinders", C.c_void_p),
                 ("n_cyl", C.c_int32), ("reserved_", C.c_int32), ("next_stamp", C.c_double),
@@ -252,6 +258,7 @@ PROTOTYPES = {
     "sogm_tick_clock": (_i, [_vp, C.POINTER(C.c_int64)]),
     "sogm_cloud_block_bounds": (_i, [_vp, _i, _i, _vp, _vp]),
     "sogm_update_world": (_i, [_vp, C.POINTER(SogmWorld), _vp, _vp, _vp, _i, _vp, _vp]),
+    "sogm_world_frames": (_i, [C.POINTER(SogmWorldTimeline), _i, _i, C.POINTER(SogmWorld), _vp]),
     "sogm_set_future_risk": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sogm_download_reference_layout": (_i, [_vp, _i, _vp]),
     "sogm_tick_inputs": (_i, [_vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),

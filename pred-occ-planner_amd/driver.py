@@ -22,7 +22,7 @@ import torch
 
 from . import _abi, config, scene as scene_mod
 from .planner import SogmPlanner, traj_eval
-from .sogm import SogmMap, World, _dev, _stream, upload_scene
+from .sogm import SogmMap, World, WorldTimelineDev, _dev, _stream, upload_scene
 
 TICK_PERIOD = 0.1        # fsm/replan_duration (sim_fake.yaml:7)
 REPLAN_START_TIME = 0.02  # fsm/replan_start_time (sim_fake.yaml:8)
@@ -237,7 +237,7 @@ class HipCompute:
     device = "cuda"
 
     def __init__(self, spec, scene, lo, hi, device, overlap_clear=True, double_buffer=None, grids=None, tuning=None,
-                 moving_world=None):
+                 moving_world=None, device_world=None, world_pool=None):
         half = (spec.L // 2) * 0.15
         A_loc = hi - lo
         loc = dict(scene)
@@ -252,6 +252,16 @@ class HipCompute:
         self.timeline = scene_mod.WorldTimeline(scene, TICK_PERIOD, moving=bool(moving_world))
         self.use_world = moving_world is not None
         self._frames = {}
+        # device_world (None: the environment's SOGM_DEVICE_WORLD, default 0): the frames are WRITTEN on the device from the
+        # tick-0 world (sogm_world_frames, sogm.WorldTimelineDev) into a pool of world_pool frames — no host-to-device copy
+        # after tick 0, constant memory however long the run.  Needs world frames; off: the uploads below, as before.
+        if device_world is None:
+            device_world = os.environ.get("SOGM_DEVICE_WORLD", "0") != "0" and self.use_world
+        elif device_world and not self.use_world:
+            raise ValueError("HipCompute(device_world=True) needs world frames (moving_world=True / False)")
+        self.device_world = bool(device_world)
+        self.world_pool = int(world_pool) if world_pool is not None else 8
+        self._tl_dev, self._held = None, {}
         if self.use_world:
             self.dev = upload_scene(loc, cloud=np.zeros((1, 3), np.float32), cloud_range=np.zeros((A_loc, 2), np.int32))
             self.cloud_points = 0   # (per-agent counts are the device-side crop's: sogm_map_traffic / bench)
@@ -277,19 +287,51 @@ class HipCompute:
         """The device copy of tick k's sensor frame (uploaded on first use; prepare() uploads a range ahead of a timed
         region so that no host-to-device copy falls inside it).  A frozen world has one frame."""
         key = k if self.timeline.moving else 0
+        if self.device_world:
+            w = self._held.get(key)
+            return w if w is not None and w.tick == key else self._write_frames(key, 1)[0]
         w = self._frames.get(key)
         if w is None:
             f = self.timeline.frame(key)
             w = self._frames[key] = World(f["cloud"], f["cylinders"])
         return w
 
+    def _timeline_dev(self, n):
+        """the device timeline, its pool holding at least n frames (tick 0 is uploaded on first use)"""
+        if self._tl_dev is None:
+            self._tl_dev = WorldTimelineDev.from_timeline(self.timeline, pool=max(self.world_pool, n))
+        self._tl_dev.reserve(n)
+        return self._tl_dev
+
+    def _write_frames(self, k0, n):
+        tl = self._timeline_dev(n)
+        out = tl.frames(k0, n)
+        self._held = {s.tick: s for s in tl._slots if s.tick is not None}
+        return out
+
+    def frames(self, k0, n):
+        """The frames of ticks k0 .. k0 + n - 1 (a flight's).  device_world: ONE batched sogm_world_frames call; the pool
+        grows to n if it is smaller, so that it holds the frames of a flight in the air."""
+        if not self.device_world:
+            return [self.world(k0 + i) for i in range(n)]
+        if not self.timeline.moving:
+            return [self.world(0)] * n
+        held = [self._held.get(k0 + i) for i in range(n)]
+        if all(w is not None and w.tick == k0 + i for i, w in enumerate(held)):
+            return held
+        return self._write_frames(k0, n)
+
     def prepare(self, k0, k1):
+        if self.device_world:   # the pool and the tick-0 upload; the frames themselves are written where they are used
+            self._timeline_dev(1)
+            torch.cuda.synchronize()
+            return
         for k in range(k0, k1):
             self.world(k)
         torch.cuda.synchronize()
 
     def forget(self, before):
-        """drop the uploaded frames of ticks < before"""
+        """drop the uploaded frames of ticks < before (device_world: nothing to drop, the pool's slots are reused)"""
         for k in [k for k in self._frames if k < before and self.timeline.moving]:
             del self._frames[k]
 
@@ -365,7 +407,8 @@ class SwarmTick:
     def __init__(self, grid="cfg2", agents_per_rank=None, rank=0, world=1, device=0, seed=0x5069,
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
-                 moving_world=None, neighbour_lag=1, audit=False, device_fsm=False, traj_server=None):
+                 moving_world=None, neighbour_lag=1, audit=False, device_fsm=False, traj_server=None, device_world=None,
+                 world_pool=None):
         self.rank, self.world, self.dist = rank, world, dist
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
@@ -385,7 +428,8 @@ class SwarmTick:
             # up) so that they find room.  NOT measured on hardware: no multi-GPU box.
             tuning = dict(tuning or {}, flight_exchange_units=1, flight_map_units=3)
         self.compute = compute if compute is not None else HipCompute(
-            self.spec, self.scene, lo, hi, device, overlap_clear, double_buffer, grids, tuning, moving_world)
+            self.spec, self.scene, lo, hi, device, overlap_clear, double_buffer, grids, tuning, moving_world, device_world,
+            world_pool)
         c = self.compute
         # the HIP objects, for the bench / tools / tests that use the staged entry points beside step()
         self.map, self.planner, self.dev = getattr(c, "map", None), getattr(c, "planner", None), getattr(c, "dev", None)
@@ -686,7 +730,7 @@ class SwarmTick:
         assert 1 <= n_ticks <= _abi.FLIGHT_MAX_TICKS
         log_r = torch.zeros((n_ticks, self.A_loc, _abi.TRAJ_RECORD_BYTES), dtype=torch.uint8, device="cuda")
         log_ok = torch.zeros((n_ticks, self.A_loc), dtype=torch.int32, device="cuda")
-        worlds = [c.world(self.tick + i) for i in range(n_ticks)]
+        worlds = c.frames(self.tick, n_ticks)
         sided = self.auditor is not None or self.server is not None
         executed = self.own.clone() if sided else None   # the table before the call
         fsm_log = None
@@ -745,7 +789,7 @@ class SwarmTick:
             # in-place all-gather of this rank's rows and the release of the next-but-one tick's overlays are queued on the
             # context's exchange stream; no host step between ticks, every rank passes the same n_ticks
             assert 1 <= n_ticks <= _abi.FLIGHT_MAX_TICKS
-            worlds = [c.world(self.tick + i) for i in range(n_ticks)]
+            worlds = c.frames(self.tick, n_ticks)
             self.planner.flight(worlds, self.tick, self.t0, TICK_PERIOD, REPLAN_START_TIME, self.goals, self.dev["ego_ids"],
                                 self.hover, self.own, self._fl_tables, log_r, log_ok, n_total=self.A_tot, agent0=lo,
                                 comm=self.exchange.handle)
@@ -756,7 +800,7 @@ class SwarmTick:
         done = 0
         while done < n_ticks:
             n = min(2, n_ticks - done)
-            worlds = [c.world(self.tick + i) for i in range(n)]
+            worlds = c.frames(self.tick, n)
             # (flight_guard: a test that runs several ranks as threads on ONE device serialises their calls with it — two
             #  flights at once would fight for the same compute-unit partitions, each holding what the other's kernels need)
             guard = getattr(self, "flight_guard", None)

@@ -189,6 +189,12 @@ class RiskMap {
                          const SogmCylinder *cyl, int n_cyl) {
     return SogmWorld{cloud_xyz, bounds, cyl, n_points, (n_points + block_points - 1) / block_points, block_points, n_cyl};
   }
+  // The frames of ticks first_tick .. first_tick + n_ticks - 1 of a moving world, written on the device from its tick-0
+  // state (include/sogm_abi.h "world timeline"): frames[i]'s cloud, block bounds and records are OUTPUTS here.
+  static void worldFrames(const SogmWorldTimeline &tl, int first_tick, int n_ticks, const SogmWorld *frames,
+                          hipStream_t st = nullptr) {
+    check(sogm_world_frames(&tl, first_tick, n_ticks, frames, st), "sogm_world_frames");
+  }
   void updateWorld(const SogmWorld &frame, const float *poses, const double *stamps, const SogmTrajRecord *records = nullptr,
                    int n_records = 0, const int32_t *ego_ids = nullptr, hipStream_t st = nullptr) {
     check(sogm_update_world(ctx_, &frame, poses, stamps, records, n_records, ego_ids, st), "sogm_update_world");

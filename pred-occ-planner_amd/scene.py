@@ -239,7 +239,12 @@ class WorldTimeline:
         t = float(k) * self.dt
         off = (self.cyl0[:, 3:5] * t).astype(np.float32)          # per cylinder
         out = self.cloud0.copy()
-        out[:, :2] += off[self.owner]
+        owner = np.asarray(self.owner)
+        owned = (owner >= 0) & (owner < len(off))
+        if owned.all():
+            out[:, :2] += off[owner]
+        else:   # an owner of -1 (any outside the records): a static point, not off[-1]
+            out[owned, :2] += off[owner[owned]]
         return out
 
     def frame(self, k):

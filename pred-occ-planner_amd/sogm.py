@@ -312,6 +312,94 @@ class World:
                                 self.block_points, self.n_cyl)
 
 
+class WorldFrame:
+    """One pool slot of WorldTimelineDev: World's attributes (cloud, bounds, cylinders, n_points, n_blocks, block_points,
+    n_cyl, c) over buffers that sogm_world_frames writes; `tick` is the tick the slot was last written for."""
+
+    def __init__(self, n_points, n_cyl, block_points, device):
+        self.n_points, self.n_cyl, self.block_points = int(n_points), int(n_cyl), int(block_points)
+        self.n_blocks = (self.n_points + self.block_points - 1) // self.block_points
+        self.cloud = torch.zeros((max(self.n_points, 1), 3), dtype=torch.float32, device=device)
+        self.bounds = torch.zeros((max(self.n_blocks, 1), 4), dtype=torch.float32, device=device)
+        self.cylinders = torch.zeros((max(self.n_cyl, 1) * _abi.CYLINDER_BYTES,), dtype=torch.uint8, device=device)
+        self.tick = None
+        self.c = _abi.SogmWorld(self.cloud.data_ptr(), self.bounds.data_ptr(),
+                                self.cylinders.data_ptr() if self.n_cyl else None, self.n_points, self.n_blocks,
+                                self.block_points, self.n_cyl)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.cloud, self.bounds, self.cylinders))
+
+
+class WorldTimelineDev:
+    """The moving world's timeline on the device (SogmWorldTimeline): the cloud, its owners and the obstacle states of
+    tick 0 are uploaded ONCE; frames(first_tick, n) writes the frames of n consecutive ticks with one sogm_world_frames
+    call into a pool of at most `pool` frames and returns them — World-compatible objects, no host-to-device copy.
+    `cloud0` [n, 3] float32, `owner` int32 [n] (None: every point is static), `cylinders0` numpy (n, 5) rows
+    {x, y, w, vx, vy} or a ctypes SogmCylinder array (then n_cyl says how many).
+
+    The pool's slots are taken in turn, so a returned frame is rewritten by the pool-th frame requested after it, by a kernel
+    queued on the caller's stream.  That is safe once everything that reads the frame is ordered before that kernel:
+    sogm_flight_run joins all its streams into the caller's before it returns (a pool as large as the flight in the air is
+    enough); sogm_update_world under the tuning key update_flow and a sogm_replan that pre-stamps from the frame keep reading
+    on streams of the library's own until the context's NEXT update or replan call joins them — so a lock-step consumer needs
+    pool >= 2: frame k's slot is rewritten for tick k + 2 at the earliest, behind the calls of tick k + 1."""
+
+    def __init__(self, cloud0, owner, cylinders0, dt, n_cyl=None, moving=True, block_points=256, pool=8, device="cuda"):
+        from .scene import cylinders_to_struct
+        if not isinstance(cylinders0, C.Array):
+            n_cyl = len(cylinders0)
+            cylinders0 = cylinders_to_struct(cylinders0)
+        self.n_points, self.n_cyl, self.block_points = int(len(cloud0)), int(n_cyl), int(block_points)
+        if owner is None:
+            owner = np.full((self.n_points,), -1, np.int32)
+        if len(owner) != self.n_points:
+            raise ValueError("WorldTimelineDev: one owner per cloud point")
+        self.device, self.dt, self.moving = device, float(dt), bool(moving)
+        self.cloud0 = _dev(cloud0 if self.n_points else np.zeros((1, 3), np.float32), np.float32, device)
+        self.owner = _dev(owner if self.n_points else np.zeros((1,), np.int32), np.int32, device)
+        self.cylinders0 = _dev(cylinders0, None, device)
+        self.c = _abi.SogmWorldTimeline(self.cloud0.data_ptr(), self.owner.data_ptr(),
+                                        self.cylinders0.data_ptr() if self.n_cyl else None, self.n_points, self.n_cyl,
+                                        self.block_points, 1 if self.moving else 0, self.dt)
+        self._slots, self._next = [], 0
+        self.reserve(pool)
+
+    @classmethod
+    def from_timeline(cls, tl, **kw):
+        """from a scene.WorldTimeline"""
+        return cls(tl.cloud0, tl.owner, tl.cyl0, tl.dt, moving=tl.moving, **kw)
+
+    @property
+    def pool(self):
+        return len(self._slots)
+
+    def reserve(self, pool):
+        """grow the pool to `pool` frames (never shrinks: frames handed out stay valid)"""
+        if pool < 1:
+            raise ValueError("WorldTimelineDev: pool must be >= 1")
+        while len(self._slots) < pool:
+            self._slots.append(WorldFrame(self.n_points, self.n_cyl, self.block_points, self.device))
+
+    def pool_bytes(self):
+        """device memory held by the pool's frames"""
+        return sum(s.nbytes() for s in self._slots)
+
+    def frames(self, first_tick, n):
+        """The frames of ticks first_tick .. first_tick + n - 1, written by one call queued on the current stream."""
+        if not 1 <= n <= self.pool:
+            raise ValueError(f"WorldTimelineDev.frames: {n} frames from a pool of {self.pool}")
+        out = [self._slots[(self._next + i) % self.pool] for i in range(n)]
+        self._next = (self._next + n) % self.pool
+        arr = (_abi.SogmWorld * n)(*[s.c for s in out])
+        for s in out:
+            s.tick = None
+        check(lib().sogm_world_frames(C.byref(self.c), int(first_tick), n, arr, _stream()), "sogm_world_frames")
+        for i, s in enumerate(out):
+            s.tick = int(first_tick) + i
+        return out
+
+
 def upload_scene(scene, device="cuda", cloud=None, cloud_range=None):
     """numpy scene -> dict of device tensors in the ABI's layouts.  By default every agent sees the
     whole cloud; pass per-agent crops (scene.crop_clouds) to bound each agent's scan."""
