@@ -534,6 +534,74 @@ int sogm_gridmap_query_inflate(sogm_gridmap *g, const int32_t *agent_idx, const 
                                int8_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* ring obstacles: the second obstacle kind of the ground-truth record (type 2), as the depth     */
+/*   camera and the flight audit below take it.  The reference only attributes ring velocities   */
+/*   in its map (fake_particle_risk_voxel.cpp:139-150); what a ring IS to a camera or to a body  */
+/*   is the build's OWN definition, held by two independent implementations each                 */
+/*   (csrc/sogm_ring.hpp; tests/depth_ring_reference.py and tests/audit_ring_reference.py).      */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * All arithmetic is fp64, in exactly the order written, one IEEE operation at a time (+ - * / sqrt), without contraction:
+ * the host and the device give the same bits.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2.
+ *
+ * Geometry: a SogmCylinder record of type 2 is a solid torus.
+ *   centre  c = (x, y, z).  z and the orientation never change; x, y are the record's (depth camera: "of the same
+ *           instant") or advance with vx, vy (flight audit).
+ *   R   = 0.5*w   major radius (the reference's cyl.w / 2, fake_particle_risk_voxel.cpp:147)
+ *   rho = h       tube radius.  This choice is the build's own: scene.add_rings writes h = 0.1, the half width of the
+ *                 3 x 3 tube section it puts into the cloud.
+ *   frame   qn = sqrt(((qw*qw + qx*qx) + qy*qy) + qz*qz);  w = qw/qn; x = qx/qn; y = qy/qn; z = qz/qn  (these four
+ *           letters: the unit quaternion, only in the next three lines)
+ *             e1 = ( 1 - 2*(y*y + z*z),  2*(x*y + w*z),      2*(x*z - w*y)     )
+ *             e2 = ( 2*(x*y - w*z),      1 - 2*(x*x + z*z),  2*(y*z + w*x)     )
+ *             n  = ( 2*(x*z + w*y),      2*(y*z - w*x),      1 - 2*(x*x + y*y) )
+ *           the columns of scene._quat_to_matrix; the circle is c + R (cos e1 + sin e2), the reference's plane through
+ *           c, c + q(0,1,0), c + q(1,0,0) (:141-143).
+ *   not a ring: any of x, y, z, w, h, vx, vy, qw, qx, qy, qz not finite, or not R > 0, or not rho > 0, or not rho < R, or
+ *           qn not finite or not > 0.  The camera counts such a record as unsupported and does not draw it; the audit
+ *           treats it as it treats an unsupported type.
+ *
+ * Ray against ring (depth camera; t is the camera's z-depth parameter, the ray is p + t d):
+ *   o = p - c;  alpha = dot(d, d);  beta = dot(o, d);  gamma = dot(o, o);  no = dot(n, o);  nd = dot(n, d)
+ *   alpha > 0, else no hit.
+ *   bounding sphere:  S = R + rho;  cs = gamma - S*S;  disc = beta*beta - alpha*cs;  disc < 0: no hit.
+ *                     s = sqrt(disc);  t0 = (-beta - s)/alpha;  t1 = (-beta + s)/alpha
+ *   slab |no + t nd| <= rho:  nd == 0: no hit unless |no| <= rho.  Otherwise ta = (-rho - no)/nd;  tb = (rho - no)/nd;
+ *                     t0 = max(t0, min(ta, tb));  t1 = min(t1, max(ta, tb))
+ *   t0 = max(t0, 0);  no hit unless t0 <= t1.
+ *   inside the torus means f(t) < 0,  f(t) = (((c4*t + c3)*t + c2)*t + c1)*t + c0  with
+ *     RR = R*R;  K = (gamma + RR) - rho*rho
+ *     c4 = alpha*alpha
+ *     c3 = (4*alpha)*beta
+ *     c2 = ((4*beta)*beta + (2*alpha)*K) - (4*RR)*(alpha - nd*nd)
+ *     c1 = (4*beta)*K - (8*RR)*(beta - no*nd)
+ *     c0 = K*K - (4*RR)*(gamma - no*no)
+ *   f(t0) <= 0 and t0 == 0: the camera is inside the tube and this ring gives the pixel NO return (for a cylinder the
+ *     camera sees the inner wall; here it does not).
+ *   f(t0) <= 0 and t0 > 0: the hit is t0.
+ *   otherwise search: hs = (t1 - t0)/32; node_i = t0 + i*hs for i = 1 .. 31, node_32 = t1.  The first node with
+ *     f(node_i) <= 0 brackets the entry: lo = node_(i-1) (node_0 = t0), hi = node_i.  48 times: m = 0.5*(lo + hi);
+ *     f(m) <= 0 moves hi to m, otherwise lo to m.  The hit is hi.  No such node: no hit.
+ *   The sphere, the slab and the empty interval are part of the rule, not an approximation of it.  A thin near-side
+ *   crossing that lies wholly between two nodes is not found: the far side (or nothing) is returned.
+ *
+ * Body box against ring (flight audit):
+ *   table of 64 unit vectors by arc halving: u_0 = (1,0), u_16 = (0,1), u_32 = (-1,0), u_48 = (0,-1); then for
+ *     step = 8, 4, 2, 1 every u_i with i an odd multiple of step is mid(u_(i-step), u_(i+step)) (indices mod 64), where
+ *     mid(a, b):  sx = a0 + b0;  sy = a1 + b1;  nn = sqrt(sx*sx + sy*sy);  (sx/nn, sy/nn).
+ *   box: lo_i = a_i - 0.5*body_i;  hi_i = a_i + 0.5*body_i  (a: the agent's position)
+ *   g(u):  P_i = c_i + R*(u0*e1_i + u1*e2_i);  q_i = lo_i if P_i < lo_i, hi_i if P_i > hi_i, else P_i;  dd_i = P_i - q_i;
+ *          g = sqrt((dd_0*dd_0 + dd_1*dd_1) + dd_2*dd_2)
+ *   the vertex with the smallest g (lowest index on ties) is m, its table neighbours l and r.  Twelve times:
+ *     ml = mid(l, m);  mr = mid(m, r);  if g(ml) < g(m) and g(ml) <= g(mr): (l, m, r) = (l, ml, m);
+ *     else if g(mr) < g(m): (l, m, r) = (m, mr, r);  else (l, m, r) = (ml, m, mr).
+ *   gap = g(m) - rho;  a collision is gap < 0.  Unlike the cylinder's, this gap is three-dimensional: there is no
+ *   z-overlap gate, it takes part in min_gap at every sample.
+ */
+enum { SOGM_DEPTH_RINGS = 1 };   /* SogmDepthCamera.flags */
+enum { SOGM_AUDIT_RINGS = 1 };   /* SogmAuditParams.flags */
+
+/* ------------------------------------------------------------------------------------------ */
 /* depth camera: the frames the two front ends above see of a SogmWorld                          */
 /*   The reference took them from its uav_simulator submodule, an empty directory in its tree:   */
 /*   this camera is the build's OWN (SURVEY section 8 d), as the intrinsics of the GridMap       */
@@ -546,8 +614,10 @@ int sogm_gridmap_query_inflate(sogm_gridmap *g, const int32_t *agent_idx, const 
  * (scene.camera_pose; the same array sogm_gridmap_update takes), cam_pos the camera centre p.
  * Obstacles: the SogmCylinder records of a SogmWorld, "of the same instant" — vx, vy are not used.  Geometry as the
  * flight audit's: type 3 is a vertical cylinder of diameter w with its axis at (x, y), z extent [z - h/2, z + h/2],
- * closed by two discs.  Optionally a ground plane z = ground_z.  Records of any other type (rings, type 2) are not
- * rendered: they are counted per agent (out_unsupported) and the image is what it would be without them.
+ * closed by two discs.  Optionally a ground plane z = ground_z.  With SOGM_DEPTH_RINGS set in flags, a type-2 record
+ * that is a ring ("ring obstacles" above) is drawn by that section's ray rule: its hit is one more accepted t.  Every
+ * other record — another type, a type 2 that is not a ring, every type 2 with the flag clear — is not rendered: it is
+ * counted per agent (out_unsupported) and the image is what it would be without it.
  *
  * All arithmetic is fp64, in exactly this order, without contraction (the library is built with -ffp-contract=off).
  * Pixel (row v, column u) of agent a:
@@ -571,8 +641,8 @@ int sogm_gridmap_query_inflate(sogm_gridmap *g, const int32_t *agent_idx, const 
  *     d16 == 0 -> three quiet NaNs (sogm_filter_point_cloud skips non-finite points: every agent hands over exactly
  *     rows*cols points, raw_range[a] = {a*rows*cols, (a+1)*rows*cols}, no compaction)
  *
- * The result is a minimum over the cylinders: it depends neither on their order nor on any culling of cylinders
- * that cannot be hit within max_depth.
+ * The result is a minimum over everything accepted (cylinder sides, caps, ground, rings): it depends neither on the
+ * records' order nor on any culling of records that cannot be hit within max_depth.
  */
 typedef struct SogmDepthCamera {
   double  fx, fy, cx, cy;
@@ -581,14 +651,14 @@ typedef struct SogmDepthCamera {
   double  ground_z;
   int32_t rows, cols;
   int32_t use_ground;
-  int32_t reserved_;
+  int32_t flags;         /* SOGM_DEPTH_RINGS; other bits are ignored */
 } SogmDepthCamera;       /* 72 bytes */
 /*
  * Renders every agent's frame of `world` (only cylinders / n_cyl are read).  Context-free like sogm_traj_eval: the
  * current device, stream-ordered, no allocation, no host synchronisation.
  * dev cam_pos [n*3] fp64, dev cam_rot [n*9] fp64, dev out_depth [n*rows*cols] uint16 (what sogm_gridmap_update takes),
  * dev out_cloud_xyz [n*rows*cols*3] fp32 or NULL (what sogm_filter_point_cloud takes as raw_xyz),
- * dev out_unsupported [n] int32: obstacles of a type other than 3.
+ * dev out_unsupported [n] int32: the records that are not drawn (above).
  * SOGM_ERR_INVALID_ARG (checked first, as in sogm_create): rows, cols or n_agents < 1, n_cyl < 0, fx, fy, max_depth or
  * depth_scale not positive, max_depth*depth_scale > 65535, intrinsics that are not finite, a null required pointer, an
  * image of more than 2^31 - 1 pixels.  SOGM_ERR_NO_DEVICE without a GPU.
@@ -596,7 +666,7 @@ typedef struct SogmDepthCamera {
 int sogm_render_depth(const SogmWorld *world, const SogmDepthCamera *cam, int n_agents,
                       const double *cam_pos /* dev [n*3] */, const double *cam_rot /* dev [n*9] */,
                       uint16_t *out_depth /* dev [n*rows*cols] */, float *out_cloud_xyz /* dev [n*rows*cols*3] or NULL */,
-                      int32_t *out_unsupported /* dev [n]: obstacles of a type other than 3 */, void *stream);
+                      int32_t *out_unsupported /* dev [n]: records that are not drawn */, void *stream);
 
 /*
  * Tick glue of a batched planner service, each ONE launch (the FSM bookkeeping around replan()):
@@ -1111,7 +1181,12 @@ int sogm_replan(sogm_planner *p, const double *start_pva, const double *goal,
  *   - Agent-obstacle collision (SogmCylinder type 3): diameter w, z extent [z - h/2, z + h/2], axis at time t at
  *     (x + vx (t - t_obstacles), y + vy (t - t_obstacles)).  The z extents overlap if |pz - z| < (h + bz) / 2.  The gap is
  *     the xy distance from the axis to the body's xy rectangle minus w / 2 (-w / 2 when the axis is inside the rectangle);
- *     a collision is z overlap and gap < 0.  Only type 3 is audited: rings (type 2) and any other type are refused (below).
+ *     a collision is z overlap and gap < 0.
+ *   - Agent-ring (type 2, only with SOGM_AUDIT_RINGS set in flags): the body-box rule of "ring obstacles" with the centre
+ *     at time t at (x + vx (t - t_obstacles), y + vy (t - t_obstacles), z).  Its gap takes part in min_gap at every sample
+ *     and a collision is gap < 0; `other` / min_gap_obstacle is the record's index in cylinders[], kind stays
+ *     SOGM_AUDIT_OBSTACLE.  With the flag clear type 2 is refused like any other type, and so is a type 2 that is not a
+ *     ring with the flag set (below).
  *   - Goal: the first sample with |p - goal| < goal_tolerance (1.0: fsm/goal_tolerance, sim_fake.yaml:5).
  *   - Path length: sum of |p(t_i) - p(t_(i-1))| over consecutive samples, carried across calls (last_pos).
  *   - Minima break ties by the earliest sample, then the lowest index.  Events: one per colliding (sample, agent, other or
@@ -1125,7 +1200,7 @@ typedef struct SogmAuditParams {
   double  goal_tolerance;   /* 1.0 */
   double  t_obstacles;      /* the instant cylinders[] describes */
   int32_t event_capacity;   /* entries of events[] (>= 0) */
-  int32_t reserved_;
+  int32_t flags;            /* SOGM_AUDIT_RINGS; other bits are ignored */
 } SogmAuditParams;
 
 /* One audited agent's accumulator; sogm_audit_init_agents sets +inf minima, -1 times and indices, zero counts. */
@@ -1156,8 +1231,8 @@ int sogm_audit_init_agents(SogmAuditAgent *acc, int n_local, void *stream);
  * dev goals [n_local][3], dev cylinders [n_cyl] (NULL if n_cyl == 0), dev acc [n_local] in/out, dev events [event_capacity]
  * (NULL if the capacity is 0), dev n_events [1] in/out: every colliding sample seen so far, kept or not.
  * SOGM_ERR_INVALID_ARG (with sogm_last_error text) for null pointers, counts out of range, period / sample_dt not whole.
- * The cylinders are device data the call does not read on the host: a cylinder whose type is not 3 makes the call add
- * nothing and set *n_events = -1, which every later call keeps (the Python binding refuses such obstacles on the host).
+ * The cylinders are device data the call does not read on the host: a record that is not audited (a type other than 3;
+ * with SOGM_AUDIT_RINGS, other than 3 or a type 2 that is a ring) makes the call add nothing and set *n_events = -1, which every later call keeps (the Python binding refuses such obstacles on the host).
  */
 int sogm_swarm_audit(const SogmAuditParams *prm, const SogmTrajRecord *tables, int n_ticks, int n_total,
                      const SogmTrajRecord *prev_table, double t0, int first_tick, double period, int agent0, int n_local,

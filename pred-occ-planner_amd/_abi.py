@@ -69,7 +69,7 @@ class SogmGridMapParams(C.Structure):
 class SogmDepthCamera(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("max_depth", C.c_double), ("depth_scale", C.c_double), ("ground_z", C.c_double),
-                ("rows", C.c_int32), ("cols", C.c_int32), ("use_ground", C.c_int32), ("reserved_", C.c_int32)]
+                ("rows", C.c_int32), ("cols", C.c_int32), ("use_ground", C.c_int32), ("flags", C.c_int32)]
 
 
 class SogmCylinder(C.Structure):
@@ -135,7 +135,7 @@ class SogmFlight(C.Structure):
 
 class SogmAuditParams(C.Structure):
     _fields_ = [("body", C.c_double * 3), ("sample_dt", C.c_double), ("goal_tolerance", C.c_double),
-                ("t_obstacles", C.c_double), ("event_capacity", C.c_int32), ("reserved_", C.c_int32)]
+                ("t_obstacles", C.c_double), ("event_capacity", C.c_int32), ("flags", C.c_int32)]
 
 
 class SogmAuditAgent(C.Structure):
@@ -152,6 +152,7 @@ class SogmAuditEvent(C.Structure):
 
 
 SOGM_AUDIT_AGENT, SOGM_AUDIT_OBSTACLE = 0, 1
+SOGM_DEPTH_RINGS, SOGM_AUDIT_RINGS = 1, 1   # SogmDepthCamera.flags, SogmAuditParams.flags
 AUDIT_AGENT_BYTES = C.sizeof(SogmAuditAgent)  # 104
 AUDIT_EVENT_BYTES = C.sizeof(SogmAuditEvent)  # 24
 

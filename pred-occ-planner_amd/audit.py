@@ -36,10 +36,11 @@ def cylinder_table(rows, moving=True):
 class SwarmAudit:
     """Audits rows [agent0, agent0 + n_local) of an n_total swarm.  goals [n_local][3], fallback_pos [n_total][3] (where an
     agent hovers before its first trajectory), cylinders: (n, 5) rows {x, y, w, vx, vy} at t_obstacles, or a SogmCylinder
-    ctypes array (type 3 only)."""
+    ctypes array (type 3 only; with rings=True also type 2, audited as rings: include/sogm_abi.h "ring obstacles")."""
 
     def __init__(self, n_total, goals, fallback_pos, cylinders, t_obstacles, agent0=0, n_local=None, moving=True,
-                 body=BODY, sample_dt=SAMPLE_DT, goal_tolerance=GOAL_TOLERANCE, event_capacity=4096, device="cuda"):
+                 body=BODY, sample_dt=SAMPLE_DT, goal_tolerance=GOAL_TOLERANCE, event_capacity=4096, device="cuda",
+                 rings=False):
         self.n_total, self.agent0 = int(n_total), int(agent0)
         self.n_local = int(n_local) if n_local is not None else self.n_total - self.agent0
         if not (0 <= self.agent0 and 1 <= self.n_local <= self.n_total - self.agent0):
@@ -51,9 +52,11 @@ class SwarmAudit:
             if not moving:
                 for c in cyl:
                     c.vx = c.vy = 0.0
-        bad = [i for i in range(n_cyl) if cyl[i].type != 3]
+        bad = [i for i in range(n_cyl) if cyl[i].type != 3 and not (rings and cyl[i].type == 2)]
         if bad:
-            raise ValueError(f"SwarmAudit audits cylinders (type 3) only; obstacles {bad[:8]} are of another type")
+            raise ValueError(f"SwarmAudit audits cylinders (type 3) only; obstacles {bad[:8]} are of another type"
+                             if not rings else
+                             f"SwarmAudit(rings=True) audits types 3 and 2 only; obstacles {bad[:8]} are of another type")
         self.n_cyl = n_cyl
         self.cyl = torch.frombuffer(bytearray(bytes(cyl)[:n_cyl * _abi.CYLINDER_BYTES]) or bytearray(_abi.CYLINDER_BYTES),
                                     dtype=torch.uint8).to(device)
@@ -63,6 +66,7 @@ class SwarmAudit:
         self.prm.body[:] = [float(b) for b in body]
         self.prm.sample_dt, self.prm.goal_tolerance = float(sample_dt), float(goal_tolerance)
         self.prm.t_obstacles, self.prm.event_capacity = float(t_obstacles), int(event_capacity)
+        self.prm.flags = _abi.SOGM_AUDIT_RINGS if rings else 0
         self.acc = torch.empty((self.n_local, _abi.AUDIT_AGENT_BYTES), dtype=torch.uint8, device=device)
         self.events = torch.zeros((max(int(event_capacity), 1), _abi.AUDIT_EVENT_BYTES), dtype=torch.uint8, device=device)
         self.n_events = torch.zeros((1,), dtype=torch.int32, device=device)

@@ -7,7 +7,12 @@
 //                   the same kernel again in its writing form puts the events at their scanned offsets
 //   k_audit_scan    one workgroup: exclusive scan of the per-(sample, agent) event counts (their order IS the event order)
 //   k_audit_fold    one lane per audited agent walks the samples in order and updates its accumulator
+// With SOGM_AUDIT_RINGS k_audit_sample runs in its RINGS form: the same lane per (sample, agent) walks the same chunks of
+// records in index order — which IS the event order and the tie rule of min_gap — and takes sogm_ring.hpp's ring_box_gap
+// for a type-2 record where it takes the cylinder's gap for every other; the chunk's ring frames are staged in LDS by the
+// lanes that load the records, the 64 unit vectors are built in LDS once per workgroup.
 #include "sogm_device.hpp"
+#include "sogm_ring.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -21,6 +26,16 @@ struct AuditDims {
   double t0, period, sample_dt, t_obs;
   double bx, by, bz, goal_tol;
   int    first_tick, m, n_ticks, n_total, agent0, n_local, n_cyl, capacity;
+};
+
+// a record of a chunk as the ring form stages it
+struct AuditRing {
+  RingBody body;
+  int      is_ring, valid;
+};
+template <bool RINGS>
+struct AuditRingLds {
+  static constexpr int N = RINGS ? AUDIT_WG : 1;
 };
 
 // sample s of the call (tick s / m, sample s % m of that tick): times built from integers
@@ -69,7 +84,7 @@ struct AuditCell {
 };
 
 // WRITE = false: minima and counts into cells / counts; WRITE = true: the events at base + offs[cell] (capacity permitting)
-template <bool WRITE>
+template <bool WRITE, bool RINGS>
 __global__ __launch_bounds__(AUDIT_WG) void k_audit_sample(AuditDims d, const double *__restrict__ pos,
                                                            const SogmCylinder *__restrict__ cyl,
                                                            AuditCell *__restrict__ cells, int32_t *__restrict__ counts,
@@ -78,6 +93,18 @@ __global__ __launch_bounds__(AUDIT_WG) void k_audit_sample(AuditDims d, const do
                                                            SogmAuditEvent *__restrict__ events) {
   __shared__ double s_p[AUDIT_WG][3];
   __shared__ double s_c[AUDIT_WG][5];   // x, y (at the sample's time), z, w, h: per chunk of cylinders
+  __shared__ AuditRing s_r[AuditRingLds<RINGS>::N];          // the chunk's type-2 records
+  __shared__ double    s_tab[AuditRingLds<RINGS>::N][2];     // the 64 unit vectors
+  if (RINGS) {  // level by level: entry i needs its two neighbours of the coarser level (AUDIT_WG == RING_TABLE lanes)
+    static_assert(!RINGS || AUDIT_WG == RING_TABLE, "one lane per table entry");
+    const int i = threadIdx.x;
+    if ((i & 15) == 0) ring_table_axis(s_tab, i);
+    for (int step = 8; step >= 1; step >>= 1) {
+      __syncthreads();
+      if ((i & (2 * step - 1)) == step) ring_table_level(s_tab, i, step);
+    }
+    __syncthreads();
+  }
   const int  s = blockIdx.y, i = blockIdx.x * AUDIT_WG + threadIdx.x;
   const bool live = i < d.n_local;
   const int  cell = s * d.n_local + i;
@@ -132,15 +159,33 @@ __global__ __launch_bounds__(AUDIT_WG) void k_audit_sample(AuditDims d, const do
       s_c[threadIdx.x][2]   = o.z;
       s_c[threadIdx.x][3]   = o.w;
       s_c[threadIdx.x][4]   = o.h;
+      if (RINGS) {
+        AuditRing &q = s_r[threadIdx.x];
+        RingFrame  f;
+        q.is_ring = o.type == 2;
+        q.valid   = q.is_ring && ring_frame(o, f);
+        if (q.valid) {
+          q.body.c[0] = s_c[threadIdx.x][0], q.body.c[1] = s_c[threadIdx.x][1], q.body.c[2] = o.z;
+          q.body.R = f.R, q.body.rho = f.rho;
+          for (int e = 0; e < 3; ++e) q.body.e1[e] = f.e1[e], q.body.e2[e] = f.e2[e];
+        }
+      }
     }
     __syncthreads();
     const int nc = min(AUDIT_WG, d.n_cyl - c0);
     if (!live) continue;
     for (int u = 0; u < nc; ++u) {
-      if (!(fabs(pz - s_c[u][2]) < (s_c[u][4] + d.bz) * 0.5)) continue;   // no z overlap
-      const double ex  = fmax(fabs(s_c[u][0] - px) - d.bx * 0.5, 0.0);
-      const double ey  = fmax(fabs(s_c[u][1] - py) - d.by * 0.5, 0.0);
-      const double gap = sqrt(ex * ex + ey * ey) - s_c[u][3] * 0.5;
+      double gap;
+      if (RINGS && s_r[u].is_ring) {
+        if (!s_r[u].valid) continue;   // not a ring: k_audit_scan refuses the call
+        const double a[3] = {px, py, pz}, body[3] = {d.bx, d.by, d.bz};
+        gap = ring_box_gap(s_r[u].body, a, body, s_tab);
+      } else {
+        if (!(fabs(pz - s_c[u][2]) < (s_c[u][4] + d.bz) * 0.5)) continue;   // no z overlap
+        const double ex = fmax(fabs(s_c[u][0] - px) - d.bx * 0.5, 0.0);
+        const double ey = fmax(fabs(s_c[u][1] - py) - d.by * 0.5, 0.0);
+        gap             = sqrt(ex * ex + ey * ey) - s_c[u][3] * 0.5;
+      }
       if (gap < c.min_gap) {
         c.min_gap = gap;
         c.gap_idx = c0 + u;
@@ -158,10 +203,10 @@ __global__ __launch_bounds__(AUDIT_WG) void k_audit_sample(AuditDims d, const do
   }
 }
 
-// one workgroup of 1024 lanes: offs = exclusive scan of counts; *n_events += total (saturating); a cylinder of another type
-// than 3 poisons *n_events (-1).  base_out = *n_events before this call (-1: poisoned, nothing is written or folded).
+// one workgroup of 1024 lanes: offs = exclusive scan of counts; *n_events += total (saturating); a record that is not
+// audited (a type other than 3; with `rings`, other than 3 or a type 2 that is a ring) poisons *n_events (-1).  base_out = *n_events before this call (-1: poisoned, nothing is written or folded).
 __global__ __launch_bounds__(1024) void k_audit_scan(const int32_t *__restrict__ counts, long long n,
-                                                     const SogmCylinder *__restrict__ cyl, int n_cyl,
+                                                     const SogmCylinder *__restrict__ cyl, int n_cyl, int rings,
                                                      long long *__restrict__ offs, long long *__restrict__ base_out,
                                                      int32_t *__restrict__ n_events) {
   __shared__ long long s_sum[1024];
@@ -171,7 +216,10 @@ __global__ __launch_bounds__(1024) void k_audit_scan(const int32_t *__restrict__
   if (tid == 0) s_bad = 0;
   __syncthreads();
   for (int c = tid; c < n_cyl; c += 1024)
-    if (cyl[c].type != 3) s_bad = 1;
+    if (cyl[c].type != 3) {
+      RingFrame f;
+      if (!(rings && cyl[c].type == 2 && ring_frame(cyl[c], f))) s_bad = 1;
+    }
   long long sum = 0;
   for (long long q = lo; q < hi; ++q) sum += counts[q];
   s_sum[tid] = sum;
@@ -322,11 +370,22 @@ extern "C" int sogm_swarm_audit(const SogmAuditParams *prm, const SogmTrajRecord
   long long *base  = offs + cells;
   const dim3 g_smp((n_local + AUDIT_WG - 1) / AUDIT_WG, ns);
   hipLaunchKernelGGL(k_audit_pos, dim3(n_total, n_ticks), dim3(AUDIT_WG), 0, st, d, tables, prev_table, fallback_pos, pos);
-  hipLaunchKernelGGL(k_audit_sample<false>, g_smp, dim3(AUDIT_WG), 0, st, d, pos, cylinders, cell, cnt, nullptr, nullptr,
-                     nullptr);
-  hipLaunchKernelGGL(k_audit_scan, dim3(1), dim3(1024), 0, st, cnt, cells, cylinders, n_cyl, offs, base, n_events);
-  if (d.capacity > 0)
-    hipLaunchKernelGGL(k_audit_sample<true>, g_smp, dim3(AUDIT_WG), 0, st, d, pos, cylinders, cell, cnt, offs, base, events);
+  const int  rings = prm->flags & SOGM_AUDIT_RINGS;
+  if (rings)
+    hipLaunchKernelGGL((k_audit_sample<false, true>), g_smp, dim3(AUDIT_WG), 0, st, d, pos, cylinders, cell, cnt, nullptr,
+                       nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((k_audit_sample<false, false>), g_smp, dim3(AUDIT_WG), 0, st, d, pos, cylinders, cell, cnt, nullptr,
+                       nullptr, nullptr);
+  hipLaunchKernelGGL(k_audit_scan, dim3(1), dim3(1024), 0, st, cnt, cells, cylinders, n_cyl, rings, offs, base, n_events);
+  if (d.capacity > 0) {
+    if (rings)
+      hipLaunchKernelGGL((k_audit_sample<true, true>), g_smp, dim3(AUDIT_WG), 0, st, d, pos, cylinders, cell, cnt, offs, base,
+                         events);
+    else
+      hipLaunchKernelGGL((k_audit_sample<true, false>), g_smp, dim3(AUDIT_WG), 0, st, d, pos, cylinders, cell, cnt, offs, base,
+                         events);
+  }
   hipLaunchKernelGGL(k_audit_fold, dim3((n_local + AUDIT_WG - 1) / AUDIT_WG), dim3(AUDIT_WG), 0, st, d, pos, cell, goals,
                      base, acc);
   const hipError_t e = hipGetLastError();

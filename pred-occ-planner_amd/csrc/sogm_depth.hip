@@ -6,9 +6,14 @@
 //                   first, so no cylinder is ever dropped — then every lane walks the list for its 8 pixels and keeps the
 //                   smallest accepted t of each, and stores 16 B of depth and 6 x 16 B of cloud (scalar stores for row
 //                   tails and for pieces that are not 16-byte aligned).
+// k_render_depth<true> (SOGM_DEPTH_RINGS) also draws the valid type-2 records ("ring obstacles"): they take the same
+// cull-and-compact trip into a second LDS list beside the cylinders' (both are rendered and emptied when either would
+// overflow) and every lane runs sogm_ring.hpp's ring_ray_hit for its pixels.  k_render_depth<false> is the kernel without
+// any of that.
 // The header's arithmetic is evaluated as written (fp64, -ffp-contract=off).  What is NOT evaluated is skipped only where
 // the header's own expressions cannot yield an accepted t <= max_depth; each skip says why next to it.
 #include "sogm_device.hpp"
+#include "sogm_ring.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -40,6 +45,12 @@ struct DepthArgs {
 
 struct Ray {
   double d0, d1, d2, a;  // direction and a = d0*d0 + d1*d1
+};
+
+// LDS of the ring instantiation (the other one gets a single entry it never touches)
+template <bool RINGS>
+struct RingList {
+  static constexpr int CAP = RINGS ? DEPTH_CAP : 1;
 };
 
 __device__ inline void keep_min(double t, double &best) {
@@ -95,9 +106,12 @@ __device__ inline Ray make_ray(const double *R, double xc, double yc) {
   return r;
 }
 
+template <bool RINGS>
 __global__ __launch_bounds__(DEPTH_WG) void k_render_depth(DepthArgs g) {
   __shared__ DepthCand s_list[DEPTH_CAP];
+  __shared__ RingCand  s_ring[RingList<RINGS>::CAP];
   __shared__ int       s_wave_n[DEPTH_WG / 64];
+  __shared__ int       s_wave_r[DEPTH_WG / 64];
   __shared__ int       s_unsupported;
 
   const SogmDepthCamera &cam = g.cam;
@@ -125,33 +139,67 @@ __global__ __launch_bounds__(DEPTH_WG) void k_render_depth(DepthArgs g) {
                               fmax(make_ray(R, x_lo, y_hi).a, make_ray(R, x_hi, y_hi).a));
     reach = cam.max_depth * sqrt(a_max) * (1.0 + 1e-6);
   }
+  // The same in three dimensions, for the rings: a point with t <= max_depth is t |d| from the camera, and |d|^2 = a + d2^2
+  // is convex in (xc, yc) as well.
+  double reach3 = 0;
+  if (RINGS) {
+    const double x_lo = (0.0 - cam.cx) / cam.fx, x_hi = ((double)(cam.cols - 1) - cam.cx) / cam.fx;
+    const double y_lo = (0.0 - cam.cy) / cam.fy, y_hi = ((double)(cam.rows - 1) - cam.cy) / cam.fy;
+    double       m = 0;
+    for (int e = 0; e < 4; ++e) {
+      const Ray r = make_ray(R, e & 1 ? x_hi : x_lo, e & 2 ? y_hi : y_lo);
+      m           = fmax(m, r.a + r.d2 * r.d2);
+    }
+    reach3 = cam.max_depth * sqrt(m) * (1.0 + 1e-6);
+  }
 
   double best[DEPTH_PX];
 #pragma unroll
   for (int k = 0; k < DEPTH_PX; ++k) best[k] = INFINITY;
 
   // every live lane: its pixels against the first n entries of the list
-  auto render_list = [&](int n) {
-    if (n == 0) return;
+  auto render_list = [&](int n, int n_ring) {
+    if (n == 0 && n_ring == 0) return;
 #pragma unroll
     for (int k = 0; k < DEPTH_PX; ++k) {
       if (k >= npx) continue;
       const Ray r = make_ray(R, ((double)(u0 + k) - cam.cx) / cam.fx, yc);
       double    t = best[k];
       for (int j = 0; j < n; ++j) hit_cylinder(s_list[j], r, pz, t_reach, t);
+      if (RINGS) {
+        const double d[3] = {r.d0, r.d1, r.d2};
+        for (int j = 0; j < n_ring; ++j) {
+          // a hit that is not below the pixel's t so far, or beyond the camera's range, cannot change the image
+          double th;
+          if (ring_ray_hit(s_ring[j], d, fmin(t, t_reach), th)) keep_min(th, t);
+        }
+      }
       best[k] = t;
     }
   };
 
   if (tid == 0) s_unsupported = 0;
-  int n_list = 0, n_other = 0;
+  int n_list = 0, n_ring = 0, n_other = 0;
   for (int c0 = 0; c0 < g.n_cyl; c0 += DEPTH_WG) {
     const int i    = c0 + tid;
-    bool      keep = false;
+    bool      keep = false, keep_ring = false;
     DepthCand q{};
+    RingCand  qr{};
     if (i < g.n_cyl) {
       const SogmCylinder &o = g.cyl[i];
-      if (o.type != 3) {
+      if (RINGS && o.type == 2) {
+        RingFrame f;
+        if (!ring_frame(o, f)) {
+          ++n_other;  // not a ring: counted, not drawn
+        } else {
+          const double c[3] = {o.x, o.y, o.z}, p[3] = {px, py, pz};
+          qr = ring_ray_prepare(f, c, p);
+          // a hit point lies within R + rho of the centre (the bounding sphere the rule starts from) and within `reach3`
+          // of the camera; 1e-6 as for the cylinders
+          const double far = reach3 + (f.R + f.rho) * (1.0 + 1e-6);
+          keep_ring        = qr.gamma <= far * far;
+        }
+      } else if (o.type != 3) {
         ++n_other;
       } else {
         const double r = 0.5 * o.w;
@@ -168,7 +216,9 @@ __global__ __launch_bounds__(DEPTH_WG) void k_render_depth(DepthArgs g) {
       }
     }
     const unsigned long long mask = __ballot(keep);
+    const unsigned long long mask_r = RINGS ? __ballot(keep_ring) : 0ull;
     if (lane == 0) s_wave_n[wave] = __popcll(mask);
+    if (RINGS && lane == 0) s_wave_r[wave] = __popcll(mask_r);
     __syncthreads();
     int before = 0, total = 0;
 #pragma unroll
@@ -176,16 +226,29 @@ __global__ __launch_bounds__(DEPTH_WG) void k_render_depth(DepthArgs g) {
       before += w < wave ? s_wave_n[w] : 0;
       total += s_wave_n[w];
     }
-    if (n_list + total > DEPTH_CAP) {  // (uniform) render what is listed, start an empty list: total <= DEPTH_WG fits
-      render_list(n_list);
-      n_list = 0;
+    int before_r = 0, total_r = 0;
+    if (RINGS) {
+#pragma unroll
+      for (int w = 0; w < DEPTH_WG / 64; ++w) {
+        before_r += w < wave ? s_wave_r[w] : 0;
+        total_r += s_wave_r[w];
+      }
+    }
+    // (uniform) render what is listed, start empty lists: a trip's survivors, total + total_r <= DEPTH_WG, fit either
+    if (n_list + total > DEPTH_CAP || (RINGS && n_ring + total_r > DEPTH_CAP)) {
+      render_list(n_list, n_ring);
+      n_list = n_ring = 0;
       __syncthreads();
     }
     if (keep) s_list[n_list + before + __popcll(mask & ((1ull << lane) - 1ull))] = q;
     n_list += total;
+    if (RINGS) {
+      if (keep_ring) s_ring[n_ring + before_r + __popcll(mask_r & ((1ull << lane) - 1ull))] = qr;
+      n_ring += total_r;
+    }
     __syncthreads();
   }
-  render_list(n_list);
+  render_list(n_list, n_ring);
 
   if (wg == 0) {  // one workgroup per agent reports the records of another type
     if (n_other) atomicAdd(&s_unsupported, n_other);
@@ -296,7 +359,10 @@ extern "C" int sogm_render_depth(const SogmWorld *world, const SogmDepthCamera *
   g.depth            = out_depth;
   g.cloud            = out_cloud_xyz;
   g.unsupported      = out_unsupported;
-  hipLaunchKernelGGL(k_render_depth, dim3((unsigned)(wgs * n_agents)), dim3(DEPTH_WG), 0, (hipStream_t)stream, g);
+  if (cam->flags & SOGM_DEPTH_RINGS)
+    hipLaunchKernelGGL(k_render_depth<true>, dim3((unsigned)(wgs * n_agents)), dim3(DEPTH_WG), 0, (hipStream_t)stream, g);
+  else
+    hipLaunchKernelGGL(k_render_depth<false>, dim3((unsigned)(wgs * n_agents)), dim3(DEPTH_WG), 0, (hipStream_t)stream, g);
   SOGM_HIP_CHECK(hipGetLastError());
   return SOGM_OK;
 }

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._abi import SogmDepthCamera, check, lib
+from ._abi import SOGM_DEPTH_RINGS, SogmDepthCamera, check, lib
 from .gridmap import make_gridmap_params
 from .sogm import _dev, _stream
 
@@ -23,11 +23,16 @@ def make_depth_camera(rows=480, cols=640, max_depth=5.0, depth_scale=1000.0, gro
     return cam
 
 
-def render_depth(world, cam, cam_pos, cam_rot, want_cloud=True):
+def render_depth(world, cam, cam_pos, cam_rot, want_cloud=True, rings=False):
     """world: sogm.World; cam_pos [A, 3], cam_rot [A, 9] (or [A, 3, 3]) fp64, row-major camera-to-world (scene.camera_pose).
     Returns device tensors (depth [A, rows, cols] int16 storage of the uint16 image, cloud [A*rows*cols, 3] float32 with
     NaN where there is no return — None unless want_cloud —, raw_range [A, 2] int32, unsupported [A] int32: the
-    world's records of a type other than 3, which are not drawn).  Stream-ordered, no synchronisation."""
+    world's records that are not drawn: with rings=False every type other than 3; with rings=True the valid type-2 records
+    are drawn as rings (include/sogm_abi.h "ring obstacles") and only what is left is counted).  Stream-ordered, no
+    synchronisation."""
+    if bool(cam.flags & SOGM_DEPTH_RINGS) != bool(rings):   # the caller's camera is not changed
+        cam = SogmDepthCamera.from_buffer_copy(cam)
+        cam.flags = (cam.flags | SOGM_DEPTH_RINGS) if rings else (cam.flags & ~SOGM_DEPTH_RINGS)
     dev = world.cylinders.device
     pos = _dev(np.asarray(cam_pos, np.float64) if not isinstance(cam_pos, torch.Tensor) else cam_pos, None, dev)
     rot = _dev(np.asarray(cam_rot, np.float64) if not isinstance(cam_rot, torch.Tensor) else cam_rot, None, dev)

@@ -293,7 +293,11 @@ class HipCompute:
         w = self._frames.get(key)
         if w is None:
             f = self.timeline.frame(key)
-            w = self._frames[key] = World(f["cloud"], f["cylinders"])
+            if "rings" in f:
+                arr, n = self.timeline.records(key)
+                w = self._frames[key] = World(f["cloud"], arr, n_cyl=n)
+            else:
+                w = self._frames[key] = World(f["cloud"], f["cylinders"])
         return w
 
     def _timeline_dev(self, n):
@@ -408,7 +412,7 @@ class SwarmTick:
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
                  moving_world=None, neighbour_lag=1, audit=False, device_fsm=False, traj_server=None, device_world=None,
-                 world_pool=None):
+                 world_pool=None, n_rings=0):
         self.rank, self.world, self.dist = rank, world, dist
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
@@ -419,7 +423,8 @@ class SwarmTick:
         self.A_loc = agents_per_rank if agents_per_rank is not None else config.AGENTS.get(grid, 4)
         self.A_tot = self.A_loc * world
         half = (self.spec.L // 2) * 0.15
-        self.scene = scene if scene is not None else scene_mod.make_scene(self.A_tot, half, seed=seed)
+        # n_rings > 0: the scene also has that many ring obstacles (scene.make_scene); the audit then audits them
+        self.scene = scene if scene is not None else scene_mod.make_scene(self.A_tot, half, seed=seed, n_rings=int(n_rings))
         lo, hi = shard_bounds(rank, world, self.A_loc)
         if world > 1 and compute is None and dist is not None and "flight_engines" not in (tuning or {}) \
                 and "flight_exchange_units" not in (tuning or {}):
@@ -497,8 +502,12 @@ class SwarmTick:
         if audit:
             from .audit import SwarmAudit
             tl = getattr(c, "timeline", None) or scene_mod.WorldTimeline(self.scene, TICK_PERIOD, moving=False)
-            self.auditor = SwarmAudit(self.A_tot, self.scene["goals"][lo:hi], self.scene["starts"], tl.cylinders(0),
-                                      self.t0, agent0=lo, n_local=self.A_loc, moving=tl.moving, device=d)
+            if getattr(tl, "rings0", None) is not None:
+                self.auditor = SwarmAudit(self.A_tot, self.scene["goals"][lo:hi], self.scene["starts"], tl.records(0)[0],
+                                          self.t0, agent0=lo, n_local=self.A_loc, moving=tl.moving, device=d, rings=True)
+            else:
+                self.auditor = SwarmAudit(self.A_tot, self.scene["goals"][lo:hi], self.scene["starts"], tl.cylinders(0),
+                                          self.t0, agent0=lo, n_local=self.A_loc, moving=tl.moving, device=d)
 
         # trajectory server (trajserver.py): the same executed tables -> every agent's 100 Hz position commands with yaw.
         # traj_server: None / False (off), True (the launched server's parameters) or a SogmTrajServerParams

@@ -90,16 +90,46 @@ def add_rings(scene, rings, first=True):
         c.x, c.y, c.z, c.w, c.h = x, y, z, w, 0.1
         c.vx, c.vy = vx, vy
         c.qw, c.qx, c.qy, c.qz = qw, qx, qy, qz
-        q = np.array([qw, qx, qy, qz])
-        R = _quat_to_matrix(q / np.linalg.norm(q))
-        r = 0.5 * w
-        n_seg = max(8, int(math.ceil(2.0 * math.pi * r / 0.1)))
-        th = np.arange(n_seg) * (2.0 * math.pi / n_seg)
-        for dr in (-0.1, 0.0, 0.1):
-            for dn in (-0.1, 0.0, 0.1):
-                local = np.stack([(r + dr) * np.cos(th), (r + dr) * np.sin(th), np.full_like(th, dn)], axis=1)
-                pts.append((local @ R.T + np.array([x, y, z])).astype(np.float32))
+        pts += ring_points(x, y, z, w, (qw, qx, qy, qz))
     scene["cloud"] = np.ascontiguousarray(np.concatenate(pts, axis=0), np.float32)
+    return arr, n
+
+
+RING_TUBE = 0.1   # SogmCylinder.h of a ring record: the half width of the 3 x 3 tube section below, the tube radius of
+#                   include/sogm_abi.h "ring obstacles"
+
+
+def ring_points(x, y, z, w, q):
+    """the cloud points of one ring: its circle at 0.10 m spacing, a 3 x 3 tube section (nine float32 arrays [n_seg, 3])"""
+    q = np.array(q, np.float64)
+    R = _quat_to_matrix(q / np.linalg.norm(q))
+    r = 0.5 * w
+    n_seg = max(8, int(math.ceil(2.0 * math.pi * r / 0.1)))
+    th = np.arange(n_seg) * (2.0 * math.pi / n_seg)
+    out = []
+    for dr in (-0.1, 0.0, 0.1):
+        for dn in (-0.1, 0.0, 0.1):
+            local = np.stack([(r + dr) * np.cos(th), (r + dr) * np.sin(th), np.full_like(th, dn)], axis=1)
+            out.append((local @ R.T + np.array([x, y, z])).astype(np.float32))
+    return out
+
+
+def records_to_struct(cyl, rings=None):
+    """The SogmCylinder array of a frame: the cylinders (n, 5) {x, y, w, vx, vy} as cylinders_to_struct makes them, then
+    the rings (m, 10) {x, y, z, w, vx, vy, qw, qx, qy, qz} as type 2 with h = RING_TUBE.  Returns (array, count)."""
+    cyl = np.asarray(cyl, np.float64).reshape(-1, 5)
+    rings = np.zeros((0, 10)) if rings is None else np.asarray(rings, np.float64).reshape(-1, 10)
+    n = len(cyl) + len(rings)
+    arr = (SogmCylinder * max(n, 1))()
+    base = cylinders_to_struct(cyl)
+    for i in range(len(cyl)):
+        C.memmove(C.addressof(arr[i]), C.addressof(base[i]), C.sizeof(SogmCylinder))
+    for i, (x, y, z, w, vx, vy, qw, qx, qy, qz) in enumerate(rings):
+        c = arr[len(cyl) + i]
+        c.type = 2
+        c.x, c.y, c.z, c.w, c.h = x, y, z, w, RING_TUBE
+        c.vx, c.vy = vx, vy
+        c.qw, c.qx, c.qy, c.qz = qw, qx, qy, qz
     return arr, n
 
 
@@ -111,11 +141,15 @@ def _quat_to_matrix(q):
 
 
 def make_scene(n_agents, half_range, seed, moving=True, n_cyl=None, circle_radius=None,
-               tick_time=100.0):
+               tick_time=100.0, n_rings=0):
     """Returns a dict of numpy arrays.
 
     half_range: map half extent in metres (grid L/2 * 0.15) — used to size the field so every
     agent's window is populated.
+    n_rings > 0: also `rings` (n_rings, 10) {x, y, z, w, vx, vy, qw, qx, qy, qz}, placed by a generator of their own in the
+    cylinders' annulus (the cylinders and everything else are what n_rings = 0 gives), alternately upright and tilted,
+    moving in xy; their circle points are appended to the cloud with owners n_cyl + ring index — the ring's index in the
+    frame's records (records_to_struct: cylinders first, then rings).
     """
     rng = SplitMix64(seed)
     # agents evenly on a circle, >= 1.5 m apart, antipodal goals, z = 1
@@ -189,7 +223,41 @@ def make_scene(n_agents, half_range, seed, moving=True, n_cyl=None, circle_radiu
     cloud = (np.concatenate(pts, axis=0) if pts else np.zeros((0, 3))).astype(np.float32)
     cloud_cyl = np.concatenate(owner) if owner else np.zeros((0,), np.int32)
 
-    return {
+    rings = None
+    if n_rings > 0:
+        rrng = SplitMix64(seed ^ 0x52494E47)   # "RING": the cylinders' sequence is not consumed
+        rows, guard = [], 0
+        while len(rows) < n_rings and guard < 50 * n_rings + 1000:
+            guard += 1
+            rho = math.sqrt(rrng.uniform(r_lo ** 2, r_hi ** 2))
+            ang = rrng.uniform(0.0, 2.0 * math.pi)
+            x, y, z = rho * math.cos(ang), rho * math.sin(ang), rrng.uniform(0.9, 1.5)
+            w = rrng.uniform(1.2, 2.0)
+            speed = rrng.uniform(0.0, 0.1) * (10.0 if moving else 0.0)
+            head = rrng.uniform(0.0, 2.0 * math.pi)
+            yaw = rrng.uniform(0.0, 2.0 * math.pi)
+            tilt = [rrng.uniform(-1.0, 1.0) for _ in range(4)]
+            if float(np.min(np.hypot(pts_sg[:, 0] - x, pts_sg[:, 1] - y))) < 1.0 + 0.5 * w + 0.6:
+                continue
+            if len(rows) % 2 == 0:   # upright: the ring's normal is horizontal, at heading yaw
+                cy_, sy_, h = math.cos(0.5 * yaw), math.sin(0.5 * yaw), math.sqrt(0.5)
+                q = (cy_ * h, cy_ * h, sy_ * h, sy_ * h)      # yaw about z after a quarter turn about x
+            else:
+                nrm = math.sqrt(sum(v * v for v in tilt))
+                if nrm < 0.1:
+                    continue
+                q = tuple(v / nrm for v in tilt)
+            rows.append((x, y, z, w, speed * math.cos(head), speed * math.sin(head)) + q)
+        rings = np.asarray(rows, dtype=np.float64).reshape(-1, 10)
+        rp, ro = [cloud], [cloud_cyl]
+        for ri, (x, y, z, w, _, _, qw, qx, qy, qz) in enumerate(rings):
+            p9 = ring_points(x, y, z, w, (qw, qx, qy, qz))
+            rp += p9
+            ro.append(np.full((sum(len(a) for a in p9),), len(cyl) + ri, np.int32))
+        cloud = np.concatenate(rp, axis=0).astype(np.float32)
+        cloud_cyl = np.concatenate(ro)
+
+    out = {
         "n_agents": n_agents,
         "cloud": np.ascontiguousarray(cloud),
         "cloud_cyl": cloud_cyl,      # the cylinder every cloud point was sampled from (WorldTimeline moves it along)
@@ -201,6 +269,9 @@ def make_scene(n_agents, half_range, seed, moving=True, n_cyl=None, circle_radiu
         "ego_ids": np.arange(n_agents, dtype=np.int32),
         "circle_radius": circle_radius,
     }
+    if rings is not None:
+        out["rings"] = rings
+    return out
 
 
 class WorldTimeline:
@@ -213,11 +284,15 @@ class WorldTimeline:
     its cloud points — contiguous runs of the cloud — moved with it.  Pure numpy, a function of (scene, k): the oracle
     flights of the tests and the device uploads of the driver use the same arrays.
     moving=False: every frame is the scene at tick 0 (the frozen world of the earlier rounds, kept for the tests that
-    compare single builds)."""
+    compare single builds).
+    A scene with rings (make_scene(n_rings=...)): the ring rows move the same way, their cloud points are owned by record
+    index n_cyl + i, and frame(k) carries them as "rings"; records(k) is the frame's SogmCylinder array."""
 
     def __init__(self, scene, dt=0.1, moving=True):
         self.scene, self.dt, self.moving = scene, float(dt), bool(moving)
         self.cyl0 = np.asarray(scene["cylinders"], np.float64).reshape(-1, 5)
+        r0 = scene.get("rings")
+        self.rings0 = None if r0 is None or not len(r0) else np.asarray(r0, np.float64).reshape(-1, 10)
         self.cloud0 = np.ascontiguousarray(scene["cloud"], np.float32)
         self.owner = scene.get("cloud_cyl")
         if self.moving and (self.owner is None or len(self.owner) != len(self.cloud0)):
@@ -238,6 +313,8 @@ class WorldTimeline:
             return self.cloud0
         t = float(k) * self.dt
         off = (self.cyl0[:, 3:5] * t).astype(np.float32)          # per cylinder
+        if self.rings0 is not None:                                # then per ring: the records' order
+            off = np.concatenate([off, (self.rings0[:, 4:6] * t).astype(np.float32)], axis=0)
         out = self.cloud0.copy()
         owner = np.asarray(self.owner)
         owned = (owner >= 0) & (owner < len(off))
@@ -247,8 +324,26 @@ class WorldTimeline:
             out[owned, :2] += off[owner[owned]]
         return out
 
+    def rings(self, k):
+        """(m, 10) ring rows at tick k (x, y advance as a cylinder's), or None for a scene without rings"""
+        if self.rings0 is None:
+            return None
+        r = self.rings0.copy()
+        if self.moving:
+            t = float(k) * self.dt
+            r[:, 0] = self.rings0[:, 0] + self.rings0[:, 4] * t
+            r[:, 1] = self.rings0[:, 1] + self.rings0[:, 5] * t
+        return r
+
+    def records(self, k):
+        """(SogmCylinder array, count) of tick k: cylinders first, then rings"""
+        return records_to_struct(self.cylinders(k), self.rings(k))
+
     def frame(self, k):
-        return {"cloud": self.cloud(k), "cylinders": self.cylinders(k)}
+        f = {"cloud": self.cloud(k), "cylinders": self.cylinders(k)}
+        if self.rings0 is not None:
+            f["rings"] = self.rings(k)
+        return f
 
 
 def straight_records(scene, speed=1.0, t_start=None, n_pieces=6, piece_dur=0.3):

@@ -368,6 +368,10 @@ class WorldTimelineDev:
     @classmethod
     def from_timeline(cls, tl, **kw):
         """from a scene.WorldTimeline"""
+        if getattr(tl, "rings0", None) is not None:
+            from .scene import records_to_struct
+            arr, n = records_to_struct(tl.cyl0, tl.rings0)      # cylinders first, then rings: the owners' indices
+            return cls(tl.cloud0, tl.owner, arr, tl.dt, n_cyl=n, moving=tl.moving, **kw)
         return cls(tl.cloud0, tl.owner, tl.cyl0, tl.dt, moving=tl.moving, **kw)
 
     @property
@@ -407,13 +411,16 @@ def upload_scene(scene, device="cuda", cloud=None, cloud_range=None):
     A = scene["n_agents"]
     pts = scene["cloud"] if cloud is None else cloud
     n_pts = pts.shape[0]
-    cyl = cylinders_to_struct(scene["cylinders"])
+    cyl, n_rec = cylinders_to_struct(scene["cylinders"]), int(len(scene["cylinders"]))
+    if scene.get("rings") is not None:
+        from .scene import records_to_struct
+        cyl, n_rec = records_to_struct(scene["cylinders"], scene["rings"])
     rng = np.tile(np.asarray([[0, n_pts]], dtype=np.int32), (A, 1)) if cloud_range is None else cloud_range
     return {
         "cloud": _dev(pts if n_pts else np.zeros((1, 3), np.float32), np.float32, device),
         "cloud_range": _dev(rng, np.int32, device),
         "cylinders": _dev(cyl, None, device),
-        "n_cyl": int(len(scene["cylinders"])),
+        "n_cyl": n_rec,
         "poses": _dev(scene["poses"], np.float32, device),
         "stamps": _dev(scene["stamps"], np.float64, device),
         "ego_ids": _dev(scene["ego_ids"], np.int32, device),

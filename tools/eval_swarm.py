@@ -1,7 +1,10 @@
 """Fly a swarm with the flight audit on and print ONE JSON line: the audit's report (arrivals, collisions of each kind,
 minimum separation and gap) and its cost.
 
-    python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight|flight_fsm [--frozen] [--events N]
+    python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight|flight_fsm [rings] [--frozen] [--events N]
+
+rings (optional, default 0): that many ring obstacles in the scene (scene.make_scene(n_rings=...)), audited as rings; the
+report then also has ring_agents / ring_samples / min_ring_gap, counted from the event list and the per-agent minima.
 
 flight_fsm: the flight with every agent-tick one FSMCallback on the device (sogm_planner_set_flight_fsm) — the closed loop
 of `fsm` on the schedule of `flight`.
@@ -23,7 +26,8 @@ def run(driver, args, audit):
     import torch
     flight = args.mode in ("flight", "flight_fsm")
     sw = driver.SwarmTick(args.grid, args.agents, moving_world=not args.frozen, prestamp=False if flight else None,
-                          fsm=args.mode in ("fsm", "flight_fsm"), device_fsm=args.mode == "flight_fsm", audit=audit)
+                          fsm=args.mode in ("fsm", "flight_fsm"), device_fsm=args.mode == "flight_fsm", audit=audit,
+                          n_rings=args.rings)
     sw.compute.prepare(0, args.ticks)
     audit_ms = []
     if audit:   # time every audit call with events of its own on the same stream
@@ -52,6 +56,16 @@ def run(driver, args, audit):
     torch.cuda.synchronize()
     ms = start.elapsed_time(end) / args.ticks
     rep = sw.audit_report() if audit else None
+    if audit and args.rings:
+        # the ring column: the records after the cylinders are the rings; per (sample, agent) collisions from the events
+        # (complete only when the list was not truncated), the smallest gap among the agents whose nearest obstacle is a ring
+        n_cyl = len(sw.scene["cylinders"])
+        ev = [e for e in rep["events"] if e[3] == 1 and e[2] >= n_cyl]
+        acc = sw.auditor.per_agent()
+        near = acc["min_gap_obstacle"] >= n_cyl
+        rep.update(rings=args.rings, ring_agents=len({e[1] for e in ev}), ring_samples=len({(e[0], e[1]) for e in ev}),
+                   ring_events_complete=not rep["events_truncated"],
+                   min_ring_gap_where_nearest=float(acc["min_gap"][near].min()) if near.any() else None)
     a_ms = sum(e0.elapsed_time(e1) for e0, e1 in audit_ms) / args.ticks if audit else None
     sw.close()
     return ms, rep, a_ms
@@ -63,6 +77,7 @@ def main():
     ap.add_argument("agents", type=int)
     ap.add_argument("ticks", type=int)
     ap.add_argument("mode", choices=("lockstep", "fsm", "flight", "flight_fsm"))
+    ap.add_argument("rings", type=int, nargs="?", default=0, help="ring obstacles in the scene (default 0)")
     ap.add_argument("--frozen", action="store_true", help="a frozen world (moving_world=False)")
     ap.add_argument("--events", type=int, default=20, help="events printed (the report counts all)")
     args = ap.parse_args()
