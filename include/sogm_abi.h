@@ -668,6 +668,58 @@ int sogm_render_depth(const SogmWorld *world, const SogmDepthCamera *cam, int n_
                       uint16_t *out_depth /* dev [n*rows*cols] */, float *out_cloud_xyz /* dev [n*rows*cols*3] or NULL */,
                       int32_t *out_unsupported /* dev [n]: records that are not drawn */, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* agent bodies: the other vehicles of a swarm as the depth camera sees them, and a per-pixel   */
+/*   hit index.  The reference has no camera (above); a vehicle is what the flight audit below   */
+/*   already takes it for, the axis-aligned box body[] (0.4 x 0.4 x 0.45, sim_fake.yaml:85-87).  */
+/*   The build's OWN definition, held by two independent implementations                         */
+/*   (csrc/sogm_body.hpp; tests/depth_bodies_reference.py), bit for bit.                         */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * All arithmetic is fp64, in exactly the order written, one IEEE operation at a time (+ - * /), without contraction.
+ * Here min(x, y) is x if x < y, else y; max(x, y) is x if x > y, else y.
+ *
+ * Geometry: body j is the axis-aligned box of size size[3] centred at b = body_pos[j]:
+ *     half_i = 0.5*size_i;  lo_i = b_i - half_i;  hi_i = b_i + half_i        i = 0, 1, 2
+ *   This is the audit's box.  Yaw does not turn it, as it does not in the audit.
+ * Not a body: if any of the three coordinates b_i is not finite, the body is not drawn.  It is counted per camera in
+ *   out_unsupported, together with the world's undrawn records.
+ * Own body: camera a skips body cam_body[a].  It is neither drawn nor counted.  cam_body == NULL means cam_body[a] = a.
+ *   A value outside [0, n_bodies) means "this camera is carried by no body" and nothing is skipped.
+ * Ray against body: the ray is p + t d, where t is the camera's z-depth parameter and d is as in "depth camera".
+ *   Start with tn = -inf, tf = +inf.  For i = 0, 1, 2:
+ *     if d_i == 0:  no hit unless lo_i <= p_i && p_i <= hi_i.
+ *     otherwise:    ta = (lo_i - p_i)/d_i;  tb = (hi_i - p_i)/d_i;  tn = max(tn, min(ta, tb));  tf = min(tf, max(ta, tb))
+ *   No hit unless tn <= tf.
+ *   The accepted t is tn if tn > 0.  Otherwise it is tf if tf > 0: a camera inside another vehicle's box sees its inner
+ *   wall, as it does a cylinder's.  Otherwise there is no hit.
+ * The image stays a minimum over everything accepted — cylinder sides, caps, rings when SOGM_DEPTH_RINGS is set, bodies,
+ *   ground.  It still depends on neither order nor culling.  Quantisation and the cloud are unchanged.
+ * Hit index (out_hit, int32 per pixel, optional): SOGM_HIT_NONE when d16 == 0.  Otherwise the code of what gave t*:
+ *   record i of the world -> i;  body j -> n_cyl + j;  the ground -> SOGM_HIT_GROUND.  Among equal t the winner is the
+ *   lowest record index, then the lowest body index, then the ground: the code is that of the smallest (t, code) pair
+ *   over records and bodies, and the ground wins only with a strictly smaller t.  It does not depend on the order in which
+ *   an implementation visits records and bodies.
+ */
+enum { SOGM_HIT_GROUND = -1, SOGM_HIT_NONE = -2 };
+typedef struct SogmDepthBodies {
+  const double  *pos;       /* dev [n_bodies*3] fp64 */
+  const int32_t *cam_body;  /* dev [n_agents] or NULL */
+  double         size[3];   /* 0.4 0.4 0.45 */
+  int32_t        n_bodies, reserved_;
+} SogmDepthBodies;          /* 48 bytes */
+/*
+ * sogm_render_depth with the bodies drawn and, when out_hit is given, the hit index.  bodies == NULL: none (the images are
+ * sogm_render_depth's).  Context-free, stream-ordered, no allocation, no host synchronisation, like sogm_render_depth.
+ * dev out_hit [n*rows*cols] int32 or NULL; every other array as in sogm_render_depth.
+ * SOGM_ERR_INVALID_ARG: sogm_render_depth's refusals, checked first; then n_bodies < 0, n_bodies > 0 with a null pos, a
+ * size[i] that is not finite or not > 0.  SOGM_ERR_NO_DEVICE without a GPU.
+ */
+int sogm_render_depth_swarm(const SogmWorld *world, const SogmDepthCamera *cam, const SogmDepthBodies *bodies /* NULL: none */,
+                            int n_agents, const double *cam_pos, const double *cam_rot, uint16_t *out_depth,
+                            float *out_cloud_xyz /* or NULL */, int32_t *out_hit /* dev [n*rows*cols] or NULL */,
+                            int32_t *out_unsupported, void *stream);
+
 /*
  * Tick glue of a batched planner service, each ONE launch (the FSM bookkeeping around replan()):
  * sogm_tick_inputs — the replan start state of every agent: its executing trajectory own_records[a] sampled at

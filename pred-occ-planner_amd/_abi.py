@@ -72,6 +72,11 @@ class SogmDepthCamera(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32), ("use_ground", C.c_int32), ("flags", C.c_int32)]
 
 
+class SogmDepthBodies(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("cam_body", C.c_void_p), ("size", C.c_double * 3),
+                ("n_bodies", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class SogmCylinder(C.Structure):
     _fields_ = [("type", C.c_int32), ("_pad", C.c_int32)] + [
         (k, C.c_double) for k in ("x", "y", "z", "w", "h", "vx", "vy", "qw", "qx", "qy", "qz")]
@@ -211,6 +216,8 @@ FLIGHT_STAT_NAMES = ("gate_wait", "map", "search", "corridor", "qp", "finish", "
 TRAJ_RECORD_BYTES = C.sizeof(SogmTrajRecord)  # 2064
 CYLINDER_BYTES = C.sizeof(SogmCylinder)  # 96
 DEPTH_CAMERA_BYTES = C.sizeof(SogmDepthCamera)  # 72
+DEPTH_BODIES_BYTES = C.sizeof(SogmDepthBodies)  # 48
+SOGM_HIT_GROUND, SOGM_HIT_NONE = -1, -2   # out_hit of sogm_render_depth_swarm
 
 
 class SogmTrajServerState(C.Structure):
@@ -299,6 +306,8 @@ PROTOTYPES = {
     "sogm_gridmap_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_query_inflate": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "sogm_render_depth": (_i, [C.POINTER(SogmWorld), C.POINTER(SogmDepthCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sogm_render_depth_swarm": (_i, [C.POINTER(SogmWorld), C.POINTER(SogmDepthCamera), C.POINTER(SogmDepthBodies), _i, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_download": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_force_frame": (_i, [_vp, _i]),
     "sogm_traj_safe": (_i, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

@@ -323,6 +323,15 @@ class GridMap {
                           hipStream_t st = nullptr) {
     check(sogm_render_depth(&frame, &cam, n_agents, cam_pos, cam_rot, depth, cloud_xyz, unsupported, st), "sogm_render_depth");
   }
+  // The same with the other vehicles drawn (sogm_abi.h "agent bodies"): bodies (nullptr: none) holds the box centres, the
+  // body that carries each camera and the box's size; hit [n rows cols] (may be nullptr) gets per pixel the record index,
+  // n_cyl + the body's index, SOGM_HIT_GROUND or SOGM_HIT_NONE.  unsupported also counts bodies with a non-finite centre.
+  static void renderDepthSwarm(const SogmWorld &frame, const SogmDepthCamera &cam, const SogmDepthBodies *bodies, int n_agents,
+                               const double *cam_pos, const double *cam_rot, uint16_t *depth, float *cloud_xyz, int32_t *hit,
+                               int32_t *unsupported, hipStream_t st = nullptr) {
+    check(sogm_render_depth_swarm(&frame, &cam, bodies, n_agents, cam_pos, cam_rot, depth, cloud_xyz, hit, unsupported, st),
+          "sogm_render_depth_swarm");
+  }
   // int getInflateOccupancy(Eigen::Vector3d pos) for a batch of device-resident queries
   void getInflateOccupancy(const int32_t *agent_idx, const double *pos, int n, int8_t *out, hipStream_t st = nullptr) {
     check(sogm_gridmap_query_inflate(h_, agent_idx, pos, n, out, st), "sogm_gridmap_query_inflate");

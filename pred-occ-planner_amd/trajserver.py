@@ -4,7 +4,7 @@ publishes, from the tables the agents execute (sogm_traj_server_run).
 
 TrajServer keeps the states and the rings on the device; run() queues one call per batch of executed tables and never
 synchronises; commands / states() read the result back; camera_poses() turns commands into the camera poses
-sogm_render_depth takes, on the device."""
+sogm_render_depth takes, on the device, and body_positions() into the box centres sogm_render_depth_swarm takes."""
 import ctypes as C
 import math
 
@@ -125,3 +125,12 @@ class TrajServer:
         rc = _abi.lib().sogm_camera_poses(first.data_ptr(), n, k, c2b, off, pos.data_ptr(), rot.data_ptr(), _stream())
         _abi.check(rc, "sogm_camera_poses")
         return pos, rot
+
+    def body_positions(self, sample=-1, cmd=None):
+        """The commanded positions of every agent at command `sample` of the last call (or of `cmd`, uint8 [n][k][112]): an
+        fp64 device tensor [n][3], the body centres depth.render_depth_swarm takes.  A copy made by torch: no kernel of the
+        library's, no host synchronisation."""
+        cmd = self.cmd if cmd is None else cmd
+        k = int(cmd.shape[1])
+        off = COMMAND_DTYPE.fields["pos"][1]
+        return cmd[:, sample % k, off:off + 24].contiguous().view(torch.float64)

@@ -5,7 +5,12 @@ every one is inside the GridMap's 40 x 40 m map.  HIP events on the launch strea
 resident before the first one.  Prints one JSON line.
 
 Three more renders of the same frames say what bounds the kernel: the image alone (the same arithmetic, 2 of the 14 bytes
-per pixel), an empty world with the ground (all 14 bytes, next to no arithmetic), and the full render."""
+per pixel), an empty world with the ground (all 14 bytes, next to no arithmetic), and the full render.
+
+--bodies N renders through sogm_render_depth_swarm ("agent bodies") instead: every camera's own carrier (a 0.4 x 0.4 x 0.45
+box 0.1 m behind and 0.05 m below the camera, not drawn for it) plus N - cameras bystanders hovering inside the circle
+become bodies (N below the number of cameras: only the first N cameras are carried); --bodies 0 is that entry without
+bodies, i.e. the cost of carrying the hit codes.  --hit also asks for the hit image (4 more bytes per pixel)."""
 import argparse, importlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -34,7 +39,18 @@ def camera_ring(pop, A):
             for a, t in enumerate(th)]
 
 
-def run(A, steps=30, warmup=5, rings=0):
+def swarm_bodies(pop, pos, rot, n_bodies):
+    """(body centres [n_bodies, 3], cam_body [A]) of --bodies: carriers first, then bystanders from SplitMix64"""
+    A = len(pos)
+    ahead = rot.reshape(-1, 3, 3)[:, :, 2]
+    carriers = pos - 0.1 * ahead * [1.0, 1.0, 0.0] - [0.0, 0.0, 0.05]
+    rng = pop.scene.SplitMix64(0xB0D1)
+    extra = [[rng.uniform(-11.0, 11.0), rng.uniform(-11.0, 11.0), rng.uniform(0.5, 2.0)] for _ in range(max(n_bodies - A, 0))]
+    bodies = np.concatenate([carriers[:min(n_bodies, A)], np.array(extra, np.float64).reshape(-1, 3)])
+    return bodies, np.array([a if a < n_bodies else -1 for a in range(A)], np.int32)
+
+
+def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False):
     pop = importlib.import_module("pred-occ-planner_amd")
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     gm = importlib.import_module("pred-occ-planner_amd.gridmap")
@@ -68,9 +84,16 @@ def run(A, steps=30, warmup=5, rings=0):
         return {"mean": round(float(ms.mean()), 4), "min": round(float(ms.min()), 4), "max": round(float(ms.max()), 4)}
 
     keep = {}
+    if bodies >= 0:
+        body_h, own_h = swarm_bodies(pop, pos, rot, bodies)
+        body_d, own_d = sogm._dev(body_h, np.float64), sogm._dev(own_h, np.int32)
 
     def render(k, want_cloud=True, world=None):
-        keep["out"] = depth.render_depth(world or worlds[k], cam, pos_d, rot_d, want_cloud, rings=bool(rings))
+        if bodies >= 0:
+            keep["out"] = depth.render_depth_swarm(world or worlds[k], cam, pos_d, rot_d, body_d, own_d, rings=bool(rings),
+                                                   want_cloud=want_cloud, want_hit=hit)[:4]
+        else:
+            keep["out"] = depth.render_depth(world or worlds[k], cam, pos_d, rot_d, want_cloud, rings=bool(rings))
         return keep["out"]
 
     def render_gridmap(k):
@@ -100,6 +123,8 @@ def run(A, steps=30, warmup=5, rings=0):
            "gridmap_update_ms": t_gridmap, "render_then_gridmap_ms": t_rg,
            "filter_ms": t_filter, "render_then_filter_ms": t_rf,
            "gridmap_updated": int(keep["upd"].sum().item()), "filtered_points_agent0": int(keep["flt"][1][0].item())}
+    if bodies >= 0:
+        out.update({"entry": "sogm_render_depth_swarm", "bodies": int(len(body_h)), "hit_image": bool(hit)})
     g.close()
     m.close()
     return out
@@ -111,8 +136,11 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rings", type=int, default=0, help="ring obstacles in the world, drawn (default 0: cylinders only)")
+    ap.add_argument("--bodies", type=int, default=-1, help="render through sogm_render_depth_swarm with N bodies (default: "
+                    "sogm_render_depth, today's run)")
+    ap.add_argument("--hit", action="store_true", help="with --bodies: also ask for the hit image")
     a = ap.parse_args()
     assert a.steps >= 20 and torch.cuda.is_available(), "needs a GPU and at least 20 timed frames"
     print(json.dumps({"workload": "sogm_render_depth, 480x640 per camera, cfg2 moving world (seed 0x5069), cameras on a 12 m "
                                   "circle; ms per frame: HIP events on the launch stream around each call",
-                      "runs": [run(A, a.steps, a.warmup, a.rings) for A in a.agents]}))
+                      "runs": [run(A, a.steps, a.warmup, a.rings, a.bodies, a.hit) for A in a.agents]}))
