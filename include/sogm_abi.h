@@ -720,6 +720,58 @@ int sogm_render_depth_swarm(const SogmWorld *world, const SogmDepthCamera *cam, 
                             float *out_cloud_xyz /* or NULL */, int32_t *out_hit /* dev [n*rows*cols] or NULL */,
                             int32_t *out_unsupported, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* ground-truth labels: the hit index carried through the voxel filter, leaf by leaf, into the   */
+/*   per-point {vx, vy, vz, intensity} labels sogm_update_dsp takes.  The reference's main mode   */
+/*   (FakeParticleRiskVoxel) gives its map ground-truth velocities; this is the same for the      */
+/*   perception path: rendered depth -> filtered cloud with exact labels -> particle SOGM.        */
+/*   The build's OWN definition, held by two independent implementations                         */
+/*   (csrc/sogm_labels.hpp; tests/filter_labels_reference.py), bit for bit.                      */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Label arithmetic is fp32, in exactly the order written, one IEEE operation at a time, without contraction.
+ *
+ * Points: exactly sogm_filter_point_cloud's — the same leaves (leaf index floorf(p * inv_leaf) per axis, fp32), the same
+ *   ascending leaf order, the same axis swap, isInRange and cap, the same out_count (-1 included).  Centroids carry that
+ *   entry's caveat: the fp32 summation order inside a leaf is unspecified, so they agree to 1e-4, not bit for bit.
+ * raw_code[i] is the hit code of raw point i: out_hit of sogm_render_depth_swarm, flattened, in the layout raw_xyz has.
+ * Leaf winner: among the FINITE raw points of a leaf (a point with a coordinate that is not finite is skipped with its
+ *   code), the winner is the one with the smallest camera-frame z — the front-most surface, the one a sensor would
+ *   attribute the leaf to.  z is compared by the order-preserving key of its fp32 bits
+ *     key(f) = bits(f) has its sign bit set ? ~bits(f) : bits(f) | 0x80000000        (unsigned compare)
+ *   so -0 comes before +0.  Among equal z the LARGEST code wins: a body over a record, a record over the ground, the ground
+ *   over SOGM_HIT_NONE.  This is a minimum over a set: it depends on neither point order nor scheduling.
+ * Label of the winner's code c:
+ *     0 <= c < n_cyl:                     v = ((float)cylinders[c].vx, (float)cylinders[c].vy, 0.0f)     (any record type)
+ *     n_cyl <= c < n_cyl + n_bodies:      v_k = (float)body_vel[3*(c - n_cyl) + k]                        k = 0, 1, 2
+ *     any other c (SOGM_HIT_GROUND, SOGM_HIT_NONE, out of range):  v = (0, 0, 0)
+ *     s2 = (vx*vx + vy*vy) + vz*vz
+ *   The label is {vx, vy, vz, 1.0f} if all three components (as fp32) are finite and s2 > min_speed*min_speed; otherwise
+ *   {0, 0, 0, 0}.  (The reference draws the intensity uniformly from (0.1, 1) "for visualization"; only "> 0.01" is ever
+ *   read: sogm_update_dsp takes a point with intensity > 0.01 as born dynamic with that velocity.)
+ *   Velocities are in WORLD axes: sogm_update_dsp copies labels as given, next to points it has itself turned by the sensor's
+ *   orientation and moved to the sensor's position (input_cloud_with_velocity) — a label is never rotated.
+ * Outputs: out_labels row r of agent a, and out_code[a*cap + r] if given (the winner's code, as it came), belong to point r
+ *   of out_xyz.  Rows at and beyond out_count[a] are not written.  Labels and codes are bit-identical from run to run.
+ * Memory: a key array of n_agents * max_cells * 8 bytes (sogm_filter_reserve; 1 GiB at 128 agents with the default 2^20
+ *   leaves) is allocated on the FIRST labelled call of a context, never by sogm_filter_point_cloud.  Plain and labelled
+ *   calls may alternate on one context in any order.
+ * SOGM_ERR_INVALID_ARG: sogm_filter_point_cloud's refusals, checked first; then a null raw_code, out_labels or src,
+ *   n_cyl < 0, n_cyl > 0 with null cylinders, n_bodies < 0, n_bodies > 0 with null body_vel, min_speed negative or not finite.
+ */
+typedef struct SogmLabelSources {
+  const SogmCylinder *cylinders;   /* dev [n_cyl]: the frame the hit image was rendered from (NULL if n_cyl == 0) */
+  const double       *body_vel;    /* dev [n_bodies*3] fp64, world axes (NULL only if n_bodies == 0)               */
+  int32_t             n_cyl, n_bodies;
+  float               min_speed;   /* >= 0 */
+  int32_t             reserved_;
+} SogmLabelSources;                /* 32 bytes */
+int sogm_filter_point_cloud_labelled(sogm_ctx *ctx, const float *raw_xyz, const int32_t *raw_code,
+                                     const int32_t *raw_range, float filter_res, int cap,
+                                     const SogmLabelSources *src, float *out_xyz, int32_t *out_count,
+                                     float *out_labels /* dev [n_agents*cap*4] */,
+                                     int32_t *out_code /* dev [n_agents*cap] or NULL */, void *stream);
+
 /*
  * Tick glue of a batched planner service, each ONE launch (the FSM bookkeeping around replan()):
  * sogm_tick_inputs — the replan start state of every agent: its executing trajectory own_records[a] sampled at

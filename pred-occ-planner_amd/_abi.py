@@ -82,6 +82,11 @@ class SogmCylinder(C.Structure):
         (k, C.c_double) for k in ("x", "y", "z", "w", "h", "vx", "vy", "qw", "qx", "qy", "qz")]
 
 
+class SogmLabelSources(C.Structure):
+    _fields_ = [("cylinders", C.c_void_p), ("body_vel", C.c_void_p), ("n_cyl", C.c_int32), ("n_bodies", C.c_int32),
+                ("min_speed", C.c_float), ("reserved_", C.c_int32)]
+
+
 class SogmTrajRecord(C.Structure):
     _fields_ = [("drone_id", C.c_int32), ("n_pieces", C.c_int32), ("time_start", C.c_double),
                 ("duration", C.c_double * SOGM_MAX_PIECES),
@@ -218,6 +223,7 @@ CYLINDER_BYTES = C.sizeof(SogmCylinder)  # 96
 DEPTH_CAMERA_BYTES = C.sizeof(SogmDepthCamera)  # 72
 DEPTH_BODIES_BYTES = C.sizeof(SogmDepthBodies)  # 48
 SOGM_HIT_GROUND, SOGM_HIT_NONE = -1, -2   # out_hit of sogm_render_depth_swarm
+LABEL_SOURCES_BYTES = C.sizeof(SogmLabelSources)  # 32
 
 
 class SogmTrajServerState(C.Structure):
@@ -341,6 +347,8 @@ PROTOTYPES = {
     "sogm_comm_handle": (_vp, [_vp]),
     "sogm_comm_info": (_i, [_vp, _vp]),
     "sogm_filter_point_cloud": (_i, [_vp, _vp, _vp, C.c_float, _i, _vp, _vp, _vp]),
+    "sogm_filter_point_cloud_labelled": (_i, [_vp, _vp, _vp, _vp, C.c_float, _i, C.POINTER(SogmLabelSources), _vp, _vp, _vp,
+                                              _vp, _vp]),
     "sogm_filter_reserve": (_i, [_vp, _i]),
     "sogm_dsp_create": (_i, [_vp, C.POINTER(SogmDspParams), _vp, _vp, _i, _vp, _i, _i, C.POINTER(_vp)]),
     "sogm_dsp_destroy": (None, [_vp]),

@@ -637,6 +637,7 @@ struct sogm_ctx {
   void          *d_filter_box;
   int           *d_filter_blocks;
   int            filter_max_cells;
+  unsigned long long *d_filter_keys;  // [A][max_cells] leaf winners of the labelled filter, all-ones between calls (first labelled call)
   unsigned      *d_stamp_bits;     // [A][ceil(V / 32)] occupancy bits of slice 0 between k_stamp_bits and k_stamp_marks (lazy)
   // pre-stamp (sogm_planner_set_prestamp): the replan builds the next tick's map into the pool's next grid with the
   // next map centres / stamps in d_poses_next / d_stamps_next; sogm_update_prestamped adopts both

@@ -286,6 +286,16 @@ class DspMap {
     check(sogm_filter_point_cloud(map.ctx(), raw_xyz, raw_range, filter_res, cap, out_xyz, out_count, st),
           "sogm_filter_point_cloud");
   }
+  // The same with ground-truth velocity labels (sogm_abi.h "ground-truth labels"): raw_code is the hit image of
+  // GridMap::renderDepthSwarm in raw_xyz's order, src the frame's records and the bodies' world-axes velocities; labels
+  // [n cap 4] is what update() below takes, code [n cap] (may be nullptr) the winning hit code of every output point.
+  static void filterPointCloudLabelled(RiskMap &map, const float *raw_xyz, const int32_t *raw_code, const int32_t *raw_range,
+                                       float filter_res, const SogmLabelSources &src, float *out_xyz, int32_t *out_count,
+                                       float *out_labels, int32_t *out_code = nullptr, int cap = 5000,
+                                       hipStream_t st = nullptr) {
+    check(sogm_filter_point_cloud_labelled(map.ctx(), raw_xyz, raw_code, raw_range, filter_res, cap, &src, out_xyz,
+                                           out_count, out_labels, out_code, st), "sogm_filter_point_cloud_labelled");
+  }
   // int DSPMap::update(n, 3, pts, px, py, pz, stamp, qw, qx, qy, qz) for the whole batch (device pointers)
   // labels == nullptr: velocityEstimationThread (clustering + association, :1487-1678) runs on the GPU
   void update(const float *points, const float *labels, const int32_t *cloud_range, const float *sensor_pos,

@@ -130,6 +130,38 @@ class SogmMap:
                                             out.data_ptr(), cnt.data_ptr(), _stream()), "sogm_filter_point_cloud")
         return out, cnt
 
+    def filterPointCloudLabelled(self, raw_xyz, raw_code, raw_range, world, body_vel=None, min_speed=0.0, filter_res=0.15,
+                                 cap=5000, want_code=False):
+        """filterPointCloud with ground-truth velocity labels (include/sogm_abi.h "ground-truth labels",
+        sogm_filter_point_cloud_labelled): raw_code int32, one hit code per raw point (depth.render_depth_swarm's hit image, any
+        shape with raw_xyz's order); world: the sogm.World / WorldFrame the frame was rendered from (its records' vx, vy);
+        body_vel [B, 3] fp64 world-axes velocities of the bodies (TrajServer.body_velocities; None or empty: no bodies).
+        Returns (points [A, cap, 3], counts [A], labels [A, cap, 4] float32 {vx, vy, vz, intensity} — what DspMap.update takes
+        as labels —, code [A, cap] int32 or None): rows at and beyond counts[a] are not written.  Stream-ordered, no
+        synchronisation."""
+        dev = raw_xyz.device
+        code = raw_code.to(torch.int32).reshape(-1).contiguous()
+        assert code.numel() * 3 == raw_xyz.numel(), (tuple(raw_code.shape), tuple(raw_xyz.shape))
+        src = _abi.SogmLabelSources()
+        src.n_cyl = int(world.n_cyl)
+        src.cylinders = world.cylinders.data_ptr() if src.n_cyl else None
+        vel = None               # (kept alive until the call is queued; the stream orders its release)
+        if body_vel is not None:
+            vel = _dev(np.asarray(body_vel, np.float64) if not isinstance(body_vel, torch.Tensor) else body_vel, None, dev)
+            vel = vel.to(torch.float64).reshape(-1, 3).contiguous()
+            src.n_bodies = int(vel.shape[0])
+            src.body_vel = vel.data_ptr() if src.n_bodies else None
+        src.min_speed = float(min_speed)
+        out = torch.empty((self.n_agents, cap, 3), dtype=torch.float32, device=dev)
+        cnt = torch.empty((self.n_agents,), dtype=torch.int32, device=dev)
+        lab = torch.empty((self.n_agents, cap, 4), dtype=torch.float32, device=dev)
+        hit = torch.empty((self.n_agents, cap), dtype=torch.int32, device=dev) if want_code else None
+        check(lib().sogm_filter_point_cloud_labelled(self._ctx, raw_xyz.data_ptr(), code.data_ptr(), raw_range.data_ptr(),
+                                                     filter_res, cap, C.byref(src), out.data_ptr(), cnt.data_ptr(),
+                                                     lab.data_ptr(), hit.data_ptr() if want_code else None, _stream()),
+              "sogm_filter_point_cloud_labelled")
+        return out, cnt, lab, hit
+
     # ---- sparse reset (sogm_abi.h: sogm_set_sparse_reset) ----
     def set_sparse_reset(self, on=True, log_capacity=0):
         check(lib().sogm_set_sparse_reset(self._ctx, 1 if on else 0, int(log_capacity)), "sogm_set_sparse_reset")

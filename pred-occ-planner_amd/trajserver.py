@@ -134,3 +134,12 @@ class TrajServer:
         k = int(cmd.shape[1])
         off = COMMAND_DTYPE.fields["pos"][1]
         return cmd[:, sample % k, off:off + 24].contiguous().view(torch.float64)
+
+    def body_velocities(self, sample=-1, cmd=None):
+        """The commanded velocities (world axes) of every agent at command `sample`, body_positions' sibling: an fp64 device
+        tensor [n][3], the body_vel SogmMap.filterPointCloudLabelled takes.  A copy made by torch: no kernel of the library's,
+        no host synchronisation."""
+        cmd = self.cmd if cmd is None else cmd
+        k = int(cmd.shape[1])
+        off = COMMAND_DTYPE.fields["vel"][1]
+        return cmd[:, sample % k, off:off + 24].contiguous().view(torch.float64)

@@ -10,7 +10,11 @@ per pixel), an empty world with the ground (all 14 bytes, next to no arithmetic)
 --bodies N renders through sogm_render_depth_swarm ("agent bodies") instead: every camera's own carrier (a 0.4 x 0.4 x 0.45
 box 0.1 m behind and 0.05 m below the camera, not drawn for it) plus N - cameras bystanders hovering inside the circle
 become bodies (N below the number of cameras: only the first N cameras are carried); --bodies 0 is that entry without
-bodies, i.e. the cost of carrying the hit codes.  --hit also asks for the hit image (4 more bytes per pixel)."""
+bodies, i.e. the cost of carrying the hit codes.  --hit also asks for the hit image (4 more bytes per pixel).
+
+--labels (with --bodies N) also times the labelled filter (sogm_filter_point_cloud_labelled, "ground-truth labels") in the same
+run, next to the plain one: the render then always writes the hit image, every body gets a velocity from SplitMix64, and
+filter_labelled_ms / render_then_filter_labelled_ms stand beside filter_ms / render_then_filter_ms, with their ratio."""
 import argparse, importlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -50,7 +54,7 @@ def swarm_bodies(pop, pos, rot, n_bodies):
     return bodies, np.array([a if a < n_bodies else -1 for a in range(A)], np.int32)
 
 
-def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False):
+def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False, labels=False):
     pop = importlib.import_module("pred-occ-planner_amd")
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     gm = importlib.import_module("pred-occ-planner_amd.gridmap")
@@ -87,11 +91,17 @@ def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False):
     if bodies >= 0:
         body_h, own_h = swarm_bodies(pop, pos, rot, bodies)
         body_d, own_d = sogm._dev(body_h, np.float64), sogm._dev(own_h, np.int32)
+        vrng = pop.scene.SplitMix64(0xB0D2)
+        vel_d = sogm._dev(np.array([[vrng.uniform(-1.0, 1.0) for _ in range(3)] for _ in body_h], np.float64).reshape(-1, 3),
+                          np.float64)
+    hit = hit or labels
 
     def render(k, want_cloud=True, world=None):
         if bodies >= 0:
             keep["out"] = depth.render_depth_swarm(world or worlds[k], cam, pos_d, rot_d, body_d, own_d, rings=bool(rings),
-                                                   want_cloud=want_cloud, want_hit=hit)[:4]
+                                                   want_cloud=want_cloud, want_hit=hit)
+            keep["hit"] = keep["out"][4]
+            keep["out"] = keep["out"][:4]
         else:
             keep["out"] = depth.render_depth(world or worlds[k], cam, pos_d, rot_d, want_cloud, rings=bool(rings))
         return keep["out"]
@@ -112,8 +122,20 @@ def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False):
     t_gridmap = timed(lambda k: keep.__setitem__("upd", g.update(d16, pos_d, rot_d)))
     t_rg = timed(render_gridmap)
     _, cl, rng, _ = render(n - 1)
+    hit_last = keep.get("hit")      # the hit image of the frame `cl` is
     t_filter = timed(lambda k: keep.__setitem__("flt", m.filterPointCloud(cl, rng, 0.15, 5000)))
     t_rf = timed(render_filter)
+    if labels:
+        def filter_labelled(k):
+            keep["lab"] = m.filterPointCloudLabelled(cl, hit_last, rng, worlds[n - 1], vel_d, 0.05, 0.15, 5000)
+
+        def render_filter_labelled(k):
+            _, cl_k, rng_k, _ = render(k)
+            keep["lab"] = m.filterPointCloudLabelled(cl_k, keep["hit"], rng_k, worlds[k], vel_d, 0.05, 0.15, 5000)
+
+        t_fl = timed(filter_labelled)
+        t_rfl = timed(render_filter_labelled)
+        t_filter_again = timed(lambda k: keep.__setitem__("flt", m.filterPointCloud(cl, rng, 0.15, 5000)))
     nbytes = A * cam.rows * cam.cols * 14
     out = {"agents": A, "cylinders": int(len(sc["cylinders"])), "rings": int(rings), "frames_timed": steps,
            "render_ms": t_render, "render_GBps_algorithmic": round(nbytes / (t_render["mean"] * 1e-3) / 1e9, 1),
@@ -125,6 +147,12 @@ def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False):
            "gridmap_updated": int(keep["upd"].sum().item()), "filtered_points_agent0": int(keep["flt"][1][0].item())}
     if bodies >= 0:
         out.update({"entry": "sogm_render_depth_swarm", "bodies": int(len(body_h)), "hit_image": bool(hit)})
+    if labels:
+        lab, cnt0 = keep["lab"][2], int(keep["lab"][1][0].item())
+        out.update({"filter_labelled_ms": t_fl, "render_then_filter_labelled_ms": t_rfl,
+                    "filter_ms_after_labelled": t_filter_again,      # the plain entry once the key array exists
+                    "filter_labelled_over_filter": round(t_fl["mean"] / t_filter["mean"], 3),
+                    "labelled_points_agent0": int((lab[0, :cnt0, 3] > 0).sum().item()), "filtered_points_labelled_agent0": cnt0})
     g.close()
     m.close()
     return out
@@ -139,8 +167,11 @@ if __name__ == "__main__":
     ap.add_argument("--bodies", type=int, default=-1, help="render through sogm_render_depth_swarm with N bodies (default: "
                     "sogm_render_depth, today's run)")
     ap.add_argument("--hit", action="store_true", help="with --bodies: also ask for the hit image")
+    ap.add_argument("--labels", action="store_true", help="with --bodies: also time sogm_filter_point_cloud_labelled on the hit "
+                    "image (implies --hit)")
     a = ap.parse_args()
     assert a.steps >= 20 and torch.cuda.is_available(), "needs a GPU and at least 20 timed frames"
+    assert not a.labels or a.bodies >= 0, "--labels needs --bodies N (the hit image comes from sogm_render_depth_swarm)"
     print(json.dumps({"workload": "sogm_render_depth, 480x640 per camera, cfg2 moving world (seed 0x5069), cameras on a 12 m "
                                   "circle; ms per frame: HIP events on the launch stream around each call",
-                      "runs": [run(A, a.steps, a.warmup, a.rings, a.bodies, a.hit) for A in a.agents]}))
+                      "runs": [run(A, a.steps, a.warmup, a.rings, a.bodies, a.hit, a.labels) for A in a.agents]}))
