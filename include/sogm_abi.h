@@ -1344,6 +1344,97 @@ int sogm_swarm_audit(const SogmAuditParams *prm, const SogmTrajRecord *tables, i
                      SogmAuditAgent *acc, SogmAuditEvent *events, int32_t *n_events, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* map audit: how far a perceived SOGM is from the ground-truth SOGM, agent by agent and future   */
+/*   slice by future slice.  The reference has no such figure: this is the build's OWN            */
+/*   instrument, held by two readings (csrc/sogm_mapaudit.hpp + csrc/sogm_mapaudit.hip, and the   */
+/*   numpy restatement tests/map_audit_reference.py), count for count.                            */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Two contexts, `test` (the map under judgement: e.g. a SOGM_MAP_RISKVOXEL context that sogm_dsp_publish fills) and `truth`
+ * (e.g. a SOGM_MAP_FAKE context that sogm_update_world fills), on the same device, with the same n_agents, L, W, H and a
+ * resolution equal bit for bit.  T, map_kind and storage (fp32 / fp16 cells, rows / 2 x 2 x 2 tiles) may differ.  A cell is
+ * named by its LOGICAL index (ix, iy, iz), 0 <= ix < L, 0 <= iy < W, 0 <= iz < H, whatever the storage.
+ *
+ * Occupancy.  O(c) = value(c) > thr, where value(c) is the stored cell converted to fp32 (an fp16 cell: the stored half,
+ *   converted exactly) and the comparison is fp32 and strict: a value equal to thr is not occupied, a NaN is not occupied.
+ *   The test side uses thr_test, the truth side thr_truth.
+ *
+ * Region R (the same for every slice of an agent).  A cell is in R when box_lo[d] <= i_d < box_hi[d] for d = 0, 1, 2 (all six
+ *   zero: the whole grid) and, with SOGM_MAPAUDIT_FRUSTUM set in flags, it passes the frustum test.  All of it fp64, in
+ *   exactly this order, without contraction; R is the row-major camera-to-world rotation cam_rot[agent] of "depth camera"
+ *   (camera frame: x right, y down, z forward) and the camera sits at the map centre, where sogm_dsp_publish puts it:
+ *     p_d = ((double)i_d + 0.5) * (double)resolution - (double)range_d       d = 0, 1, 2
+ *           range_0 = (float)(L / 2) * resolution, range_1 = (float)(W / 2) * resolution, range_2 = (float)(H / 2) * resolution
+ *           (fp32 products, integer halves: the map's local_update_range)
+ *     q_j = (R[0][j]*p_0 + R[1][j]*p_1) + R[2][j]*p_2                         j = 0 (x), 1 (y), 2 (z)
+ *     in view iff  q_z > near_z  &&  q_z <= far_z  &&  fabs(q_x) <= q_z*tan_h  &&  fabs(q_y) <= q_z*tan_v
+ *   A rotation that is not finite puts no cell in view (every comparison with a NaN is false; far_z is finite).
+ *
+ * Neighbourhood.  D_r(O)(c) is true when some cell c' of the grid (anywhere in it, not only in R) has O(c') and
+ *   max(|ix - ix'|, |iy - iy'|, |iz - iz'|) <= r.  Grid edges do not wrap.  r = tolerance, 0 .. 3.
+ *
+ * Counts.  Test slice t of agent a is compared with truth slice s = slice_map[t]; out[a * T_test + t] is
+ *     n_region      |R|
+ *     n_test        |O_test  &  R|
+ *     n_truth       |O_truth &  R|
+ *     n_both        |O_test  &  O_truth  &  R|
+ *     n_test_near   |O_test  &  D_r(O_truth)  &  R|     (test cells with a truth cell within r: the numerator of precision)
+ *     n_truth_near  |O_truth &  D_r(O_test)   &  R|     (truth cells with a test cell within r: the numerator of recall)
+ *     truth_slice   s
+ *     status        0 audited | SOGM_MAPAUDIT_CENTRE | SOGM_MAPAUDIT_SKIPPED
+ *   With r = 0 both near counts equal n_both.  Precision (n_test_near / n_test) and recall (n_truth_near / n_truth) are the
+ *   caller's divisions.  Rows are overwritten, not accumulated; only integer adds are used, so the output is bit-identical
+ *   from run to run.
+ *   SOGM_MAPAUDIT_CENTRE: the two maps' centres of this agent (sogm_map_state's) differ in any bit of their three floats:
+ *     the cells do not coincide, all six counts of all its rows are zero (truth_slice is still slice_map[t]); other agents are
+ *     not affected.
+ *   SOGM_MAPAUDIT_SKIPPED: slice_map[t] == -1: all six counts are zero, truth_slice is -1.  (An agent with differing centres
+ *     reports SOGM_MAPAUDIT_SKIPPED for such a row.)
+ *   out_dt[a] = test stamp - truth stamp (fp64, sogm_map_state's times): reported, not judged.
+ */
+enum { SOGM_MAPAUDIT_FRUSTUM = 1 };                            /* SogmMapAuditParams.flags; other bits are ignored */
+enum { SOGM_MAPAUDIT_CENTRE = 1, SOGM_MAPAUDIT_SKIPPED = 2 };  /* SogmMapAuditRow.status */
+#define SOGM_MAPAUDIT_MAX_T 32
+typedef struct SogmMapAuditParams {
+  float   thr_test, thr_truth;   /* occupancy thresholds, one per side */
+  int32_t tolerance;             /* r, 0 .. 3 cells */
+  int32_t flags;                 /* SOGM_MAPAUDIT_FRUSTUM */
+  int32_t box_lo[3], box_hi[3];  /* logical cells [lo, hi); all six zero: the whole grid */
+  int32_t slab_layers;           /* 0: the layout chooses; otherwise an upper bound on the z layers a workgroup holds at a
+                                    time.  The rows never depend on it. */
+  int32_t reserved_;
+  double  near_z, far_z;         /* frustum: finite, 0 <= near_z < far_z */
+  double  tan_h, tan_v;          /* frustum: finite, > 0: the tangents of the half angles (0.5 * cols / fx, 0.5 * rows / fy) */
+  int32_t slice_map[SOGM_MAPAUDIT_MAX_T];  /* truth slice of test slice t, or -1: skip it; entries at and beyond T_test are
+                                              not read */
+} SogmMapAuditParams;            /* 208 bytes */
+typedef struct SogmMapAuditRow {
+  int32_t n_region, n_test, n_truth, n_both, n_test_near, n_truth_near, truth_slice, status;
+} SogmMapAuditRow;               /* 32 bytes */
+
+/* thresholds 0, tolerance 0, no flags, the whole grid, slab_layers 0, frustum parameters 0, slice_map = the identity on
+ * min(T_test, T_truth) slices and -1 beyond.  SOGM_ERR_INVALID_ARG for a null prm or a T outside 1 .. SOGM_MAPAUDIT_MAX_T. */
+int sogm_map_audit_default_params(int T_test, int T_truth, SogmMapAuditParams *out_prm_host);
+/*
+ * Audits the two contexts' CURRENT maps.  The call joins an update flow still building either map on `stream`, then reads
+ * the two grids, map centres and stamps; it writes nothing to either context, allocates nothing, and does not synchronise
+ * with the host.  prm is a host record; dev cam_rot [n_agents * 9] fp64 (NULL without SOGM_MAPAUDIT_FRUSTUM), dev out
+ * [n_agents][T_test], dev out_dt [n_agents] fp64 or NULL.
+ * SOGM_ERR_INVALID_ARG (with sogm_last_error text; checked first, before anything is queued on the device): a null test,
+ * truth, prm or out; tolerance outside 0 .. 3; SOGM_MAPAUDIT_FRUSTUM without cam_rot, or with near_z, far_z, tan_h or tan_v
+ * not finite, near_z < 0, far_z <= near_z, tan_h <= 0 or tan_v <= 0; a box that is empty or leaves the grid (unless all six
+ * are zero); a slice_map entry of a test slice below -1 or at or above T_truth; a T above SOGM_MAPAUDIT_MAX_T on either
+ * side; contexts on different devices, with different n_agents, L, W, H or resolution bits; a grid of which not even one z
+ * layer fits one compute unit's LDS (W * ceil(L / 64) * 8 bytes * (5 + 8 r), 3 with r = 0, above 159 KB).
+ * SOGM_ERR_NO_DEVICE without a GPU (no context exists on such a host: it is what a call gets there once its pointers are
+ * not null and prm's own fields have passed).  SOGM_ERR_STATE when either map has never been updated.
+ */
+int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *prm,
+                   const double *cam_rot /* dev [n_agents*9] or NULL */,
+                   SogmMapAuditRow *out /* dev [n_agents][T_test] */, double *out_dt /* dev [n_agents] or NULL */,
+                   void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory server: the 100 Hz position commands (with yaw) a vehicle consumes                  */
 /*   (traj_server/src/bezier_traj_server.cpp, bezier_traj_server_rotors.cpp)                      */
 /* ------------------------------------------------------------------------------------------ */

@@ -166,6 +166,22 @@ SOGM_DEPTH_RINGS, SOGM_AUDIT_RINGS = 1, 1   # SogmDepthCamera.flags, SogmAuditPa
 AUDIT_AGENT_BYTES = C.sizeof(SogmAuditAgent)  # 104
 AUDIT_EVENT_BYTES = C.sizeof(SogmAuditEvent)  # 24
 
+# map audit (include/sogm_abi.h "map audit")
+SOGM_MAPAUDIT_FRUSTUM = 1
+SOGM_MAPAUDIT_CENTRE, SOGM_MAPAUDIT_SKIPPED = 1, 2
+SOGM_MAPAUDIT_MAX_T = 32
+
+
+class SogmMapAuditParams(C.Structure):
+    _fields_ = [("thr_test", C.c_float), ("thr_truth", C.c_float), ("tolerance", C.c_int32), ("flags", C.c_int32),
+                ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("slab_layers", C.c_int32), ("reserved_", C.c_int32),
+                ("near_z", C.c_double), ("far_z", C.c_double), ("tan_h", C.c_double), ("tan_v", C.c_double),
+                ("slice_map", C.c_int32 * SOGM_MAPAUDIT_MAX_T)]
+
+
+MAPAUDIT_ROW_FIELDS = ("n_region", "n_test", "n_truth", "n_both", "n_test_near", "n_truth_near", "truth_slice", "status")
+MAPAUDIT_PARAMS_BYTES = C.sizeof(SogmMapAuditParams)  # 208
+
 
 class SogmFsmParams(C.Structure):
     _fields_ = [("replan_duration", C.c_double), ("replan_start_time", C.c_double), ("goal_tolerance", C.c_double),
@@ -335,6 +351,8 @@ PROTOTYPES = {
     "sogm_audit_init_agents": (_i, [_vp, _i, _vp]),
     "sogm_swarm_audit": (_i, [C.POINTER(SogmAuditParams), _vp, _i, _i, _vp, C.c_double, _i, C.c_double, _i, _i, _vp, _vp,
                               _vp, _i, _vp, _vp, _vp, _vp]),
+    "sogm_map_audit_default_params": (_i, [_i, _i, C.POINTER(SogmMapAuditParams)]),
+    "sogm_map_audit": (_i, [_vp, _vp, C.POINTER(SogmMapAuditParams), _vp, _vp, _vp, _vp]),
     "sogm_traj_server_init": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp]),
     "sogm_traj_server_run": (_i, [C.POINTER(SogmTrajServerParams), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i,
                                   C.c_double, C.c_double, _vp, _vp]),

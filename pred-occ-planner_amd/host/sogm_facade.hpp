@@ -257,8 +257,35 @@ class RiskMap {
     pts_.get(h.data(), h.size());
     for (int i = 0; i < n; ++i) points.push_back({h[i * 3], h[i * 3 + 1], h[i * 3 + 2]});
   }
+  // Map audit (include/sogm_abi.h "map audit"; no reference counterpart): this map — the perceived one — against `truth`,
+  // agent by agent and slice by slice.  auditParams() is sogm_map_audit_default_params for the two maps with each spec's
+  // risk_threshold as the occupancy thresholds; the caller sets tolerance, box, frustum and slice_map on it.  cam_rot_host:
+  // [agents * 9] row-major camera-to-world rotations, needed with SOGM_MAPAUDIT_FRUSTUM only.  Returns the rows
+  // [agents][T of this map]; out_dt_host (agents values, optional): this map's stamp minus truth's.  Synchronises `st`.
+  SogmMapAuditParams auditParams(const RiskMap &truth) const {
+    SogmMapAuditParams prm;
+    check(sogm_map_audit_default_params(spec_.T, truth.spec_.T, &prm), "sogm_map_audit_default_params");
+    prm.thr_test  = spec_.risk_threshold;
+    prm.thr_truth = truth.spec_.risk_threshold;
+    return prm;
+  }
+  std::vector<SogmMapAuditRow> auditAgainst(RiskMap &truth, const SogmMapAuditParams &prm, const double *cam_rot_host = nullptr,
+                                            double *out_dt_host = nullptr, hipStream_t st = nullptr) {
+    const size_t rows = (size_t)n_ * (size_t)spec_.T;
+    audit_rows_.resize(rows);
+    u_.resize((size_t)n_);
+    if (cam_rot_host) pts_.put(cam_rot_host, (size_t)n_ * 9);
+    check(sogm_map_audit(ctx_, truth.ctx_, &prm, cam_rot_host ? pts_.data() : nullptr, audit_rows_.data(), u_.data(), st),
+          "sogm_map_audit");
+    if (hipStreamSynchronize(st) != hipSuccess) throw std::runtime_error("auditAgainst: hipStreamSynchronize failed");
+    std::vector<SogmMapAuditRow> out(rows);
+    audit_rows_.get(out.data(), rows);
+    if (out_dt_host) u_.get(out_dt_host, (size_t)n_);
+    return out;
+  }
 
  private:
+  DevBuf<SogmMapAuditRow> audit_rows_;
   sogm_ctx       *ctx_ = nullptr;
   int             n_;
   SogmSpec        spec_;

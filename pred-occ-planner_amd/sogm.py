@@ -299,6 +299,56 @@ class SogmMap:
               "sogm_download_reference_layout")
         return out
 
+    # ---- map audit (include/sogm_abi.h "map audit") ----
+    def audit_against(self, truth, thr_test=None, thr_truth=None, tolerance=0, box=None, frustum=None, cam_rot=None,
+                      slice_map=None, slab_layers=0):
+        """Scores this map (the perceived one) against `truth` (another SogmMap of the same grid), agent by agent and slice
+        by slice (sogm_map_audit).  thr_*: occupancy thresholds (default: each spec's risk_threshold); tolerance: r cells,
+        0 .. 3; box: (lo [3], hi [3]) logical cells or None (the whole grid); frustum: (near_z, far_z, tan_h, tan_v) with
+        cam_rot [n_agents, 9] fp64 (row-major camera-to-world, numpy or a device tensor), or None; slice_map: the truth slice of
+        every test slice (-1: skip; default: the identity on the slices both maps have).  Returns a dict of numpy int32 arrays
+        [n_agents, T_test] (n_region, n_test, n_truth, n_both, n_test_near, n_truth_near, truth_slice, status) plus `dt`
+        (float64 [n_agents]: this map's stamp minus truth's).  Synchronises to read the rows back."""
+        rows, dt = self.audit_against_device(truth, thr_test, thr_truth, tolerance, box, frustum, cam_rot, slice_map, slab_layers)
+        host = rows.cpu().numpy()
+        out = {name: np.ascontiguousarray(host[:, :, k]) for k, name in enumerate(_abi.MAPAUDIT_ROW_FIELDS)}
+        out["dt"] = dt.cpu().numpy()
+        return out
+
+    def audit_against_device(self, truth, thr_test=None, thr_truth=None, tolerance=0, box=None, frustum=None, cam_rot=None,
+                             slice_map=None, slab_layers=0):
+        """audit_against without the read-back: (rows int32 [n_agents, T_test, 8] in SogmMapAuditRow's field order, dt float64
+        [n_agents]) as device tensors, stream-ordered, no synchronisation (a cam_rot given as a device tensor is used as is)."""
+        prm = _abi.SogmMapAuditParams()
+        T = self.spec.T
+        check(lib().sogm_map_audit_default_params(min(T, _abi.SOGM_MAPAUDIT_MAX_T), min(truth.spec.T, _abi.SOGM_MAPAUDIT_MAX_T),
+                                                  C.byref(prm)), "sogm_map_audit_default_params")
+        prm.thr_test = self.spec.risk_threshold if thr_test is None else thr_test
+        prm.thr_truth = truth.spec.risk_threshold if thr_truth is None else thr_truth
+        prm.tolerance, prm.slab_layers = int(tolerance), int(slab_layers)
+        if box is not None:
+            for d in range(3):
+                prm.box_lo[d], prm.box_hi[d] = int(box[0][d]), int(box[1][d])
+        if slice_map is not None:
+            if len(slice_map) != T:
+                raise ValueError("audit_against: one slice_map entry per test slice")
+            for t in range(min(T, _abi.SOGM_MAPAUDIT_MAX_T)):
+                prm.slice_map[t] = int(slice_map[t])
+        rot = None
+        if frustum is not None:
+            prm.flags = _abi.SOGM_MAPAUDIT_FRUSTUM
+            prm.near_z, prm.far_z, prm.tan_h, prm.tan_v = (float(v) for v in frustum)
+            if cam_rot is not None:
+                rot = _dev(cam_rot if isinstance(cam_rot, torch.Tensor) else np.asarray(cam_rot, np.float64))
+                rot = rot.to(torch.float64).reshape(-1).contiguous()
+                if rot.numel() != 9 * self.n_agents:
+                    raise ValueError("audit_against: cam_rot is [n_agents, 9]")
+        rows = torch.empty((self.n_agents, T, 8), dtype=torch.int32, device="cuda")
+        dt = torch.empty((self.n_agents,), dtype=torch.float64, device="cuda")
+        check(lib().sogm_map_audit(self._ctx, truth.ctx, C.byref(prm), rot.data_ptr() if rot is not None else None,
+                                   rows.data_ptr(), dt.data_ptr(), _stream()), "sogm_map_audit")
+        return rows, dt
+
     # ---- queries ----
     def getClearOcccupancy(self, agent_idx, pos, t, t_is_index=False):
         """Batched getClearOcccupancy; agent_idx int32[n], pos float64[n,3], t float64[n]."""
@@ -434,6 +484,17 @@ class WorldTimelineDev:
         for i, s in enumerate(out):
             s.tick = int(first_tick) + i
         return out
+
+
+def audit_precision_recall(rows):
+    """(strict precision, strict recall, precision within r, recall within r) of SogmMap.audit_against's rows, float64 arrays
+    of the rows' shape: n_both / n_test, n_both / n_truth, n_test_near / n_test, n_truth_near / n_truth, NaN where the
+    denominator is 0"""
+    def ratio(num, den):
+        num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+        return np.divide(num, den, out=np.full(den.shape, np.nan), where=den != 0)
+    return (ratio(rows["n_both"], rows["n_test"]), ratio(rows["n_both"], rows["n_truth"]),
+            ratio(rows["n_test_near"], rows["n_test"]), ratio(rows["n_truth_near"], rows["n_truth"]))
 
 
 def upload_scene(scene, device="cuda", cloud=None, cloud_range=None):

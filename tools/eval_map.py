@@ -1,0 +1,129 @@
+"""Map audit of the perception path on BASELINE configs[1] (16 agents, 100^3 x 15 SOGM, 480 x 640 depth frames): for k frames
+of the moving world every agent's camera is rendered (sogm_render_depth_swarm), filtered, fed to the particle SOGM
+(sogm_update_dsp) and published (sogm_dsp_publish) into the TEST map; a ground-truth map (SOGM_MAP_FAKE, sogm_update_world of
+the same frame) is built at the centre and stamp sogm_map_state reports for the test map; sogm_map_audit then counts, per
+agent and future slice, the cells on which the two agree — strictly and within --tolerance cells — inside the camera's
+frustum (near 0, far = max_depth, tan_h = 0.5 cols / fx, tan_v = 0.5 rows / fy; no ground plane is rendered).  One JSON line: strict and within-r
+precision and recall per test slice (counts summed over agents and frames), the audit's ms per call (HIP events on the
+launch stream around the two launches), its algorithmic bytes/s — n_agents x sum over audited slices of V x (cell bytes of
+the test map + of the truth map), halo re-reads not counted — and, for comparison, the same run's dense clear of the truth
+map (sparse reset off, profiling slot CLEAR).
+
+--labels gt         the filter is sogm_filter_point_cloud_labelled: every point carries the velocity of the record the
+                    camera's ray hit.  The rows then score the particle filter's prediction given perfect velocities.
+--labels estimator  the plain filter and labels = NULL: the on-device velocity estimation (clustering + association) runs.
+                    The difference between the two runs' future slices is what the estimator costs.
+
+Which truth slice a test slice is held to.  Slice t of the particle SOGM is the future status at the INSTANT
+prediction_times[t] = 0.3 (t + 1) s after the map stamp (dsp.make_dsp_params).  Slice s of the ground-truth map stands for
+the interval [s, s + 1) x time_resolution (0.2 s): it is the slice getClearOcccupancy(pos, dt) reads for such a dt.  So
+test slice t is mapped to s = floor(prediction_times[t] / time_resolution) — 1, 3, 4, 6, 7, 9, 10, 12, 13 for t = 0 .. 8 —
+the slice a planner would read on the truth map for that instant, and to -1 (skipped, status 2) when that lies beyond the
+truth map's last slice (t >= 9 at T = 15).  Test slice 0 is therefore NOT "now": the particle map publishes no present
+slice."""
+import argparse, importlib, json, math, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np, torch
+
+
+def slice_map_for(prediction_times, T_test, T_truth, time_resolution):
+    out = []
+    for t in range(T_test):
+        s = int(math.floor(float(prediction_times[t]) / float(time_resolution) + 1e-6))
+        out.append(s if s < T_truth else -1)
+    return out
+
+
+def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, cols=640, seed=0x5067, dt=0.1, slab_layers=0):
+    pop = importlib.import_module("pred-occ-planner_amd")
+    sogm = importlib.import_module("pred-occ-planner_amd.sogm")
+    dsp = importlib.import_module("pred-occ-planner_amd.dsp")
+    depth = importlib.import_module("pred-occ-planner_amd.depth")
+    A = agents or pop.config.AGENTS[grid]
+    spec = pop.config.make_spec(grid, map_kind=pop._abi.SOGM_MAP_RISKVOXEL)
+    tspec = pop.config.make_spec(grid)
+    cap = 5000
+    m, truth = sogm.SogmMap(spec, A), sogm.SogmMap(tspec, A)
+    prm = dsp.make_dsp_params(spec.T)
+    g = dsp.DspMap(m, prm, dsp.make_tables(5), max_points=cap)
+    truth.set_sparse_reset(False)                      # every truth update clears densely: the comparison figure
+    truth.set_profiling(slots=[pop._abi.PROF_CLEAR])
+    sc = pop.scene.make_scene(A, spec.L // 2 * spec.resolution, seed)
+    tl = sogm.WorldTimelineDev.from_timeline(pop.scene.WorldTimeline(sc, dt=dt), pool=2)
+    # every camera at its agent's start, looking at its goal
+    yaw = np.arctan2(sc["goals"][:, 1] - sc["starts"][:, 1], sc["goals"][:, 0] - sc["starts"][:, 0])
+    poses = [pop.scene.camera_pose(*sc["starts"][a], yaw[a]) for a in range(A)]
+    pos, rot = np.stack([p for p, _ in poses]), np.stack([R.reshape(9) for _, R in poses])
+    pos_d, rot_d = sogm._dev(pos, np.float64), sogm._dev(rot, np.float64)
+    pos32 = sogm._dev(pos.astype(np.float32), np.float32)
+    quat = sogm._dev(np.stack([np.cos(yaw / 2), 0 * yaw, 0 * yaw, np.sin(yaw / 2)], axis=1), np.float32)
+    cam = depth.make_depth_camera(rows, cols, use_ground=False)   # the ground-truth map holds no ground either
+    frustum = (0.0, cam.max_depth, 0.5 * cols / cam.fx, 0.5 * rows / cam.fy)
+    smap = slice_map_for(prm.prediction_times, spec.T, tspec.T, tspec.time_resolution)
+    base = torch.arange(A, dtype=torch.int32, device="cuda") * cap
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
+    total = np.zeros((spec.T, 8), np.int64)
+    status = set()
+    for k in range(frames):
+        frame = tl.frames(k, 1)[0]
+        stamps = sogm._dev(np.full(A, float(sc["stamps"][0]) + k * dt), np.float64)
+        _, cl, raw_rng, _, hit = depth.render_depth_swarm(frame, cam, pos_d, rot_d, None, want_hit=True)
+        if labels == "gt":
+            pts, cnt, lab, _ = m.filterPointCloudLabelled(cl, hit, raw_rng, frame, None, 0.0, 0.15, cap)
+            lab = lab.view(-1, 4)
+        else:
+            pts, cnt = m.filterPointCloud(cl, raw_rng, 0.15, cap)
+            lab = None
+        g.update(pts.view(-1, 3), lab, torch.stack([base, base + cnt], dim=1).contiguous(), pos32, quat, stamps)
+        g.publish()
+        state = [m.map_state(a) for a in range(A)]
+        truth.updateWorld(frame, sogm._dev(np.stack([c for _, c in state]), np.float32),
+                          sogm._dev(np.array([t for t, _ in state]), np.float64))
+        ev[k][0].record()
+        rows_d, dt_d = m.audit_against_device(truth, None, None, tolerance, None, frustum, rot_d, smap, slab_layers)
+        ev[k][1].record()
+        r = rows_d.cpu().numpy()
+        status |= set(r[:, :, 7].reshape(-1).tolist())
+        total += r.astype(np.int64).sum(axis=0)
+        assert not dt_d.cpu().numpy().any()
+    torch.cuda.synchronize()
+    ms = np.array([a.elapsed_time(b) for a, b in ev])
+    audited = [t for t in range(spec.T) if smap[t] >= 0]
+    cb = lambda s: 2 if s.storage & 1 else 4                                                  # noqa: E731
+    nbytes = float(A) * len(audited) * m.V * (cb(spec) + cb(tspec))
+    steady = ms[1:] if frames > 1 else ms             # the first call loads the code object
+    clear_ms = truth.profile_read_all(pop._abi.PROF_CLEAR)
+    clear = None
+    if clear_ms:
+        c = float(np.median(clear_ms[1:] if len(clear_ms) > 1 else clear_ms))
+        clear = {"ms": c, "bytes": truth.grid_bytes(), "TB_per_s": truth.grid_bytes() / (c * 1e-3) / 1e12, "launches": len(clear_ms)}
+    ratio = lambda n, d: [None if d[t] == 0 else round(float(n[t]) / float(d[t]), 4) for t in audited]   # noqa: E731
+    out = {"workload": f"{A} agents, {spec.L}x{spec.W}x{spec.H}x{spec.T} particle SOGM against the ground-truth SOGM, "
+                       f"{rows}x{cols} depth frames, {frames} frames of the moving world, labels={labels}, r={tolerance}, slab_layers={slab_layers}",
+           "slice_map": smap, "audited_slices": audited, "status_seen": sorted(int(s) for s in status),
+           "n_region": total[audited, 0].tolist(), "n_test": total[audited, 1].tolist(), "n_truth": total[audited, 2].tolist(),
+           "precision_strict": ratio(total[:, 3], total[:, 1]), "recall_strict": ratio(total[:, 3], total[:, 2]),
+           f"precision_within_{tolerance}": ratio(total[:, 4], total[:, 1]),
+           f"recall_within_{tolerance}": ratio(total[:, 5], total[:, 2]),
+           "audit_ms_per_call": float(np.median(steady)), "audit_ms_all": ms.round(4).tolist(),
+           "audit_bytes_per_call": nbytes, "audit_TB_per_s": nbytes / (float(np.median(steady)) * 1e-3) / 1e12,
+           "audit_frac_of_8TB_per_s": nbytes / (float(np.median(steady)) * 1e-3) / 8e12,
+           "dense_clear_same_run": clear}
+    g.close()
+    m.close()
+    truth.close()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", default="cfg1")
+    ap.add_argument("--agents", type=int, default=None)
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--labels", choices=["gt", "estimator"], default="gt")
+    ap.add_argument("--tolerance", type=int, default=1)
+    ap.add_argument("--rows", type=int, default=480)
+    ap.add_argument("--cols", type=int, default=640)
+    ap.add_argument("--slab-layers", type=int, default=0, help="SogmMapAuditParams.slab_layers (0: the layout chooses)")
+    a = ap.parse_args()
+    print(json.dumps(run(a.grid, a.agents, a.frames, a.labels, a.tolerance, a.rows, a.cols, slab_layers=a.slab_layers)))
