@@ -1435,6 +1435,89 @@ int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *pr
                    void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* view mask: the cells of an agent's map that its depth image says something about, as a region */
+/*   for the map audit.  The build's OWN instrument, like "map audit", held by two readings        */
+/*   (csrc/sogm_viewmask.hpp + csrc/sogm_viewmask.hip, and the numpy restatement                   */
+/*   tests/view_mask_reference.py), bit for bit.                                                   */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Every logical cell (ix, iy, iz) of agent a gets ONE class from the agent's uint16 depth image ("depth camera": what
+ * sogm_render_depth[_swarm] leaves on the device).  All arithmetic is fp64, in exactly this order, one IEEE operation at a
+ * time, without contraction:
+ *
+ *   p_d = (((double)i_d + 0.5) * (double)resolution - (double)range_d) - off_d      d = 0, 1, 2
+ *         ("map audit"'s cell centre; off = cam_offset[a], the camera centre minus the map centre.  cam_offset == NULL: the
+ *         subtraction is not made at all — the camera sits at the map centre, as in "map audit")
+ *   q_j = (R[0][j]*p_0 + R[1][j]*p_1) + R[2][j]*p_2                                  j = 0 (x), 1 (y), 2 (z);  R = cam_rot[a]
+ *   SOGM_VIEW_OUTSIDE (0)   unless  q_z > near_z && q_z <= far_z && fabs(q_x) <= q_z*tan_h && fabs(q_y) <= q_z*tan_v
+ *                           ("map audit"'s frustum test, comparison for comparison)
+ *   uf = (q_x / q_z) * fx + cx;   vf = (q_y / q_z) * fy + cy
+ *   u  = floor(uf + 0.5);         v  = floor(vf + 0.5)          (doubles.  The nearest pixel centre: pixel u of "depth camera"
+ *                                                                looks along xc = (u - cx) / fx)
+ *   SOGM_VIEW_OFFIMAGE (1)  unless  u >= 0 && u < cols && v >= 0 && v < rows        (a NaN fails, and lands here)
+ *   d16 = depth[(a * rows + (int)v) * cols + (int)u]
+ *   SOGM_VIEW_FREE (2)      if d16 == 0                         (no return within max_depth: the ray is free as far as far_z,
+ *                                                                which is why far_z <= max_depth is required)
+ *   z_hit = (double)d16 / depth_scale                           (the zq of "depth camera")
+ *   SOGM_VIEW_FREE (2)      if q_z <  z_hit - band
+ *   SOGM_VIEW_SURFACE (3)   else if q_z <= z_hit + band
+ *   SOGM_VIEW_HIDDEN (4)    otherwise
+ *
+ * Known coarseness, on purpose: ONE pixel per cell.  A near cell covers many pixels and a silhouette can cut through it; the
+ * class is that of the pixel nearest its centre's projection.  No footprint, no stencil.
+ *
+ * Mask.  out_mask is [n_agents][H][W][row_words] 64-bit words, row_words = ceil(L / 64); cell ix is bit ix % 64 of word
+ * ix / 64 of its row; the spare bits of a row's last word are clear.  A cell's bit is set when bit `class` of prm->classes is
+ * set.  This is the layout sogm_map_audit_masked reads.
+ * Counts.  out_counts[a][c], c = 0 .. 4: the cells of class c (they sum to L*W*H);  [5]: the bits set in the agent's mask;
+ * [6], [7]: zero.  Overwritten by every call, produced by integer adds only: bit-identical from run to run.
+ */
+enum { SOGM_VIEW_OUTSIDE = 0, SOGM_VIEW_OFFIMAGE = 1, SOGM_VIEW_FREE = 2, SOGM_VIEW_SURFACE = 3, SOGM_VIEW_HIDDEN = 4 };
+enum {                            /* SogmViewParams.classes: bit c stands for class c */
+  SOGM_VIEWBIT_OUTSIDE = 1, SOGM_VIEWBIT_OFFIMAGE = 2, SOGM_VIEWBIT_FREE = 4, SOGM_VIEWBIT_SURFACE = 8, SOGM_VIEWBIT_HIDDEN = 16,
+  SOGM_VIEWBIT_ALL = 31
+};
+typedef struct SogmViewParams {
+  double  fx, fy, cx, cy;        /* the camera's intrinsics */
+  double  depth_scale;           /* > 0 */
+  double  max_depth;             /* > 0: what a zero pixel speaks for */
+  double  near_z, far_z;         /* 0 <= near_z < far_z <= max_depth */
+  double  tan_h, tan_v;          /* > 0 */
+  double  band;                  /* metres, >= 0: half the thickness of SURFACE along the optical axis */
+  int32_t rows, cols;
+  int32_t classes;               /* SOGM_VIEWBIT_*, not zero */
+  int32_t reserved_;
+} SogmViewParams;                /* 104 bytes */
+
+/* The camera's intrinsics, depth_scale, max_depth, rows and cols; near_z = 0, far_z = max_depth, tan_h = 0.5 * cols / fx,
+ * tan_v = 0.5 * rows / fy, band = 0, classes = FREE | SURFACE.  SOGM_ERR_INVALID_ARG for a null pointer. */
+int sogm_view_default_params(const SogmDepthCamera *cam, SogmViewParams *out_prm_host);
+/*
+ * Classifies every cell of every agent of `map`'s grid.  The context supplies only the geometry (n_agents, L, W, H,
+ * resolution): no map is read or written, and a map that has never been updated is fine.  Stream-ordered, allocates
+ * nothing, does not synchronise with the host; depth, cam_rot and cam_offset are only read.
+ * SOGM_ERR_INVALID_ARG (with sogm_last_error text; checked first, before anything is queued on the device): a null map, prm,
+ * depth, cam_rot or out_mask; rows or cols < 1, or an image of more than 2^31 - 1 pixels; fx, fy, cx, cy, depth_scale,
+ * max_depth, band, near_z, far_z, tan_h or tan_v not finite; fx, fy, depth_scale, max_depth, tan_h or tan_v <= 0;
+ * near_z < 0; far_z <= near_z; far_z > max_depth; band < 0; classes zero or with a bit above class 4.
+ * SOGM_ERR_NO_DEVICE without a GPU (what a call gets there once its pointers are not null and prm has passed).
+ */
+int sogm_view_mask(sogm_ctx *map, const SogmViewParams *prm, const uint16_t *depth /* dev [n*rows*cols] */,
+                   const double *cam_rot /* dev [n*9] */, const double *cam_offset /* dev [n*3] or NULL */,
+                   uint64_t *out_mask /* dev [n][H][W][row_words] */, int32_t *out_counts /* dev [n][8] or NULL */,
+                   void *stream);
+/*
+ * sogm_map_audit on a given region: R = box && the cell's bit of `mask` (the layout above; e.g. sogm_view_mask's).
+ * Everything else — occupancy, neighbourhood, counts, status, out_dt, refusals, SOGM_ERR_STATE — is sogm_map_audit's.
+ * SOGM_MAPAUDIT_FRUSTUM must be clear: with it set the call is SOGM_ERR_INVALID_ARG; near_z, far_z, tan_h and tan_v are
+ * not read.  A null mask is SOGM_ERR_INVALID_ARG.  Bits of `mask` beyond a row's L cells are ignored.
+ */
+int sogm_map_audit_masked(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *prm,
+                          const uint64_t *mask /* dev [n_agents][H][W][row_words] */,
+                          SogmMapAuditRow *out /* dev [n_agents][T_test] */, double *out_dt /* dev [n_agents] or NULL */,
+                          void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory server: the 100 Hz position commands (with yaw) a vehicle consumes                  */
 /*   (traj_server/src/bezier_traj_server.cpp, bezier_traj_server_rotors.cpp)                      */
 /* ------------------------------------------------------------------------------------------ */

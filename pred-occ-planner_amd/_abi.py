@@ -182,6 +182,22 @@ class SogmMapAuditParams(C.Structure):
 MAPAUDIT_ROW_FIELDS = ("n_region", "n_test", "n_truth", "n_both", "n_test_near", "n_truth_near", "truth_slice", "status")
 MAPAUDIT_PARAMS_BYTES = C.sizeof(SogmMapAuditParams)  # 208
 
+# view mask (include/sogm_abi.h "view mask"): the classes, and their bits in SogmViewParams.classes
+SOGM_VIEW_OUTSIDE, SOGM_VIEW_OFFIMAGE, SOGM_VIEW_FREE, SOGM_VIEW_SURFACE, SOGM_VIEW_HIDDEN = 0, 1, 2, 3, 4
+SOGM_VIEWBIT_OUTSIDE, SOGM_VIEWBIT_OFFIMAGE, SOGM_VIEWBIT_FREE, SOGM_VIEWBIT_SURFACE, SOGM_VIEWBIT_HIDDEN = 1, 2, 4, 8, 16
+SOGM_VIEWBIT_ALL = 31
+VIEW_CLASS_NAMES = ("outside", "offimage", "free", "surface", "hidden")
+
+
+class SogmViewParams(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("depth_scale", C.c_double),
+                ("max_depth", C.c_double), ("near_z", C.c_double), ("far_z", C.c_double), ("tan_h", C.c_double),
+                ("tan_v", C.c_double), ("band", C.c_double), ("rows", C.c_int32), ("cols", C.c_int32), ("classes", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+VIEW_PARAMS_BYTES = C.sizeof(SogmViewParams)  # 104
+
 
 class SogmFsmParams(C.Structure):
     _fields_ = [("replan_duration", C.c_double), ("replan_start_time", C.c_double), ("goal_tolerance", C.c_double),
@@ -353,6 +369,9 @@ PROTOTYPES = {
                               _vp, _i, _vp, _vp, _vp, _vp]),
     "sogm_map_audit_default_params": (_i, [_i, _i, C.POINTER(SogmMapAuditParams)]),
     "sogm_map_audit": (_i, [_vp, _vp, C.POINTER(SogmMapAuditParams), _vp, _vp, _vp, _vp]),
+    "sogm_view_default_params": (_i, [C.POINTER(SogmDepthCamera), C.POINTER(SogmViewParams)]),
+    "sogm_view_mask": (_i, [_vp, C.POINTER(SogmViewParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sogm_map_audit_masked": (_i, [_vp, _vp, C.POINTER(SogmMapAuditParams), _vp, _vp, _vp, _vp]),
     "sogm_traj_server_init": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp]),
     "sogm_traj_server_run": (_i, [C.POINTER(SogmTrajServerParams), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i,
                                   C.c_double, C.c_double, _vp, _vp]),

@@ -2,7 +2,8 @@
 // ground-truth SOGM agree, strictly and within r cells, per agent and test slice.  Two launches, stream-ordered:
 //   k_map_audit_rows   one lane per (agent, test slice): the row zeroed, its truth_slice and status; out_dt
 //   k_map_audit        one workgroup per (agent, slab of z layers), looping over the test slices:
-//     once per slab    the region's bits (box, frustum in fp64) by 64-wide ballots, one wave per word, into LDS
+//     once per slab    the region's bits (box, frustum in fp64) by 64-wide ballots, one wave per word, into LDS; or, in
+//                      sogm_map_audit_masked's instantiation, copied from a given mask of the same layout and ANDed with the box
 //     per slice        both maps' cells of layers z0 - r .. z1 + r streamed with 16-byte loads over the slab's CONTIGUOUS
 //                      physical range (rows: whole layers; tiles: whole pairs of layers), whatever the cell type; a lane
 //                      decodes its chunk's first cell once (GridGeom's rows or tiles), walks the 4 or 8 cells and ORs the
@@ -178,9 +179,13 @@ __device__ inline void BitStream::consume(const AuditLayout &lay, int c0, const 
   }
 }
 
+// MASKED: the region's second source (sogm_map_audit_masked) — a mask in region[]'s own [layer][y][word] layout, ANDed with
+// the box.  The frustum instantiation <false> is the kernel as it was; `mask` is not read there.
+template <bool MASKED>
 __global__ __launch_bounds__(MAPAUDIT_WG) void k_map_audit(MapView test, MapView truth, MapAuditArgs p,
                                                            const double *__restrict__ cam_rot,
-                                                           SogmMapAuditRow *__restrict__ out) {
+                                                           SogmMapAuditRow *__restrict__ out,
+                                                           const unsigned long long *__restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];
   __shared__ int s_cnt[N_COUNTS];
   const AuditLayout &lay = p.lay;
@@ -192,23 +197,37 @@ __global__ __launch_bounds__(MAPAUDIT_WG) void k_map_audit(MapView test, MapView
   unsigned long long *region = lds + lay.region_off;
   if (tid < N_COUNTS) s_cnt[tid] = 0;
 
-  // ---- the region's bits, once per slab: one wave per word, one lane per cell ----
-  AuditFrustum f{};
-  if (p.frustum) {
-    for (int k = 0; k < 9; ++k) f.R[k] = cam_rot[a * 9 + k];
-    f.near_z = p.near_z, f.far_z = p.far_z, f.tan_h = p.tan_h, f.tan_v = p.tan_v;
-  }
   int n_reg = 0;
-  for (int i = wave; i < nz * lw; i += MAPAUDIT_WG / 64) {
-    const int zl = i / lw, rem = i - zl * lw, y = rem / lay.row_words, w = rem - y * lay.row_words;
-    const int x = (w << 6) + lane, z = z0 + zl;
-    bool      in = x < g.L && x >= p.lo[0] && x < p.hi[0] && y >= p.lo[1] && y < p.hi[1] && z >= p.lo[2] && z < p.hi[2];
-    if (in && p.frustum)
-      in = audit_in_view(f, audit_centre(x, g.res, g.rx), audit_centre(y, g.res, g.ry), audit_centre(z, g.res, g.rz));
-    const unsigned long long m = __ballot(in);
-    if (lane == 0) {
+  if constexpr (MASKED) {
+    // ---- the region's bits from the mask: the slab's words are contiguous, a lane per word; the box as bits of the word ----
+    const unsigned long long *src = mask + ((size_t)a * g.H + z0) * (size_t)lw;
+    for (int i = tid; i < nz * lw; i += MAPAUDIT_WG) {
+      const int zl = i / lw, rem = i - zl * lw, y = rem / lay.row_words, w = rem - y * lay.row_words, z = z0 + zl;
+      const bool               in  = y >= p.lo[1] && y < p.hi[1] && z >= p.lo[2] && z < p.hi[2];
+      const unsigned long long box = in ? audit_row_mask(p.hi[0], w) & ~audit_row_mask(p.lo[0], w) : 0ull;  // (hi[0] <= L)
+      const unsigned long long m   = src[i] & box;
       region[i] = m;
       n_reg += __popcll(m);
+    }
+    n_reg = wave_sum(n_reg);  // (valid in lane 0, which is the lane that adds it below)
+  } else {
+    // ---- the region's bits, once per slab: one wave per word, one lane per cell ----
+    AuditFrustum f{};
+    if (p.frustum) {
+      for (int k = 0; k < 9; ++k) f.R[k] = cam_rot[a * 9 + k];
+      f.near_z = p.near_z, f.far_z = p.far_z, f.tan_h = p.tan_h, f.tan_v = p.tan_v;
+    }
+    for (int i = wave; i < nz * lw; i += MAPAUDIT_WG / 64) {
+      const int zl = i / lw, rem = i - zl * lw, y = rem / lay.row_words, w = rem - y * lay.row_words;
+      const int x = (w << 6) + lane, z = z0 + zl;
+      bool      in = x < g.L && x >= p.lo[0] && x < p.hi[0] && y >= p.lo[1] && y < p.hi[1] && z >= p.lo[2] && z < p.hi[2];
+      if (in && p.frustum)
+        in = audit_in_view(f, audit_centre(x, g.res, g.rx), audit_centre(y, g.res, g.ry), audit_centre(z, g.res, g.rz));
+      const unsigned long long m = __ballot(in);
+      if (lane == 0) {
+        region[i] = m;
+        n_reg += __popcll(m);
+      }
     }
   }
   __syncthreads();
@@ -290,9 +309,9 @@ __global__ __launch_bounds__(MAPAUDIT_WG) void k_map_audit(MapView test, MapView
   }
 }
 
-int refuse(const char *what) {
+int refuse(const char *what, const char *entry = "sogm_map_audit") {
   char buf[256];
-  std::snprintf(buf, sizeof(buf), "sogm_map_audit: %s", what);
+  std::snprintf(buf, sizeof(buf), "%s: %s", entry, what);
   set_error_text(buf);
   return SOGM_ERR_INVALID_ARG;
 }
@@ -310,12 +329,18 @@ extern "C" int sogm_map_audit_default_params(int T_test, int T_truth, SogmMapAud
   return SOGM_OK;
 }
 
-extern "C" int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *prm, const double *cam_rot,
-                              SogmMapAuditRow *out, double *out_dt, void *stream) {
-  using namespace sogm;
-  if (!test || !truth || !prm || !out) return refuse("null pointer");
+namespace sogm {
+namespace {
+// the body of both entries: MASKED takes the region from `mask` (and the box), the other from the box and the frustum
+template <bool MASKED>
+int map_audit_entry(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *prm, const double *cam_rot,
+                    const uint64_t *mask, SogmMapAuditRow *out, double *out_dt, void *stream) {
+  const char *entry = MASKED ? "sogm_map_audit_masked" : "sogm_map_audit";
+  const auto  refuse = [entry](const char *what) { return sogm::refuse(what, entry); };
+  if (!test || !truth || !prm || !out || (MASKED && !mask)) return refuse("null pointer");
   if (prm->tolerance < 0 || prm->tolerance > 3) return refuse("tolerance outside 0 .. 3");
   const bool frustum = (prm->flags & SOGM_MAPAUDIT_FRUSTUM) != 0;
+  if (MASKED && frustum) return refuse("SOGM_MAPAUDIT_FRUSTUM is set: the mask is the region");
   if (frustum) {
     if (!cam_rot) return refuse("SOGM_MAPAUDIT_FRUSTUM without cam_rot");
     if (!std::isfinite(prm->near_z) || !std::isfinite(prm->far_z) || !std::isfinite(prm->tan_h) || !std::isfinite(prm->tan_v))
@@ -326,7 +351,7 @@ extern "C" int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAudi
   {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-      set_error_text("sogm_map_audit: no HIP device");
+      set_error_text(MASKED ? "sogm_map_audit_masked: no HIP device" : "sogm_map_audit: no HIP device");
       return SOGM_ERR_NO_DEVICE;
     }
   }
@@ -352,7 +377,7 @@ extern "C" int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAudi
   p.lay = audit_layout(a.L, a.W, a.H, prm->tolerance, prm->slab_layers);
   if (p.lay.layers < 1) return refuse("one z layer of the grid does not fit a compute unit's LDS");
   if (!test->updated || !truth->updated) {
-    set_error_text("sogm_map_audit: a map has never been updated");
+    set_error_text(MASKED ? "sogm_map_audit_masked: a map has never been updated" : "sogm_map_audit: a map has never been updated");
     return SOGM_ERR_STATE;
   }
   p.thr[0] = prm->thr_test, p.thr[1] = prm->thr_truth;
@@ -367,10 +392,22 @@ extern "C" int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAudi
   const int     rows = test->n_agents * a.T;
   hipLaunchKernelGGL(k_map_audit_rows, dim3((rows + 63) / 64), dim3(64), 0, st, vt, vg, p, out, out_dt);
   // (more dynamic LDS than the 64 KB a launch gets by default: the attribute is a host-side setting of the function)
-  SOGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_map_audit), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     AUDIT_LDS_BYTES - AUDIT_LDS_RESERVED));
-  hipLaunchKernelGGL(k_map_audit, dim3(p.lay.slabs, test->n_agents), dim3(MAPAUDIT_WG), (size_t)p.lay.bytes, st, vt, vg, p,
-                     cam_rot, out);
+  SOGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_map_audit<MASKED>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, AUDIT_LDS_BYTES - AUDIT_LDS_RESERVED));
+  hipLaunchKernelGGL(k_map_audit<MASKED>, dim3(p.lay.slabs, test->n_agents), dim3(MAPAUDIT_WG), (size_t)p.lay.bytes, st, vt, vg,
+                     p, cam_rot, out, reinterpret_cast<const unsigned long long *>(mask));
   SOGM_HIP_CHECK(hipGetLastError());
   return SOGM_OK;
+}
+}  // namespace
+}  // namespace sogm
+
+extern "C" int sogm_map_audit(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *prm, const double *cam_rot,
+                              SogmMapAuditRow *out, double *out_dt, void *stream) {
+  return sogm::map_audit_entry<false>(test, truth, prm, cam_rot, nullptr, out, out_dt, stream);
+}
+
+extern "C" int sogm_map_audit_masked(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditParams *prm, const uint64_t *mask,
+                                     SogmMapAuditRow *out, double *out_dt, void *stream) {
+  return sogm::map_audit_entry<true>(test, truth, prm, nullptr, mask, out, out_dt, stream);
 }

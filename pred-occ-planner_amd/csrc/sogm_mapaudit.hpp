@@ -1,7 +1,8 @@
 // sogm_mapaudit.hpp — the rules of the map audit (include/sogm_abi.h "map audit" is the definition), written ONCE for the
 // host and the device:
 //   audit_occupied                 the occupancy test of one cell value
-//   audit_centre / audit_in_view   the centre of a logical cell in the map frame and the frustum test
+//   audit_centre / audit_in_view   the centre of a logical cell in the map frame and the frustum test (its two halves,
+//                                  audit_to_camera and audit_in_frustum, are also what sogm_viewmask.hpp is built on)
 //   audit_row_words / audit_row_mask / audit_dilate_word / audit_dilate_row
 //                                  an x-row of L cells as ceil(L / 64) 64-bit words (cell x is bit x % 64 of word x / 64) and
 //                                  its dilation by r cells: shifts and ORs with carries between neighbouring words, the spare
@@ -39,11 +40,21 @@ struct AuditFrustum {
 // q_j = (R[0][j] p_0 + R[1][j] p_1) + R[2][j] p_2;  in view iff q_z > near_z && q_z <= far_z && |q_x| <= q_z tan_h &&
 // |q_y| <= q_z tan_v.  A non-finite R makes a non-finite q, and every comparison with a NaN is false; an infinite q_z fails
 // q_z <= far_z (far_z is finite).
-SOGM_MAPAUDIT_HD inline bool audit_in_view(const AuditFrustum &f, double p0, double p1, double p2) {
-  const double qx = (f.R[0] * p0 + f.R[3] * p1) + f.R[6] * p2;
-  const double qy = (f.R[1] * p0 + f.R[4] * p1) + f.R[7] * p2;
-  const double qz = (f.R[2] * p0 + f.R[5] * p1) + f.R[8] * p2;
+// The two halves are one body for audit_in_view and for view_class of sogm_viewmask.hpp ("view mask" uses the same q and the
+// same four comparisons).
+SOGM_MAPAUDIT_HD inline void audit_to_camera(const AuditFrustum &f, double p0, double p1, double p2, double &qx, double &qy,
+                                             double &qz) {
+  qx = (f.R[0] * p0 + f.R[3] * p1) + f.R[6] * p2;
+  qy = (f.R[1] * p0 + f.R[4] * p1) + f.R[7] * p2;
+  qz = (f.R[2] * p0 + f.R[5] * p1) + f.R[8] * p2;
+}
+SOGM_MAPAUDIT_HD inline bool audit_in_frustum(const AuditFrustum &f, double qx, double qy, double qz) {
   return qz > f.near_z && qz <= f.far_z && __builtin_fabs(qx) <= qz * f.tan_h && __builtin_fabs(qy) <= qz * f.tan_v;
+}
+SOGM_MAPAUDIT_HD inline bool audit_in_view(const AuditFrustum &f, double p0, double p1, double p2) {
+  double qx, qy, qz;
+  audit_to_camera(f, p0, p1, p2, qx, qy, qz);
+  return audit_in_frustum(f, qx, qy, qz);
 }
 
 // ---- bit rows -------------------------------------------------------------------------------------------------------------

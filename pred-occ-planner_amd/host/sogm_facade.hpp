@@ -283,6 +283,43 @@ class RiskMap {
     if (out_dt_host) u_.get(out_dt_host, (size_t)n_);
     return out;
   }
+  // View mask (include/sogm_abi.h "view mask"; no reference counterpart): the cells of every agent's grid that its depth
+  // image speaks for.  viewParams() is sogm_view_default_params of the camera the images were rendered with; the caller sets
+  // band, classes and the frustum on it.  depth_dev: device [agents * rows * cols] (GridMap::renderDepth's); cam_rot_host
+  // [agents * 9]; cam_offset_host [agents * 3], camera centre minus map centre, or nullptr (the camera at the map centre);
+  // mask_dev: device [viewMaskWords()] 64-bit words, what auditAgainstMasked reads.  Only this map's geometry is used.
+  // Returns the counts [agents][8] (five classes, the mask's bits, two zeros).  Synchronises `st`.
+  static SogmViewParams viewParams(const SogmDepthCamera &cam) {
+    SogmViewParams prm;
+    check(sogm_view_default_params(&cam, &prm), "sogm_view_default_params");
+    return prm;
+  }
+  size_t viewMaskWords() const { return (size_t)n_ * (size_t)spec_.H * (size_t)spec_.W * (size_t)((spec_.L + 63) / 64); }
+  std::vector<int32_t> viewMask(const SogmViewParams &prm, const uint16_t *depth_dev, const double *cam_rot_host,
+                                const double *cam_offset_host, uint64_t *mask_dev, hipStream_t st = nullptr) {
+    pts_.put(cam_rot_host, (size_t)n_ * 9);
+    if (cam_offset_host) q_.put(cam_offset_host, (size_t)n_ * 3);
+    a_.resize((size_t)n_ * 8);
+    check(sogm_view_mask(ctx_, &prm, depth_dev, pts_.data(), cam_offset_host ? q_.data() : nullptr, mask_dev, a_.data(), st),
+          "sogm_view_mask");
+    if (hipStreamSynchronize(st) != hipSuccess) throw std::runtime_error("viewMask: hipStreamSynchronize failed");
+    std::vector<int32_t> counts((size_t)n_ * 8);
+    a_.get(counts.data(), counts.size());
+    return counts;
+  }
+  // auditAgainst with the region given as a mask (sogm_map_audit_masked): prm without SOGM_MAPAUDIT_FRUSTUM; the box still cuts.
+  std::vector<SogmMapAuditRow> auditAgainstMasked(RiskMap &truth, const SogmMapAuditParams &prm, const uint64_t *mask_dev,
+                                                  double *out_dt_host = nullptr, hipStream_t st = nullptr) {
+    const size_t rows = (size_t)n_ * (size_t)spec_.T;
+    audit_rows_.resize(rows);
+    u_.resize((size_t)n_);
+    check(sogm_map_audit_masked(ctx_, truth.ctx_, &prm, mask_dev, audit_rows_.data(), u_.data(), st), "sogm_map_audit_masked");
+    if (hipStreamSynchronize(st) != hipSuccess) throw std::runtime_error("auditAgainstMasked: hipStreamSynchronize failed");
+    std::vector<SogmMapAuditRow> out(rows);
+    audit_rows_.get(out.data(), rows);
+    if (out_dt_host) u_.get(out_dt_host, (size_t)n_);
+    return out;
+  }
 
  private:
   DevBuf<SogmMapAuditRow> audit_rows_;

@@ -299,24 +299,70 @@ class SogmMap:
               "sogm_download_reference_layout")
         return out
 
+    # ---- view mask (include/sogm_abi.h "view mask") ----
+    def view_mask(self, depth, cam, cam_rot, band=0.0, classes=None, far=None, cam_offset=None):
+        """The cells of every agent's grid that its depth image speaks for (sogm_view_mask).  depth: [n_agents, rows, cols]
+        uint16 image (a device tensor of int16 storage as render_depth returns it, or numpy uint16); cam: the SogmDepthCamera
+        the image was rendered with, or a filled SogmViewParams (then band, classes and far are not applied); cam_rot
+        [n_agents, 9] fp64; band: metres, the half thickness of the SURFACE class; classes: a set of SOGM_VIEWBIT_* (default
+        FREE | SURFACE); far: far_z (default max_depth); cam_offset [n_agents, 3] fp64, camera centre minus map centre, or None
+        (the camera at the map centre).  Only this map's geometry is used.  Returns device tensors (mask int64 storage of the
+        uint64 words [n_agents, H, W, ceil(L / 64)], counts int32 [n_agents, 8]: the five classes' cells, the mask's bits, two
+        zeros).  Stream-ordered, no synchronisation."""
+        if isinstance(cam, _abi.SogmViewParams):
+            prm = _abi.SogmViewParams.from_buffer_copy(cam)
+        else:
+            prm = _abi.SogmViewParams()
+            check(lib().sogm_view_default_params(C.byref(cam), C.byref(prm)), "sogm_view_default_params")
+            prm.band = float(band)
+            if classes is not None:
+                prm.classes = int(classes)
+            if far is not None:
+                prm.far_z = float(far)
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.uint16).view(np.int16))
+        depth = depth.to("cuda").contiguous()
+        if depth.element_size() != 2 or depth.numel() != self.n_agents * prm.rows * prm.cols:
+            raise ValueError("view_mask: depth is [n_agents, rows, cols] of 16-bit pixels")
+        rot = _dev(cam_rot if isinstance(cam_rot, torch.Tensor) else np.asarray(cam_rot, np.float64))
+        rot = rot.to(torch.float64).reshape(-1).contiguous()
+        if rot.numel() != 9 * self.n_agents:
+            raise ValueError("view_mask: cam_rot is [n_agents, 9]")
+        off = None
+        if cam_offset is not None:
+            off = _dev(cam_offset if isinstance(cam_offset, torch.Tensor) else np.asarray(cam_offset, np.float64))
+            off = off.to(torch.float64).reshape(-1).contiguous()
+            if off.numel() != 3 * self.n_agents:
+                raise ValueError("view_mask: cam_offset is [n_agents, 3]")
+        s = self.spec
+        mask = torch.empty((self.n_agents, s.H, s.W, (s.L + 63) // 64), dtype=torch.int64, device="cuda")
+        counts = torch.empty((self.n_agents, 8), dtype=torch.int32, device="cuda")
+        check(lib().sogm_view_mask(self._ctx, C.byref(prm), depth.data_ptr(), rot.data_ptr(),
+                                   off.data_ptr() if off is not None else None, mask.data_ptr(), counts.data_ptr(), _stream()),
+              "sogm_view_mask")
+        return mask, counts
+
     # ---- map audit (include/sogm_abi.h "map audit") ----
     def audit_against(self, truth, thr_test=None, thr_truth=None, tolerance=0, box=None, frustum=None, cam_rot=None,
-                      slice_map=None, slab_layers=0):
+                      slice_map=None, slab_layers=0, mask=None):
         """Scores this map (the perceived one) against `truth` (another SogmMap of the same grid), agent by agent and slice
         by slice (sogm_map_audit).  thr_*: occupancy thresholds (default: each spec's risk_threshold); tolerance: r cells,
         0 .. 3; box: (lo [3], hi [3]) logical cells or None (the whole grid); frustum: (near_z, far_z, tan_h, tan_v) with
         cam_rot [n_agents, 9] fp64 (row-major camera-to-world, numpy or a device tensor), or None; slice_map: the truth slice of
         every test slice (-1: skip; default: the identity on the slices both maps have).  Returns a dict of numpy int32 arrays
         [n_agents, T_test] (n_region, n_test, n_truth, n_both, n_test_near, n_truth_near, truth_slice, status) plus `dt`
-        (float64 [n_agents]: this map's stamp minus truth's).  Synchronises to read the rows back."""
-        rows, dt = self.audit_against_device(truth, thr_test, thr_truth, tolerance, box, frustum, cam_rot, slice_map, slab_layers)
+        (float64 [n_agents]: this map's stamp minus truth's).  Synchronises to read the rows back.  mask: a view_mask (device
+        tensor [n_agents, H, W, ceil(L / 64)] of 64-bit words) as the region instead of the frustum (sogm_map_audit_masked);
+        frustum must then be None."""
+        rows, dt = self.audit_against_device(truth, thr_test, thr_truth, tolerance, box, frustum, cam_rot, slice_map, slab_layers,
+                                             mask)
         host = rows.cpu().numpy()
         out = {name: np.ascontiguousarray(host[:, :, k]) for k, name in enumerate(_abi.MAPAUDIT_ROW_FIELDS)}
         out["dt"] = dt.cpu().numpy()
         return out
 
     def audit_against_device(self, truth, thr_test=None, thr_truth=None, tolerance=0, box=None, frustum=None, cam_rot=None,
-                             slice_map=None, slab_layers=0):
+                             slice_map=None, slab_layers=0, mask=None):
         """audit_against without the read-back: (rows int32 [n_agents, T_test, 8] in SogmMapAuditRow's field order, dt float64
         [n_agents]) as device tensors, stream-ordered, no synchronisation (a cam_rot given as a device tensor is used as is)."""
         prm = _abi.SogmMapAuditParams()
@@ -345,6 +391,14 @@ class SogmMap:
                     raise ValueError("audit_against: cam_rot is [n_agents, 9]")
         rows = torch.empty((self.n_agents, T, 8), dtype=torch.int32, device="cuda")
         dt = torch.empty((self.n_agents,), dtype=torch.float64, device="cuda")
+        if mask is not None:
+            s = self.spec
+            if mask.element_size() != 8 or mask.numel() != self.n_agents * s.H * s.W * ((s.L + 63) // 64) or not mask.is_cuda:
+                raise ValueError("audit_against: mask is a device tensor [n_agents, H, W, ceil(L / 64)] of 64-bit words")
+            mask = mask.contiguous()
+            check(lib().sogm_map_audit_masked(self._ctx, truth.ctx, C.byref(prm), mask.data_ptr(), rows.data_ptr(), dt.data_ptr(),
+                                              _stream()), "sogm_map_audit_masked")
+            return rows, dt
         check(lib().sogm_map_audit(self._ctx, truth.ctx, C.byref(prm), rot.data_ptr() if rot is not None else None,
                                    rows.data_ptr(), dt.data_ptr(), _stream()), "sogm_map_audit")
         return rows, dt

@@ -20,7 +20,15 @@ the interval [s, s + 1) x time_resolution (0.2 s): it is the slice getClearOcccu
 test slice t is mapped to s = floor(prediction_times[t] / time_resolution) — 1, 3, 4, 6, 7, 9, 10, 12, 13 for t = 0 .. 8 —
 the slice a planner would read on the truth map for that instant, and to -1 (skipped, status 2) when that lies beyond the
 truth map's last slice (t >= 9 at T = 15).  Test slice 0 is therefore NOT "now": the particle map publishes no present
-slice."""
+slice.
+
+--region frustum    (default) the region is the camera's frustum, as above: it holds an obstacle's whole volume.
+--region visible    the region is what the camera saw (include/sogm_abi.h "view mask"): sogm_view_mask classifies every cell
+                    against the frame's own depth image — cam_offset = camera position minus the test map's map_state centre,
+                    the same frustum, --band METRES as the half thickness of the seen surface — and the cells that are FREE
+                    or SURFACE are handed to sogm_map_audit_masked.  The line then also carries the five class counts (summed
+                    over agents and frames), the view mask's ms per call, and, from the SAME run and the same maps, the
+                    frustum audit's ms per call and ratios ("frustum_same_run"): the masked audit's time is held to that."""
 import argparse, importlib, json, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -34,7 +42,8 @@ def slice_map_for(prediction_times, T_test, T_truth, time_resolution):
     return out
 
 
-def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, cols=640, seed=0x5067, dt=0.1, slab_layers=0):
+def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, cols=640, seed=0x5067, dt=0.1, slab_layers=0,
+        region="frustum", band=0.0):
     pop = importlib.import_module("pred-occ-planner_amd")
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     dsp = importlib.import_module("pred-occ-planner_amd.dsp")
@@ -64,10 +73,14 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
     total = np.zeros((spec.T, 8), np.int64)
     status = set()
+    visible = region == "visible"
+    ev_view = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
+    ev_fr = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
+    total_fr, classes = np.zeros((spec.T, 8), np.int64), np.zeros(5, np.int64)
     for k in range(frames):
         frame = tl.frames(k, 1)[0]
         stamps = sogm._dev(np.full(A, float(sc["stamps"][0]) + k * dt), np.float64)
-        _, cl, raw_rng, _, hit = depth.render_depth_swarm(frame, cam, pos_d, rot_d, None, want_hit=True)
+        img, cl, raw_rng, _, hit = depth.render_depth_swarm(frame, cam, pos_d, rot_d, None, want_hit=True)
         if labels == "gt":
             pts, cnt, lab, _ = m.filterPointCloudLabelled(cl, hit, raw_rng, frame, None, 0.0, 0.15, cap)
             lab = lab.view(-1, 4)
@@ -79,9 +92,23 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
         state = [m.map_state(a) for a in range(A)]
         truth.updateWorld(frame, sogm._dev(np.stack([c for _, c in state]), np.float32),
                           sogm._dev(np.array([t for t, _ in state]), np.float64))
-        ev[k][0].record()
-        rows_d, dt_d = m.audit_against_device(truth, None, None, tolerance, None, frustum, rot_d, smap, slab_layers)
-        ev[k][1].record()
+        if visible:
+            off = sogm._dev(pos - np.stack([c for _, c in state]).astype(np.float64), np.float64)
+            ev_view[k][0].record()
+            mask, counts = m.view_mask(img, cam, rot_d, band=band, cam_offset=off)
+            ev_view[k][1].record()
+            ev[k][0].record()
+            rows_d, dt_d = m.audit_against_device(truth, None, None, tolerance, None, None, None, smap, slab_layers, mask=mask)
+            ev[k][1].record()
+            ev_fr[k][0].record()
+            rows_f, _ = m.audit_against_device(truth, None, None, tolerance, None, frustum, rot_d, smap, slab_layers)
+            ev_fr[k][1].record()
+            total_fr += rows_f.cpu().numpy().astype(np.int64).sum(axis=0)
+            classes += counts.cpu().numpy()[:, :5].astype(np.int64).sum(axis=0)
+        else:
+            ev[k][0].record()
+            rows_d, dt_d = m.audit_against_device(truth, None, None, tolerance, None, frustum, rot_d, smap, slab_layers)
+            ev[k][1].record()
         r = rows_d.cpu().numpy()
         status |= set(r[:, :, 7].reshape(-1).tolist())
         total += r.astype(np.int64).sum(axis=0)
@@ -109,6 +136,19 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
            "audit_bytes_per_call": nbytes, "audit_TB_per_s": nbytes / (float(np.median(steady)) * 1e-3) / 1e12,
            "audit_frac_of_8TB_per_s": nbytes / (float(np.median(steady)) * 1e-3) / 8e12,
            "dense_clear_same_run": clear}
+    if visible:
+        after_first = lambda pairs: np.array([a.elapsed_time(b) for a, b in pairs])[1 if frames > 1 else 0:]   # noqa: E731
+        ms_view, ms_fr = after_first(ev_view), after_first(ev_fr)
+        names = pop._abi.VIEW_CLASS_NAMES
+        out.update({"region": "visible", "band": band, "class_counts": {names[c]: int(classes[c]) for c in range(5)},
+                    "view_mask_ms_per_call": float(np.median(ms_view)), "view_mask_ms_after_first": ms_view.round(4).tolist(),
+                    "frustum_same_run": {
+                        "audit_ms_per_call": float(np.median(ms_fr)), "audit_ms_after_first": ms_fr.round(4).tolist(),
+                        "n_region": total_fr[audited, 0].tolist(), "n_test": total_fr[audited, 1].tolist(),
+                        "n_truth": total_fr[audited, 2].tolist(),
+                        "precision_strict": ratio(total_fr[:, 3], total_fr[:, 1]), "recall_strict": ratio(total_fr[:, 3], total_fr[:, 2]),
+                        f"precision_within_{tolerance}": ratio(total_fr[:, 4], total_fr[:, 1]),
+                        f"recall_within_{tolerance}": ratio(total_fr[:, 5], total_fr[:, 2])}})
     g.close()
     m.close()
     truth.close()
@@ -125,5 +165,9 @@ if __name__ == "__main__":
     ap.add_argument("--rows", type=int, default=480)
     ap.add_argument("--cols", type=int, default=640)
     ap.add_argument("--slab-layers", type=int, default=0, help="SogmMapAuditParams.slab_layers (0: the layout chooses)")
+    ap.add_argument("--region", choices=["frustum", "visible"], default="frustum",
+                    help="visible: only the cells the frame's depth image shows free or on the seen surface")
+    ap.add_argument("--band", type=float, default=0.0, help="metres: half the thickness of the seen surface (--region visible)")
     a = ap.parse_args()
-    print(json.dumps(run(a.grid, a.agents, a.frames, a.labels, a.tolerance, a.rows, a.cols, slab_layers=a.slab_layers)))
+    print(json.dumps(run(a.grid, a.agents, a.frames, a.labels, a.tolerance, a.rows, a.cols, slab_layers=a.slab_layers,
+                         region=a.region, band=a.band)))
