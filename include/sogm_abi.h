@@ -1231,7 +1231,7 @@ int sogm_planner_counters(sogm_planner *p, int64_t *out_host, int reset);
  * The codes — which kernel waited for what (the same values in sogm_flight_stats out_hdr[4] for a flight, and, as 100 + code,
  * in sogm_planner_flow_failures after a failed flight; enum FlowCode of csrc/sogm_handover.hpp):
  *    1  k_flow_gate: every search workgroup of the replan resident
- *    2  k_corridor_flow / k_finish_flow / k_prestamp_flow: its entry of the ready list (searches done / QPs done / records published)
+ *    2  k_worker_flow (corridor blocks / finishing blocks) / k_prestamp_flow: its entry of the ready list (searches done / QPs done / records published)
  *    3  k_qp_flow: its entry of the list of agents whose corridors are final
  *    4  the second search attempt (k_astar, k_flight_search): the first attempt's verdict
  *    6  k_prestamp_flow, k_update_flow, the heads of k_flight_map: a stage counter (the lower tickets of the agent's stamp; the

@@ -22,7 +22,7 @@ int sogm_sparse_reset_state(sogm_ctx *ctx, int32_t *out_host);
  * SOGM_SPARSE_RESET, SOGM_FLOW and SOGM_RCCL_LIB).  Keys (defaults in parentheses):
  *   read by sogm_planner_create (set them before):  "groups" (2) agent groups of the grouped-stream replan,
  *     "spec_astar" (1) speculative second search, "clear_gate_frac" (1.0);
- *   read at every call:  "qp_wgs" (0 = half the CUs) persistent QP workgroups, "stamp_wgs" (256), "stamp_bits_wgs" (0 = stamp_wgs), "stamp_cached" (0), "stamp_lds_log" (1), "stamp_lds_kb" (0), "splat_wgs" (256),
+ *   read at every call:  "qp_wgs" (0 = half the CUs) persistent QP workgroups, "finish_wgs" (0 = min(agents, 64)) finishing and "corridor_wgs" (0 = min(4 per CU, one per segment slot)) corridor blocks of the dataflow replan's worker kernel, "stamp_wgs" (256), "stamp_bits_wgs" (0 = stamp_wgs), "stamp_cached" (0), "stamp_lds_log" (1), "stamp_lds_kb" (0), "splat_wgs" (256),
  *     "splat_overlap" (1), "reset_wgs" (32), "reset_lanes" (0 = auto: 2 under the replan, 4 alone), "reset_unroll"
  *     (0 = auto: 1 / 8), "reset_late" (1), "prestamp_bits" (32), "prestamp_marks" (64), "prestamp_wgs" (0 = 8 per CU), "prestamp_stream" (1), "prestamp_gate_frac" (0.9: the pre-stamp of the next map starts when that share of the agents' corridors is final — an event recorded behind a gate kernel on the resets' stream; 1.0: when all are),
  *     "prestamp_late_agents" (8), "prestamp_late_bits" (128), "prestamp_late_marks" (256), and the dense clear's
@@ -218,6 +218,14 @@ int sogm_finish_batched(sogm_planner *counters_of, double corridor_tau, const in
  * and verdict of the planner now and of what a parallel rules hook left set (0: every finalising wave cleaned up).
  * Synchronises the device. */
 int sogm_debug_corridor_pairs(sogm_planner *p, unsigned long long *out4);
+
+/* Diagnostics: the number of HIP streams the planner and its map context hold now (the return value; negative: an SOGM_ERR_*
+ * code).  Every stream takes a place in the runtime's pool of hardware queues, so streams are
+ * created by the first call that launches on them: 1 after sogm_create (the resets' side stream), 3 once a dataflow
+ * sogm_replan has run (+ its worker and QP streams; the searches run on the caller's stream), one more each for a pre-stamp on
+ * a stream of its own, the dense-clear mode's wide launch, the grouped path's group streams, the update flow, the trajectory
+ * exchange, a flight's four masked streams and sogm_debug_flow_peek.  Host-side count, no HIP call. */
+int sogm_debug_streams_held(sogm_planner *p);
 
 /* Diagnostics: every agent's last QP solve as its workgroup clocked it, host out[n_agents][SOGM_QP_STAT_N].  Times are
  * ticks of the device's 100 MHz wall clock unless said otherwise.  Synchronises the device. */

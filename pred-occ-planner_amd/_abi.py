@@ -336,6 +336,7 @@ PROTOTYPES = {
     "sogm_finish_batched": (_i, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
                                  _vp, _vp, _i, _vp]),
     "sogm_debug_corridor_pairs": (_i, [_vp, _vp]),
+    "sogm_debug_streams_held": (_i, [_vp]),
     "sogm_debug_qp_stats": (_i, [_vp, _vp]),  # [A][QP_STAT_N] int64
     "sogm_debug_qp_layout": (_i, [_vp, _i, _vp, _vp]),
     "sogm_replan": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -400,7 +400,15 @@ static int launch_clear_impl(sogm_ctx *c, hipStream_t st, float *grid, bool poli
   const int    nblk     = (int)(want < 1 ? 1 : (want > max_wgs ? max_wgs : want));
   // clear_wide_wgs = 0 switches the adaptive width off; clear_wide_bound: stores in flight per wave of the wide launch
   const int wide_wgs = c->tune_i(SOGM_TUNE_CLEAR_WIDE_WGS), wide_bound = c->tune_i(SOGM_TUNE_CLEAR_WIDE_BOUND);
-  if (polite && part == 0 && c->clear_gate && c->clear_cursor && c->side2 && wide_wgs > 0 && nt) {
+  // The wide part belongs to the dense-clear mode, where a whole grid is cleared under every replan.  With the sparse reset on,
+  // a dense clear happens once per grid (first use) or behind a dense writer: it stays one narrow launch on `st`, and the
+  // context holds no stream for a second one.
+  if (polite && part == 0 && c->clear_gate && c->clear_cursor && !c->sparse && wide_wgs > 0 && nt) {
+    if (!c->side2) {  // the wide part's stream, at its first launch
+      Resources::Setup setup(c->res);
+      SOGM_HIP_CHECK(c->res.stream(&c->side2));
+      setup.done();
+    }
     const size_t        nchunks = (nall + CLEAR_CHUNK_V4 - 1) / CLEAR_CHUNK_V4;
     unsigned long long *cur = c->clear_cursor + (c->clear_seq & 1), *nxt = c->clear_cursor + ((c->clear_seq + 1) & 1);
     ++c->clear_seq;

@@ -106,9 +106,9 @@ int sogm_create(const SogmSpec *spec, int n_agents, int device, sogm_ctx **out) 
   if (e == hipSuccess) e = c->res.device(&c->d_stamps, sizeof(double) * n_agents, true);
   if (e == hipSuccess) e = c->res.device(&c->d_scratch_vt, sizeof(float) * (size_t)c->geom.V * spec->T);
   if (e == hipSuccess) e = c->res.device(&c->clear_cursor, 2 * sizeof(unsigned long long), true);
+  // (side2 and pstream are created by the first launch that uses them — a dense clear's wide part, a pre-stamp with a
+  // stream of its own: every stream takes a place in the runtime's pool of hardware queues)
   if (e == hipSuccess) e = c->res.stream(&c->side);
-  if (e == hipSuccess) e = c->res.stream(&c->side2);
-  if (e == hipSuccess) e = c->res.stream(&c->pstream);
   if (e == hipSuccess) e = c->res.event(&c->ev_side2_go);
   if (e == hipSuccess) e = c->res.event(&c->ev_side2_done);
   if (e == hipSuccess) e = c->res.event(&c->ev_grid_free);

@@ -24,10 +24,12 @@
 // The device bodies the kernels inline are in sogm_corridor.hpp (points, FIRI segment, bookkeeping, the segment slot), the
 // ellipsoid optimiser in sogm_mvie.hpp, the wave LP and the LDS layouts in sogm_lp.hpp.  The flight's worker kernel, which
 // runs the same segment slot, is written in sogm_flight_light.hpp and compiled here.  How a replan ends (isSafeAfterOpt,
-// records, counters) is sogm_finish.hip.
+// records, counters) is sogm_finish.hpp / sogm_finish.hip; the dataflow replan's finishing role runs in this file's worker
+// kernel (k_worker_flow).
 #include <hip/hip_runtime.h>
 
 #include "sogm_corridor.hpp"
+#include "sogm_finish.hpp"
 
 namespace sogm {
 
@@ -146,19 +148,48 @@ __global__ void k_pairs_residue(const unsigned *words, int n, unsigned long long
 }
 
 // =================================================================================================
-// Dataflow kernel C (sogm_replan, pipelining modes 0 / 2 / 3): ONE persistent launch for the whole corridor stage.
-// A workgroup (one wave) takes tickets; ticket k is segment k % 16 of the (k / 16)-th agent whose A* search has
-// finished (k_astar publishes agents in completion order), so an agent's corridors start the moment ITS search is
-// done — not when the slowest search of a group is.  The wave extracts the segment's obstacle points itself, runs
-// FIRI / MVIE / shrink / validity, and the wave that completes an agent's last segment does the per-agent
+// Dataflow kernel W (sogm_replan, pipelining modes 0 / 2 / 3): ONE persistent launch of one-wave workgroups for the
+// corridor stage and for the end of every agent's replan, the role given by the block index (the flight's k_flight_light
+// is the same fusion over one queue; both are compiled in this unit, sogm_flight_light.hpp says why).  One launch, one
+// stream: with the caller's stream, the QP kernel's and the resets' the tick keeps four streams busy, ROCm's default number
+// of hardware queues.
+// Blocks [0, wg_f) finish: a wave takes the agent whose QP finished ticket-th, runs finish_agent (what k_safe_after_opt +
+// k_pack_records do in the grouped path) and hands the agent to the pre-stamp.  The lowest indices are dispatched first:
+// the finishers are resident from the start, and each draws its first FLOW_F_TICKET as it starts — k_prestamp_gate
+// reads that word as "finishing waves resident".
+// The other blocks are the corridor stage.  A wave takes tickets; ticket k is segment k % 16 of the (k / 16)-th agent
+// whose A* search has finished (k_astar publishes agents in completion order), so an agent's corridors start the moment
+// ITS search is done — not when the slowest search of a group is.  The wave extracts the segment's obstacle points itself,
+// runs FIRI / MVIE / shrink / validity, and the wave that completes an agent's last segment does the per-agent
 // bookkeeping (adjacent intersections, goal projection) and publishes the agent to the QP kernel's ready list.
 // Waiting is a bounded spin (s_sleep polling of one word); a timeout raises FlowCtl::err and every kernel of the
-// tick drains.
+// tick drains.  Dynamic LDS: the segment layout's, of which the finishers use the prefix LpLds (sogm_lp.hpp).
 // =================================================================================================
-__global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerParams pp, CorridorWorkspace ws,
-                                                      FlowCtl fc, CorridorIO io, int n_agents) {
+__global__ __launch_bounds__(64) void k_worker_flow(MapView m, SogmPlannerParams pp, CorridorWorkspace ws, FlowCtl fc,
+                                                    CorridorIO io, FinishArgs f, int n_agents, int wg_f) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane  = threadIdx.x;
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x < wg_f) {  // ---- finishing role ----
+    for (;;) {
+      const int k = flow_ticket(&fc.hdr[FLOW_F_TICKET]);
+      if (k >= n_agents) break;
+      const int a = flow_wait_slot(fc.f_ready + k, &fc.hdr[FLOW_ERR]);
+      if (a < 0) break;
+      __threadfence();
+      const int  code = finish_agent(f, a, LpLds::carve(smem), lane);
+      const bool safe = (code & 1) != 0;
+      if (fc.p_ready) {  // the agent's record is final: hand it to the pre-stamp
+        __threadfence();
+        if (lane == 0) publish_next(fc.p_ready, &fc.hdr[FLOW_P_READY_N], a);
+      }
+      if (lane == 0) {
+        fc.ts[a * 8 + 6] = wall_clock64();
+        finish_count(f, a, safe);
+      }
+    }
+    return;
+  }
+  // ---- corridor role ----
   const int total = n_agents * SOGM_MAX_PIECES;
   for (;;) {
     const int k = flow_ticket(&fc.hdr[FLOW_C_TICKET]);
@@ -177,10 +208,11 @@ __global__ __launch_bounds__(64) void k_corridor_flow(MapView m, SogmPlannerPara
   }
 }
 
-hipError_t launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                                const FlowCtl &fc, int n_agents, int n_workgroups, const CorridorIO &io, hipStream_t st) {
-  hipLaunchKernelGGL(k_corridor_flow, dim3(n_workgroups), dim3(64), SegmentLds<6>::bytes(pp.pc_capacity), st, m, pp,
-                     ws, fc, io, n_agents);
+hipError_t launch_worker_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlowCtl &fc,
+                              int n_agents, int n_finish, int n_corridor, const CorridorIO &io, const FinishArgs &f,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(k_worker_flow, dim3(n_finish + n_corridor), dim3(64), SegmentLds<6>::bytes(pp.pc_capacity), st, m, pp,
+                     ws, fc, io, f, n_agents, n_finish);
   return hipGetLastError();
 }
 

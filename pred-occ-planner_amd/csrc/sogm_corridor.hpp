@@ -702,7 +702,7 @@ __device__ __forceinline__ void corridor_finalize_body(const SogmPlannerParams &
   }
 }
 
-// One segment slot of an agent, run by a one-wave workgroup of k_corridor_flow or k_flight_light: its obstacle points, its
+// One segment slot of an agent, run by a one-wave workgroup of k_worker_flow or k_flight_light: its obstacle points, its
 // polytope, its completion counted in seg_done[agent] and — if that made it the agent's last slot (`cumulative`: the counter
 // runs on over the flight's ticks) — the per-agent bookkeeping, with the LP view laid over the segment layout's head
 // (SegmentLds).  True if this wave finalised the agent: publishing it is the caller's.  stamps: the flight's (null: none).

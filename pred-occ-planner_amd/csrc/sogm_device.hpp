@@ -526,6 +526,8 @@ __device__ inline bool traj_eval_record(const SogmTrajRecord &r, double t_abs, d
   X(SPEC_ASTAR, "spec_astar", 1, 0, 1)           /* [planner create] speculative second search beside the first          */  \
   X(CLEAR_GATE_FRAC, "clear_gate_frac", 1, 0, 1) /* [planner create] fraction of agents with final corridors that opens the wide clear */ \
   X(QP_WGS, "qp_wgs", 0, 0, 1024)                   /* persistent QP workgroups of the dataflow replan; 0 = half the CUs    */  \
+  X(FINISH_WGS, "finish_wgs", 0, 0, 64)           /* finishing blocks of the dataflow replan's worker kernel; 0 = min(agents, 64) */  \
+  X(CORRIDOR_WGS, "corridor_wgs", 0, 0, 65536)    /* corridor blocks of that kernel; 0 = min(4 per CU, one per segment slot) */  \
   X(QP_ABLATE, "qp_ablate", 0, 0, 255)             /* phase ablation mask (only in -DSOGM_QP_ABLATE_BUILD libraries)       */  \
   X(CLEAR_WGS, "clear_wgs", 0, 0, 65536)             /* dense clear: workgroups; 0 = 64 / 80 polite, 2048 alone              */  \
   X(CLEAR_THROTTLE, "clear_throttle", 0, 0, 64)   /* dense clear: stores in flight per wave when clear_wgs is set         */  \
@@ -609,7 +611,8 @@ struct sogm_ctx {
   int            overlap;     // tick pipelining: 0 off, 1 pre-clear in place, 2 / 3 pre-clear of spare grids
   sogm::GridPool pool;      // the 1 to 3 grids d_grid rotates through, their logs and histories (sogm_gridpool.hpp)
   hipStream_t    side;
-  hipStream_t    pstream;     // the pre-stamp's stream (tuning key prestamp_stream; the resets stay on `side`)
+  hipStream_t    pstream;     // the pre-stamp's stream (tuning key prestamp_stream; the resets stay on `side`); created by the
+                              // first replan that pre-stamps on it
   hipEvent_t     ev_gate_frac;  // (the same for prestamp_gate_frac < 1: recorded behind a gate kernel with that share of the agents as its target)
   int            gate_frac_valid, gate_frac_agents;  // gate_frac_agents: set per replan before queue_spare_clears (0: no such gate)
   hipEvent_t     ev_gate_open;  // recorded on `side` behind the reset's gate kernel of the replan being queued ("every
@@ -631,7 +634,7 @@ struct sogm_ctx {
   int                 wide_clear_pending;  // a dense adaptive clear was queued since the last update wrote epoch 0
   unsigned long long *clear_cursor;  // [2], used in turn (clear_seq)
   unsigned            clear_seq;
-  hipStream_t         side2;  // the wide part's stream
+  hipStream_t         side2;  // the wide part's stream (created at its first launch: dense-clear mode only)
   hipEvent_t          ev_side2_go, ev_side2_done;
   float         *d_filter_cells;   // filterPointCloud leaf accumulators [A][max_cells][4] (lazy)
   void          *d_filter_box;
@@ -662,7 +665,7 @@ struct sogm_ctx {
   // set by a publishing sogm_replan: the event after which `records_final_ptr` (the host's own records) and every
   // reader of the swarm table inside that replan are done — the finishing kernel's end.  sogm_traj_allgather of exactly
   // those records starts from it instead of from the caller's stream position, i.e. under the pre-stamp's tail.
-  hipEvent_t            ev_records_final;  // an alias of the planner's ev_fdone[3]: not owned here
+  hipEvent_t            ev_records_final;  // an alias of the planner's ev_records (behind the worker kernel): not owned here
   const SogmTrajRecord *records_final_ptr;
   int                   records_final_valid;
   // set by a pre-stamping sogm_replan: the caller's stream is NOT joined to the pre-stamp's end inside that call — the

@@ -1,7 +1,7 @@
 // sogm_finish.hip — the end of a replan in all its forms: isSafeAfterOpt and the record / outcome count of every agent.
 // Grouped path (sogm_replan, pipelining mode 1, and the per-stage entry sogm_safe_after_opt): k_fill_i32 + k_safe_after_opt
-// (launch_deconflict), then k_pack_records.  Dataflow replan: k_finish_flow, one persistent launch that does both per agent
-// as its QP finishes.  The flight's finish is the WK_FINISH branch of k_flight_light (sogm_flight_light.hip).  All of them
+// (launch_deconflict), then k_pack_records.  Dataflow replan: the finishing blocks of k_worker_flow (sogm_corridor.hip), which
+// do both per agent as its QP finishes.  The flight's finish is the WK_FINISH branch of k_flight_light (sogm_flight_light.hpp).  All of them
 // share the device bodies and the outcome rule of sogm_finish.hpp.
 // Test hook (sogm_finish_batched, include/sogm_abi_debug.h): both forms on a FinishArgs the caller injects — the grouped
 // launchers as they are, or k_finish_wave, finish_agent + finish_count per agent without the dataflow's hand-over control.
@@ -32,32 +32,8 @@ __global__ void k_fill_i32(int32_t *p, int n, int32_t v, int agent0) {
   if (i < n) p[agent0 + i] = v;
 }
 
-// Dataflow kernel F (sogm_replan): ONE persistent launch; a wave takes the agent whose QP finished ticket-th, runs
-// finish_agent (what k_safe_after_opt + k_pack_records do in the grouped path) and hands the agent to the pre-stamp.
-__global__ __launch_bounds__(64) void k_finish_flow(FlowCtl fc, FinishArgs f, int n_agents) {
-  extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-  const int lane = threadIdx.x;
-  for (;;) {
-    const int k = flow_ticket(&fc.hdr[FLOW_F_TICKET]);
-    if (k >= n_agents) break;
-    const int a = flow_wait_slot(fc.f_ready + k, &fc.hdr[FLOW_ERR]);
-    if (a < 0) break;
-    __threadfence();
-    const int  code = finish_agent(f, a, LpLds::carve(s_dyn), lane);
-    const bool safe = (code & 1) != 0;
-    if (fc.p_ready) {  // the agent's record is final: hand it to the pre-stamp
-      __threadfence();
-      if (lane == 0) publish_next(fc.p_ready, &fc.hdr[FLOW_P_READY_N], a);
-    }
-    if (lane == 0) {
-      fc.ts[a * 8 + 6] = wall_clock64();
-      finish_count(f, a, safe);
-    }
-  }
-}
-
 // The finishing wave alone (sogm_finish_batched with SOGM_FINISH_WAVE): one one-wave workgroup per agent runs what
-// k_finish_flow and k_flight_light inline for an agent, with no ticket, ready list or hand-over around it.
+// k_worker_flow and k_flight_light inline for an agent, with no ticket, ready list or hand-over around it.
 __global__ __launch_bounds__(64) void k_finish_wave(FinishArgs f) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   const int a = blockIdx.x, lane = threadIdx.x;
@@ -86,7 +62,7 @@ __global__ void k_pack_records(int A, FinishArgs f, int agent0) {
   for (int i = 0; i < SOGM_MAX_PIECES * 15; ++i)
     r.cpts[i] = (good && i < npoly * 15) ? f.cpts[(size_t)a * SOGM_MAX_PIECES * 15 + i] : 0.0;
   f.out_ok[a] = good ? 1 : 0;
-  if (f.pub_own) {  // publication, as k_finish_flow does it (sogm_planner_set_publish)
+  if (f.pub_own) {  // publication, as the dataflow replan's finishers do it (sogm_planner_set_publish)
     if (good) f.pub_own[a] = r;
     if (f.pub_table) f.pub_table[a] = f.pub_own[a];
   }
@@ -99,11 +75,6 @@ hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *np
   if (n_rec > 0)
     hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), LpLds::bytes(), st, cpts, npoly, rec, n_rec,
                        ego_ids, t_now, out_safe, agent0, counters);
-  return hipGetLastError();
-}
-
-hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st) {
-  hipLaunchKernelGGL(k_finish_flow, dim3(n_workgroups), dim3(64), LpLds::bytes(), st, fc, f, n_agents);
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // sogm_finish.hpp — how a replan ends.  The outcome rule is plain C++ for host and device (tests/finish_rules_host_test.cpp
 // builds it with the host compiler); behind __HIPCC__ the device bodies the finishing kernels inline: isSafeAfterOpt for one
-// pair, its one-lane-per-record prefilter, and what the finishing role does for one agent (sogm_finish.hip's k_finish_flow,
+// pair, its one-lane-per-record prefilter, and what the finishing role does for one agent (the finishing blocks of sogm_corridor.hip's k_worker_flow,
 // sogm_flight_light.hpp's k_flight_light).
 #pragma once
 #include "sogm_lp.hpp"
@@ -9,7 +9,7 @@ namespace sogm {
 
 // where replan() ended (baseline_fake.cpp: :292 no path, :405-419 corridors, :447 QP, :455 unsafe): a SOGM_CNT_* index.
 // replan_outcome_of takes the QP's status as a callable and reads it only behind a search and corridors — the device's
-// wave-per-agent bodies have always loaded it there, and the code the compiler makes of k_finish_flow and k_flight_light
+// wave-per-agent bodies have always loaded it there, and the code the compiler makes of the finishing blocks of k_worker_flow and k_flight_light
 // follows these loads (profiles/EXPERIMENTS.md); replan_outcome is the same rule over plain values.
 template <class Status>
 LDS_HD inline int replan_outcome_of(int ret, int npoly, Status status, bool safe) {
@@ -230,7 +230,7 @@ __device__ inline bool deconflict_prefilter(const double *sA, int nA, const doub
 }
 
 // What the finishing role does for one agent (one wave): ParticleATC::isSafeAfterOpt against every record of the swarm
-// (when a swarm is set), then the agent's SogmTrajRecord / ok flag and the publication — shared by k_finish_flow
+// (when a swarm is set), then the agent's SogmTrajRecord / ok flag and the publication — shared by the finishing blocks of k_worker_flow
 // (sogm_replan) and k_flight_light (sogm_flight_run).  Returns bit 0 = safe, bit 1 = replan() returned true.
 __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, const LpScratch &sc, int lane) {
   const int M    = f.npoly[a];

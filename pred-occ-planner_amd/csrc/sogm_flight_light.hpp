@@ -61,7 +61,7 @@ __device__ inline void flight_fsm_apply(const FlightFsmDev &u, const FinishArgs 
 
 // Flight kernel L (sogm_flight_run): role-less one-wave workgroups over the corridor + finish work queue.  A wave takes a
 // ticket (one atomicAdd), waits for the descriptor at that position and does what it says.  WK_CORRIDOR: one of the 16
-// segment slots of an agent whose search is done, as in k_corridor_flow; the wave that completes the agent's last slot
+// segment slots of an agent whose search is done, as in k_worker_flow; the wave that completes the agent's last slot
 // finalises its corridors and queues the QP.  WK_FINISH: finish_agent against table ver(k - 2), the record into ver(k) and
 // the flight log, then the tick's accounting and the agent's next map head.  17 descriptors per (agent, tick).
 __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParams pp, CorridorWorkspace ws, FlightCtl fl,

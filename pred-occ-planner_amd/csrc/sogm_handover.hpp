@@ -16,7 +16,7 @@ namespace sogm {
 // kernels of one tick hand agents to each other through ready lists instead of stream order.
 //   hdr[FLOW_*] counters; seg_done[A] finished segment slots per agent; a_ready[A] agents in A* completion order;
 //   q_ready[A] agents in corridor completion order (entries are -1 until published).
-//   f_ready[A] agents in QP completion order; p_ready[A] agents whose record is published (k_finish_flow done), the
+//   f_ready[A] agents in QP completion order; p_ready[A] agents whose record is published (the finishing blocks of k_worker_flow done), the
 //   pre-stamp's input; stage[A] per-agent progress counter of the pre-stamp (0 at the start of a replan).
 enum { FLOW_A_RESIDENT = 0, FLOW_A_READY_N = 1, FLOW_C_TICKET = 2, FLOW_Q_READY_N = 3, FLOW_Q_TICKET = 4,
        FLOW_ERR = 5, FLOW_F_READY_N = 6, FLOW_F_TICKET = 7, FLOW_P_READY_N = 8, FLOW_P_TICKET = 9,
@@ -284,7 +284,7 @@ constexpr unsigned wk_advance_sub(unsigned desc0, int i) { return desc0 + ((unsi
 enum FlowCode : int {
   FLOW_CODE_NONE           = 0,   // nothing is raised (k_astar's wait for the reset generation: the finishing kernel's own limit fails the tick)
   FLOW_CODE_RESIDENCY_GATE = 1,   // replan, k_flow_gate: every search workgroup resident (hdr[FLOW_A_RESIDENT])
-  FLOW_CODE_READY_SLOT     = 2,   // replan, flow_wait_slot: k_corridor_flow for a_ready, k_finish_flow for f_ready, k_prestamp_flow for p_ready
+  FLOW_CODE_READY_SLOT     = 2,   // replan, flow_wait_slot: k_worker_flow: its corridor blocks for a_ready, its finishing blocks for f_ready, k_prestamp_flow for p_ready
   FLOW_CODE_QP_ITEM        = 3,   // replan, k_qp_flow: its q_ready slot
   FLOW_CODE_VERDICT        = 4,   // replan and flight, the second search attempt (k_astar, k_flight_search): the first one's verdict
   FLOW_CODE_STAGE_COUNT    = 6,   // flow_wait_count: a stage counter — k_prestamp_flow and k_update_flow (the lower tickets of the agent's

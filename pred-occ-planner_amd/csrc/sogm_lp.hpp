@@ -31,7 +31,7 @@ struct LpScratch {
   LDS_HD double *A() const { return rows; }                    // [rows][D], D <= 4
   LDS_HD double *b() const { return rows + LP_MAX_ROWS * 4; }  // [rows]
 };
-// LDS of a wave that only solves LPs (k_corridor_finalize, k_safe_after_opt, k_finish_flow, k_linprog): work, rows, perm
+// LDS of a wave that only solves LPs (k_corridor_finalize, k_safe_after_opt, the finishing blocks of k_worker_flow, k_linprog): work, rows, perm
 struct LpLds {
   static constexpr int    work = 0, rows = work + LP_WORK_DOUBLES, end = rows + LP_MAX_ROWS * 5;  // in doubles
   static constexpr size_t perm = sizeof(double) * end;                                             // in bytes, as bytes()
@@ -41,7 +41,7 @@ struct LpLds {
 // LDS of a corridor segment's wave; MB = capacity of the boundary block (6: k_corridor_segment / _flow, k_flight_light; 32:
 // k_firi_direct).  The LP's work and rows, then in doubles: lm (L-BFGS history), maxVolInsEllipsoid's hand-off words, alpha / ys,
 // fH, poly, the small shared state, the flag words (one bit per obstacle point); then, at bytes that depend on pc_capacity, the
-// LP's perm and 16 ints.  BETWEEN two segments k_corridor_flow and k_flight_light lay LpLds over the same bytes (finalise,
+// LP's perm and 16 ints.  BETWEEN two segments k_worker_flow and k_flight_light lay LpLds over the same bytes (finalise,
 // finish): its perm is then the head of lm, which only a running segment uses (asserted below).
 template <int MB>
 constexpr int firi_small_doubles() { return 34 + 9 * MB; }

@@ -1011,7 +1011,7 @@ __global__ __launch_bounds__(256) void k_splat_neighbours(
 // ------------------------------------------------------------------------------------------------
 // Pre-stamp: the NEXT tick's map built inside this tick's replan (dataflow replan only).
 // The tick's critical path was "stamp (1.8 ms, nothing else running) -> chain of the slowest agent"; but an agent's
-// next map centre only depends on its OWN new record, which is final the moment k_finish_flow publishes it.  This
+// next map centre only depends on its OWN new record, which is final the moment a finishing block of k_worker_flow publishes it.  This
 // persistent kernel (launched behind the gate that holds stores back until every agent's corridors are final)
 // takes agents in publication order and, for each: samples the start state of the next tick (k_tick_inputs' rule),
 // culls the cylinders, sets the occupancy bits and writes the marks + log entries into the pool's next grid — split

@@ -146,17 +146,18 @@ static int planner_acquire(sogm_planner *p) {
     SOGM_HIP_CHECK(p->res.event(&p->ev_done[g]));
   }
   SOGM_HIP_CHECK(p->res.event(&p->ev_in));
-  // dataflow replan: control block + four streams (needs >= 5 hardware queues to overlap with the clear)
+  // dataflow replan: control block and events.  Its two streams are created by the first dataflow replan (flow_streams):
+  // with the caller's stream and the context's `side` the default tick keeps four streams busy — ROCm's default number of
+  // hardware queues — and holds no others (the pre-stamp's own stream and the dense clear's wide part make a fifth)
   SOGM_HIP_CHECK(p->res.device(&p->d_flow, sizeof(int) * FlowBlock::words(A), true));
   FlowBlock::carve(p->d_flow, A, &p->fc);
   SOGM_HIP_CHECK(p->res.event(&p->ev_pdone));
   // [A][8] chain stamps, then [A][4] pre-stamp stamps (record seen, cull done, bits done, marks done)
   SOGM_HIP_CHECK(p->res.device(&p->d_flow_ts, sizeof(long long) * 12 * (size_t)A, true));
   p->fc.ts = p->d_flow_ts;
-  for (int k = 0; k < 4; ++k) {
-    SOGM_HIP_CHECK(p->res.stream(&p->fstream[k]));
-    SOGM_HIP_CHECK(p->res.event(&p->ev_fdone[k]));
-  }
+  SOGM_HIP_CHECK(p->res.event(&p->ev_records));
+  SOGM_HIP_CHECK(p->res.event(&p->ev_wdone));
+  SOGM_HIP_CHECK(p->res.event(&p->ev_qdone));
   SOGM_HIP_CHECK(p->res.event(&p->ev_gate));
   SOGM_HIP_CHECK(p->res.device(&p->d_epoch, sizeof(int), true));
   SOGM_HIP_CHECK(p->res.pinned(&p->h_flow_fail, sizeof(int) * 2, hipHostMallocMapped));
@@ -437,6 +438,12 @@ int sogm_debug_flow_peek(sogm_planner *p, int *out_host, int n) {
   return SOGM_OK;
 }
 
+// diagnostics: streams the context's and the planner's Resources hold now (host-side count, no HIP call)
+int sogm_debug_streams_held(sogm_planner *p) {
+  if (!p || !p->map) return SOGM_ERR_INVALID_ARG;
+  return p->map->res.streams_held() + p->res.streams_held();
+}
+
 // diagnostics (tools/ only): per-agent stage timestamps of the last dataflow replan, [A][8] ticks of 10 ns
 int sogm_debug_flow_times(sogm_planner *p, long long *out_host) {
   if (!p || !out_host) return SOGM_ERR_INVALID_ARG;
@@ -587,10 +594,15 @@ int sogm_planner_set_swarm(sogm_planner *p, const SogmTrajRecord *records, int n
   return SOGM_OK;
 }
 
-// The dataflow replan: five launches for the whole tick.  k_astar (one workgroup per agent) publishes agents as their
-// searches finish; k_corridor_flow, k_qp_flow and k_finish_flow are persistent and chain per agent through ready
-// lists in HBM, so a slow search / corridor / QP only delays its own agent's chain.  k_flow_gate makes the waiting
-// kernels dispatch only after every search is resident (they could otherwise fill the CUs and starve it).
+// The dataflow replan: a handful of launches for the whole tick.  k_astar (one workgroup per agent) publishes agents as their
+// searches finish; k_worker_flow (corridor blocks and finishing blocks) and k_qp_flow are persistent and chain per agent
+// through ready lists in HBM, so a slow search / corridor / QP only delays its own agent's chain.  k_flow_gate makes the
+// waiting kernels dispatch only after every search is resident (they could otherwise fill the CUs and starve it).
+// Streams: the caller's (k_astar), the worker stream (k_flow_reset -> k_flow_gate -> k_worker_flow -> k_flow_report), the QP
+// stream (behind ev_gate) and the context's `side` (the gate and sparse reset of the grid the update swapped out) — four
+// busy streams for ROCm's default of four hardware queues.  Streams that share a queue run one after the other, and a
+// persistent kernel that waits holds back whatever is queued behind it.  The pre-stamp on a stream of its own and the
+// dense-clear mode's wide launch are a fifth busy stream: those variants want five queues to run at full speed.
 // The dataflow replan's control block and outputs back to their start values: counters / seg_done 0, ready lists -1,
 // verdicts 0, ok 0, records empty.
 // epoch_word (dense clear's gate, sogm_device.hpp): this replan's epoch, written by the block that reset the counters
@@ -651,16 +663,24 @@ struct FlowCall {
   hipStream_t     pst;       // ... on this stream (the tick's report follows it there)
 };
 
+// 0. the planner's two streams, at the first dataflow replan (a planner that only ever runs the grouped path holds none)
+static int flow_streams(sogm_planner *p) {
+  if (p->wstream && p->qstream) return SOGM_OK;
+  sogm::Resources::Setup setup(p->res);
+  SOGM_HIP_CHECK(p->res.stream(&p->wstream));
+  SOGM_HIP_CHECK(p->res.stream(&p->qstream));
+  return setup.done();
+}
 // 1. reset the control block in stream order: counters and seg_done to 0, ready lists to -1
 // (one launch instead of five memset nodes: each cost a dispatch gap on the tick's critical path)
-// k_finish_flow writes ok / the record of every agent whose chain completes; an agent whose chain does NOT (a wait
+// The finishing blocks write ok / the record of every agent whose chain completes; an agent whose chain does NOT (a wait
 // timed out, FLOW_ERR) must report ok = 0 and an empty record, not the previous tick's
 static int flow_reset(sogm_planner *p, FlowCall &call) {
   sogm_ctx         *c    = p->map;
-  const hipStream_t main = call.main, sC = p->fstream[1];
+  const hipStream_t main = call.main, sC = p->wstream;
   const int         A    = c->n_agents;
   const bool        spec = call.spec;
-  // The reset on the corridor stream: behind the previous replan's report (that stream's last kernel: below) and, in the
+  // The reset on the worker stream: behind the previous replan's report (that stream's last kernel: below) and, in the
   // pre-stamping variant, behind the pre-stamp's end; the waiting kernels of THIS replan follow it on the same stream or
   // behind ev_gate.  The readers of the swarm table on those streams wait for an all-gather in flight themselves.
   SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_pdone, 0));  // (never recorded, or long complete, without a pre-stamp: no wait)
@@ -682,12 +702,26 @@ static int flow_reset(sogm_planner *p, FlowCall &call) {
   call.gen_word = gen_word;
   return SOGM_OK;
 }
-// 2. the searches on the caller's stream, then the residency gate and the persistent corridor and QP kernels on theirs
+// Whether this replan pre-stamps: known before the worker kernel is launched, whose finishers publish to p_ready only then.
+// (only with the sparse reset: the pre-stamp runs behind the target grid's reset on the side stream, and with
+//  SOGM_SPARSE_RESET=0 a dense clear fills that stream for the whole tick.  On the first ticks of a flight — and
+//  after a dense writer — queue_spare_clears has queued dense clears even in sparse mode: the pre-stamp, the
+//  report and ev_pdone then sit behind them, the next sogm_update_prestamped overlay waits per agent for as long
+//  (tests/test_pipelining_gpu.py::test_overlay_under_the_prestamp_tail_at_full_size flies exactly that).)
+// The target is the front of the ready queue as queue_spare_clears leaves it at the end of flow_launch_chain: a grid that
+// is ready now, or the first dirty spare, whose reset that call queues.
+static bool flow_prestamps(const sogm_planner *p) {
+  const sogm_ctx *c = p->map;
+  return p->ps_on && c->sparse && c->overlap >= 2 && (c->pool.front_ready() >= 0 || c->pool.first_dirty() >= 0) && p->pub_own &&
+         c->clear_gate;
+}
+// 2. the searches on the caller's stream, then the residency gate and the worker kernel on the worker stream, the QP kernel
+// on its own
 // (the searches run on the caller's stream: they are the first kernel of the chain, and a hop to another stream
 //  costs an event round trip on the critical path)
 static int flow_launch_chain(sogm_planner *p, FlowCall &call) {
   sogm_ctx         *c    = p->map;
-  const hipStream_t main = call.main, sA = main, sC = p->fstream[1], sQ = p->fstream[2], sF = p->fstream[3];
+  const hipStream_t main = call.main, sA = main, sC = p->wstream, sQ = p->qstream;
   const int         A    = c->n_agents;
   const MapView     mv   = view_of(c);
   const bool        spec = call.spec;
@@ -695,8 +729,10 @@ static int flow_launch_chain(sogm_planner *p, FlowCall &call) {
   const double     *start_pva = call.start_pva, *goal = call.goal, *t_start = call.t_start;
   SogmTrajRecord   *out_records = call.out_records;
   int32_t          *out_ok      = call.out_ok;
-  if (c->exchange_pending)
-    for (int k = 1; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(p->fstream[k], c->ev_xdone, 0));
+  if (c->exchange_pending) {
+    SOGM_HIP_CHECK(hipStreamWaitEvent(sC, c->ev_xdone, 0));
+    SOGM_HIP_CHECK(hipStreamWaitEvent(sQ, c->ev_xdone, 0));
+  }
   prof_begin(c, SOGM_PROF_ASTAR, sA);
   // an update flow still building this tick's maps (sogm_update_world with update_flow): the searches are launched beside
   // it and every search workgroup waits for ITS agent's map; the caller's stream joins the flow's end at the fan-in
@@ -719,25 +755,35 @@ static int flow_launch_chain(sogm_planner *p, FlowCall &call) {
   if (int rc = launched("sogm_replan: k_flow_gate", sogm::launch_flow_gate(p->fc, spec ? 2 * A : A, sC))) return rc;
   SOGM_HIP_CHECK(hipEventRecord(p->ev_gate, sC));
   SOGM_HIP_CHECK(hipStreamWaitEvent(sQ, p->ev_gate, 0));
-  SOGM_HIP_CHECK(hipStreamWaitEvent(sF, p->ev_gate, 0));
   // persistent workgroups: one wave each for the corridor items (4 per CU fit), half of the CUs' worth of QP
   // workgroups (each takes a whole CU's LDS while it runs; with fewer, agents queue for a solver — measured: 64 / 96
   // / 128 / 160 workgroups -> 6.3 / 6.9 / 7.5 / 7.4 k replans/s), a handful of finishing waves
+  // (finish_wgs / corridor_wgs: tuning aids; tests starve a role with them so that its loop runs more than one trip)
   int n_cu = 256;
   (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
   int wg_c = 4 * n_cu;
+  if (c->tune_i(SOGM_TUNE_CORRIDOR_WGS) > 0) wg_c = c->tune_i(SOGM_TUNE_CORRIDOR_WGS);
   if (wg_c > A * SOGM_MAX_PIECES) wg_c = A * SOGM_MAX_PIECES;
   int wg_q = n_cu / 2;
   if (c->tune_i(SOGM_TUNE_QP_WGS) > 0) wg_q = c->tune_i(SOGM_TUNE_QP_WGS);  // tuning aid
   if (wg_q > A) wg_q = A;
   if (wg_q < 1) wg_q = 1;
-  int wg_f = A < 64 ? A : 64;
+  int wg_f = 64;
+  if (c->tune_i(SOGM_TUNE_FINISH_WGS) > 0) wg_f = c->tune_i(SOGM_TUNE_FINISH_WGS);
+  if (wg_f > A) wg_f = A;
   call.n_cu = n_cu, call.wg_q = wg_q, call.wg_f = wg_f;
+  // the worker kernel: the finishers (lowest block indices: dispatched first) and the corridor stage in one launch
+  call.prestamp     = flow_prestamps(p);
+  sogm::FlowCtl fcw = p->fc;
+  if (!call.prestamp) fcw.p_ready = nullptr;
   prof_begin(c, SOGM_PROF_CORRIDOR, sC);
-  if (int rc = launched("sogm_replan: k_corridor_flow",
-                        sogm::launch_corridor_flow(mv, p->pp, p->cw, p->fc, A, wg_c, corridor_io(p, start_pva, t_start), sC)))
+  if (int rc = launched("sogm_replan: k_worker_flow",
+                        sogm::launch_worker_flow(mv, p->pp, p->cw, fcw, A, wg_f, wg_c, corridor_io(p, start_pva, t_start),
+                                                 finish_args(p, t_start, call.drone_ids, out_records, out_ok), sC)))
     return rc;
   prof_end(c, SOGM_PROF_CORRIDOR, sC);
+  // every record is published behind the worker kernel (sogm_traj_allgather starts from here: flow_fan_in)
+  SOGM_HIP_CHECK(hipEventRecord(p->ev_records, sC));
   // (a QP workgroup takes a whole CU — registers and LDS — from the moment it is resident, and the first corridors are
   //  final long after an update flow has ended: the QP kernel is dispatched behind the flow's end, not beside it)
   if (c->update_pending) SOGM_HIP_CHECK(hipStreamWaitEvent(sQ, c->ev_udone, 0));
@@ -763,24 +809,7 @@ static int flow_launch_chain(sogm_planner *p, FlowCall &call) {
   }
   return SOGM_OK;
 }
-// 3. the finishing kernel; decides whether this replan pre-stamps (call.prestamp)
-static int flow_finish(sogm_planner *p, FlowCall &call) {
-  sogm_ctx         *c  = p->map;
-  const hipStream_t sF = p->fstream[3];
-  const int         A  = c->n_agents;
-  sogm::FlowCtl fcf = p->fc;
-  // (only with the sparse reset: the pre-stamp runs behind the target grid's reset on the side stream, and with
-  //  SOGM_SPARSE_RESET=0 a dense clear fills that stream for the whole tick.  On the first ticks of a flight — and
-  //  after a dense writer — queue_spare_clears above has queued dense clears even in sparse mode: the pre-stamp, the
-  //  report and ev_pdone then sit behind them, the next sogm_update_prestamped overlay waits per agent for as long
-  //  (tests/test_pipelining_gpu.py::test_overlay_under_the_prestamp_tail_at_full_size flies exactly that).)
-  const bool prestamp = p->ps_on && c->sparse && c->overlap >= 2 && c->pool.front_ready() >= 0 && p->pub_own && c->clear_gate;
-  if (!prestamp) fcf.p_ready = nullptr;
-  call.prestamp = prestamp;
-  return launched("sogm_replan: k_finish_flow",
-                  sogm::launch_finish_flow(fcf, A, call.wg_f, finish_args(p, call.t_start, call.drone_ids, call.out_records, call.out_ok), sF));
-}
-// 4. the pre-stamp's arguments from sogm_planner_set_prestamp's and the tuning: no HIP call (tgt and frame.cb: flow_prestamp)
+// 3. the pre-stamp's arguments from sogm_planner_set_prestamp's and the tuning: no HIP call (tgt and frame.cb: flow_prestamp)
 static sogm::PrestampDev prestamp_args(const sogm_planner *p) {
   const sogm_ctx   *c = p->map;
   const int         A = c->n_agents;
@@ -804,19 +833,26 @@ static sogm::PrestampDev prestamp_args(const sogm_planner *p) {
   d.n_marks_late = c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) > 0 ? c->tune_i(SOGM_TUNE_PRESTAMP_LATE_MARKS) : nm;
   return d;
 }
-// 5. pre-stamp (sogm_planner_set_prestamp): the next tick's map, agent by agent as their records are published, into
+// 4. pre-stamp (sogm_planner_set_prestamp): the next tick's map, agent by agent as their records are published, into
 // the pool's next grid — behind the gate that keeps store streams away from the searches and point scans, and
 // behind that grid's reset
 static int flow_prestamp(sogm_planner *p, FlowCall &call) {
   sogm_ctx *c = p->map;
   const int A = c->n_agents;
   c->pool.clear_prestamp_target();
-  // the pre-stamp's stream (why it has one of its own: below); the tick's report follows it there
-  const bool        own_stream = c->tune_i(SOGM_TUNE_PRESTAMP_STREAM) != 0 && c->pstream != nullptr;
-  const hipStream_t pst        = own_stream ? c->pstream : c->side;
+  // the pre-stamp's stream (why it has one of its own: below; created by the first replan that pre-stamps on it — it is the
+  // tick's fifth busy stream, and a replan that does not pre-stamp holds no place in the pool of hardware queues for it);
+  // the tick's report follows it there
+  const bool own_stream = c->tune_i(SOGM_TUNE_PRESTAMP_STREAM) != 0 && call.prestamp;
+  if (own_stream && !c->pstream) {
+    sogm::Resources::Setup setup(c->res);
+    SOGM_HIP_CHECK(c->res.stream(&c->pstream));
+    setup.done();
+  }
+  const hipStream_t pst = own_stream ? c->pstream : c->side;
   call.pst = pst;
   if (call.prestamp) {
-    const int nxt = c->pool.front_ready();
+    const int nxt = c->pool.front_ready();  // (>= 0: flow_prestamps saw a ready or a dirty spare, and the dirty ones are queued by now)
     sogm::PrestampDev d = prestamp_args(p);
     if (int rc = sogm::map_target(c, nxt, true, nullptr, &d.tgt)) return rc;
     if (p->ps_world_on)  // the frame's blocks + the context's crop lists (built by each agent's first ticket)
@@ -855,11 +891,11 @@ static int flow_prestamp(sogm_planner *p, FlowCall &call) {
   }
   return SOGM_OK;
 }
-// 6. fan-in.  Without a pre-stamp the tick's report runs on the corridor stream behind the QP and finishing kernels, so that
+// 5. fan-in.  Without a pre-stamp the tick's report runs on the worker stream behind the worker and QP kernels, so that
 // the NEXT replan's reset — same stream — is ordered behind it without an event on the caller's stream
 static int flow_fan_in(sogm_planner *p, const FlowCall &call) {
   sogm_ctx         *c    = p->map;
-  const hipStream_t main = call.main, sC = p->fstream[1], pst = call.pst;
+  const hipStream_t main = call.main, sC = p->wstream, sQ = p->qstream, pst = call.pst;
   const int         A    = c->n_agents;
   const int         retire     = c->tune_i(SOGM_TUNE_CLEAR_RETIRE_AT_END);  // measured: tick -2 %, but the clear 14.5 -> 15.5 ms; off
   auto report = [&](hipStream_t st) {
@@ -868,15 +904,14 @@ static int flow_fan_in(sogm_planner *p, const FlowCall &call) {
     return hipGetLastError();
   };
   const bool report_on_sc = !c->pool.prestamp_pending();
-  for (int k = 0; k < 4; ++k)
-    if (k != 1) SOGM_HIP_CHECK(hipEventRecord(p->ev_fdone[k], p->fstream[k]));
+  SOGM_HIP_CHECK(hipEventRecord(p->ev_qdone, sQ));
   if (report_on_sc) {
-    SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_fdone[2], 0));
-    SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_fdone[3], 0));
+    SOGM_HIP_CHECK(hipStreamWaitEvent(sC, p->ev_qdone, 0));
     SOGM_HIP_CHECK(report(sC));
   }
-  SOGM_HIP_CHECK(hipEventRecord(p->ev_fdone[1], sC));
-  for (int k = 0; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->ev_fdone[k], 0));
+  SOGM_HIP_CHECK(hipEventRecord(p->ev_wdone, sC));
+  SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->ev_wdone, 0));
+  SOGM_HIP_CHECK(hipStreamWaitEvent(main, p->ev_qdone, 0));
   if (int rc = sogm::join_update(c, main)) return rc;  // (complete long ago: every search waited for its agent's map)
   if (c->d_update_order && c->tune_i(SOGM_TUNE_UPDATE_FLOW) != 0) {
     // the next update flow takes the agents in the order of this tick's chain lengths, longest first (a schedule only)
@@ -888,7 +923,8 @@ static int flow_fan_in(sogm_planner *p, const FlowCall &call) {
   if (c->pool.prestamp_pending()) {
     // the tick's report behind the pre-stamp on ITS stream (the last kernel of the tick to end), so that the caller's
     // stream goes from the fan-in straight to the next tick's first kernel instead of through one more launch
-    for (int k = 1; k < 4; ++k) SOGM_HIP_CHECK(hipStreamWaitEvent(pst, p->ev_fdone[k], 0));
+    SOGM_HIP_CHECK(hipStreamWaitEvent(pst, p->ev_wdone, 0));
+    SOGM_HIP_CHECK(hipStreamWaitEvent(pst, p->ev_qdone, 0));
     SOGM_HIP_CHECK(report(pst));
     SOGM_HIP_CHECK(hipEventRecord(p->ev_pdone, pst));
     const int defer = c->tune_i(SOGM_TUNE_SPLAT_OVERLAP) != 0;  // 0: the caller's stream waits for the pre-stamp's end here
@@ -904,10 +940,11 @@ static int flow_fan_in(sogm_planner *p, const FlowCall &call) {
     }
     reported = true;
   }
-  // the exchange of the records this replan publishes may start when the finishing kernel is done (sogm_traj_allgather)
+  // the exchange of the records this replan publishes may start when the worker kernel — its finishers — is done
+  // (sogm_traj_allgather): the event recorded behind that kernel and in front of the report
   c->records_final_valid = 0;
   if (p->pub_own) {
-    c->ev_records_final    = p->ev_fdone[3];
+    c->ev_records_final    = p->ev_records;
     c->records_final_ptr   = p->pub_own;
     c->records_final_valid = 1;
   }
@@ -921,9 +958,9 @@ static int replan_flow(sogm_planner *p, const double *start_pva, const double *g
                 .out_ok = out_ok, .main = (hipStream_t)stream, .spec = p->spec_astar != 0};
   if (p->swarm)
     if (int rc = sogm::join_exchange(p->map, call.main)) return rc;
+  if (int rc = flow_streams(p)) return rc;
   if (int rc = flow_reset(p, call)) return rc;
   if (int rc = flow_launch_chain(p, call)) return rc;
-  if (int rc = flow_finish(p, call)) return rc;
   if (int rc = flow_prestamp(p, call)) return rc;
   return flow_fan_in(p, call);
 }

@@ -264,11 +264,12 @@ hipError_t launch_pack_records(int n_agents, const FinishArgs &f, hipStream_t st
 hipError_t launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, int n_agents,
                            const CorridorIO &io, hipStream_t st, int agent0 = 0, hipEvent_t ev_map_read = nullptr);
 
-// dataflow replan launchers (persistent kernels; see k_corridor_flow / k_qp_flow / k_finish_flow)
+// dataflow replan launchers (persistent kernels; see k_worker_flow / k_qp_flow).  The worker kernel: n_finish finishing
+// blocks at the lowest block indices, then n_corridor corridor blocks
 hipError_t launch_flow_gate(const FlowCtl &fc, int expected, hipStream_t st);
-hipError_t launch_corridor_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws,
-                                const FlowCtl &fc, int n_agents, int n_workgroups, const CorridorIO &io, hipStream_t st);
-hipError_t launch_finish_flow(const FlowCtl &fc, int n_agents, int n_workgroups, const FinishArgs &f, hipStream_t st);
+hipError_t launch_worker_flow(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, const FlowCtl &fc,
+                              int n_agents, int n_finish, int n_corridor, const CorridorIO &io, const FinishArgs &f,
+                              hipStream_t st);
 
 // Per-agent QP row storage in HBM, used only when a problem's rows do not fit in LDS (what lives where: sogm_qp_layout.hpp,
 // which also sizes both buffers: qp_scratch_bytes_per_agent(max_faces), qp_k1_scratch_bytes_per_agent()).
@@ -346,13 +347,17 @@ struct sogm_planner {
   int           *d_flow;      // the control block (layout: sogm::FlowBlock)
   long long     *d_flow_ts;   // [A][8]
   sogm::FlowCtl  fc;
-  hipStream_t    fstream[4];  // A*, corridors, QP, finish
+  // its two streams, created by the first dataflow replan (the searches run on the caller's stream): the worker stream —
+  // reset, residency gate, k_worker_flow, report — and the QP kernel's
+  hipStream_t    wstream, qstream;
   hipEvent_t     ev_pdone;
   sogm::PrestampDev ps;       // the host's part of the pre-stamp arguments
   int            ps_on;
   int            ps_world_on;  // the pre-stamp's inputs are a SogmWorld frame (copied at sogm_planner_set_prestamp)
   SogmWorld      ps_world;
-  hipEvent_t     ev_gate, ev_fdone[4];
+  hipEvent_t     ev_gate;
+  hipEvent_t     ev_records;  // behind the worker kernel, in front of the report: every record is published (the context's ev_records_final)
+  hipEvent_t     ev_wdone, ev_qdone;  // the fan-in: the worker stream's end (with the report, when it runs there), the QP kernel's end
   int           *d_epoch;      // device word: the clear epoch of the replan in flight (sogm_ctx::clear_epoch_word)
   int            reset_epoch;  // generation of the control block's reset (k_flow_reset writes it into the block's word FlowBlock::gen)
   int           *h_flow_fail;  // pinned, device-visible: {last FLOW_ERR code, ticks that failed} (k_flow_report)

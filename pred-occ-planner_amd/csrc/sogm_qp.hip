@@ -1784,7 +1784,7 @@ __global__ __launch_bounds__(QP_NT) void k_qp(SogmPlannerParams pp, SogmQpSettin
 }
 
 // Dataflow kernel Q (sogm_replan): ONE persistent launch; a workgroup takes tickets and solves the agent whose
-// corridors became final ticket-th (k_corridor_flow publishes agents in completion order), so a 4000-iteration QP
+// corridors became final ticket-th (k_worker_flow publishes agents in completion order), so a 4000-iteration QP
 // only delays its own agent.  The solved agent is handed to the finishing kernel (deconfliction + record packing).
 __global__ __launch_bounds__(QP_NT) void k_qp_flow(SogmPlannerParams pp, SogmQpSettings qs, QpWorkspace ws,
                                                  QpConst qc, FlowCtl fc, QpIO io, int ablate_arg, int n_agents) {

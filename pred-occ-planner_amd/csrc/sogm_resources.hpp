@@ -67,6 +67,13 @@ class Resources {
     *field = nullptr;
   }
 
+  // streams currently held (sogm_debug_streams_held): every one of them takes a place in the runtime's pool of hardware queues
+  int streams_held() const {
+    int n = 0;
+    for (const Held &h : held_) n += h.kind == STREAM ? 1 : 0;
+    return n;
+  }
+
   size_t mark() const { return held_.size(); }
   // Releases everything acquired since `mark`: streams (each synchronised, then destroyed), then events, then memory,
   // within a kind in reverse order of acquisition.  A field that still holds its handle is nulled.

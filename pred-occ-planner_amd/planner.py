@@ -133,6 +133,14 @@ class SogmPlanner:
         check(lib().sogm_planner_counters(self._p, out, 1 if reset else 0), "sogm_planner_counters")
         return dict(zip(_abi.COUNTER_NAMES, [int(v) for v in out]))
 
+    def streams_held(self):
+        """HIP streams the planner and its map context hold now (sogm_debug_streams_held): 3 in the default lock-step
+        tick, which with the caller's stream keeps four hardware queues busy.  No synchronisation."""
+        n = int(lib().sogm_debug_streams_held(self._p))
+        if n < 0:
+            check(n, "sogm_debug_streams_held")
+        return n
+
     def corridor_pairs(self):
         """The adjacent-pair LPs of the corridor bookkeeping since the last call (sogm_debug_corridor_pairs): a dict of
         eager (run by a segment's wave), late (run inside the bookkeeping, no verdict there), consumed (taken from a
