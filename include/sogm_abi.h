@@ -1518,6 +1518,86 @@ int sogm_map_audit_masked(sogm_ctx *test, sogm_ctx *truth, const SogmMapAuditPar
                           void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* velocity audit: the new-born list of a particle map's last update — what the on-device        */
+/*   velocity estimation (sogm_update_dsp with labels == NULL) made of the cloud — scored point   */
+/*   by point against truth labels ("ground-truth labels": out_labels and out_code of             */
+/*   sogm_filter_point_cloud_labelled, in the same point order).  The build's OWN instrument,      */
+/*   like "map audit", held by two readings (csrc/sogm_velaudit.hpp + csrc/sogm_velaudit.hip, and  */
+/*   the numpy restatement tests/velocity_audit_reference.py), field for field.                    */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * All arithmetic is fp32, in exactly this order, one IEEE operation at a time, without contraction.  Every output is an
+ * integer and bit-identical from run to run.
+ *
+ * The list.  sogm_update_dsp leaves per agent the new-born list (rows {x, y, z, vx, vy, vz, intensity}, n_born of them) and,
+ *   beside it, the SOURCE INDEX of every row: the index, inside the agent's range of the input cloud, of the point the row
+ *   came from.  With labels given the list is the cloud in input order and the index is the identity; with labels == NULL the
+ *   estimator reorders the list ([possibly-dynamic clusters][ground][static clusters]) and drops the points of rejected
+ *   clusters, and the index says which is which.  (sogm_abi_debug.h: sogm_dsp_download_born_source.)
+ * Per agent: n_in = min(cloud_range end - begin, max_points).  truth_labels[(begin + i)*4 ..] and truth_code[begin + i] belong
+ *   to input point i, as `labels` do in sogm_update_dsp.
+ * Estimate class of input point i — the tests the map itself applies to the list when it creates particles:
+ *     DROPPED (3)     no born row names i
+ *   and for the born row {.., vx, vy, vz, inten} that names it
+ *     STATIC (0)      unless inten > 0.01f
+ *     TRACKED (1)     if inten > 0.01f && vx > -100.f
+ *     UNTRACKED (2)   otherwise (the -10000 label of a possibly-dynamic cluster without a match: the map gives its
+ *                     particles a random velocity)
+ * Truth class: MOVING (1) if truth_labels[i].intensity > 0.01f, else STILL (0).
+ * Truth velocity: (tvx, tvy) = the label's (vx, vy) if MOVING, else (0, 0).  Only the HORIZONTAL components are scored: the
+ *   map reads vx and vy of a label and nothing else.
+ * Quantities of a TRACKED row:
+ *     ex = vx - tvx;  ey = vy - tvy;  e2 = ex*ex + ey*ey
+ *     s_e = vx*vx + vy*vy;  s_t = tvx*tvx + tvy*tvy;  dot = vx*tvx + vy*tvy;  m = s_e*s_t
+ *   NaN: a TRACKED row whose e2 or m is NaN counts in the confusion matrix (and in its code's `tracked` column) and in
+ *     n_nan, and nowhere else.  Every other TRACKED row is SCORED:
+ *   speed bin = the number of T in {0.1f, 0.25f, 0.5f, 1.0f, 2.0f} with e2 > T*T                              (0 .. 5)
+ *   direction bin (MOVING rows):  4 if s_e == 0 (an estimate faster than 5 m/s is zeroed, but matched);
+ *     else 0 if dot > 0 && dot*dot >= 0.9330127f*m (within 15 degrees);  else 1 if dot > 0 && dot*dot >= 0.5f*m (within 45);
+ *     else 2 if dot > 0;  else 3
+ *   within = e2 <= tol*tol,  tol = speed_tolerance
+ *   e2_um = (int64)(min(e2, 1.0e4f) * 1.0e6f), truncated toward zero
+ * Output row per agent, SOGM_VELAUDIT_ROW = 32 int64:
+ *     [0] n_in   [1] n_born   [2] status bits   [3] n_nan
+ *     [4 .. 11]   confusion [truth: STILL, MOVING][estimate: STATIC, TRACKED, UNTRACKED, DROPPED]  (sums to n_in)
+ *     [12 .. 17]  speed bins of the scored MOVING x TRACKED rows
+ *     [18 .. 23]  speed bins of the scored STILL x TRACKED rows (spurious velocity)
+ *     [24 .. 28]  direction bins of the scored MOVING x TRACKED rows
+ *     [29] the sum of e2_um, [30] the number within, both over the scored MOVING x TRACKED rows   [31] 0
+ * Status: SOGM_VELAUDIT_SKIPPED — the agent's last update was rejected or never ran, or its range is empty: every count is 0;
+ *   SOGM_VELAUDIT_BAD_SOURCE — a born row whose source index is outside [0, n_in), or names a point a row with a smaller
+ *   index names already: that row is ignored;  SOGM_VELAUDIT_CLIPPED — the range was longer than max_points.
+ * Per-code table (optional; needs truth_code): int64 [n_agents][n_codes + 2][6], row r = {static, tracked, untracked, dropped,
+ *   n_within, sum of e2_um}; input point i lands in row c = truth_code[begin + i] if 0 <= c < n_codes, in row n_codes if
+ *   c == SOGM_HIT_GROUND, in row n_codes + 1 otherwise.  Here n_within and the sum cover EVERY scored row of the code, moving
+ *   or still, against the truth velocity above: which obstacle or body the estimator sees, and which it loses.
+ */
+#define SOGM_VELAUDIT_ROW 32
+enum { SOGM_VEL_STATIC = 0, SOGM_VEL_TRACKED = 1, SOGM_VEL_UNTRACKED = 2, SOGM_VEL_DROPPED = 3 };
+enum { SOGM_VELAUDIT_SKIPPED = 1, SOGM_VELAUDIT_BAD_SOURCE = 2, SOGM_VELAUDIT_CLIPPED = 4 }; /* status bits */
+enum { SOGM_VELAUDIT_ACCUMULATE = 1 };                                                       /* SogmVelAuditParams.flags */
+typedef struct SogmVelAuditParams {
+  float   speed_tolerance; /* m/s, finite, >= 0 */
+  int32_t n_codes;         /* >= 0, n_codes + 2 <= 1024 */
+  int32_t flags;           /* SOGM_VELAUDIT_ACCUMULATE or 0 */
+  int32_t reserved_;
+} SogmVelAuditParams;      /* 16 bytes */
+/*
+ * Scores every agent of `d` after a sogm_update_dsp on the same stream (cloud_range: the one that update was given).  Without
+ * SOGM_VELAUDIT_ACCUMULATE the outputs are zeroed first and then written; with it every count is ADDED to what out_rows and
+ * out_per_code hold and the status is ORed: a run over many frames needs one read-back.
+ * Stream-ordered, allocates nothing, does not synchronise with the host, writes nothing to the handle.
+ * SOGM_ERR_INVALID_ARG (with sogm_last_error text; checked first, before anything is queued on the device): a null d,
+ * truth_labels, cloud_range, prm or out_rows; out_per_code without truth_code; n_codes < 0; n_codes + 2 > 1024 (the table of
+ * an agent lives in 48 KB of LDS); speed_tolerance negative or not finite; an undefined flag.
+ * SOGM_ERR_NO_DEVICE without a GPU (what a call gets there once its pointers are not null and prm has passed).
+ */
+int sogm_dsp_velocity_audit(sogm_dsp *d, const float *truth_labels /* dev [points*4] */,
+                            const int32_t *truth_code /* dev [points] or NULL */, const int32_t *cloud_range /* dev [n*2] */,
+                            const SogmVelAuditParams *prm, int64_t *out_rows /* dev [n][32] */,
+                            int64_t *out_per_code /* dev [n][n_codes + 2][6] or NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory server: the 100 Hz position commands (with yaw) a vehicle consumes                  */
 /*   (traj_server/src/bezier_traj_server.cpp, bezier_traj_server_rotors.cpp)                      */
 /* ------------------------------------------------------------------------------------------ */

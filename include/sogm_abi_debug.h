@@ -149,6 +149,11 @@ int sogm_dsp_upload_state(sogm_dsp *d, int agent, const float *store_host, const
  * A cloud longer than max_points is clamped to its first max_points points and counted in counters[12] of
  * sogm_dsp_download_state (once per clamped update), not here. */
 int sogm_dsp_download_born(sogm_dsp *d, int agent, float *born_host, int cap, int32_t *n_born, int32_t *counters4);
+/* The source index of that list (sogm_abi.h "velocity audit"; synchronous like the call above): out_host[k], k < min(n_born,
+ * cap), is the index inside the agent's range of the input cloud of the point row k of the list came from.  The identity after
+ * an update with labels; after one without, the order the velocity estimation gave the list, the points of rejected clusters
+ * missing.  Rows at and beyond n_born are not meaningful. */
+int sogm_dsp_download_born_source(sogm_dsp *d, int agent, int32_t *out_host, int cap, int32_t *n_born);
 /* Observation tables of the last update: nobs[n_pyramids], pc[n_pyramids*obs_max*5], maxlen[n_pyramids] */
 int sogm_dsp_download_observations(sogm_dsp *d, int agent, int32_t *nobs_host, float *pc_host,
                                    float *maxlen_host);

@@ -198,6 +198,21 @@ class SogmViewParams(C.Structure):
 
 VIEW_PARAMS_BYTES = C.sizeof(SogmViewParams)  # 104
 
+# velocity audit (include/sogm_abi.h "velocity audit"): estimate classes, status bits, the flag, the row's layout
+SOGM_VELAUDIT_ROW = 32
+SOGM_VEL_STATIC, SOGM_VEL_TRACKED, SOGM_VEL_UNTRACKED, SOGM_VEL_DROPPED = 0, 1, 2, 3
+SOGM_VELAUDIT_SKIPPED, SOGM_VELAUDIT_BAD_SOURCE, SOGM_VELAUDIT_CLIPPED = 1, 2, 4
+SOGM_VELAUDIT_ACCUMULATE = 1
+VEL_ESTIMATE_NAMES = ("static", "tracked", "untracked", "dropped")
+VELAUDIT_CODE_COLUMNS = ("static", "tracked", "untracked", "dropped", "n_within", "sum_e2_um")
+
+
+class SogmVelAuditParams(C.Structure):
+    _fields_ = [("speed_tolerance", C.c_float), ("n_codes", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
+
+
+VELAUDIT_PARAMS_BYTES = C.sizeof(SogmVelAuditParams)  # 16
+
 
 class SogmFsmParams(C.Structure):
     _fields_ = [("replan_duration", C.c_double), ("replan_start_time", C.c_double), ("goal_tolerance", C.c_double),
@@ -395,6 +410,8 @@ PROTOTYPES = {
     "sogm_dsp_download_state": (_i, [_vp, _i, _vp, _vp, _vp]),
     "sogm_dsp_upload_state": (_i, [_vp, _i, _vp, _vp, C.c_double, _vp]),
     "sogm_dsp_download_born": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "sogm_dsp_download_born_source": (_i, [_vp, _i, _vp, _i, _vp]),
+    "sogm_dsp_velocity_audit": (_i, [_vp, _vp, _vp, _vp, C.POINTER(SogmVelAuditParams), _vp, _vp, _vp]),
     "sogm_dsp_download_observations": (_i, [_vp, _i, _vp, _vp, _vp]),
 }
 

@@ -807,6 +807,16 @@ struct MapTarget;
 // and stamps — the NEXT ones for a pre-stamp.  Allocates the scratch and the *_next arrays on first use (`st`: the stream
 // that zeroes the new occupancy bits).
 int  map_target(sogm_ctx *c, int slot, bool next_poses, hipStream_t st, MapTarget *out);
+// what the velocity audit (sogm_velaudit.hip) reads of a particle map handle (sogm_dsp.hip), as plain device pointers: the
+// new-born list of the last update, its source index, and per agent "the update was accepted" and the list's length (two ints
+// of the agent's scalars, `stride` ints from one agent to the next)
+struct DspBornView {
+  const float   *born;      // [n_agents][max_pts][7]
+  const int32_t *born_src;  // [n_agents][max_pts]
+  const int32_t *ok, *n_born;
+  int            stride, n_agents, max_pts, device;
+};
+int dsp_born_view(const sogm_dsp *h, DspBornView *out);
 }  // namespace sogm
 
 #define SOGM_HIP_CHECK(expr)                    \

@@ -84,6 +84,7 @@ struct DspDev {
   int      *obs_list;  // [A][max_pts] pi*OM + seq of every stored observation
   float    *bp_h, *bp_v;  // [A][(nph+1)*3], [A][(npv+1)*3]
   float    *born;  // [A][max_pts][7]
+  int      *born_src;  // [A][max_pts] input index of every row of `born` (the velocity audit's link; rows >= n_born: stale)
   unsigned short *vel_adj;  // [A][max_pts][VEL_ADJ_CAP] neighbour lists of the clustering (velocity estimation)
   int            *vel_deg;  // [A][max_pts]
   // candidates of the prediction step (movers + in-FOV stays)
@@ -299,6 +300,7 @@ __global__ __launch_bounds__(256) void k_dsp_observe(DspDev d, const float *__re
       born[(size_t)k * 7 + 0] = r[0] + c0;
       born[(size_t)k * 7 + 1] = r[1] + c1;
       born[(size_t)k * 7 + 2] = r[2] + c2;
+      d.born_src[(size_t)a * d.max_pts + k] = k;  // (k_dsp_velocity rewrites it with the list)
       for (int j = 0; j < 4; ++j)  // labels == NULL: k_dsp_velocity fills (and reorders) the list afterwards
         born[(size_t)k * 7 + 3 + j] = labels ? labels[(size_t)(begin + k) * 4 + j] : 0.f;
       pi = pyramid_of(s_bh, s_bv, d.nph, d.npv, r[0], r[1], r[2]);
@@ -832,6 +834,7 @@ __global__ __launch_bounds__(1024) void k_dsp_velocity(DspDev d, const int32_t *
     o[1]     = px[t][1];
     o[2]     = px[t][2];
     for (int j = 0; j < 4; ++j) o[3 + j] = lv[j];
+    d.born_src[(size_t)a * MP + pos] = t * 1024 + tid;  // the input index of px[t]
   }
 }
 
@@ -1543,6 +1546,21 @@ struct sogm_dsp {
   Resources          res;  // owns every buffer of `d`
 };
 
+// (sogm_device.hpp) the handle's arrays as sogm_velaudit.hip reads them: nothing of the handle is written through this view
+int sogm::dsp_born_view(const sogm_dsp *h, DspBornView *out) {
+  if (!h || !out) return SOGM_ERR_INVALID_ARG;
+  static_assert(sizeof(DspAgent) % sizeof(int32_t) == 0, "the agents' scalars are strided in ints");
+  out->born     = h->d.born;
+  out->born_src = h->d.born_src;
+  out->ok       = &h->d.ag->ok;
+  out->n_born   = &h->d.ag->n_born;
+  out->stride   = (int)(sizeof(DspAgent) / sizeof(int32_t));
+  out->n_agents = h->d.A;
+  out->max_pts  = h->d.max_pts;
+  out->device   = h->map->device;
+  return SOGM_OK;
+}
+
 namespace {
 template <typename T>
 int dupload(sogm_dsp *h, const T **out, const T *src, size_t n) {
@@ -1666,6 +1684,7 @@ int sogm_dsp_create(sogm_ctx *map, const SogmDspParams *P, const float *p_gauss,
   bad |= h->res.array(&d.bp_h, A * (d.nph + 1) * 3);
   bad |= h->res.array(&d.bp_v, A * (d.npv + 1) * 3);
   bad |= h->res.array(&d.born, A * MP * 7);
+  bad |= h->res.array(&d.born_src, A * MP);
   bad |= h->res.array(&d.vel_adj, A * MP * VEL_ADJ_CAP);
   bad |= h->res.array(&d.vel_deg, A * MP);
   bad |= h->res.array(&d.c_key, A * CC);
@@ -1961,6 +1980,22 @@ int sogm_dsp_download_born(sogm_dsp *h, int agent, float *born_host, int cap, in
   if (born_host) {
     const size_t n = (size_t)(ag.n_born < cap ? ag.n_born : cap);
     SOGM_HIP_CHECK(hipMemcpy(born_host, d.born + (size_t)agent * d.max_pts * 7, n * 7 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return SOGM_OK;
+}
+
+// The source index of that list (sogm_abi_debug.h): born_src rows 0 .. n_born - 1.
+int sogm_dsp_download_born_source(sogm_dsp *h, int agent, int32_t *out, int cap, int32_t *n_born) {
+  if (!h || agent < 0 || agent >= h->d.A || cap < 0) return SOGM_ERR_INVALID_ARG;
+  DspDev &d = h->d;
+  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
+  SOGM_HIP_CHECK(hipDeviceSynchronize());
+  DspAgent ag;
+  SOGM_HIP_CHECK(hipMemcpy(&ag, d.ag + agent, sizeof(ag), hipMemcpyDeviceToHost));
+  if (n_born) *n_born = ag.n_born;
+  if (out) {
+    const size_t n = (size_t)(ag.n_born < cap ? ag.n_born : cap);
+    SOGM_HIP_CHECK(hipMemcpy(out, d.born_src + (size_t)agent * d.max_pts, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   return SOGM_OK;
 }

@@ -6,7 +6,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._abi import SOGM_DSP_MAX_T, SogmDspParams, check, lib
+from ._abi import (SOGM_DSP_MAX_T, SOGM_VELAUDIT_ACCUMULATE, SOGM_VELAUDIT_ROW, SogmDspParams, SogmVelAuditParams, check,
+                   lib)
 from .sogm import _stream
 
 
@@ -83,6 +84,41 @@ class DspMap:
               "sogm_dsp_download_born")
         return born[:n.value].copy(), list(cnt)
 
+    def download_born_source(self, agent):
+        """The source index of download_born's rows (sogm_dsp_download_born_source): row k of the list came from input point
+        src[k] of the agent's range.  The identity after an update with labels."""
+        src = np.zeros(self.max_points, np.int32)
+        n = C.c_int32(0)
+        check(lib().sogm_dsp_download_born_source(self._h, agent, src.ctypes.data_as(C.c_void_p), self.max_points,
+                                                  C.byref(n)), "sogm_dsp_download_born_source")
+        return src[:n.value].copy()
+
+    def audit_velocity(self, truth_labels, truth_code, cloud_range, n_codes=0, speed_tolerance=0.25, per_code=False,
+                       accumulate_into=None):
+        """sogm_dsp_velocity_audit (sogm_abi.h "velocity audit") of the last update: device tensors (rows int64 [n_agents, 32],
+        per-code table int64 [n_agents, n_codes + 2, 6] or None).  truth_labels [points, 4] and truth_code [points] (or None)
+        are in the order of the cloud that update was given, cloud_range is its range.  accumulate_into = (rows, table or None)
+        of an earlier call: the counts are added to them and they are returned."""
+        A = self.map.n_agents
+        prm = SogmVelAuditParams()
+        prm.speed_tolerance, prm.n_codes = speed_tolerance, n_codes
+        if accumulate_into is not None:
+            rows, table = accumulate_into
+            prm.flags = SOGM_VELAUDIT_ACCUMULATE
+            assert rows.dtype == torch.int64 and rows.is_contiguous() and tuple(rows.shape) == (A, SOGM_VELAUDIT_ROW)
+            assert (table is not None) == bool(per_code)
+        else:
+            rows = torch.empty((A, SOGM_VELAUDIT_ROW), dtype=torch.int64, device=truth_labels.device)
+            table = torch.empty((A, n_codes + 2, 6), dtype=torch.int64, device=truth_labels.device) if per_code else None
+        if table is not None:
+            assert table.dtype == torch.int64 and table.is_contiguous() and tuple(table.shape) == (A, n_codes + 2, 6)
+        check(lib().sogm_dsp_velocity_audit(self._h, truth_labels.data_ptr(),
+                                            truth_code.data_ptr() if truth_code is not None else None,
+                                            cloud_range.data_ptr(), C.byref(prm), rows.data_ptr(),
+                                            table.data_ptr() if table is not None else None, _stream()),
+              "sogm_dsp_velocity_audit")
+        return rows, table
+
     def publish(self):
         """RiskVoxel::publishMap's map half: future status -> SOGM grid (+ inflate-kernel zeroing)."""
         n = torch.zeros(self.map.n_agents, dtype=torch.int32, device="cuda")
@@ -120,3 +156,27 @@ class DspMap:
                                                    pc.ctypes.data_as(C.c_void_p), ml.ctypes.data_as(C.c_void_p)),
               "sogm_dsp_download_observations")
         return nobs, pc, ml
+
+
+def velocity_scores(rows):
+    """What a velocity-audit row (or rows: they are summed) says, as a dict.  `detected` = TRACKED or UNTRACKED: the estimator
+    took the point for something that moves.  Ratios with an empty denominator are None."""
+    r = np.asarray(rows.cpu() if hasattr(rows, "cpu") else rows, np.int64).reshape(-1, SOGM_VELAUDIT_ROW).sum(axis=0)
+    conf = r[4:12].reshape(2, 4)                      # [truth still, moving][static, tracked, untracked, dropped]
+    moving, still = int(conf[1].sum()), int(conf[0].sum())
+    det_moving, det_still = int(conf[1, 1] + conf[1, 2]), int(conf[0, 1] + conf[0, 2])
+    scored = int(r[12:18].sum())                      # MOVING x TRACKED rows that are not NaN
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else None
+
+    return {
+        "n_in": int(r[0]), "n_born": int(r[1]), "moving": moving, "still": still,
+        "detection_precision": ratio(det_moving, det_moving + det_still),
+        "detection_recall": ratio(det_moving, moving),
+        "tracked_share_of_moving": ratio(int(conf[1, 1]), moving),
+        "dropped_share": ratio(int(conf[0, 3] + conf[1, 3]), int(r[0])),
+        "dropped_share_of_moving": ratio(int(conf[1, 3]), moving),
+        "rms_error": (float(r[29]) * 1e-6 / scored) ** 0.5 if scored else None,
+        "within_tolerance_share": ratio(int(r[30]), scored),
+    }

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <array>
+#include <cmath>
 #include <limits>
 #include <stdexcept>
 #include <string>
@@ -332,6 +333,20 @@ class RiskMap {
   DevBuf<int8_t>  o_;
 };
 
+// One agent's row of the velocity audit (sogm_abi.h "velocity audit"): the SOGM_VELAUDIT_ROW int64 values, by name.
+struct VelAuditRow {
+  int64_t n_in, n_born, status, n_nan;
+  int64_t confusion[2][4];    // [truth: still, moving][estimate: SOGM_VEL_STATIC, _TRACKED, _UNTRACKED, _DROPPED]
+  int64_t speed_moving[6];    // speed-error bins of the scored moving x tracked rows
+  int64_t speed_still[6];     // ... of the still x tracked rows: spurious velocity
+  int64_t direction[5];       // within 15 degrees, within 45, ahead, behind, a zero estimate
+  int64_t sum_e2_um, n_within;  // over the scored moving x tracked rows
+  int64_t zero_;
+  int64_t scored() const { int64_t n = 0; for (int64_t v : speed_moving) n += v; return n; }
+  double  rmsError() const { return scored() ? std::sqrt((double)sum_e2_um * 1e-6 / (double)scored()) : 0.0; }
+};
+static_assert(sizeof(VelAuditRow) == SOGM_VELAUDIT_ROW * sizeof(int64_t), "VelAuditRow names the 32 values of a row");
+
 // ---- DspMap : dsp_map::DSPMap as owned by RiskVoxel (risk_voxel.cpp:42-50,138-153,237-254) ----------
 // One instance serves every agent of a RiskMap created with map_kind = SOGM_MAP_RISKVOXEL.
 class DspMap {
@@ -339,7 +354,8 @@ class DspMap {
   // DSPMap() + setPredictionVariance / setObservationStdDev / setNewBornParticle* (risk_voxel.cpp:42-49);
   // the Gaussian and rand() tables the reference seeds from time(0) are supplied by the caller.
   DspMap(RiskMap &map, const SogmDspParams &p, const std::vector<float> &p_gauss,
-         const std::vector<float> &v_gauss, const std::vector<int32_t> &rand_tab, int max_points = 5000) {
+         const std::vector<float> &v_gauss, const std::vector<int32_t> &rand_tab, int max_points = 5000)
+      : n_(map.agents()) {
     check(sogm_dsp_create(map.ctx(), &p, p_gauss.data(), v_gauss.data(), (int)p_gauss.size(), rand_tab.data(),
                           (int)rand_tab.size(), max_points, &h_), "sogm_dsp_create");
   }
@@ -371,9 +387,31 @@ class DspMap {
   void publishMap(int32_t *out_n_occupied = nullptr, hipStream_t st = nullptr) {
     check(sogm_dsp_publish(h_, out_n_occupied, st), "sogm_dsp_publish");
   }
+  // Velocity audit (sogm_abi.h "velocity audit"; no reference counterpart) of the last update(): its new-born list against
+  // truth labels in the order of the cloud that update was given — filterPointCloudLabelled's labels [points 4] and code
+  // [points] (or nullptr), device pointers; cloud_range: that update's.  per_code_host: nullptr, or host room for
+  // agents x (n_codes + 2) x 6 values.  Returns one row per agent.  Synchronises `st`.
+  std::vector<VelAuditRow> auditVelocity(const float *truth_labels, const int32_t *truth_code, const int32_t *cloud_range,
+                                         int n_codes = 0, float speed_tolerance = 0.25f, int64_t *per_code_host = nullptr,
+                                         hipStream_t st = nullptr) {
+    SogmVelAuditParams prm{};
+    prm.speed_tolerance = speed_tolerance, prm.n_codes = n_codes;
+    const size_t n_tab = per_code_host && n_codes >= 0 ? (size_t)n_ * (size_t)(n_codes + 2) * 6 : 0;
+    vel_rows_.resize((size_t)n_ * SOGM_VELAUDIT_ROW);
+    if (n_tab) vel_tab_.resize(n_tab);
+    check(sogm_dsp_velocity_audit(h_, truth_labels, truth_code, cloud_range, &prm, vel_rows_.data(),
+                                  per_code_host ? vel_tab_.data() : nullptr, st), "sogm_dsp_velocity_audit");
+    if (hipStreamSynchronize(st) != hipSuccess) throw std::runtime_error("auditVelocity: hipStreamSynchronize failed");
+    std::vector<VelAuditRow> out((size_t)n_);
+    vel_rows_.get(reinterpret_cast<int64_t *>(out.data()), (size_t)n_ * SOGM_VELAUDIT_ROW);
+    if (n_tab) vel_tab_.get(per_code_host, n_tab);
+    return out;
+  }
 
  private:
   sogm_dsp *h_ = nullptr;
+  int       n_ = 0;
+  DevBuf<int64_t> vel_rows_, vel_tab_;
 };
 
 // ---- GridMap : depth-image occupancy front end (plan_env/src/grid_map.cpp) ------------------------------

@@ -28,7 +28,15 @@ slice.
                     the same frustum, --band METRES as the half thickness of the seen surface — and the cells that are FREE
                     or SURFACE are handed to sogm_map_audit_masked.  The line then also carries the five class counts (summed
                     over agents and frames), the view mask's ms per call, and, from the SAME run and the same maps, the
-                    frustum audit's ms per call and ratios ("frustum_same_run"): the masked audit's time is held to that."""
+                    frustum audit's ms per call and ratios ("frustum_same_run"): the masked audit's time is held to that.
+
+--velocity          (meaningful with --labels estimator) the velocity audit (include/sogm_abi.h "velocity audit") of every
+                    frame's update: the points then come from sogm_filter_point_cloud_labelled — the same leaves in the same
+                    order as the plain filter, centroids to 1e-4 — whose labels and codes are the truth; with --labels estimator
+                    the update still gets labels = NULL.  Every frame is audited with SOGM_VELAUDIT_ACCUMULATE and n_codes = the
+                    world's record count, and read back once.  The line then carries "velocity_audit": the summed row, the
+                    confusion matrix, dsp.velocity_scores of it, the audit's ms per call, and the five codes with the most
+                    moving points (their per-code rows).  Without it the tool does what it did and prints the keys it printed."""
 import argparse, importlib, json, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -43,7 +51,7 @@ def slice_map_for(prediction_times, T_test, T_truth, time_resolution):
 
 
 def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, cols=640, seed=0x5067, dt=0.1, slab_layers=0,
-        region="frustum", band=0.0):
+        region="frustum", band=0.0, velocity=False):
     pop = importlib.import_module("pred-occ-planner_amd")
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     dsp = importlib.import_module("pred-occ-planner_amd.dsp")
@@ -77,17 +85,33 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
     ev_view = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
     ev_fr = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
     total_fr, classes = np.zeros((spec.T, 8), np.int64), np.zeros(5, np.int64)
+    vel_acc, vel_moving = None, None
+    ev_vel = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
     for k in range(frames):
         frame = tl.frames(k, 1)[0]
         stamps = sogm._dev(np.full(A, float(sc["stamps"][0]) + k * dt), np.float64)
         img, cl, raw_rng, _, hit = depth.render_depth_swarm(frame, cam, pos_d, rot_d, None, want_hit=True)
-        if labels == "gt":
-            pts, cnt, lab, _ = m.filterPointCloudLabelled(cl, hit, raw_rng, frame, None, 0.0, 0.15, cap)
-            lab = lab.view(-1, 4)
+        truth_lab = truth_code = None
+        if labels == "gt" or velocity:
+            pts, cnt, truth_lab, truth_code = m.filterPointCloudLabelled(cl, hit, raw_rng, frame, None, 0.0, 0.15, cap,
+                                                                         want_code=velocity)
+            truth_lab = truth_lab.view(-1, 4)
+            lab = truth_lab if labels == "gt" else None
         else:
             pts, cnt = m.filterPointCloud(cl, raw_rng, 0.15, cap)
             lab = None
-        g.update(pts.view(-1, 3), lab, torch.stack([base, base + cnt], dim=1).contiguous(), pos32, quat, stamps)
+        crange = torch.stack([base, base + cnt], dim=1).contiguous()
+        g.update(pts.view(-1, 3), lab, crange, pos32, quat, stamps)
+        if velocity:
+            n_codes = int(frame.n_cyl)
+            ev_vel[k][0].record()
+            vel_acc = g.audit_velocity(truth_lab, truth_code.view(-1), crange, n_codes=n_codes, per_code=True, accumulate_into=vel_acc)
+            ev_vel[k][1].record()
+            # moving points per code (a record's points share its label), on the device: read back once, with the rows
+            live = (torch.arange(cap, device="cuda")[None, :] < cnt[:, None]).view(-1)
+            mv = live & (truth_lab[:, 3] > 0.01) & (truth_code.view(-1) >= 0) & (truth_code.view(-1) < n_codes)
+            add = torch.bincount(truth_code.view(-1)[mv].to(torch.int64), minlength=n_codes)
+            vel_moving = add if vel_moving is None else vel_moving + add
         g.publish()
         state = [m.map_state(a) for a in range(A)]
         truth.updateWorld(frame, sogm._dev(np.stack([c for _, c in state]), np.float32),
@@ -149,6 +173,21 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
                         "precision_strict": ratio(total_fr[:, 3], total_fr[:, 1]), "recall_strict": ratio(total_fr[:, 3], total_fr[:, 2]),
                         f"precision_within_{tolerance}": ratio(total_fr[:, 4], total_fr[:, 1]),
                         f"recall_within_{tolerance}": ratio(total_fr[:, 5], total_fr[:, 2])}})
+    if velocity:
+        rows_v, table = vel_acc[0].cpu().numpy(), vel_acc[1].cpu().numpy().sum(axis=0)
+        summed = rows_v.sum(axis=0)
+        summed[2] = np.bitwise_or.reduce(rows_v[:, 2])
+        moving = vel_moving.cpu().numpy()
+        top = [int(c) for c in np.argsort(-moving, kind="stable")[:5] if moving[c] > 0]
+        ms_v = np.array([a.elapsed_time(b) for a, b in ev_vel])[1 if frames > 1 else 0:]
+        cols = pop._abi.VELAUDIT_CODE_COLUMNS
+        out["velocity_audit"] = {
+            "n_codes": int(table.shape[0] - 2), "speed_tolerance": 0.25, "row": summed.tolist(),
+            "confusion": {"still": dict(zip(pop._abi.VEL_ESTIMATE_NAMES, summed[4:8].tolist())),
+                          "moving": dict(zip(pop._abi.VEL_ESTIMATE_NAMES, summed[8:12].tolist()))},
+            "scores": dsp.velocity_scores(summed), "audit_ms_per_call": float(np.median(ms_v)),
+            "ground": dict(zip(cols, table[-2].tolist())), "other": dict(zip(cols, table[-1].tolist())),
+            "top_moving_codes": [dict(code=c, moving_points=int(moving[c]), **dict(zip(cols, table[c].tolist()))) for c in top]}
     g.close()
     m.close()
     truth.close()
@@ -168,6 +207,7 @@ if __name__ == "__main__":
     ap.add_argument("--region", choices=["frustum", "visible"], default="frustum",
                     help="visible: only the cells the frame's depth image shows free or on the seen surface")
     ap.add_argument("--band", type=float, default=0.0, help="metres: half the thickness of the seen surface (--region visible)")
+    ap.add_argument("--velocity", action="store_true", help="also score every update's new-born list against the truth labels")
     a = ap.parse_args()
     print(json.dumps(run(a.grid, a.agents, a.frames, a.labels, a.tolerance, a.rows, a.cols, slab_layers=a.slab_layers,
-                         region=a.region, band=a.band)))
+                         region=a.region, band=a.band, velocity=a.velocity)))
