@@ -721,6 +721,78 @@ int sogm_render_depth_swarm(const SogmWorld *world, const SogmDepthCamera *cam, 
                             int32_t *out_unsupported, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* sensor noise: a deterministic noise pass over the frames the depth camera leaves on the      */
+/*   device — axial noise that grows with range, uniform dropout, dropout at depth edges and a   */
+/*   minimum range.  The reference intended depth noise and never shipped it                     */
+/*   (grid_map.cpp:160-161, 263-264 are commented out); like the camera this is the build's OWN  */
+/*   definition, held by two independent implementations (csrc/sogm_depthnoise.hpp;              */
+/*   tests/depth_noise_reference.py), bit for bit.                                               */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * All fp64 is one IEEE operation at a time (+ - * / floor) in the written order, without contraction.  No transcendentals.
+ * Integers are uint64 and wrap.
+ *
+ * Counter-based draws — no state, no dependence on scheduling or on the branch a pixel takes:
+ *   mix(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *            x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  return x ^ (x >> 31)            (splitmix64's step)
+ *   g   = ((uint64)(agent_base + a) * rows + v) * cols + u          (the pixel's index in the whole swarm's frame)
+ *   h   = mix( mix( mix(seed) ^ frame ) ^ g )
+ *   w_k = mix(h + k)                                    k = 0 .. 4
+ *   U(w) = (double)(w >> 11) * 2^-53                                in [0, 1)
+ *   S   = sum over k in (2, 3, 4), j in (0, 1, 2, 3) of (w_k >> 16 j) & 0xFFFF          (12 pieces: Irwin-Hall)
+ *   n   = ((double)S - 393210.0) * 2^-16                            mean 0, variance 1 - 2^-32, support about +-6
+ * Known answers: mix(0) = 0xE220A8397B1DCDAF.  seed 0x5067, frame 3, g 0: h = 0x52E3CB0B7BF29351, S = 436624,
+ *   n = 0x1.532cp-1.  Over g = 0 .. 199999 at that seed and frame: mean(n) = -0.0047, var(n) = 0.9972, share of
+ *   U(w_0) < 0.05 = 0.0508.
+ *
+ * Pixel (a, v, u) with input d16 (camera: "depth camera" above):
+ *   1. d16 == 0: no return in, no return out; nothing is counted.
+ *   2. z = (double)d16 / depth_scale; count returns_in.
+ *   3. uniform dropout: if U(w_0) < p_drop, count drop_uniform; no return.
+ *   4. edge dropout, only when edge_jump > 0: the pixel is an edge pixel if any of its up to 8 neighbours INSIDE the image
+ *      has d16_n == 0 or fabs(z_n - z) > edge_jump (z_n formed like z).  Neighbours outside the image do not exist: a 1 x 1
+ *      image has no edge pixel.  An edge pixel with U(w_1) < p_edge counts drop_edge; no return.  Edges are those of the
+ *      INPUT image, never of noised neighbours.
+ *   5. axial noise: s = (sigma2*z + sigma1)*z + sigma0;  zn = z + s*n
+ *   6. range: if !(zn >= min_depth), count below_min; no return.  Else if zn > max_depth, count beyond_max; no return.
+ *      Else q = floor(zn*depth_scale + 0.5); q == 0 counts below_min (no return); otherwise d16' = (uint16)q, count
+ *      returns_out (max_depth*depth_scale <= 65535 is required of the camera: q fits).
+ *   7. cloud point: "depth camera"'s back-projection of d16' (three quiet NaNs for 0).
+ *   8. hit: in_hit where d16' != 0, SOGM_HIT_NONE where it is 0.
+ * out_counts[a*6 + i], i = 0 .. 5: returns_in, drop_uniform, drop_edge, below_min, beyond_max, returns_out.  Per agent
+ *   returns_in == drop_uniform + drop_edge + below_min + beyond_max + returns_out.  The call zeroes them in stream order and
+ *   adds integers: they are the same bits from run to run.
+ * With every sigma, probability, edge_jump and min_depth 0 the pass is the identity on image, cloud and hit wherever
+ *   d16/depth_scale <= max_depth and floor((d16/depth_scale)*depth_scale + 0.5) == d16 — every d16 the camera gives at
+ *   depth_scale 1000 and a max_depth that is a whole number of quanta.
+ */
+typedef struct SogmDepthNoise {
+  uint64_t seed;
+  uint64_t frame;
+  int32_t  agent_base;   /* the global index of local agent 0: a rank's shard draws what the whole swarm would */
+  int32_t  flags;        /* reserved; other bits are ignored */
+  double   sigma0, sigma1, sigma2;   /* s = (sigma2*z + sigma1)*z + sigma0, metres */
+  double   p_drop;       /* [0, 1] */
+  double   edge_jump;    /* metres; 0: no edge dropout */
+  double   p_edge;       /* [0, 1] */
+  double   min_depth;    /* metres */
+} SogmDepthNoise;        /* 80 bytes */
+/*
+ * The pass over n_agents frames of cam's size.  Context-free, stream-ordered, no allocation, no host synchronisation, like
+ * sogm_render_depth.  dev in_depth [n*rows*cols] uint16 and in_hit [n*rows*cols] int32 (or NULL) are only read; dev out_depth
+ * [n*rows*cols] uint16, out_cloud_xyz [n*rows*cols*3] fp32 or NULL, out_hit [n*rows*cols] int32 or NULL (needs in_hit; may BE
+ * in_hit: that path is per pixel), out_counts [n*6] int32.
+ * SOGM_ERR_INVALID_ARG (checked first; sogm_last_error() names the rule): sogm_render_depth's camera refusals; a null noise,
+ * in_depth, out_depth or out_counts; out_hit without in_hit; a parameter that is not finite; a sigma, edge_jump or min_depth
+ * below 0; a probability outside [0, 1]; agent_base < 0; out_depth overlapping in_depth (the 3 x 3 test reads neighbours other
+ * workgroups own, so an in-place pass is refused).  SOGM_ERR_NO_DEVICE without a GPU.
+ */
+int sogm_depth_noise(const SogmDepthCamera *cam, const SogmDepthNoise *noise, int n_agents,
+                     const uint16_t *in_depth /* dev [n*rows*cols] */, const int32_t *in_hit /* dev [n*rows*cols] or NULL */,
+                     uint16_t *out_depth /* dev [n*rows*cols] */, float *out_cloud_xyz /* dev [n*rows*cols*3] or NULL */,
+                     int32_t *out_hit /* dev [n*rows*cols] or NULL */, int32_t *out_counts /* dev [n*6] */, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* ground-truth labels: the hit index carried through the voxel filter, leaf by leaf, into the   */
 /*   per-point {vx, vy, vz, intensity} labels sogm_update_dsp takes.  The reference's main mode   */
 /*   (FakeParticleRiskVoxel) gives its map ground-truth velocities; this is the same for the      */

@@ -77,6 +77,12 @@ class SogmDepthBodies(C.Structure):
                 ("n_bodies", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class SogmDepthNoise(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("frame", C.c_uint64), ("agent_base", C.c_int32), ("flags", C.c_int32),
+                ("sigma0", C.c_double), ("sigma1", C.c_double), ("sigma2", C.c_double), ("p_drop", C.c_double),
+                ("edge_jump", C.c_double), ("p_edge", C.c_double), ("min_depth", C.c_double)]
+
+
 class SogmCylinder(C.Structure):
     _fields_ = [("type", C.c_int32), ("_pad", C.c_int32)] + [
         (k, C.c_double) for k in ("x", "y", "z", "w", "h", "vx", "vy", "qw", "qx", "qy", "qz")]
@@ -270,6 +276,8 @@ CYLINDER_BYTES = C.sizeof(SogmCylinder)  # 96
 DEPTH_CAMERA_BYTES = C.sizeof(SogmDepthCamera)  # 72
 DEPTH_BODIES_BYTES = C.sizeof(SogmDepthBodies)  # 48
 SOGM_HIT_GROUND, SOGM_HIT_NONE = -1, -2   # out_hit of sogm_render_depth_swarm
+DEPTH_NOISE_BYTES = C.sizeof(SogmDepthNoise)  # 80
+DEPTH_NOISE_COUNTERS = ("returns_in", "drop_uniform", "drop_edge", "below_min", "beyond_max", "returns_out")
 LABEL_SOURCES_BYTES = C.sizeof(SogmLabelSources)  # 32
 
 
@@ -362,6 +370,7 @@ PROTOTYPES = {
     "sogm_render_depth": (_i, [C.POINTER(SogmWorld), C.POINTER(SogmDepthCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_render_depth_swarm": (_i, [C.POINTER(SogmWorld), C.POINTER(SogmDepthCamera), C.POINTER(SogmDepthBodies), _i, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sogm_depth_noise": (_i, [C.POINTER(SogmDepthCamera), C.POINTER(SogmDepthNoise), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_download": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "sogm_gridmap_force_frame": (_i, [_vp, _i]),
     "sogm_traj_safe": (_i, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

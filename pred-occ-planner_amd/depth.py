@@ -2,13 +2,13 @@
 cylinders and ground plane, rendered on the device (sogm_render_depth) in the layouts the two perception front ends
 read — the uint16 image GridMap.update takes and the camera-frame cloud SogmMap.filterPointCloud takes.
 render_depth_swarm also draws the other vehicles of a swarm (sogm_render_depth_swarm, "agent bodies") and can say per pixel
-what was hit.  No CPU path."""
+what was hit.  add_depth_noise runs the sensor-noise pass (sogm_depth_noise, "sensor noise") over such frames.  No CPU path."""
 import ctypes as C
 
 import numpy as np
 import torch
 
-from ._abi import SOGM_DEPTH_RINGS, SogmDepthBodies, SogmDepthCamera, check, lib
+from ._abi import SOGM_DEPTH_RINGS, SogmDepthBodies, SogmDepthCamera, SogmDepthNoise, check, lib
 from .gridmap import make_gridmap_params
 from .sogm import _dev, _stream
 
@@ -97,3 +97,37 @@ def render_depth_swarm(world, cam, cam_pos, cam_rot, body_pos, cam_body=None, bo
     begin = torch.arange(A, dtype=torch.int64, device=dev) * n
     raw_range = torch.stack([begin, begin + n], dim=1).to(torch.int32)
     return depth, cloud, raw_range, unsupported, hit
+
+
+def make_depth_noise(seed=0, frame=0, agent_base=0, sigma=(0.0, 0.0, 0.0), p_drop=0.0, edge_jump=0.0, p_edge=0.0, min_depth=0.0):
+    """The parameters of include/sogm_abi.h "sensor noise": axial noise s = (sigma[2] z + sigma[1]) z + sigma[0] metres, uniform
+    dropout p_drop, dropout p_edge at depth steps above edge_jump metres (0: none), no return below min_depth.  The default is
+    the identity.  agent_base: the global index of local agent 0."""
+    n = SogmDepthNoise()
+    n.seed, n.frame, n.agent_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame) & 0xFFFFFFFFFFFFFFFF, int(agent_base)
+    n.sigma0, n.sigma1, n.sigma2 = (float(v) for v in sigma)
+    n.p_drop, n.edge_jump, n.p_edge, n.min_depth = float(p_drop), float(edge_jump), float(p_edge), float(min_depth)
+    return n
+
+
+def add_depth_noise(cam, noise, depth, hit=None, want_cloud=True):
+    """The noise pass over rendered frames: depth [A, rows, cols] int16 storage of the uint16 image (render_depth's), hit
+    [A, rows, cols] int32 or None.  Returns new device tensors (depth in the same storage, cloud [A*rows*cols, 3] float32 with
+    NaN where there is no return — None unless want_cloud —, hit with SOGM_HIT_NONE where the return was lost — None without
+    hit —, counts [A, 6] int32: _abi.DEPTH_NOISE_COUNTERS).  The caller's tensors are untouched.  Stream-ordered, no
+    synchronisation."""
+    assert depth.dtype == torch.int16 and depth.is_cuda, (depth.dtype, depth.device)
+    depth = depth.reshape(-1, cam.rows, cam.cols).contiguous()
+    A, n, dev = int(depth.shape[0]), cam.rows * cam.cols, depth.device
+    if hit is not None:
+        assert hit.dtype == torch.int32 and hit.numel() == A * n, (hit.dtype, hit.shape)
+        hit = hit.reshape(A, cam.rows, cam.cols).contiguous()
+    out = torch.empty_like(depth)
+    cloud = torch.empty((A * n, 3), dtype=torch.float32, device=dev) if want_cloud else None
+    out_hit = torch.empty_like(hit) if hit is not None else None
+    counts = torch.empty((A, 6), dtype=torch.int32, device=dev)
+    check(lib().sogm_depth_noise(C.byref(cam), C.byref(noise), A, depth.data_ptr(), hit.data_ptr() if hit is not None else None,
+                                 out.data_ptr(), cloud.data_ptr() if want_cloud else None,
+                                 out_hit.data_ptr() if hit is not None else None, counts.data_ptr(), _stream()),
+          "sogm_depth_noise")
+    return out, cloud, out_hit, counts

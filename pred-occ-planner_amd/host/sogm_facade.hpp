@@ -444,6 +444,15 @@ class GridMap {
     check(sogm_render_depth_swarm(&frame, &cam, bodies, n_agents, cam_pos, cam_rot, depth, cloud_xyz, hit, unsupported, st),
           "sogm_render_depth_swarm");
   }
+  // The sensor-noise pass over such frames (sogm_abi.h "sensor noise"): axial noise, uniform and edge dropout and a minimum
+  // range, drawn per pixel from (seed, frame, agent_base + agent, v, u) alone.  in_depth / in_hit (may be nullptr) are only
+  // read; depth must not overlap in_depth; cloud_xyz and hit may be nullptr, hit may be in_hit; counts [n * 6]: returns_in,
+  // drop_uniform, drop_edge, below_min, beyond_max, returns_out per agent.
+  static void addDepthNoise(const SogmDepthCamera &cam, const SogmDepthNoise &noise, int n_agents, const uint16_t *in_depth,
+                            const int32_t *in_hit, uint16_t *depth, float *cloud_xyz, int32_t *hit, int32_t *counts,
+                            hipStream_t st = nullptr) {
+    check(sogm_depth_noise(&cam, &noise, n_agents, in_depth, in_hit, depth, cloud_xyz, hit, counts, st), "sogm_depth_noise");
+  }
   // int getInflateOccupancy(Eigen::Vector3d pos) for a batch of device-resident queries
   void getInflateOccupancy(const int32_t *agent_idx, const double *pos, int n, int8_t *out, hipStream_t st = nullptr) {
     check(sogm_gridmap_query_inflate(h_, agent_idx, pos, n, out, st), "sogm_gridmap_query_inflate");

@@ -14,7 +14,12 @@ bodies, i.e. the cost of carrying the hit codes.  --hit also asks for the hit im
 
 --labels (with --bodies N) also times the labelled filter (sogm_filter_point_cloud_labelled, "ground-truth labels") in the same
 run, next to the plain one: the render then always writes the hit image, every body gets a velocity from SplitMix64, and
-filter_labelled_ms / render_then_filter_labelled_ms stand beside filter_ms / render_then_filter_ms, with their ratio."""
+filter_labelled_ms / render_then_filter_labelled_ms stand beside filter_ms / render_then_filter_ms, with their ratio.
+
+--noise also times the sensor-noise pass (sogm_depth_noise, "sensor noise": sigma 0.002, 0.003, 0.004, 5 % dropout, half the
+pixels at 0.15 m edges, nothing below 0.3 m) on the last rendered frame — with the cloud (and the hit image, when the render
+gave one), the image alone — and behind the render; noise_GBps_algorithmic counts the bytes the definition moves: 2 + 2 per
+pixel, + 12 with the cloud, + 4 + 4 with the hit image."""
 import argparse, importlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -54,7 +59,7 @@ def swarm_bodies(pop, pos, rot, n_bodies):
     return bodies, np.array([a if a < n_bodies else -1 for a in range(A)], np.int32)
 
 
-def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False, labels=False):
+def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False, labels=False, noise=False):
     pop = importlib.import_module("pred-occ-planner_amd")
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     gm = importlib.import_module("pred-occ-planner_amd.gridmap")
@@ -136,6 +141,19 @@ def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False, labels=False):
         t_fl = timed(filter_labelled)
         t_rfl = timed(render_filter_labelled)
         t_filter_again = timed(lambda k: keep.__setitem__("flt", m.filterPointCloud(cl, rng, 0.15, 5000)))
+    if noise:
+        nz = [depth.make_depth_noise(0x5067, k, 0, (0.002, 0.003, 0.004), 0.05, 0.15, 0.5, 0.3) for k in range(n)]
+        d_last = render(n - 1)[0]
+        h_noise = keep.get("hit")
+
+        def render_noise(k):
+            d_k = render(k)[0]
+            keep["noise"] = depth.add_depth_noise(cam, nz[k], d_k, keep.get("hit"))
+
+        t_noise = timed(lambda k: keep.__setitem__("noise", depth.add_depth_noise(cam, nz[k], d_last, h_noise)))
+        noise_counts = keep["noise"][3].sum(dim=0).tolist()
+        t_noise_image = timed(lambda k: keep.__setitem__("noise", depth.add_depth_noise(cam, nz[k], d_last, None, want_cloud=False)))
+        t_rn = timed(render_noise)
     nbytes = A * cam.rows * cam.cols * 14
     out = {"agents": A, "cylinders": int(len(sc["cylinders"])), "rings": int(rings), "frames_timed": steps,
            "render_ms": t_render, "render_GBps_algorithmic": round(nbytes / (t_render["mean"] * 1e-3) / 1e9, 1),
@@ -153,6 +171,11 @@ def run(A, steps=30, warmup=5, rings=0, bodies=-1, hit=False, labels=False):
                     "filter_ms_after_labelled": t_filter_again,      # the plain entry once the key array exists
                     "filter_labelled_over_filter": round(t_fl["mean"] / t_filter["mean"], 3),
                     "labelled_points_agent0": int((lab[0, :cnt0, 3] > 0).sum().item()), "filtered_points_labelled_agent0": cnt0})
+    if noise:
+        nb = A * cam.rows * cam.cols * (16 + (8 if h_noise is not None else 0))
+        out.update({"noise_ms": t_noise, "noise_image_only_ms": t_noise_image, "render_then_noise_ms": t_rn,
+                    "noise_algorithmic_bytes": nb, "noise_GBps_algorithmic": round(nb / (t_noise["mean"] * 1e-3) / 1e9, 1),
+                    "noise_counters": dict(zip(pop._abi.DEPTH_NOISE_COUNTERS, noise_counts))})
     g.close()
     m.close()
     return out
@@ -169,9 +192,10 @@ if __name__ == "__main__":
     ap.add_argument("--hit", action="store_true", help="with --bodies: also ask for the hit image")
     ap.add_argument("--labels", action="store_true", help="with --bodies: also time sogm_filter_point_cloud_labelled on the hit "
                     "image (implies --hit)")
+    ap.add_argument("--noise", action="store_true", help="also time the sensor-noise pass (sogm_depth_noise) on the rendered frames")
     a = ap.parse_args()
     assert a.steps >= 20 and torch.cuda.is_available(), "needs a GPU and at least 20 timed frames"
     assert not a.labels or a.bodies >= 0, "--labels needs --bodies N (the hit image comes from sogm_render_depth_swarm)"
     print(json.dumps({"workload": "sogm_render_depth, 480x640 per camera, cfg2 moving world (seed 0x5069), cameras on a 12 m "
                                   "circle; ms per frame: HIP events on the launch stream around each call",
-                      "runs": [run(A, a.steps, a.warmup, a.rings, a.bodies, a.hit, a.labels) for A in a.agents]}))
+                      "runs": [run(A, a.steps, a.warmup, a.rings, a.bodies, a.hit, a.labels, a.noise) for A in a.agents]}))

@@ -36,7 +36,13 @@ slice.
                     the update still gets labels = NULL.  Every frame is audited with SOGM_VELAUDIT_ACCUMULATE and n_codes = the
                     world's record count, and read back once.  The line then carries "velocity_audit": the summed row, the
                     confusion matrix, dsp.velocity_scores of it, the audit's ms per call, and the five codes with the most
-                    moving points (their per-code rows).  Without it the tool does what it did and prints the keys it printed."""
+                    moving points (their per-code rows).  Without it the tool does what it did and prints the keys it printed.
+
+--noise S0,S1,S2 --drop P --edge JUMP,P --min-depth M --noise-seed N
+                    With any of them every rendered frame goes through the sensor-noise pass (include/sogm_abi.h "sensor noise",
+                    sogm_depth_noise) before the filter — image, cloud and hit index, frame = the frame's index — and the line
+                    gains "depth_noise": the settings and the six counters summed over agents and frames.  Without them
+                    the tool does what it did and prints the keys it printed."""
 import argparse, importlib, json, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -51,7 +57,7 @@ def slice_map_for(prediction_times, T_test, T_truth, time_resolution):
 
 
 def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, cols=640, seed=0x5067, dt=0.1, slab_layers=0,
-        region="frustum", band=0.0, velocity=False):
+        region="frustum", band=0.0, velocity=False, noise=None):
     pop = importlib.import_module("pred-occ-planner_amd")
     sogm = importlib.import_module("pred-occ-planner_amd.sogm")
     dsp = importlib.import_module("pred-occ-planner_amd.dsp")
@@ -86,11 +92,15 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
     ev_fr = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
     total_fr, classes = np.zeros((spec.T, 8), np.int64), np.zeros(5, np.int64)
     vel_acc, vel_moving = None, None
+    noise_counts = None
     ev_vel = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(frames)]
     for k in range(frames):
         frame = tl.frames(k, 1)[0]
         stamps = sogm._dev(np.full(A, float(sc["stamps"][0]) + k * dt), np.float64)
         img, cl, raw_rng, _, hit = depth.render_depth_swarm(frame, cam, pos_d, rot_d, None, want_hit=True)
+        if noise is not None:
+            img, cl, hit, cnt6 = depth.add_depth_noise(cam, depth.make_depth_noise(frame=k, **noise), img, hit)
+            noise_counts = cnt6 if noise_counts is None else noise_counts + cnt6
         truth_lab = truth_code = None
         if labels == "gt" or velocity:
             pts, cnt, truth_lab, truth_code = m.filterPointCloudLabelled(cl, hit, raw_rng, frame, None, 0.0, 0.15, cap,
@@ -188,13 +198,18 @@ def run(grid="cfg1", agents=None, frames=8, labels="gt", tolerance=1, rows=480, 
             "scores": dsp.velocity_scores(summed), "audit_ms_per_call": float(np.median(ms_v)),
             "ground": dict(zip(cols, table[-2].tolist())), "other": dict(zip(cols, table[-1].tolist())),
             "top_moving_codes": [dict(code=c, moving_points=int(moving[c]), **dict(zip(cols, table[c].tolist()))) for c in top]}
+    if noise is not None:
+        summed = noise_counts.cpu().numpy().astype(np.int64).sum(axis=0)
+        out["depth_noise"] = {"settings": {k: (list(v) if isinstance(v, tuple) else v) for k, v in noise.items()},
+                              "counters": dict(zip(pop._abi.DEPTH_NOISE_COUNTERS, summed.tolist()))}
     g.close()
     m.close()
     truth.close()
     return out
 
 
-if __name__ == "__main__":
+def parse_args(argv=None):
+    floats = lambda n: (lambda s: _floats(s, n))                                              # noqa: E731
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", default="cfg1")
     ap.add_argument("--agents", type=int, default=None)
@@ -208,6 +223,32 @@ if __name__ == "__main__":
                     help="visible: only the cells the frame's depth image shows free or on the seen surface")
     ap.add_argument("--band", type=float, default=0.0, help="metres: half the thickness of the seen surface (--region visible)")
     ap.add_argument("--velocity", action="store_true", help="also score every update's new-born list against the truth labels")
-    a = ap.parse_args()
+    ap.add_argument("--noise", type=floats(3), default=None, metavar="S0,S1,S2",
+                    help="axial noise s = (S2 z + S1) z + S0 metres on every rendered frame")
+    ap.add_argument("--drop", type=float, default=None, metavar="P", help="uniform dropout probability")
+    ap.add_argument("--edge", type=floats(2), default=None, metavar="JUMP,P", help="dropout P at depth steps above JUMP metres")
+    ap.add_argument("--min-depth", type=float, default=None, metavar="M", help="no return below M metres")
+    ap.add_argument("--noise-seed", type=lambda s: int(s, 0), default=None, metavar="N")
+    return ap.parse_args(argv)
+
+
+def _floats(text, n):
+    vals = tuple(float(v) for v in text.split(","))
+    if len(vals) != n:
+        raise argparse.ArgumentTypeError(f"{n} comma-separated numbers expected, got {text!r}")
+    return vals
+
+
+def noise_settings(a):
+    """make_depth_noise's keywords (without frame) if any noise flag was given, else None"""
+    if a.noise is None and a.drop is None and a.edge is None and a.min_depth is None and a.noise_seed is None:
+        return None
+    edge = a.edge or (0.0, 0.0)
+    return dict(seed=0x5067 if a.noise_seed is None else a.noise_seed, sigma=a.noise or (0.0, 0.0, 0.0), p_drop=a.drop or 0.0,
+                edge_jump=edge[0], p_edge=edge[1], min_depth=a.min_depth or 0.0)
+
+
+if __name__ == "__main__":
+    a = parse_args()
     print(json.dumps(run(a.grid, a.agents, a.frames, a.labels, a.tolerance, a.rows, a.cols, slab_layers=a.slab_layers,
-                         region=a.region, band=a.band, velocity=a.velocity)))
+                         region=a.region, band=a.band, velocity=a.velocity, noise=noise_settings(a))))
