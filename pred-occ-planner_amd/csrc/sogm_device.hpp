@@ -807,7 +807,7 @@ struct MapTarget;
 // and stamps — the NEXT ones for a pre-stamp.  Allocates the scratch and the *_next arrays on first use (`st`: the stream
 // that zeroes the new occupancy bits).
 int  map_target(sogm_ctx *c, int slot, bool next_poses, hipStream_t st, MapTarget *out);
-// what the velocity audit (sogm_velaudit.hip) reads of a particle map handle (sogm_dsp.hip), as plain device pointers: the
+// what the velocity audit (sogm_velaudit.hip) reads of a particle map handle (sogm_dsp_state.hip), as plain device pointers: the
 // new-born list of the last update, its source index, and per agent "the update was accepted" and the list's length (two ints
 // of the agent's scalars, `stride` ints from one agent to the next)
 struct DspBornView {

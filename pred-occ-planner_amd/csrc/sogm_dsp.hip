@@ -27,177 +27,9 @@
 // Everything is HBM/latency-bound gather-scatter work; no MFMA.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-#include <vector>
-
-#include "sogm_device.hpp"
+#include "sogm_dsp.hpp"
 
 namespace sogm {
-
-enum : uint8_t { F_EMPTY = 0, F_VALID = 1, F_RESAMP = 2, F_MOVED = 3, F_NEW = 4, F_DEPART = 5, F_KILLED = 6 };
-#define DSP_SLOTS 16   // storage slots per voxel (>= SAFE_PARTICLE_NUM_VOXEL)
-#define DSP_ROUNDS 6   // place/pyramid fixed-point rounds issued per update
-
-#define VEL_MAX_CLUSTERS 256  // accepted clusters per frame (more: error counter)
-#define VEL_MAX_DYN 64        // possibly-dynamic clusters per frame taking part in the association
-#define VEL_ADJ_CAP 128       // neighbours within the cluster tolerance kept per point
-
-struct DspAgent {  // per-agent scalars (device)
-  float  last_p[3];
-  int    first;
-  double last_t;
-  float  cur[3];
-  float  update_time;
-  float  quat[4];
-  float  odom[4];  // -dx, -dy, -dz, dt
-  int    pseq, vseq, rseq;
-  int    ok;
-  int    n_born, n_obs, valid_points;
-  float  enb;  // expected_new_born_objects
-  float  w_new;
-  int    cand_cnt, born_cnt;
-  int    changed[DSP_ROUNDS];
-  int    dbg_voxel_full, dbg_pyr_full, dbg_out;
-  int    err_unconverged, err_pool, err_points;
-  int    n_occupied;
-  // velocity estimation (velocityEstimationThread): previous frame's possibly-dynamic clusters and counters
-  int    vel_n_last;
-  int    vel_clusters, vel_dynamic, vel_matched, vel_err;
-  float  vel_last[VEL_MAX_DYN][5];  // centre x, y, z, intensity, point_num (as float)
-};
-
-struct DspDev {
-  int   A, V, S, L, W, H, T, NP, nph, npv, SP, OM, cand_cap, max_pts, nb, maxp, n_gauss, n_rand;
-  float res, hx, hy, hz, sigma, Pd, kappa, w_nb, thick;
-  float pred_t[SOGM_DSP_MAX_T];
-  DspAgent *ag;
-  uint8_t  *flag;  // [A][V][16]
-  float    *f[6];  // vx vy px py pz w : [A][V][16]
-  float    *fut;   // [A][T][V]
-  float    *occ;   // [A][4][V]
-  float    *pc;    // [A][NP][OM][5]
-  int      *nobs;  // [A][NP]
-  int      *maxlen;  // [A][NP] float bits (>= 0) or -1
-  int      *obs_list;  // [A][max_pts] pi*OM + seq of every stored observation
-  float    *bp_h, *bp_v;  // [A][(nph+1)*3], [A][(npv+1)*3]
-  float    *born;  // [A][max_pts][7]
-  int      *born_src;  // [A][max_pts] input index of every row of `born` (the velocity audit's link; rows >= n_born: stale)
-  unsigned short *vel_adj;  // [A][max_pts][VEL_ADJ_CAP] neighbour lists of the clustering (velocity estimation)
-  int            *vel_deg;  // [A][max_pts]
-  // candidates of the prediction step (movers + in-FOV stays)
-  int     *c_key, *c_dest, *c_pyr, *c_assign, *c_vnext, *c_pnext;  // [A][cand_cap]
-  uint8_t *c_kill;                                                 // [A][cand_cap]
-  float   *c_pay;                                                  // [A][cand_cap][6]
-  int     *vhead;  // [A][V]
-  int     *phead;  // [A][NP]
-  int     *pyr_list, *pyr_n;  // [A][NP][SP] loc, [A][NP]
-  int     *pyr_key, *pyr_id;  // [A][NP][SP] selection scratch (sweep key, candidate id)
-  // new-born scratch
-  int   *b_valid, *b_nstatic, *b_vi;  // [A][max_pts]
-  float *b_c;                          // [A][max_pts][3]
-  int8_t *b_cls;                       // [A][max_pts*nb]
-  int   *b_dest, *b_vnext;             // [A][max_pts*nb]
-  float *b_pay;                        // [A][max_pts*nb][5] px py pz vx vy
-  const float *pg, *vg, *pdf, *bp_ori_h, *bp_ori_v;
-  const int   *rnd, *nbr;
-};
-
-// ---- small device helpers (arithmetic mirrors the reference, see oracle/dsp_oracle.cpp) ---------
-__device__ inline void qmul(const float a[4], const float b[4], float o[4]) {
-  o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  o[2] = a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3];
-  o[3] = a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1];
-}
-// rotateVectorByQuaternion dsp_dynamic.h:1391-1411
-__device__ inline void rotate_q(const float *v, const float *q, float *o) {
-  float vq[4] = {0.f, v[0], v[1], v[2]}, t[4], r[4];
-  float n2    = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-  float inv[4] = {q[0] / n2, -q[1] / n2, -q[2] / n2, -q[3] / n2};
-  qmul(q, vq, t);
-  qmul(t, inv, r);
-  o[0] = r[1];
-  o[1] = r[2];
-  o[2] = r[3];
-}
-__device__ inline float dot3(float x, float y, float z, const float *n) { return x * n[0] + y * n[1] + z * n[2]; }
-
-// ifInPyramidsArea + findPointPyramid{Horizontal,Vertical}Index (:1413-1474): pyramid index or -1
-__device__ inline int pyramid_of(const float *bh, const float *bv, int nph, int npv, float x, float y, float z) {
-  if (!(dot3(x, y, z, bh) >= 0.f && dot3(x, y, z, bh + nph * 3) <= 0.f && dot3(x, y, z, bv) <= 0.f &&
-        dot3(x, y, z, bv + npv * 3) >= 0.f))
-    return -1;
-  int h = -1, v = -1;
-  if (fabsf(x) + fabsf(y) + fabsf(z) < 1e-12f) {
-    // degenerate lengths: the products last*t of the reference's scan may underflow — replay it literally
-    float last = 1.f;
-    for (int i = 0; i < nph; i++) {
-      float t = dot3(x, y, z, bh + (i + 1) * 3);
-      if (last * t <= 0.f) {
-        h = i;
-        break;
-      }
-      last = t;
-    }
-    last = -1.f;
-    for (int j = 0; j < npv; j++) {
-      float t = dot3(x, y, z, bv + (j + 1) * 3);
-      if (last * t <= 0.f) {
-        v = j;
-        break;
-      }
-      last = t;
-    }
-  } else {
-    // The reference scans the boundary planes for the first sign change.  Inside the FOV the dot
-    // products are positive (h) / negative (v) up to the point's pyramid and change sign once (planes
-    // are 1 degree apart, far more than fp32 rounding), so the first index with t <= 0 (h) / t >= 0 (v)
-    // is found by bisection with the same fp32 dot products: ~13 instead of ~70 plane tests.
-    int lo = 0, hi = nph - 1;  // predicate true at nph-1 (ifInPyramidsArea: dot with plane nph <= 0)
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (dot3(x, y, z, bh + (mid + 1) * 3) <= 0.f)
-        hi = mid;
-      else
-        lo = mid + 1;
-    }
-    h  = lo;
-    lo = 0;
-    hi = npv - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (dot3(x, y, z, bv + (mid + 1) * 3) >= 0.f)
-        hi = mid;
-      else
-        lo = mid + 1;
-    }
-    v = lo;
-  }
-  if (h < 0 || v < 0) return -1;  // "should not happen" in the reference (:1449,1471)
-  return h * npv + v;
-}
-// getParticleVoxelsIndex (:1152-1166)
-__device__ inline int voxel_index(const DspDev &d, float px, float py, float pz) {
-  if (px >= d.hx || px <= -d.hx || py >= d.hy || py <= -d.hy || pz >= d.hz || pz <= -d.hz) return -1;
-  int x = (int)((px + d.hx) / d.res);
-  int y = (int)((py + d.hy) / d.res);
-  int z = (int)((pz + d.hz) / d.res);
-  int index = z * d.W * d.L + y * d.L + x;
-  if (index < 0 || index >= d.V) return -1;
-  return index;
-}
-// queryNormalPDF (:1380-1389)
-__device__ inline float query_pdf(const float *pdf, float x, float mu, float sigma) {
-  float c = (x - mu) / sigma;
-  if (c > 9.9f)
-    c = 9.9f;
-  else if (c < -9.9f)
-    c = -9.9f;
-  return pdf[(int)(c * 1000 + 10000)];
-}
 
 // ---- update: begin ------------------------------------------------------------------------------
 // DSPMap::update :176-229: odometry checks, deltas, boundary-plane rotation.
@@ -249,9 +81,9 @@ __global__ void k_dsp_begin(DspDev d, const float *__restrict__ pos, const float
   if (!s_ok) return;
   const float q[4] = {quat[a * 4], quat[a * 4 + 1], quat[a * 4 + 2], quat[a * 4 + 3]};
   for (int i = threadIdx.x; i < d.nph + 1; i += blockDim.x)
-    rotate_q(d.bp_ori_h + i * 3, q, d.bp_h + ((size_t)a * (d.nph + 1) + i) * 3);
+    rotate_q(d.bp_ori_h + i * 3, q, d.bp_h + (d.bph_base(a) + i) * 3);
   for (int i = threadIdx.x; i < d.npv + 1; i += blockDim.x)
-    rotate_q(d.bp_ori_v + i * 3, q, d.bp_v + ((size_t)a * (d.npv + 1) + i) * 3);
+    rotate_q(d.bp_ori_v + i * 3, q, d.bp_v + (d.bpv_base(a) + i) * 3);
 }
 
 // ---- update: observation binning (:231-297) -------------------------------------------------------
@@ -273,8 +105,8 @@ __global__ __launch_bounds__(256) void k_dsp_observe(DspDev d, const float *__re
     s_cnt[i] = 0;
     s_max[i] = -1;
   }
-  for (int i = threadIdx.x; i < (d.nph + 1) * 3; i += 256) s_bh[i] = d.bp_h[(size_t)a * (d.nph + 1) * 3 + i];
-  for (int i = threadIdx.x; i < (d.npv + 1) * 3; i += 256) s_bv[i] = d.bp_v[(size_t)a * (d.npv + 1) * 3 + i];
+  for (int i = threadIdx.x; i < (d.nph + 1) * 3; i += 256) s_bh[i] = d.bp_h[d.bph_base(a) * 3 + i];
+  for (int i = threadIdx.x; i < (d.npv + 1) * 3; i += 256) s_bv[i] = d.bp_v[d.bpv_base(a) * 3 + i];
   if (threadIdx.x == 0) {
     s_valid = 0;
     s_nobs  = 0;
@@ -288,8 +120,8 @@ __global__ __launch_bounds__(256) void k_dsp_observe(DspDev d, const float *__re
   }
   const float q[4] = {s.quat[0], s.quat[1], s.quat[2], s.quat[3]};
   const float c0 = s.cur[0], c1 = s.cur[1], c2 = s.cur[2];
-  float      *born = d.born + (size_t)a * d.max_pts * 7;
-  float      *pc   = d.pc + (size_t)a * d.NP * d.OM * 5;
+  float      *born = d.born + d.point_base(a) * 7;
+  float      *pc   = d.pc + d.obs_base(a) * 5;
   for (int base = 0; base < n; base += 256) {
     const int k  = base + threadIdx.x;
     int       pi = -1;
@@ -300,7 +132,7 @@ __global__ __launch_bounds__(256) void k_dsp_observe(DspDev d, const float *__re
       born[(size_t)k * 7 + 0] = r[0] + c0;
       born[(size_t)k * 7 + 1] = r[1] + c1;
       born[(size_t)k * 7 + 2] = r[2] + c2;
-      d.born_src[(size_t)a * d.max_pts + k] = k;  // (k_dsp_velocity rewrites it with the list)
+      d.born_src[d.point_base(a) + k] = k;  // (k_dsp_velocity rewrites it with the list)
       for (int j = 0; j < 4; ++j)  // labels == NULL: k_dsp_velocity fills (and reorders) the list afterwards
         born[(size_t)k * 7 + 3 + j] = labels ? labels[(size_t)(begin + k) * 4 + j] : 0.f;
       pi = pyramid_of(s_bh, s_bv, d.nph, d.npv, r[0], r[1], r[2]);
@@ -319,7 +151,7 @@ __global__ __launch_bounds__(256) void k_dsp_observe(DspDev d, const float *__re
         o[2]     = r[2];
         o[3]     = 0.f;
         o[4]     = len;
-        d.obs_list[(size_t)a * d.max_pts + atomicAdd(&s_nobs, 1)] = pi * d.OM + seq;
+        d.obs_list[d.point_base(a) + atomicAdd(&s_nobs, 1)] = pi * d.OM + seq;
       }
       atomicMax(&s_max[pi], __float_as_int(len));
       atomicAdd(&s_valid, 1);
@@ -330,511 +162,14 @@ __global__ __launch_bounds__(256) void k_dsp_observe(DspDev d, const float *__re
   }
   for (int i = threadIdx.x; i < d.NP; i += 256) {
     const int c                  = s_cnt[i];
-    d.nobs[(size_t)a * d.NP + i]   = c >= d.OM ? d.OM - 1 : c;
-    d.maxlen[(size_t)a * d.NP + i] = s_max[i];
+    d.nobs[d.pyr_base(a) + i]   = c >= d.OM ? d.OM - 1 : c;
+    d.maxlen[d.pyr_base(a) + i] = s_max[i];
   }
   if (threadIdx.x == 0) {
     s.valid_points = s_valid;
     s.n_obs        = s_nobs;
     s.enb          = d.w_nb * (float)s_valid * (float)d.nb;  // :299-300
     if (n > 0) s.n_born = n;  // velocityEstimationThread returns early on an empty cloud (:1488)
-  }
-}
-
-
-// ---- velocityEstimationThread (:1487-1678) --------------------------------------------------------------
-// One workgroup per agent (see oracle/dsp_oracle.cpp::velocityEstimation for the restated third-party pieces):
-//   ground split -> Euclidean clustering of the non-ground points (connected components under "squared distance
-//   < tolerance^2": neighbour lists by brute force over the LDS-resident cloud, min-label propagation with pointer
-//   jumping; a component's label = its smallest index = PCL's seed) -> clusters ordered like
-//   std::sort(rbegin, rend, size <) (libstdc++'s introsort restated, ties included) -> centres summed in ascending
-//   index order -> gated association with the previous frame's clusters (optimal assignment, same scan order as
-//   the oracle) -> input_cloud_with_velocity rewritten in the reference's order:
-//   [possibly-dynamic clusters][ground points][static clusters].  Points of rejected (small) clusters vanish.
-namespace vel {
-struct Item {
-  int size, id;
-};
-__device__ inline bool less_(const Item &a, const Item &b) { return a.size < b.size; }
-__device__ inline void swap_(Item &a, Item &b) {
-  const Item t = a;
-  a            = b;
-  b            = t;
-}
-// libstdc++ <bits/stl_heap.h> __adjust_heap / __push_heap with comp = less_
-__device__ inline void adjust_heap(Item *f, int hole, int len, Item value) {
-  const int top = hole;
-  int       child = hole;
-  while (child < (len - 1) / 2) {
-    child = 2 * (child + 1);
-    if (less_(f[child], f[child - 1])) child--;
-    f[hole] = f[child];
-    hole    = child;
-  }
-  if ((len & 1) == 0 && child == (len - 2) / 2) {
-    child   = 2 * (child + 1);
-    f[hole] = f[child - 1];
-    hole    = child - 1;
-  }
-  int parent = (hole - 1) / 2;
-  while (hole > top && less_(f[parent], value)) {
-    f[hole] = f[parent];
-    hole    = parent;
-    parent  = (hole - 1) / 2;
-  }
-  f[hole] = value;
-}
-__device__ inline void heap_sort(Item *f, int n) {  // __partial_sort(first, last, last): make_heap + sort_heap
-  if (n >= 2)
-    for (int parent = (n - 2) / 2;; --parent) {
-      adjust_heap(f, parent, n, f[parent]);
-      if (parent == 0) break;
-    }
-  for (int last = n; last > 1; --last) {
-    const Item v = f[last - 1];
-    f[last - 1]  = f[0];
-    adjust_heap(f, 0, last - 1, v);
-  }
-}
-__device__ inline void unguarded_linear_insert(Item *f, int last) {
-  const Item val = f[last];
-  int        next = last - 1;
-  while (less_(val, f[next])) {
-    f[last] = f[next];
-    last    = next;
-    --next;
-  }
-  f[last] = val;
-}
-__device__ inline void insertion_sort(Item *f, int first, int last) {
-  if (first == last) return;
-  for (int i = first + 1; i != last; ++i) {
-    if (less_(f[i], f[first])) {
-      const Item val = f[i];
-      for (int k = i; k > first; --k) f[k] = f[k - 1];
-      f[first] = val;
-    } else {
-      unguarded_linear_insert(f, i);
-    }
-  }
-}
-// std::sort(first, last, less_) of libstdc++ (<bits/stl_algo.h>: __introsort_loop + __final_insertion_sort)
-__device__ inline void std_sort(Item *f, int n) {
-  if (n <= 0) return;
-  int depth = 0;
-  for (int t = n; t > 1; t >>= 1) ++depth;  // __lg(n)
-  depth *= 2;
-  // explicit stack for the recursion on the right part
-  int st_first[40], st_last[40], st_depth[40], sp = 0;
-  int first = 0, last = n, dl = depth;
-  for (;;) {
-    while (last - first > 16) {
-      if (dl == 0) {
-        heap_sort(f + first, last - first);
-        break;
-      }
-      --dl;
-      // __unguarded_partition_pivot
-      const int mid = first + (last - first) / 2;
-      {  // __move_median_to_first(first, first + 1, mid, last - 1)
-        const int a = first + 1, b = mid, c = last - 1;
-        if (less_(f[a], f[b])) {
-          if (less_(f[b], f[c])) swap_(f[first], f[b]);
-          else if (less_(f[a], f[c])) swap_(f[first], f[c]);
-          else swap_(f[first], f[a]);
-        } else if (less_(f[a], f[c])) swap_(f[first], f[a]);
-        else if (less_(f[b], f[c])) swap_(f[first], f[c]);
-        else swap_(f[first], f[b]);
-      }
-      int lo = first + 1, hi = last;
-      for (;;) {  // __unguarded_partition(first + 1, last, first)
-        while (less_(f[lo], f[first])) ++lo;
-        --hi;
-        while (less_(f[first], f[hi])) --hi;
-        if (!(lo < hi)) break;
-        swap_(f[lo], f[hi]);
-        ++lo;
-      }
-      // recurse on [lo, last), continue with [first, lo)
-      st_first[sp] = lo;
-      st_last[sp]  = last;
-      st_depth[sp] = dl;
-      ++sp;
-      last = lo;
-    }
-    if (sp == 0) break;
-    --sp;
-    first = st_first[sp];
-    last  = st_last[sp];
-    dl    = st_depth[sp];
-  }
-  if (n > 16) {  // __final_insertion_sort
-    insertion_sort(f, 0, 16);
-    for (int i = 16; i < n; ++i) unguarded_linear_insert(f, i);
-  } else {
-    insertion_sort(f, 0, n);
-  }
-}
-}  // namespace vel
-
-__global__ __launch_bounds__(1024) void k_dsp_velocity(DspDev d, const int32_t *__restrict__ range, float vres) {
-  extern __shared__ __attribute__((aligned(16))) float s_vel[];
-  const int a   = blockIdx.x;
-  DspAgent &s   = d.ag[a];
-  const int tid = threadIdx.x;
-  if (!s.ok) return;
-  int n = range[a * 2 + 1] - range[a * 2];
-  if (n > d.max_pts) n = d.max_pts;
-  if (n <= 0) return;  // :1488 — input_cloud_with_velocity and the previous clusters stay as they are
-  const int MP = d.max_pts;
-  float *sx = s_vel, *sy = sx + MP, *sz = sy + MP;  // non-ground points, compacted in input order
-  int   *lab = (int *)(sz + MP);                    // component label (-> cluster slot later)
-  int   *aux = lab + MP;                            // sizes per root, then rank of a point inside its cluster
-  __shared__ int           s_scan[1024], s_base_ng, s_base_g, s_changed, s_nc, s_err;
-  __shared__ vel::Item     s_item[VEL_MAX_CLUSTERS];
-  __shared__ int           s_root[VEL_MAX_CLUSTERS], s_size[VEL_MAX_CLUSTERS], s_off[VEL_MAX_CLUSTERS],
-      s_dynseq[VEL_MAX_CLUSTERS];
-  __shared__ float         s_cx[VEL_MAX_CLUSTERS], s_cy[VEL_MAX_CLUSTERS], s_cz[VEL_MAX_CLUSTERS];
-  __shared__ float         s_v[VEL_MAX_DYN][4];  // vx vy vz intensity of the possibly-dynamic clusters
-  __shared__ int           s_total_dyn, s_n_static;
-  float *born = d.born + (size_t)a * MP * 7;
-  if (tid == 0) {
-    s_base_ng = 0;
-    s_base_g  = 0;
-    s_err     = 0;
-  }
-  __syncthreads();
-  // ---- ground split (:1497-1507), order-preserving compaction of both lists; a thread keeps its points' data
-  float px[8][3];
-  int   cidx[8];  // >= 0: index in the non-ground list; < 0: -(ground rank) - 1
-  const int trips = (n + 1023) / 1024;
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    if (t >= trips) break;
-    const int k = t * 1024 + tid;
-    float x = 0.f, y = 0.f, z = 0.f;
-    bool  in = k < n, ng = false;
-    if (in) {
-      x  = born[(size_t)k * 7];
-      y  = born[(size_t)k * 7 + 1];
-      z  = born[(size_t)k * 7 + 2];
-      ng = z > vres;
-    }
-    // two exclusive scans over the workgroup (non-ground and ground flags)
-    const unsigned long long bn = __ballot(in && ng), bg = __ballot(in && !ng);
-    const int lane = tid & 63, wave = tid >> 6;
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-    if (lane == 0) {
-      s_scan[wave]      = __popcll(bn);
-      s_scan[16 + wave] = __popcll(bg);
-    }
-    __syncthreads();
-    int on = 0, og = 0, tn = 0, tg = 0;
-    for (int w = 0; w < 16; ++w) {
-      on += w < wave ? s_scan[w] : 0;
-      og += w < wave ? s_scan[16 + w] : 0;
-      tn += s_scan[w];
-      tg += s_scan[16 + w];
-    }
-    const int rn = s_base_ng + on + __popcll(bn & lt), rg = s_base_g + og + __popcll(bg & lt);
-    px[t][0] = x;
-    px[t][1] = y;
-    px[t][2] = z;
-    cidx[t]  = !in ? 0x7fffffff : (ng ? rn : -rg - 1);
-    if (in && ng) {
-      sx[rn] = x;
-      sy[rn] = y;
-      sz[rn] = z;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      s_base_ng += tn;
-      s_base_g += tg;
-    }
-    __syncthreads();
-  }
-  // (max_points <= 8192 is checked by sogm_dsp_create: the register staging above holds 8 points per thread)
-  const int m = s_base_ng, n_ground = s_base_g;
-  // ---- neighbour lists: FLANN L2_Simple squared distance, strictly below (float)(tolerance^2)
-  const double tol = (double)(2 * vres);
-  const float  r2  = (float)(tol * tol);
-  unsigned short *adj = d.vel_adj + (size_t)a * MP * VEL_ADJ_CAP;
-  int            *deg = d.vel_deg + (size_t)a * MP;
-  for (int i = tid; i < m; i += 1024) {
-    const float ax = sx[i], ay = sy[i], az = sz[i];
-    int         c  = 0;
-    for (int j = 0; j < m; ++j) {
-      float df = ax - sx[j], d2 = 0.f;
-      d2 += df * df;
-      df = ay - sy[j];
-      d2 += df * df;
-      df = az - sz[j];
-      d2 += df * df;
-      if (d2 < r2 && j != i) {
-        if (c < VEL_ADJ_CAP) adj[(size_t)i * VEL_ADJ_CAP + c] = (unsigned short)j;
-        ++c;
-      }
-    }
-    if (c > VEL_ADJ_CAP) {
-      s_err = 2;  // denser than a voxel-filtered cloud: neighbours were dropped
-      c     = VEL_ADJ_CAP;
-    }
-    deg[i] = c;
-    lab[i] = i;
-  }
-  __syncthreads();
-  // ---- connected components: min-label propagation + pointer jumping to the fixed point
-  for (int round = 0; round < 4096; ++round) {
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
-    for (int i = tid; i < m; i += 1024) {
-      int mn = lab[i];
-      const int dg = deg[i];
-      for (int q = 0; q < dg; ++q) {
-        const int l = lab[adj[(size_t)i * VEL_ADJ_CAP + q]];
-        mn          = l < mn ? l : mn;
-      }
-      if (mn < lab[i]) {
-        atomicMin(&lab[lab[i]], mn);  // hook the old root as well
-        atomicMin(&lab[i], mn);
-        s_changed = 1;
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < m; i += 1024) {
-      int l = lab[i];
-      while (lab[l] < l) l = lab[l];
-      lab[i] = l;
-    }
-    __syncthreads();
-    if (!s_changed) break;
-    __syncthreads();
-  }
-  // ---- sizes, accepted clusters (5 <= size <= 10000) in seed (= root index) order
-  for (int i = tid; i < m; i += 1024) aux[i] = 0;
-  __syncthreads();
-  for (int i = tid; i < m; i += 1024) atomicAdd(&aux[lab[i]], 1);
-  __syncthreads();
-  if (tid == 0) {
-    int nc = 0;
-    for (int i = 0; i < m; ++i)
-      if (lab[i] == i && aux[i] >= 5 && aux[i] <= 10000) {
-        if (nc < VEL_MAX_CLUSTERS) {
-          s_root[nc] = i;
-          s_size[nc] = aux[i];
-        }
-        ++nc;
-      }
-    if (nc > VEL_MAX_CLUSTERS) {
-      s_err = 3;
-      nc    = VEL_MAX_CLUSTERS;
-    }
-    // EuclideanClusterExtraction::extract: std::sort(clusters.rbegin(), clusters.rend(), size <)
-    for (int k = 0; k < nc; ++k) {  // the reversed sequence
-      s_item[k].size = s_size[nc - 1 - k];
-      s_item[k].id   = nc - 1 - k;
-    }
-    vel::std_sort(s_item, nc);
-    s_nc = nc;
-  }
-  __syncthreads();
-  const int nc = s_nc;
-  // cluster slot c (extraction order) = s_item[nc - 1 - c]; point -> slot through its root
-  for (int i = tid; i < m; i += 1024) aux[i] = -1;
-  __syncthreads();
-  for (int c = tid; c < nc; c += 1024) aux[s_root[s_item[nc - 1 - c].id]] = c;  // slot of a root
-  __syncthreads();
-  for (int i = tid; i < m; i += 1024) {
-    const int sl = aux[lab[i]];     // lab[i] is the point's root; aux[root] the cluster's slot (or -1)
-    lab[i]       = sl >= 0 ? sl : 0xFFFF;  // 0xFFFF = in no accepted cluster
-  }
-  __syncthreads();
-  // ---- centres (sums in ascending index order, :1533-1542) and rank of every point inside its cluster
-  for (int c = tid; c < nc; c += 1024) {
-    float cx = 0.f, cy = 0.f, cz = 0.f;
-    int   cnt = 0;
-    for (int i = 0; i < m; ++i)
-      if (lab[i] == c) {
-        cx += sx[i];
-        cy += sy[i];
-        cz += sz[i];
-        aux[i] = cnt;
-        ++cnt;
-      }
-    s_cx[c]   = cx / (float)cnt;
-    s_cy[c]   = cy / (float)cnt;
-    s_cz[c]   = cz / (float)cnt;
-    s_size[c] = cnt;  // now in extraction order
-  }
-  __syncthreads();
-  // ---- possibly-dynamic split, association with the previous frame, output offsets (one lane)
-  if (tid == 0) {
-    int nd = 0, off = 0;
-    for (int c = 0; c < nc; ++c) {
-      const bool stat = s_size[c] > 200 || s_cz[c] > 1.5;  // DYNAMIC_CLUSTER_MAX_POINT_NUM / _MAX_CENTER_HEIGHT
-      if (!stat && nd >= VEL_MAX_DYN) s_err = 4;
-      s_dynseq[c] = (!stat && nd < VEL_MAX_DYN) ? nd : -1;
-      if (s_dynseq[c] >= 0) {
-        s_off[c] = off;
-        off += s_size[c];
-        s_v[nd][0] = -10000.f;
-        s_v[nd][1] = -10000.f;
-        s_v[nd][2] = -10000.f;
-        s_v[nd][3] = 0.55f;
-        ++nd;
-      }
-    }
-    s_total_dyn = off;
-    off += n_ground;
-    for (int c = 0; c < nc; ++c)
-      if (s_dynseq[c] < 0) {
-        s_off[c] = off;
-        off += s_size[c];
-      }
-    s_n_static = off - s_total_dyn - n_ground;
-    // association (:1562-1622)
-    const int   R = nd, C = s.vel_n_last;
-    const float dt = s.odom[3];  // delt_t_from_last_observation (:213)
-    int         matched = 0;
-    if (R * C > MP) s_err = 5;
-    if (R > 0 && C > 0 && R * C <= MP && dt > 0.00001 && dt < 10.0) {
-      // cost / gate matrices live in the (now free) coordinate arrays of the dynamic LDS
-      float *cost = sx, *gate = sy;  // R * C <= max_pts floats each: guarded just above (error 5 otherwise)
-      int    rows[VEL_MAX_DYN];
-      {
-        int k = 0;
-        for (int c = 0; c < nc; ++c)
-          if (s_dynseq[c] >= 0) rows[k++] = c;
-      }
-      const float distance_gate = 1.5f, maximum_velocity = 5.f;
-      const int   point_num_gate = 100;
-      for (int r = 0; r < R; ++r)
-        for (int c = 0; c < C; ++c) {
-          const int   k  = rows[r];
-          const float ex = s_cx[k] - s.vel_last[c][0], ey = s_cy[k] - s.vel_last[c][1], ez = s_cz[k] - s.vel_last[c][2];
-          const float dist = sqrtf(ex * ex + ey * ey + ez * ez);
-          const int   dn   = s_size[k] - (int)s.vel_last[c][4];
-          if ((dn < 0 ? -dn : dn) > point_num_gate || dist >= distance_gate) {
-            gate[r * C + c] = 0.f;
-            cost[r * C + c] = distance_gate * 5000.f;
-          } else {
-            gate[r * C + c] = 1.f;
-            cost[r * C + c] = dist / distance_gate * 1000.f;
-          }
-        }
-      // minimum-cost assignment, potentials form, rows <= cols (transposed view otherwise): oracle's scan order
-      const bool  tr = R > C;
-      const int   NR = tr ? C : R, NCc = tr ? R : C;
-      const float INF = 3.0e38f;
-      float u[VEL_MAX_DYN + 1], v[VEL_MAX_DYN + 1], minv[VEL_MAX_DYN + 1];
-      int   pj[VEL_MAX_DYN + 1], way[VEL_MAX_DYN + 1];
-      bool  used[VEL_MAX_DYN + 1];
-      for (int j = 0; j <= NCc; ++j) {
-        v[j]  = 0.f;
-        pj[j] = 0;
-        way[j] = 0;
-      }
-      for (int i = 0; i <= NR; ++i) u[i] = 0.f;
-      auto at = [&](int i, int j) { return tr ? cost[j * C + i] : cost[i * C + j]; };  // (row i, col j) of the NR x NCc view
-      for (int i = 1; i <= NR; ++i) {
-        pj[0]  = i;
-        int j0 = 0;
-        for (int j = 0; j <= NCc; ++j) {
-          minv[j] = INF;
-          used[j] = false;
-        }
-        do {
-          used[j0]     = true;
-          const int i0 = pj[j0];
-          float     delta = INF;
-          int       j1 = 0;
-          for (int j = 1; j <= NCc; ++j)
-            if (!used[j]) {
-              const float cur = at(i0 - 1, j - 1) - u[i0] - v[j];
-              if (cur < minv[j]) {
-                minv[j] = cur;
-                way[j]  = j0;
-              }
-              if (minv[j] < delta) {
-                delta = minv[j];
-                j1    = j;
-              }
-            }
-          for (int j = 0; j <= NCc; ++j)
-            if (used[j]) {
-              u[pj[j]] += delta;
-              v[j] -= delta;
-            } else {
-              minv[j] -= delta;
-            }
-          j0 = j1;
-        } while (pj[j0] != 0);
-        do {
-          const int j1 = way[j0];
-          pj[j0]       = pj[j1];
-          j0           = j1;
-        } while (j0);
-      }
-      for (int j = 1; j <= NCc; ++j) {
-        if (pj[j] <= 0) continue;
-        const int r = tr ? j - 1 : pj[j] - 1, c = tr ? pj[j] - 1 : j - 1;  // new cluster r <-> old cluster c
-        if (!(gate[r * C + c] > 0.01f)) continue;
-        const int k = rows[r];
-        float vx = (s_cx[k] - s.vel_last[c][0]) / dt, vy = (s_cy[k] - s.vel_last[c][1]) / dt,
-              vz = (s_cz[k] - s.vel_last[c][2]) / dt;
-        const float vv = sqrtf(vx * vx + vy * vy + vz * vz);
-        if (vv > maximum_velocity) vx = vy = vz = 0.f;
-        s_v[r][0] = vx;
-        s_v[r][1] = vy;
-        s_v[r][2] = vz;
-        s_v[r][3] = s.vel_last[c][3];
-        ++matched;
-      }
-    }
-    // clusters_feature_vector_dynamic_last = clusters_feature_vector_dynamic (:1665)
-    {
-      int k = 0;
-      for (int c = 0; c < nc; ++c)
-        if (s_dynseq[c] >= 0) {
-          s.vel_last[k][0] = s_cx[c];
-          s.vel_last[k][1] = s_cy[c];
-          s.vel_last[k][2] = s_cz[c];
-          s.vel_last[k][3] = s_v[k][3];
-          s.vel_last[k][4] = (float)s_size[c];
-          ++k;
-        }
-      s.vel_n_last = k;
-    }
-    s.vel_clusters = nc;
-    s.vel_dynamic  = nd;
-    s.vel_matched  = matched;
-    if (s_err) s.vel_err = s_err;
-    s.n_born = s_total_dyn + n_ground + s_n_static;
-  }
-  __syncthreads();
-  // ---- input_cloud_with_velocity in the reference's order (every thread writes the points it read)
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    if (t >= trips) break;
-    const int ci = cidx[t];
-    if (ci == 0x7fffffff) continue;
-    int   pos;
-    float lv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ci < 0) {
-      pos = s_total_dyn + (-ci - 1);
-    } else {
-      const int c = lab[ci];
-      if (c == 0xFFFF) continue;  // no accepted cluster: the point is dropped
-      pos = s_off[c] + aux[ci];
-      if (s_dynseq[c] >= 0)
-        for (int j = 0; j < 4; ++j) lv[j] = s_v[s_dynseq[c]][j];
-    }
-    float *o = born + (size_t)pos * 7;
-    o[0]     = px[t][0];
-    o[1]     = px[t][1];
-    o[2]     = px[t][2];
-    for (int j = 0; j < 4; ++j) o[3 + j] = lv[j];
-    d.born_src[(size_t)a * MP + pos] = t * 1024 + tid;  // the input index of px[t]
   }
 }
 
@@ -846,11 +181,11 @@ __global__ __launch_bounds__(256) void k_dsp_predict(DspDev d) {
   DspAgent &s = d.ag[a];
   if (!s.ok) return;
   __shared__ float s_bh[181 * 3], s_bv[181 * 3];
-  for (int i = threadIdx.x; i < (d.nph + 1) * 3; i += 256) s_bh[i] = d.bp_h[(size_t)a * (d.nph + 1) * 3 + i];
-  for (int i = threadIdx.x; i < (d.npv + 1) * 3; i += 256) s_bv[i] = d.bp_v[(size_t)a * (d.npv + 1) * 3 + i];
+  for (int i = threadIdx.x; i < (d.nph + 1) * 3; i += 256) s_bh[i] = d.bp_h[d.bph_base(a) * 3 + i];
+  for (int i = threadIdx.x; i < (d.npv + 1) * 3; i += 256) s_bv[i] = d.bp_v[d.bpv_base(a) * 3 + i];
   __syncthreads();
   const int    v   = blockIdx.x * 256 + threadIdx.x;
-  const size_t at0 = ((size_t)a * d.V + (v < d.V ? v : 0)) * DSP_SLOTS;
+  const size_t at0 = d.slot_base(a, v < d.V ? v : 0);
   uint4        f4  = {0u, 0u, 0u, 0u};
   if (v < d.V) f4 = *reinterpret_cast<const uint4 *>(d.flag + at0);
   if (!__any((f4.x | f4.y | f4.z | f4.w) != 0u)) return;  // wave-uniform: whole wave of empty voxels
@@ -875,7 +210,7 @@ __global__ __launch_bounds__(256) void k_dsp_predict(DspDev d) {
     const bool act = base + lane < n_act;
     const int  e   = act ? s_list[wave][base + lane] : 0;
     const int  vv = v0 + (e >> 4), p = e & (DSP_SLOTS - 1);
-    const size_t at  = ((size_t)a * d.V + (act ? vv : 0)) * DSP_SLOTS + p;
+    const size_t at  = d.slot_base(a, act ? vv : 0) + p;
     const int    gid = vv * DSP_SLOTS + p;
     float        vx = 0.f, vy = 0.f, px = 0.f, py = 0.f, pz = 0.f;
     int          nv = -1, pyr = -1;
@@ -920,7 +255,7 @@ __global__ __launch_bounds__(256) void k_dsp_predict(DspDev d) {
       if (nv != vv) d.flag[at] = F_EMPTY;
       continue;
     }
-    const size_t ci = (size_t)a * d.cand_cap + c_i;
+    const size_t ci = d.cand_base(a) + c_i;
     d.c_key[ci]    = gid;
     d.c_dest[ci]   = nv;
     d.c_pyr[ci]    = pyr;
@@ -937,9 +272,9 @@ __global__ __launch_bounds__(256) void k_dsp_predict(DspDev d) {
       pay[3]         = py;
       pay[4]         = pz;
       pay[5]         = d.f[5][at];
-      d.c_vnext[ci]  = atomicExch(&d.vhead[(size_t)a * d.V + nv], c_i);
+      d.c_vnext[ci]  = atomicExch(&d.vhead[d.voxel_base(a) + nv], c_i);
     }
-    if (pyr >= 0) d.c_pnext[ci] = atomicExch(&d.phead[(size_t)a * d.NP + pyr], c_i);
+    if (pyr >= 0) d.c_pnext[ci] = atomicExch(&d.phead[d.pyr_base(a) + pyr], c_i);
   }
 }
 
@@ -951,13 +286,13 @@ __global__ __launch_bounds__(64) void k_dsp_place(DspDev d, int round) {
   if (round > 0 && s.changed[round - 1] == 0) return;
   const int B = blockIdx.x * 64 + threadIdx.x;
   if (B >= d.V) return;
-  int head = d.vhead[(size_t)a * d.V + B];
+  int head = d.vhead[d.voxel_base(a) + B];
   if (head < 0) return;
   __shared__ int s_key[64][2 * DSP_SLOTS], s_id[64][2 * DSP_SLOTS];
   int *kb = s_key[threadIdx.x], *ib = s_id[threadIdx.x];  // [0,S): before, [16,16+S): after
   int  nb_ = 0, na_ = 0;
   const int    S = d.S, lo = B * DSP_SLOTS;
-  const size_t cb = (size_t)a * d.cand_cap;
+  const size_t cb = d.cand_base(a);
   for (int m = head; m >= 0; m = d.c_vnext[cb + m]) {
     d.c_assign[cb + m] = -1;
     if (d.c_kill[cb + m]) continue;
@@ -972,21 +307,10 @@ __global__ __launch_bounds__(64) void k_dsp_place(DspDev d, int round) {
       I = ib + DSP_SLOTS;
       N = &na_;
     }
-    // keep the S smallest keys, sorted ascending
-    int n = *N;
-    if (n == S && key > K[S - 1]) continue;
-    int j = n < S ? n : S - 1;
-    while (j > 0 && K[j - 1] > key) {
-      K[j] = K[j - 1];
-      I[j] = I[j - 1];
-      --j;
-    }
-    K[j] = key;
-    I[j] = m;
-    if (n < S) *N = n + 1;
+    keep_smallest(K, I, *N, S, key, m);
   }
   // occupancy of B before its own turn: everything non-empty (incl. departing / vanishing stays)
-  const uint8_t *fl = d.flag + ((size_t)a * d.V + B) * DSP_SLOTS;
+  const uint8_t *fl = d.flag + d.slot_base(a, B);
   unsigned occ = 0, leaving = 0;
   for (int p = 0; p < S; ++p) {
     const uint8_t c = fl[p];
@@ -994,18 +318,16 @@ __global__ __launch_bounds__(64) void k_dsp_place(DspDev d, int round) {
     if (c == F_DEPART || c == F_KILLED) leaving |= 1u << p;
   }
   const unsigned all = (1u << S) - 1u;
-  for (int i = 0; i < nb_; ++i) {
-    const unsigned fr = ~occ & all;
-    if (!fr) break;
-    const int sl = __ffs(fr) - 1;
+  for (int i = 0; i < nb_; ++i) {  // arrivals before B's own turn
+    const int sl = lowest_free(occ, all);
+    if (sl < 0) break;
     occ |= 1u << sl;
     d.c_assign[cb + ib[i]] = sl;
   }
-  occ &= ~leaving;
-  for (int i = 0; i < na_; ++i) {
-    const unsigned fr = ~occ & all;
-    if (!fr) break;
-    const int sl = __ffs(fr) - 1;
+  occ &= ~leaving;  // B's own turn
+  for (int i = 0; i < na_; ++i) {  // arrivals after it
+    const int sl = lowest_free(occ, all);
+    if (sl < 0) break;
     occ |= 1u << sl;
     d.c_assign[cb + ib[DSP_SLOTS + i]] = sl;
   }
@@ -1019,35 +341,25 @@ __global__ __launch_bounds__(64) void k_dsp_pyramids(DspDev d, int round) {
   if (round > 0 && s.changed[round - 1] == 0) return;
   const int q = blockIdx.x * 64 + threadIdx.x;
   if (q >= d.NP) return;
-  const int head = d.phead[(size_t)a * d.NP + q];
-  int      *out  = d.pyr_list + ((size_t)a * d.NP + q) * d.SP;
+  const int head = d.phead[d.pyr_base(a) + q];
+  int      *out  = d.pyr_list + (d.pyr_base(a) + q) * d.SP;
   if (head < 0) {
-    d.pyr_n[(size_t)a * d.NP + q] = 0;
+    d.pyr_n[d.pyr_base(a) + q] = 0;
     return;
   }
   // selection scratch in HBM/L2: SAFE_PARTICLE_NUM_PYRAMID grows with the grid (20 at 66x66x20, 218 at
   // 100^3) while a pyramid rarely holds more than a handful of particles
-  int *K = d.pyr_key + ((size_t)a * d.NP + q) * d.SP, *I = d.pyr_id + ((size_t)a * d.NP + q) * d.SP;
+  int *K = d.pyr_key + (d.pyr_base(a) + q) * d.SP, *I = d.pyr_id + (d.pyr_base(a) + q) * d.SP;
   int  n = 0, placed = 0;
   const int    SP = d.SP;
-  const size_t cb = (size_t)a * d.cand_cap;
+  const size_t cb = d.cand_base(a);
   for (int m = head; m >= 0; m = d.c_pnext[cb + m]) {
     if (d.c_kill[cb + m] || d.c_assign[cb + m] < 0) continue;
     ++placed;
-    const int key = d.c_key[cb + m];
-    if (n == SP && key > K[SP - 1]) continue;
-    int j = n < SP ? n : SP - 1;
-    while (j > 0 && K[j - 1] > key) {
-      K[j] = K[j - 1];
-      I[j] = I[j - 1];
-      --j;
-    }
-    K[j] = key;
-    I[j] = m;
-    if (n < SP) n = n + 1;
+    keep_smallest(K, I, n, SP, d.c_key[cb + m], m);
   }
   for (int i = 0; i < n; ++i) out[i] = d.c_dest[cb + I[i]] * DSP_SLOTS + d.c_assign[cb + I[i]];
-  d.pyr_n[(size_t)a * d.NP + q] = n;
+  d.pyr_n[d.pyr_base(a) + q] = n;
   if (placed > SP) {  // the rest found the list full: they vanish (moveParticle -> -2)
     const int last = K[SP - 1];
     int       newly = 0;
@@ -1056,7 +368,7 @@ __global__ __launch_bounds__(64) void k_dsp_pyramids(DspDev d, int round) {
       if (d.c_key[cb + m] > last) {
         d.c_kill[cb + m] = 1;
         if (d.c_vnext[cb + m] == -2)  // a stay: its slot frees up at its own turn
-          d.flag[(size_t)a * d.V * DSP_SLOTS + d.c_key[cb + m]] = F_KILLED;
+          d.flag[d.slot_base(a) + d.c_key[cb + m]] = F_KILLED;
         ++newly;
       }
     }
@@ -1072,7 +384,7 @@ __global__ __launch_bounds__(256) void k_dsp_commit_slots(DspDev d) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v == 0 && s.changed[DSP_ROUNDS - 1] != 0) s.err_unconverged += 1;
   if (v >= d.V) return;
-  const size_t at0 = ((size_t)a * d.V + v) * DSP_SLOTS;
+  const size_t at0 = d.slot_base(a, v);
   const uint4  f4  = *reinterpret_cast<const uint4 *>(d.flag + at0);
   // bytes >= 5 are the transient codes F_DEPART / F_KILLED: (b + 3) & 8 is set exactly for 5, 6 (codes <= 6)
   const unsigned w4[4] = {f4.x, f4.y, f4.z, f4.w};
@@ -1097,7 +409,7 @@ __global__ __launch_bounds__(256) void k_dsp_commit_movers(DspDev d) {
   const int m = blockIdx.x * 256 + threadIdx.x;
   const int n = s.cand_cnt < d.cand_cap ? s.cand_cnt : d.cand_cap;
   if (m >= n) return;
-  const size_t ci = (size_t)a * d.cand_cap + m;
+  const size_t ci = d.cand_base(a) + m;
   if (d.c_vnext[ci] == -2) return;  // stays live in place
   if (d.c_kill[ci]) {
     atomicAdd(&s.dbg_pyr_full, 1);
@@ -1108,7 +420,7 @@ __global__ __launch_bounds__(256) void k_dsp_commit_movers(DspDev d) {
     atomicAdd(&s.dbg_voxel_full, 1);
     return;
   }
-  const size_t at  = ((size_t)a * d.V + d.c_dest[ci]) * DSP_SLOTS + sl;
+  const size_t at  = d.slot_base(a, d.c_dest[ci]) + sl;
   const float *pay = d.c_pay + ci * 6;
   d.flag[at]       = F_MOVED;
   for (int k = 0; k < 6; ++k) d.f[k][at] = pay[k];
@@ -1122,18 +434,18 @@ __global__ __launch_bounds__(256) void k_dsp_ck(DspDev d) {
   if (!s.ok) return;
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= s.n_obs) return;
-  const int    e  = d.obs_list[(size_t)a * d.max_pts + k];
+  const int    e  = d.obs_list[d.point_base(a) + k];
   const int    pi = e / d.OM;
-  float       *o  = d.pc + ((size_t)a * d.NP * d.OM + e) * 5;
+  float       *o  = d.pc + (d.obs_base(a) + e) * 5;
   const float  ox = o[0], oy = o[1], oz = o[2];
   float        ck = 0.f;
   const int   *nb = d.nbr + pi * 10;
-  const size_t sb = (size_t)a * d.V * DSP_SLOTS;
+  const size_t sb = d.slot_base(a);
   float        sig = d.sigma;
   for (int n = 0; n < nb[0]; ++n) {
     const int  q  = nb[n + 1];
-    const int  cn = d.pyr_n[(size_t)a * d.NP + q];
-    const int *li = d.pyr_list + ((size_t)a * d.NP + q) * d.SP;
+    const int  cn = d.pyr_n[d.pyr_base(a) + q];
+    const int *li = d.pyr_list + (d.pyr_base(a) + q) * d.SP;
     for (int i = 0; i < cn; ++i) {
       const size_t at = sb + li[i];
       const float  gk = query_pdf(d.pdf, d.f[2][at], ox, sig) * query_pdf(d.pdf, d.f[3][at], oy, sig) *
@@ -1152,19 +464,19 @@ __global__ __launch_bounds__(256) void k_dsp_weight(DspDev d) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   if (gid >= d.NP * d.SP) return;
   const int i = gid / d.SP, q = gid % d.SP;
-  if (q >= d.pyr_n[(size_t)a * d.NP + i]) return;
-  const size_t at = (size_t)a * d.V * DSP_SLOTS + d.pyr_list[((size_t)a * d.NP + i) * d.SP + q];
+  if (q >= d.pyr_n[d.pyr_base(a) + i]) return;
+  const size_t at = d.slot_base(a) + d.pyr_list[(d.pyr_base(a) + i) * d.SP + q];
   const float  px = d.f[2][at], py = d.f[3][at], pz = d.f[4][at];
   const float  len = sqrtf(px * px + py * py + pz * pz);
-  const int    mb  = d.maxlen[(size_t)a * d.NP + i];
+  const int    mb  = d.maxlen[d.pyr_base(a) + i];
   const float  ml  = mb < 0 ? -1.f : __int_as_float(mb);
   if (ml > 0.f && len > ml + d.thick) return;  // occluded
   const int   *nb = d.nbr + i * 10;
-  const float *pc = d.pc + (size_t)a * d.NP * d.OM * 5;
+  const float *pc = d.pc + d.obs_base(a) * 5;
   float        sum = 0.f, sig = d.sigma;
   for (int n = 0; n < nb[0]; ++n) {
     const int ni = nb[n + 1];
-    const int cn = d.nobs[(size_t)a * d.NP + ni];
+    const int cn = d.nobs[d.pyr_base(a) + ni];
     for (int z = 0; z < cn; ++z) {
       const float *o  = pc + ((size_t)ni * d.OM + z) * 5;
       const float  gk = query_pdf(d.pdf, px, o[0], sig) * query_pdf(d.pdf, py, o[1], sig) *
@@ -1212,12 +524,12 @@ __global__ __launch_bounds__(1024) void k_dsp_newborn(DspDev d) {
   {
     const int per = (d.NP + 1023) / 1024;
     int       cnt = 0;
-    for (int i = tid * per; i < (tid + 1) * per && i < d.NP; ++i) cnt += d.nobs[(size_t)a * d.NP + i];
+    for (int i = tid * per; i < (tid + 1) * per && i < d.NP; ++i) cnt += d.nobs[d.pyr_base(a) + i];
     int       tot;
     int       off = block_scan_excl(cnt, s_tmp, &tot);
-    const float *pc = d.pc + (size_t)a * d.NP * d.OM * 5;
+    const float *pc = d.pc + d.obs_base(a) * 5;
     for (int i = tid * per; i < (tid + 1) * per && i < d.NP; ++i) {
-      const int c = d.nobs[(size_t)a * d.NP + i];
+      const int c = d.nobs[d.pyr_base(a) + i];
       for (int j = 0; j < c; ++j) s_inv[off++] = 1.f / pc[((size_t)i * d.OM + j) * 5 + 3];
     }
     __syncthreads();
@@ -1231,10 +543,10 @@ __global__ __launch_bounds__(1024) void k_dsp_newborn(DspDev d) {
   }
   const int n = s.n_born, nb = d.nb;
   const int min_static = (int)((float)nb * 0.15f), model_gen = (int)((float)nb * 0.8f);
-  const float *born = d.born + (size_t)a * d.max_pts * 7;
-  int   *b_valid = d.b_valid + (size_t)a * d.max_pts, *b_nst = d.b_nstatic + (size_t)a * d.max_pts;
-  float *b_c = d.b_c + (size_t)a * d.max_pts * 3;
-  const size_t sb = (size_t)a * d.V * DSP_SLOTS;
+  const float *born = d.born + d.point_base(a) * 7;
+  int   *b_valid = d.b_valid + d.point_base(a), *b_nst = d.b_nstatic + d.point_base(a);
+  float *b_c = d.b_c + d.point_base(a) * 3;
+  const size_t sb = d.slot_base(a);
   // per point: voxel, Dempster-Shafer split (:880-925)
   for (int k = tid; k < n; k += 1024) {
     const float cx = born[k * 7] - s.cur[0], cy = born[k * 7 + 1] - s.cur[1], cz = born[k * 7 + 2] - s.cur[2];
@@ -1288,9 +600,9 @@ __global__ __launch_bounds__(1024) void k_dsp_newborn(DspDev d) {
   // per particle: position, class; counts of velocity / rand draws
   const int total = n * nb;
   const int per   = (total + 1023) / 1024;
-  int8_t   *b_cls = d.b_cls + (size_t)a * d.max_pts * nb;
-  int      *b_dest = d.b_dest + (size_t)a * d.max_pts * nb;
-  float    *b_pay  = d.b_pay + (size_t)a * d.max_pts * nb * 5;
+  int8_t   *b_cls = d.b_cls + d.newborn_base(a);
+  int      *b_dest = d.b_dest + d.newborn_base(a);
+  float    *b_pay  = d.b_pay + d.newborn_base(a) * 5;
   int       cv = 0, cr = 0;
   for (int j = tid * per; j < (tid + 1) * per && j < total; ++j) {
     const int k = j / nb, p = j % nb;
@@ -1342,7 +654,7 @@ __global__ __launch_bounds__(1024) void k_dsp_newborn(DspDev d) {
     }
     b_pay[j * 5 + 3] = vx;
     b_pay[j * 5 + 4] = vy;
-    d.b_vnext[(size_t)a * d.max_pts * nb + j] = atomicExch(&d.vhead[(size_t)a * d.V + b_dest[j]], j);
+    d.b_vnext[d.newborn_base(a) + j] = atomicExch(&d.vhead[d.voxel_base(a) + b_dest[j]], j);
   }
   __syncthreads();
   if (tid == 0) {
@@ -1360,35 +672,27 @@ __global__ __launch_bounds__(64) void k_dsp_place_born(DspDev d) {
   if (!s.ok) return;
   const int B = blockIdx.x * 64 + threadIdx.x;
   if (B >= d.V) return;
-  const int head = d.vhead[(size_t)a * d.V + B];
+  const int head = d.vhead[d.voxel_base(a) + B];
   if (head < 0) return;
   __shared__ int s_key[64][DSP_SLOTS];
   int *K = s_key[threadIdx.x];
   int  n = 0;
   const int    S = d.S;
-  const size_t bb = (size_t)a * d.max_pts * d.nb;
+  const size_t bb = d.newborn_base(a);
   for (int m = head; m >= 0; m = d.b_vnext[bb + m]) {
-    if (n == S && m > K[S - 1]) continue;
-    int j = n < S ? n : S - 1;
-    while (j > 0 && K[j - 1] > m) {
-      K[j] = K[j - 1];
-      --j;
-    }
-    K[j] = m;
-    if (n < S) ++n;
+    keep_smallest(K, nullptr, n, S, m, m);
   }
-  uint8_t *fl  = d.flag + ((size_t)a * d.V + B) * DSP_SLOTS;
+  uint8_t *fl  = d.flag + d.slot_base(a, B);
   unsigned occ = 0;
   for (int p = 0; p < S; ++p)
     if (fl[p] != F_EMPTY) occ |= 1u << p;
   const unsigned all = (1u << S) - 1u;
   const float    w   = s.w_new;
   for (int i = 0; i < n; ++i) {
-    const unsigned fr = ~occ & all;
-    if (!fr) break;
-    const int sl = __ffs(fr) - 1;
+    const int sl = lowest_free(occ, all);
+    if (sl < 0) break;
     occ |= 1u << sl;
-    const size_t at  = ((size_t)a * d.V + B) * DSP_SLOTS + sl;
+    const size_t at  = d.slot_base(a, B) + sl;
     const float *pay = d.b_pay + (bb + K[i]) * 5;
     d.flag[at]       = F_NEW;
     d.f[0][at]       = pay[3];
@@ -1407,8 +711,8 @@ __global__ __launch_bounds__(256) void k_dsp_occupancy(DspDev d) {
   if (!s.ok) return;
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= d.V) return;
-  const size_t at0 = ((size_t)a * d.V + v) * DSP_SLOTS;
-  float       *occ = d.occ + (size_t)a * 4 * d.V;
+  const size_t at0 = d.slot_base(a, v);
+  float       *occ = d.occ + d.occ_base(a);
   const uint4  f4  = *reinterpret_cast<const uint4 *>(d.flag + at0);
   if ((f4.x | f4.y | f4.z | f4.w) == 0u) {
     occ[v] = occ[d.V + v] = occ[2 * d.V + v] = occ[3 * d.V + v] = 0.f;
@@ -1418,7 +722,7 @@ __global__ __launch_bounds__(256) void k_dsp_occupancy(DspDev d) {
   float     wsum = 0.f, vxs = 0.f, vys = 0.f, vzs = 0.f;
   int       n = 0, n_old = 0;
   unsigned  valid = 0;
-  float    *fut = d.fut + (size_t)a * d.T * d.V;
+  float    *fut = d.fut + d.fut_base(a);
   for (int p = 0; p < S; ++p) {
     const uint8_t c = d.flag[at0 + p];
     if (c == F_EMPTY) continue;
@@ -1508,21 +812,21 @@ __global__ __launch_bounds__(256) void k_dsp_publish(DspDev d, void *__restrict_
     stamps[a]        = s.last_t;
   }
   if (v >= d.V) return;
-  float *fut = d.fut + (size_t)a * d.T * d.V;
-  char  *g   = reinterpret_cast<char *>(grid) + (size_t)a * d.T * d.V * (half ? 2 : 4);
+  float *fut = d.fut + d.fut_base(a);
+  char  *g   = reinterpret_cast<char *>(grid) + d.fut_base(a) * (half ? 2 : 4);
   const int pv = gg.phys_of(v);  // (rows: v itself, the straight copy; tiles: the cell's place in the slice)
   for (int t = 0; t < d.T; ++t) {
     cell_st(g, (size_t)t * d.V + pv, fut[(size_t)t * d.V + v], half);
     fut[(size_t)t * d.V + v] = 0.f;
   }
-  if (d.occ[(size_t)a * 4 * d.V + v] > thr) atomicAdd(&s.n_occupied, 1);
+  if (d.occ[d.occ_base(a) + v] > thr) atomicAdd(&s.n_occupied, 1);
 }
 __global__ void k_dsp_publish_ego(DspDev d, void *__restrict__ grid, GridGeom gg, int inf_step,
                                   int32_t *__restrict__ out_n) {
   const int half = gg.half;
   const int a = blockIdx.x;
   const int w = 2 * inf_step + 1;
-  char     *g = reinterpret_cast<char *>(grid) + (size_t)a * d.T * d.V * (half ? 2 : 4);
+  char     *g = reinterpret_cast<char *>(grid) + d.fut_base(a) * (half ? 2 : 4);
   for (int k = threadIdx.x; k < w * w * w; k += blockDim.x) {
     const int x = k / (w * w) - inf_step, y = (k / w) % w - inf_step, z = k % w - inf_step;
     const int idx = z * d.L * d.W + y * d.L + x;  // getVoxelIndex(Vector3i) of the OFFSET (map.h:176)
@@ -1539,223 +843,25 @@ __global__ void k_dsp_publish_ego(DspDev d, void *__restrict__ grid, GridGeom gg
 
 using namespace sogm;
 
-struct sogm_dsp {
-  sogm_ctx          *map;
-  DspDev             d;
-  SogmDspParams      P;
-  Resources          res;  // owns every buffer of `d`
-};
-
-// (sogm_device.hpp) the handle's arrays as sogm_velaudit.hip reads them: nothing of the handle is written through this view
-int sogm::dsp_born_view(const sogm_dsp *h, DspBornView *out) {
-  if (!h || !out) return SOGM_ERR_INVALID_ARG;
-  static_assert(sizeof(DspAgent) % sizeof(int32_t) == 0, "the agents' scalars are strided in ints");
-  out->born     = h->d.born;
-  out->born_src = h->d.born_src;
-  out->ok       = &h->d.ag->ok;
-  out->n_born   = &h->d.ag->n_born;
-  out->stride   = (int)(sizeof(DspAgent) / sizeof(int32_t));
-  out->n_agents = h->d.A;
-  out->max_pts  = h->d.max_pts;
-  out->device   = h->map->device;
-  return SOGM_OK;
+// k_dsp_observe keeps per-pyramid counters, k_dsp_newborn the 1/C_k list in dynamic LDS
+static size_t observe_lds(const DspDev &d) { return 2 * (size_t)d.NP * sizeof(int); }
+static size_t newborn_lds(const DspDev &d) { return (size_t)d.max_pts * sizeof(float); }
+void sogm::reserve_update_lds(const DspDev &d) {
+  (void)raise_dynamic_lds<k_dsp_observe>(observe_lds(d));
+  (void)raise_dynamic_lds<k_dsp_newborn>(newborn_lds(d));
 }
 
 namespace {
-template <typename T>
-int dupload(sogm_dsp *h, const T **out, const T *src, size_t n) {
-  if (h->res.array(const_cast<T **>(out), n) != hipSuccess) return -1;
-  return hipMemcpy(const_cast<T *>(*out), src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ? -1 : 0;
-}
+// launch grids of one update: (x, agent) with one thread per x, or one workgroup per agent
+struct UpdateGrids {
+  unsigned A;
+  explicit UpdateGrids(const DspDev &d) : A((unsigned)d.A) {}
+  dim3 per(size_t n, unsigned block) const { return dim3((unsigned)((n + block - 1) / block), A); }
+  dim3 agents() const { return dim3(A); }
+};
 }  // namespace
 
 extern "C" {
-
-void sogm_dsp_destroy(sogm_dsp *h) {
-  if (!h) return;
-  (void)hipSetDevice(h->map->device);
-  h->res.release_all();
-  delete h;
-}
-
-int sogm_dsp_create(sogm_ctx *map, const SogmDspParams *P, const float *p_gauss, const float *v_gauss,
-                    int n_gauss, const int32_t *rand_tab, int n_rand, int max_points, sogm_dsp **out) {
-  if (!map || !P || !out || !p_gauss || !v_gauss || !rand_tab || n_gauss <= 0 || n_rand <= 0 ||
-      max_points <= 0 || max_points > 8192)
-    return SOGM_ERR_INVALID_ARG;
-  const SogmSpec &sp = map->spec;
-  const int       S  = P->max_particle_num_voxel * 2;
-  const int       ar = P->angle_resolution;
-  if (S > DSP_SLOTS || S < 1 || ar < 1 || sp.T > SOGM_DSP_MAX_T || P->newborn_num < 1 ||
-      P->obs_max_per_pyramid < 2 || P->half_fov_h * 2 / ar > 180 || P->half_fov_v * 2 / ar > 180)
-    return SOGM_ERR_INVALID_ARG;
-  SOGM_HIP_CHECK(hipSetDevice(map->device));
-  {
-    // k_dsp_velocity keeps the cloud in LDS: 20 B per point of dynamic LDS on top of its static arrays; the request
-    // must fit the workgroup limit of THIS device (160 KiB on gfx950: max_points <= ~7.4 k), checked here instead of
-    // failing every later sogm_update_dsp(labels = NULL) launch
-    hipFuncAttributes fa;
-    int               lds_max = 0;
-    SOGM_HIP_CHECK(hipFuncGetAttributes(&fa, (const void *)k_dsp_velocity));
-    SOGM_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, map->device));
-    if ((size_t)max_points * 20 + fa.sharedSizeBytes > (size_t)lds_max) {
-      set_error("sogm_dsp_create: max_points needs more LDS than a workgroup can have (k_dsp_velocity)", hipErrorInvalidValue);
-      return SOGM_ERR_CAPACITY;
-    }
-  }
-  sogm_dsp *h = new (std::nothrow) sogm_dsp();  // (value-initialised: `d` is zero)
-  if (!h) return SOGM_ERR_HIP;
-  h->map    = map;
-  h->P      = *P;
-  DspDev &d = h->d;
-  d.A   = map->n_agents;
-  d.L   = sp.L;
-  d.W   = sp.W;
-  d.H   = sp.H;
-  d.T   = sp.T;
-  d.V   = sp.L * sp.W * sp.H;
-  d.S   = S;
-  d.nph = P->half_fov_h * 2 / ar;
-  d.npv = P->half_fov_v * 2 / ar;
-  d.NP  = d.nph * d.npv;
-  d.SP  = (int)(d.V * P->max_particle_num_voxel + 1e5) / (360 * 180 / ar / ar) * 2;  // SAFE_PARTICLE_NUM_PYRAMID
-  if (d.SP < 1) {
-    delete h;
-    return SOGM_ERR_INVALID_ARG;
-  }
-  d.OM       = P->obs_max_per_pyramid;
-  d.cand_cap = 2 * d.V;
-  d.max_pts  = max_points;
-  d.nb       = P->newborn_num;
-  d.maxp     = P->max_particle_num_voxel;
-  d.n_gauss  = n_gauss;
-  d.n_rand   = n_rand;
-  d.res      = sp.resolution;
-  d.hx       = (d.res * (float)sp.L) * 0.5f;  // map_length_x_half (:572)
-  d.hy       = (d.res * (float)sp.W) * 0.5f;
-  d.hz       = (d.res * (float)sp.H) * 0.5f;
-  d.sigma    = P->sigma_observation;
-  d.Pd       = P->p_detection;
-  d.kappa    = P->kappa;
-  d.w_nb     = P->newborn_weight;
-  d.thick    = P->obstacle_thickness;
-  for (int t = 0; t < SOGM_DSP_MAX_T; ++t) d.pred_t[t] = P->prediction_times[t];
-
-  // host-side constant tables (setInitParameters :566-632): boundary-plane normals, neighbour table,
-  // Gaussian PDF lookup (calculateNormalPDFBuffer :1373-1378) — set-up, evaluated once with libm.
-  const float        arr = (float)ar / 180.f * 3.14159265358979323846f;
-  std::vector<float> bh((d.nph + 1) * 3), bv((d.npv + 1) * 3), pdf(20000);
-  const int          he = P->half_fov_h / ar, ve = P->half_fov_v / ar;
-  for (int i = -he; i <= he; i++) {
-    bh[(i + he) * 3 + 0] = -sinf((float)i * arr);
-    bh[(i + he) * 3 + 1] = cosf((float)i * arr);
-    bh[(i + he) * 3 + 2] = 0.f;
-  }
-  for (int i = -ve; i <= ve; i++) {
-    bv[(i + ve) * 3 + 0] = sinf((float)i * arr);
-    bv[(i + ve) * 3 + 1] = 0.f;
-    bv[(i + ve) * 3 + 2] = cosf((float)i * arr);
-  }
-  std::vector<int> nbr((size_t)d.NP * 10, 0);
-  for (int i = 0; i < d.NP; i++) {
-    int h0 = i / d.npv, v0 = i % d.npv, n = 0;
-    for (int x = -1; x <= 1; ++x)
-      for (int y = -1; y <= 1; ++y) {
-        int hh = h0 + x, vv = v0 + y;
-        if (hh >= 0 && hh < d.nph && vv >= 0 && vv < d.npv) nbr[i * 10 + 1 + n++] = hh * d.npv + vv;
-      }
-    nbr[i * 10] = n;
-  }
-  for (int i = 0; i < 20000; ++i) {
-    float value = (float)(i - 10000) * 0.001f;
-    pdf[i]      = (1.f / (sqrtf(2.f * 1.57079632679489661923f))) * expf(-powf(value, 2) / (2));
-  }
-  const size_t A = d.A, V = d.V, VS = V * DSP_SLOTS, NP = d.NP, MP = d.max_pts, NB = d.nb, CC = d.cand_cap;
-  int          bad = 0;
-  bad |= h->res.array(&d.ag, A);
-  bad |= h->res.array(&d.flag, A * VS);
-  for (int k = 0; k < 6; ++k) bad |= h->res.array(&d.f[k], A * VS);
-  bad |= h->res.array(&d.fut, A * d.T * V);
-  bad |= h->res.array(&d.occ, A * 4 * V);
-  bad |= h->res.array(&d.pc, A * NP * d.OM * 5);
-  bad |= h->res.array(&d.nobs, A * NP);
-  bad |= h->res.array(&d.maxlen, A * NP);
-  bad |= h->res.array(&d.obs_list, A * MP);
-  bad |= h->res.array(&d.bp_h, A * (d.nph + 1) * 3);
-  bad |= h->res.array(&d.bp_v, A * (d.npv + 1) * 3);
-  bad |= h->res.array(&d.born, A * MP * 7);
-  bad |= h->res.array(&d.born_src, A * MP);
-  bad |= h->res.array(&d.vel_adj, A * MP * VEL_ADJ_CAP);
-  bad |= h->res.array(&d.vel_deg, A * MP);
-  bad |= h->res.array(&d.c_key, A * CC);
-  bad |= h->res.array(&d.c_dest, A * CC);
-  bad |= h->res.array(&d.c_pyr, A * CC);
-  bad |= h->res.array(&d.c_assign, A * CC);
-  bad |= h->res.array(&d.c_vnext, A * CC);
-  bad |= h->res.array(&d.c_pnext, A * CC);
-  bad |= h->res.array(&d.c_kill, A * CC);
-  bad |= h->res.array(&d.c_pay, A * CC * 6);
-  bad |= h->res.array(&d.vhead, A * V);
-  bad |= h->res.array(&d.phead, A * NP);
-  bad |= h->res.array(&d.pyr_list, A * NP * d.SP);
-  bad |= h->res.array(&d.pyr_n, A * NP);
-  bad |= h->res.array(&d.pyr_key, A * NP * d.SP);
-  bad |= h->res.array(&d.pyr_id, A * NP * d.SP);
-  bad |= h->res.array(&d.b_valid, A * MP);
-  bad |= h->res.array(&d.b_nstatic, A * MP);
-  bad |= h->res.array(&d.b_vi, A * MP);
-  bad |= h->res.array(&d.b_c, A * MP * 3);
-  bad |= h->res.array(&d.b_cls, A * MP * NB);
-  bad |= h->res.array(&d.b_dest, A * MP * NB);
-  bad |= h->res.array(&d.b_vnext, A * MP * NB);
-  bad |= h->res.array(&d.b_pay, A * MP * NB * 5);
-  bad |= dupload(h, &d.pg, p_gauss, (size_t)n_gauss);
-  bad |= dupload(h, &d.vg, v_gauss, (size_t)n_gauss);
-  bad |= dupload(h, &d.rnd, (const int *)rand_tab, (size_t)n_rand);
-  bad |= dupload(h, &d.pdf, pdf.data(), pdf.size());
-  bad |= dupload(h, &d.bp_ori_h, bh.data(), bh.size());
-  bad |= dupload(h, &d.bp_ori_v, bv.data(), bv.size());
-  bad |= dupload(h, &d.nbr, nbr.data(), nbr.size());
-  if (bad) {
-    set_error("sogm_dsp_create: hipMalloc", hipGetLastError());
-    sogm_dsp_destroy(h);
-    return SOGM_ERR_HIP;
-  }
-  std::vector<DspAgent> ag(A);
-  std::memset(ag.data(), 0, A * sizeof(DspAgent));
-  for (auto &x : ag) {
-    x.first   = 1;
-    x.quat[0] = 1.f;
-  }
-  hipError_t e = hipMemcpy(d.ag, ag.data(), A * sizeof(DspAgent), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d.flag, 0, A * VS);
-  if (e == hipSuccess) e = hipMemset(d.fut, 0, A * d.T * V * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(d.occ, 0, A * 4 * V * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(d.nobs, 0, A * NP * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(d.pyr_n, 0, A * NP * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(d.pc, 0, A * NP * d.OM * 5 * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(d.maxlen, 0xFF, A * NP * sizeof(int));
-  for (int k = 0; k < 6 && e == hipSuccess; ++k) e = hipMemset(d.f[k], 0, A * VS * sizeof(float));
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // null-stream memsets: complete before the first update on another stream
-  if (e != hipSuccess) {
-    set_error("sogm_dsp_create: init", e);
-    sogm_dsp_destroy(h);
-    return SOGM_ERR_HIP;
-  }
-  // the observe / newborn kernels keep per-pyramid counters / the 1/C_k list in dynamic LDS (function attributes
-  // are process-wide: keep the largest request of any handle)
-  static size_t lds_obs = 0, lds_born = 0;
-  if (2 * NP * sizeof(int) > lds_obs) {
-    lds_obs = 2 * NP * sizeof(int);
-    (void)hipFuncSetAttribute((const void *)k_dsp_observe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_obs);
-  }
-  if (MP * sizeof(float) > lds_born) {
-    lds_born = MP * sizeof(float);
-    (void)hipFuncSetAttribute((const void *)k_dsp_newborn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_born);
-  }
-  *out = h;
-  return SOGM_OK;
-}
 
 int sogm_update_dsp(sogm_dsp *h, const float *points, const float *labels, const int32_t *cloud_range,
                     const float *sensor_pos, const float *sensor_quat, const double *stamps,
@@ -1764,38 +870,31 @@ int sogm_update_dsp(sogm_dsp *h, const float *points, const float *labels, const
   DspDev     &d  = h->d;
   hipStream_t st = (hipStream_t)stream;
   SOGM_HIP_CHECK(hipSetDevice(h->map->device));
-  const size_t A = d.A, V = d.V;
-  const dim3   g_vox64((unsigned)((V + 63) / 64), (unsigned)A), g_vox256((unsigned)((V + 255) / 256), (unsigned)A);
-  const dim3   g_pyr((unsigned)((d.NP + 63) / 64), (unsigned)A);
-  hipLaunchKernelGGL(k_dsp_begin, dim3((unsigned)A), dim3(128), 0, st, d, sensor_pos, sensor_quat, stamps, out_ok);
+  const UpdateGrids g(d);
+  const size_t      A = d.A, V = d.V;
+  // odometry, observations, the new-born list
+  hipLaunchKernelGGL(k_dsp_begin, g.agents(), dim3(128), 0, st, d, sensor_pos, sensor_quat, stamps, out_ok);
   SOGM_HIP_CHECK(hipMemsetAsync(d.vhead, 0xFF, A * V * sizeof(int), st));
   SOGM_HIP_CHECK(hipMemsetAsync(d.phead, 0xFF, A * d.NP * sizeof(int), st));
-  hipLaunchKernelGGL(k_dsp_observe, dim3((unsigned)A), dim3(256), 2 * d.NP * sizeof(int), st, d, points, labels,
-                     cloud_range);
-  if (!labels) {  // velocityEstimationThread (:305): labels and point order of the new-born list are computed here
-    // the attribute is per function, not per sogm_dsp: raise it whenever a handle asks for more than any before
-    // (size checked against the device limit in sogm_dsp_create)
-    static size_t attr_lds = 0;
-    const size_t  lds      = (size_t)d.max_pts * 20;
-    if (lds > attr_lds) {
-      SOGM_HIP_CHECK(hipFuncSetAttribute((const void *)k_dsp_velocity, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_lds = lds;
-    }
-    hipLaunchKernelGGL(k_dsp_velocity, dim3((unsigned)A), dim3(1024), lds, st, d, cloud_range, 0.15f);
-  }
-  hipLaunchKernelGGL(k_dsp_predict, g_vox256, dim3(256), 0, st, d);
+  hipLaunchKernelGGL(k_dsp_observe, g.agents(), dim3(256), observe_lds(d), st, d, points, labels, cloud_range);
+  if (!labels)  // velocityEstimationThread (:305): labels and point order of the new-born list are computed here
+    if (int rc = launch_dsp_velocity(d, cloud_range, 0.15f, st)) return rc;
+  // prediction: move, then the ordered first-fit to its fixed point, then commit
+  hipLaunchKernelGGL(k_dsp_predict, g.per(V, 256), dim3(256), 0, st, d);
   for (int r = 0; r < DSP_ROUNDS; ++r) {
-    hipLaunchKernelGGL(k_dsp_place, g_vox64, dim3(64), 0, st, d, r);
-    hipLaunchKernelGGL(k_dsp_pyramids, g_pyr, dim3(64), 0, st, d, r);
+    hipLaunchKernelGGL(k_dsp_place, g.per(V, 64), dim3(64), 0, st, d, r);
+    hipLaunchKernelGGL(k_dsp_pyramids, g.per(d.NP, 64), dim3(64), 0, st, d, r);
   }
-  hipLaunchKernelGGL(k_dsp_commit_slots, g_vox256, dim3(256), 0, st, d);
-  hipLaunchKernelGGL(k_dsp_commit_movers, dim3((unsigned)((d.cand_cap + 255) / 256), (unsigned)A), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(k_dsp_ck, dim3((unsigned)((d.max_pts + 255) / 256), (unsigned)A), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(k_dsp_weight, dim3((unsigned)((d.NP * d.SP + 255) / 256), (unsigned)A), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(k_dsp_commit_slots, g.per(V, 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(k_dsp_commit_movers, g.per(d.cand_cap, 256), dim3(256), 0, st, d);
+  // weights
+  hipLaunchKernelGGL(k_dsp_ck, g.per(d.max_pts, 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(k_dsp_weight, g.per(d.NP * d.SP, 256), dim3(256), 0, st, d);
+  // new-born particles, occupancy and resampling
   SOGM_HIP_CHECK(hipMemsetAsync(d.vhead, 0xFF, A * V * sizeof(int), st));
-  hipLaunchKernelGGL(k_dsp_newborn, dim3((unsigned)A), dim3(1024), d.max_pts * sizeof(float), st, d);
-  hipLaunchKernelGGL(k_dsp_place_born, g_vox64, dim3(64), 0, st, d);
-  hipLaunchKernelGGL(k_dsp_occupancy, g_vox256, dim3(256), 0, st, d);
+  hipLaunchKernelGGL(k_dsp_newborn, g.agents(), dim3(1024), newborn_lds(d), st, d);
+  hipLaunchKernelGGL(k_dsp_place_born, g.per(V, 64), dim3(64), 0, st, d);
+  hipLaunchKernelGGL(k_dsp_occupancy, g.per(V, 256), dim3(256), 0, st, d);
   SOGM_HIP_CHECK(hipGetLastError());
   return SOGM_OK;
 }
@@ -1818,185 +917,6 @@ int sogm_dsp_publish(sogm_dsp *h, int32_t *out_n_occupied, void *stream) {
                      out_n_occupied);
   SOGM_HIP_CHECK(hipGetLastError());
   c->updated = 1;
-  return SOGM_OK;
-}
-
-int sogm_dsp_download_state(sogm_dsp *h, int agent, float *store, float *objnum, int32_t *counters) {
-  if (!h || agent < 0 || agent >= h->d.A) return SOGM_ERR_INVALID_ARG;
-  DspDev &d = h->d;
-  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  const size_t V = d.V, VS = V * DSP_SLOTS;
-  if (store) {
-    std::vector<uint8_t> fl(VS);
-    std::vector<float>   f[6];
-    SOGM_HIP_CHECK(hipMemcpy(fl.data(), d.flag + (size_t)agent * VS, VS, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 6; ++k) {
-      f[k].resize(VS);
-      SOGM_HIP_CHECK(hipMemcpy(f[k].data(), d.f[k] + (size_t)agent * VS, VS * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    static const float fv[7] = {0.f, 1.f, 0.6f, 7.f, 15.f, 0.f, 0.f};
-    for (size_t v = 0; v < V; ++v)
-      for (int p = 0; p < d.S; ++p) {
-        float       *o  = store + (v * d.S + p) * 9;
-        const size_t at = v * DSP_SLOTS + p;
-        o[0]            = fv[fl[at] < 7 ? fl[at] : 0];
-        o[1]            = f[0][at];
-        o[2]            = f[1][at];
-        o[3]            = 0.f;
-        o[4]            = f[2][at];
-        o[5]            = f[3][at];
-        o[6]            = f[4][at];
-        o[7]            = f[5][at];
-        o[8]            = 0.f;
-      }
-  }
-  if (objnum) {
-    std::vector<float> occ(4 * V), fut((size_t)d.T * V);
-    SOGM_HIP_CHECK(hipMemcpy(occ.data(), d.occ + (size_t)agent * 4 * V, occ.size() * sizeof(float), hipMemcpyDeviceToHost));
-    SOGM_HIP_CHECK(hipMemcpy(fut.data(), d.fut + (size_t)agent * d.T * V, fut.size() * sizeof(float), hipMemcpyDeviceToHost));
-    const int OD = 4 + d.T;
-    for (size_t v = 0; v < V; ++v) {
-      for (int k = 0; k < 4; ++k) objnum[v * OD + k] = occ[k * V + v];
-      for (int t = 0; t < d.T; ++t) objnum[v * OD + 4 + t] = fut[(size_t)t * V + v];
-    }
-  }
-  if (counters) {
-    DspAgent s;
-    SOGM_HIP_CHECK(hipMemcpy(&s, d.ag + agent, sizeof(s), hipMemcpyDeviceToHost));
-    std::memset(counters, 0, 16 * sizeof(int32_t));
-    counters[0]  = s.dbg_voxel_full;
-    counters[1]  = s.dbg_pyr_full;
-    counters[2]  = s.dbg_out;
-    counters[3]  = s.cand_cnt;
-    counters[4]  = s.pseq;
-    counters[5]  = s.vseq;
-    counters[6]  = s.rseq;
-    counters[7]  = d.S;
-    counters[8]  = d.SP;
-    counters[9]  = d.NP;
-    counters[10] = s.err_unconverged;
-    counters[11] = s.err_pool;
-    counters[12] = s.err_points;
-    counters[13] = s.valid_points;
-    counters[14] = s.n_obs;
-    counters[15] = s.ok;
-  }
-  return SOGM_OK;
-}
-
-// Test hook (sogm_abi_debug.h): the inverse of sogm_dsp_download_state for a between-updates store.  Validated on the
-// host before anything is written; plain copies, no kernel.
-int sogm_dsp_upload_state(sogm_dsp *h, int agent, const float *store, const float *last_pos3, double last_stamp,
-                          const int32_t *cursors3) {
-  if (!h || agent < 0 || agent >= h->d.A || !store || !last_pos3 || !cursors3) return SOGM_ERR_INVALID_ARG;
-  DspDev &d = h->d;
-  if (cursors3[0] < 0 || cursors3[0] >= d.n_gauss || cursors3[1] < 0 || cursors3[1] >= d.n_gauss || cursors3[2] < 0 ||
-      cursors3[2] >= d.n_rand)
-    return SOGM_ERR_INVALID_ARG;
-  const size_t V = d.V, VS = V * DSP_SLOTS;
-  std::vector<uint8_t> fl(VS, (uint8_t)F_EMPTY);
-  std::vector<float>   f[6];
-  for (int k = 0; k < 6; ++k) f[k].assign(VS, 0.f);
-  static const int src[6] = {1, 2, 4, 5, 6, 7};  // vx vy px py pz w
-  for (size_t v = 0; v < V; ++v)
-    for (int p = 0; p < d.S; ++p) {
-      const float *o  = store + (v * d.S + p) * 9;
-      const size_t at = v * DSP_SLOTS + p;
-      uint8_t      c;
-      if (o[0] == 0.f)
-        c = F_EMPTY;
-      else if (o[0] == 1.f)
-        c = F_VALID;
-      else if (o[0] == 0.6f)
-        c = F_RESAMP;
-      else
-        return SOGM_ERR_INVALID_ARG;  // (a NaN flag compares unequal to all three)
-      if (c != F_EMPTY && !(o[3] == 0.f)) return SOGM_ERR_INVALID_ARG;
-      fl[at] = c;
-      for (int k = 0; k < 6; ++k) f[k][at] = o[src[k]];
-    }
-  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  DspAgent s;
-  SOGM_HIP_CHECK(hipMemcpy(&s, d.ag + agent, sizeof(s), hipMemcpyDeviceToHost));
-  SOGM_HIP_CHECK(hipMemcpy(d.flag + (size_t)agent * VS, fl.data(), VS, hipMemcpyHostToDevice));
-  for (int k = 0; k < 6; ++k)
-    SOGM_HIP_CHECK(hipMemcpy(d.f[k] + (size_t)agent * VS, f[k].data(), VS * sizeof(float), hipMemcpyHostToDevice));
-  SOGM_HIP_CHECK(hipMemset(d.occ + (size_t)agent * 4 * V, 0, 4 * V * sizeof(float)));
-  SOGM_HIP_CHECK(hipMemset(d.fut + (size_t)agent * d.T * V, 0, (size_t)d.T * V * sizeof(float)));
-  for (int k = 0; k < 3; ++k) s.last_p[k] = last_pos3[k];
-  s.last_t = last_stamp;
-  s.first  = 0;
-  s.pseq   = cursors3[0];
-  s.vseq   = cursors3[1];
-  s.rseq   = cursors3[2];
-  s.cand_cnt = 0;
-  s.dbg_voxel_full = s.dbg_pyr_full = s.dbg_out = 0;
-  s.err_unconverged = s.err_pool = s.err_points = 0;
-  s.vel_n_last = 0;
-  SOGM_HIP_CHECK(hipMemcpy(d.ag + agent, &s, sizeof(s), hipMemcpyHostToDevice));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  return SOGM_OK;
-}
-
-int sogm_dsp_download_observations(sogm_dsp *h, int agent, int32_t *nobs, float *pc, float *maxlen) {
-  if (!h || agent < 0 || agent >= h->d.A) return SOGM_ERR_INVALID_ARG;
-  DspDev &d = h->d;
-  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  const size_t NP = d.NP;
-  if (nobs) SOGM_HIP_CHECK(hipMemcpy(nobs, d.nobs + agent * NP, NP * sizeof(int), hipMemcpyDeviceToHost));
-  if (pc)
-    SOGM_HIP_CHECK(hipMemcpy(pc, d.pc + (size_t)agent * NP * d.OM * 5, NP * d.OM * 5 * sizeof(float), hipMemcpyDeviceToHost));
-  if (maxlen) {
-    std::vector<int> b(NP);
-    SOGM_HIP_CHECK(hipMemcpy(b.data(), d.maxlen + agent * NP, NP * sizeof(int), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < NP; ++i) {
-      float f;
-      std::memcpy(&f, &b[i], 4);
-      maxlen[i] = b[i] < 0 ? -1.f : f;
-    }
-  }
-  return SOGM_OK;
-}
-
-// Parity I/O (synchronous): input_cloud_with_velocity of the last update — rows {x, y, z, vx, vy, vz, intensity} in
-// the order new-born particles are created — and counters {clusters, possibly dynamic, matched, error code}.
-int sogm_dsp_download_born(sogm_dsp *h, int agent, float *born_host, int cap, int32_t *n_born, int32_t *counters4) {
-  if (!h || agent < 0 || agent >= h->d.A || cap < 0) return SOGM_ERR_INVALID_ARG;
-  DspDev &d = h->d;
-  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  DspAgent ag;
-  SOGM_HIP_CHECK(hipMemcpy(&ag, d.ag + agent, sizeof(ag), hipMemcpyDeviceToHost));
-  if (n_born) *n_born = ag.n_born;
-  if (counters4) {
-    counters4[0] = ag.vel_clusters;
-    counters4[1] = ag.vel_dynamic;
-    counters4[2] = ag.vel_matched;
-    counters4[3] = ag.vel_err;
-  }
-  if (born_host) {
-    const size_t n = (size_t)(ag.n_born < cap ? ag.n_born : cap);
-    SOGM_HIP_CHECK(hipMemcpy(born_host, d.born + (size_t)agent * d.max_pts * 7, n * 7 * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  return SOGM_OK;
-}
-
-// The source index of that list (sogm_abi_debug.h): born_src rows 0 .. n_born - 1.
-int sogm_dsp_download_born_source(sogm_dsp *h, int agent, int32_t *out, int cap, int32_t *n_born) {
-  if (!h || agent < 0 || agent >= h->d.A || cap < 0) return SOGM_ERR_INVALID_ARG;
-  DspDev &d = h->d;
-  SOGM_HIP_CHECK(hipSetDevice(h->map->device));
-  SOGM_HIP_CHECK(hipDeviceSynchronize());
-  DspAgent ag;
-  SOGM_HIP_CHECK(hipMemcpy(&ag, d.ag + agent, sizeof(ag), hipMemcpyDeviceToHost));
-  if (n_born) *n_born = ag.n_born;
-  if (out) {
-    const size_t n = (size_t)(ag.n_born < cap ? ag.n_born : cap);
-    SOGM_HIP_CHECK(hipMemcpy(out, d.born_src + (size_t)agent * d.max_pts, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
   return SOGM_OK;
 }
 
