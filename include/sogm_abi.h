@@ -1782,6 +1782,100 @@ int sogm_camera_poses(const SogmPositionCommand *cmd, int n, int cmd_stride, con
                       double *out_rot /* dev [n][9] */, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* radio links: every receiver's own table of the swarm's trajectories, under per-message delay,  */
+/*   loss and radio range.  The reference is decentralised: each drone keeps a ParticleATC store  */
+/*   of the BezierTraj messages that reached it (traj_coordinator/src/particles.cpp:131-191), the */
+/*   callback logs each message's delay (:156-157) and whatever arrives last overwrites the entry */
+/*   (:184-186).  The link model itself is the build's OWN definition, held by two independent    */
+/*   implementations (csrc/sogm_link.hpp; tests/link_model_reference.py), bit for bit.            */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Draws are "sensor noise"'s: mix and U as defined there, counter-based, uint64 that wraps; fp64 is one IEEE operation at
+ * a time without contraction.
+ *
+ * Messages.  At tick m sender j broadcasts row j of the table every agent executes after tick m, provided that row has
+ *   n_pieces > 0; a row with n_pieces <= 0 is not a message.  Deviation: this happens EVERY tick whether or not the record
+ *   changed (a heartbeat), where the reference sends only a new trajectory (plan_manager.cpp:364-399); the heartbeat only
+ *   re-sends what a lossless link had already delivered.
+ * Message (m, j -> a), a the receiver's global row, a != j:
+ *   h = mix( mix( mix(seed) ^ m ) ^ (j * n_total + a) )                                   (all uint64)
+ *   u = U(mix(h + 0))
+ *   d = delay_min + min( (int)floor( U(mix(h + 1)) * (double)(delay_max - delay_min + 1) ), delay_max - delay_min )
+ *   out of range, only when range > 0: with the positions of j and a at tick m, dx, dy, dz their differences,
+ *     d2 = (dx*dx + dy*dy) + dz*dz; out of range iff !(d2 <= range*range) — a NaN position is out of range.
+ *   lost iff out of range, else iff u < p_loss (the range test comes first).  A message that is not lost arrives at m + d.
+ * Known answers: seed 0x5067, n_total 5, p_loss 0.3, delay 0..2: (m 0, j 0, a 1) h = 0xF556F0F326877456,
+ *   u = 0x1.570a43181f084p-3, d 0, lost; (7, 4, 0) h = 0xECEED24989F9F5F8, u = 0x1.5e11450a71e6bp-1, d 1, not lost.
+ *
+ * Delivery at tick k — one call per tick, ticks consecutive from tick0:
+ *   1. the table and the positions are stored in slot k % (delay_max + 1) of the caller's ring;
+ *   2. for every (local receiver a, sender j != a): of the not-lost messages with tick0 <= m <= k and m + d == k the one
+ *      with the largest m wins;
+ *   3. with SOGM_LINK_NEWEST_WINS a winner with m < the send tick already held is dropped;
+ *   4. otherwise it is copied into views[a_local][j] and held_tick[a_local][j] = m — without the flag an older message
+ *      does overwrite a newer one, as `*obs_ptr = traj` does (particles.cpp:184-186);
+ *   5. no arrival leaves the view unchanged;
+ *   6. views[a_local][a], the receiver's own row, always gets the current row (held_tick = k).
+ * counters[a_local][8] int64, added to by every call (integer adds: the same bits from run to run):
+ *   0 messages of tick k addressed to the receiver   1 of those, out of range        2 of those, lost by draw
+ *   3 arrivals at tick k                             4 arrivals applied (winners copied)
+ *   5 winners older than what was held (applied, or dropped under the flag)
+ *   6 sum over heard senders of k - held_tick after delivery                        7 senders not heard yet
+ * All-zero parameters are perfect links: every view row equals the table's from the first tick on.
+ */
+#define SOGM_LINK_MAX_DELAY   7
+#define SOGM_LINK_NEWEST_WINS 1
+#define SOGM_LINK_COUNTERS    8
+typedef struct SogmLinkParams {
+  uint64_t seed;
+  double   p_loss;        /* [0, 1] */
+  double   range;         /* metres; 0: unlimited */
+  int32_t  delay_min;     /* whole ticks, 0 <= delay_min <= delay_max <= SOGM_LINK_MAX_DELAY */
+  int32_t  delay_max;
+  int32_t  flags;         /* SOGM_LINK_NEWEST_WINS; other bits are ignored */
+  int32_t  reserved_;
+} SogmLinkParams;         /* 40 bytes */
+typedef struct SogmLinkBuffers {   /* all the caller's, device memory, 16-byte aligned */
+  SogmTrajRecord *ring_table;   /* [delay_max + 1][n_total] */
+  double         *ring_pos;     /* [delay_max + 1][n_total][3]; may be NULL when range == 0 */
+  SogmTrajRecord *views;        /* [n_local][n_total]: what sogm_*_views take */
+  int32_t        *held_tick;    /* [n_local][n_total]: the send tick of the row held, -1: nothing heard */
+  int64_t        *counters;     /* [n_local][SOGM_LINK_COUNTERS] */
+} SogmLinkBuffers;              /* 40 bytes */
+/*
+ * Context-free, stream-ordered, no allocation, no host synchronisation, like sogm_depth_noise.  sogm_link_init zeroes the
+ * ring, the views and the counters and sets every held tick to -1.  sogm_link_deliver is the delivery at `tick`: dev table
+ * [n_total] and dev pos [n_total][3] fp64 (or NULL) are only read, and may be reused as soon as the call is queued.
+ * SOGM_ERR_INVALID_ARG (checked first; sogm_last_error() names the rule): a null prm, buffers, table or buffer pointer
+ * (ring_pos only with range > 0); pos == NULL with range > 0; p_loss outside [0, 1] or not finite; range negative or not
+ * finite; delays outside 0 <= delay_min <= delay_max <= SOGM_LINK_MAX_DELAY; n_total < 1, agent0 < 0, n_local outside
+ * 1 .. n_total - agent0; tick0 < 0 or tick < tick0; a record buffer that is not 16-byte aligned.  SOGM_ERR_NO_DEVICE
+ * without a GPU.
+ */
+int sogm_link_default_params(SogmLinkParams *out);
+int sogm_link_init(const SogmLinkParams *prm, int n_total, int n_local, const SogmLinkBuffers *buffers, void *stream);
+int sogm_link_deliver(const SogmLinkParams *prm, int tick, int tick0, const SogmTrajRecord *table /* dev [n_total] */,
+                      const double *pos /* dev [n_total][3] or NULL */, int n_total, int agent0, int n_local,
+                      const SogmLinkBuffers *buffers, void *stream);
+/*
+ * The consumers of per-agent tables.  Each is its namesake without `_views` with the same arguments, except that the
+ * records are dev views [n_agents][n_records] — SogmLinkBuffers.views of a model with n_local == the context's n_agents —
+ * and agent a (the context's a-th) reads views[a * n_records + r] where the namesake reads records[r].  The namesakes'
+ * results are unchanged; with every block of `views` equal to one table the results are the namesake's on that table, bit
+ * for bit.  sogm_planner_set_swarm_views is honoured by both forms of sogm_replan (the dataflow replan's finishing wave and
+ * the grouped path) and undone by sogm_planner_set_swarm; sogm_flight_run reads its own ring of tables as before, and
+ * sogm_update_prestamped has no views form.
+ */
+int sogm_project_neighbours_views(sogm_ctx *ctx, const SogmTrajRecord *views, int n_records, const int32_t *ego_ids,
+                                  void *stream);
+int sogm_update_world_views(sogm_ctx *ctx, const SogmWorld *world, const float *poses, const double *stamps,
+                            const SogmTrajRecord *views, int n_records, const int32_t *ego_ids, void *stream);
+int sogm_safe_after_opt_views(sogm_planner *p, const double *cpts, const int32_t *npoly, const SogmTrajRecord *views,
+                              int n_records, const int32_t *ego_ids, const double *t_now, int32_t *out_safe, void *stream);
+int sogm_planner_set_swarm_views(sogm_planner *p, const SogmTrajRecord *views, int n_records, const int32_t *ego_ids,
+                                 const double *t_now);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory exchange: the /broadcast_traj topic as ONE RCCL all-gather per replan tick          */
 /*   (plan_manager/src/plan_manager.cpp:364-399 publish, traj_coordinator/src/particles.cpp:131-191 receive)  */
 /* ------------------------------------------------------------------------------------------ */

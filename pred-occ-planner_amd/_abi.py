@@ -83,6 +83,16 @@ class SogmDepthNoise(C.Structure):
                 ("edge_jump", C.c_double), ("p_edge", C.c_double), ("min_depth", C.c_double)]
 
 
+class SogmLinkParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("p_loss", C.c_double), ("range", C.c_double), ("delay_min", C.c_int32),
+                ("delay_max", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SogmLinkBuffers(C.Structure):
+    _fields_ = [("ring_table", C.c_void_p), ("ring_pos", C.c_void_p), ("views", C.c_void_p), ("held_tick", C.c_void_p),
+                ("counters", C.c_void_p)]
+
+
 class SogmCylinder(C.Structure):
     _fields_ = [("type", C.c_int32), ("_pad", C.c_int32)] + [
         (k, C.c_double) for k in ("x", "y", "z", "w", "h", "vx", "vy", "qw", "qx", "qy", "qz")]
@@ -279,6 +289,10 @@ SOGM_HIT_GROUND, SOGM_HIT_NONE = -1, -2   # out_hit of sogm_render_depth_swarm
 DEPTH_NOISE_BYTES = C.sizeof(SogmDepthNoise)  # 80
 DEPTH_NOISE_COUNTERS = ("returns_in", "drop_uniform", "drop_edge", "below_min", "beyond_max", "returns_out")
 LABEL_SOURCES_BYTES = C.sizeof(SogmLabelSources)  # 32
+# radio links (include/sogm_abi.h "radio links")
+SOGM_LINK_MAX_DELAY, SOGM_LINK_NEWEST_WINS, SOGM_LINK_COUNTERS = 7, 1, 8
+LINK_PARAMS_BYTES = C.sizeof(SogmLinkParams)  # 40
+LINK_COUNTER_NAMES = ("sent", "out_of_range", "lost", "arrivals", "applied", "stale", "age_sum", "unheard")
 
 
 class SogmTrajServerState(C.Structure):
@@ -401,6 +415,13 @@ PROTOTYPES = {
     "sogm_traj_server_run": (_i, [C.POINTER(SogmTrajServerParams), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i,
                                   C.c_double, C.c_double, _vp, _vp]),
     "sogm_camera_poses": (_i, [_vp, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp]),
+    "sogm_link_default_params": (_i, [C.POINTER(SogmLinkParams)]),
+    "sogm_link_init": (_i, [C.POINTER(SogmLinkParams), _i, _i, C.POINTER(SogmLinkBuffers), _vp]),
+    "sogm_link_deliver": (_i, [C.POINTER(SogmLinkParams), _i, _i, _vp, _vp, _i, _i, _i, C.POINTER(SogmLinkBuffers), _vp]),
+    "sogm_project_neighbours_views": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "sogm_update_world_views": (_i, [_vp, C.POINTER(SogmWorld), _vp, _vp, _vp, _i, _vp, _vp]),
+    "sogm_safe_after_opt_views": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sogm_planner_set_swarm_views": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sogm_traj_allgather": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "sogm_exchange_wait": (_i, [_vp, _vp]),
     "sogm_comm_unique_id": (_i, [C.c_char_p]),

@@ -18,10 +18,11 @@ __global__ __launch_bounds__(64) void k_safe_after_opt(const double *__restrict_
                                                        const int32_t *__restrict__ ego_ids,
                                                        const double *__restrict__ t_now,
                                                        int32_t *__restrict__ out_safe, int agent0,
-                                                       unsigned long long *counters) {
+                                                       unsigned long long *counters, int rec_stride) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   const int a = blockIdx.y + agent0, i = blockIdx.x;
-  if (deconflict_pair_unsafe(cpts + (size_t)a * SOGM_MAX_PIECES * 15, npoly[a], rec[i], ego_ids[a], t_now[a],
+  // (rec_stride 0: one table; n_rec: agent a's own view, rec[a][.])
+  if (deconflict_pair_unsafe(cpts + (size_t)a * SOGM_MAX_PIECES * 15, npoly[a], rec[(size_t)a * rec_stride + i], ego_ids[a], t_now[a],
                              LpLds::carve(s_dyn), counters) &&
       threadIdx.x == 0)
     out_safe[a] = 0;  // every writer writes 0
@@ -70,11 +71,11 @@ __global__ void k_pack_records(int A, FinishArgs f, int agent0) {
 
 hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
                              int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
-                             hipStream_t st, int agent0, unsigned long long *counters) {
+                             hipStream_t st, int agent0, unsigned long long *counters, int rec_stride) {
   hipLaunchKernelGGL(k_fill_i32, dim3((n_agents + 63) / 64), dim3(64), 0, st, out_safe, n_agents, 1, agent0);
   if (n_rec > 0)
     hipLaunchKernelGGL(k_safe_after_opt, dim3(n_rec, n_agents), dim3(64), LpLds::bytes(), st, cpts, npoly, rec, n_rec,
-                       ego_ids, t_now, out_safe, agent0, counters);
+                       ego_ids, t_now, out_safe, agent0, counters, rec_stride);
   return hipGetLastError();
 }
 

@@ -242,6 +242,7 @@ __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, const Lp
     const int     ego = f.swarm_ego[a];
     const double  now = f.swarm_now[a];
     const int     nA  = 5 * M;
+    const SogmTrajRecord *swarm = f.swarm + (size_t)a * f.swarm_stride;  // the one table, or the agent's own view of it
     // set A once per agent: its points in LDS (the LP scratch is idle until a pair needs the LP), its box and
     // its projections on the ten fixed normals as wave-uniform values
     double *sA = sc.work;
@@ -295,13 +296,13 @@ __device__ __forceinline__ int finish_agent(const FinishArgs &f, int a, const Lp
     // time, in record order (first unsafe pair ends the check, as the sequential loop did)
     for (int i0 = 0; i0 < f.n_swarm && safe; i0 += 64) {
       const int  i    = i0 + lane;
-      const bool need = i < f.n_swarm && deconflict_prefilter(sA, nA, boxA, prA, f.swarm[i], ego, now);
+      const bool need = i < f.n_swarm && deconflict_prefilter(sA, nA, boxA, prA, swarm[i], ego, now);
       unsigned long long m = __ballot(need);
       bool               lp_ran = false;
       while (m != 0 && safe) {
         const int j = __builtin_ctzll(m);
         m &= m - 1;
-        if (deconflict_pair_unsafe(ca, M, f.swarm[i0 + j], ego, now, sc, f.counters)) safe = 0;
+        if (deconflict_pair_unsafe(ca, M, swarm[i0 + j], ego, now, sc, f.counters)) safe = 0;
         lp_ran = true;
       }
       if (lp_ran && safe && i0 + 64 < f.n_swarm) stage_A();  // the LP used the scratch that held set A

@@ -105,6 +105,7 @@ __global__ __launch_bounds__(64) void k_flight_light(MapView m, SogmPlannerParam
       const int kl = k - fl.first_tick;
       FinishArgs f = d.fin;
       f.swarm      = d.tables ? d.tables + (size_t)((k - fl.lag) & 3) * d.n_total : nullptr;
+      f.swarm_stride = 0;  // the flight's tables are shared: no per-agent views
       f.pub_table  = d.tables ? d.tables + (size_t)(k & 3) * d.n_total + d.agent0 : nullptr;
       f.out        = d.log_records + (size_t)kl * fl.n_agents;
       f.out_ok     = d.log_ok + (size_t)kl * fl.n_agents;

@@ -971,10 +971,10 @@ __device__ inline void splat_item(const GridGeom &g, void *__restrict__ grid, co
   }
 }
 // Overlay: record r at slice `slice` into the agent's map, and ticket `sub` of the agent's `n_sub` (one wave each) over the
-// n_rec * T items of a table.
+// n_rec * T items of a table — the one table every agent reads (o.stride 0) or the agent's own view of it (o.stride n_rec).
 __device__ __forceinline__ void overlay_item(const GridGeom &g, const OverlayIO &o, const MapTarget &t, int agent, int r,
                                              int slice) {
-  splat_item(g, t.grid, o.rec[r], agent, slice, o.ego_ids, t.poses, t.stamps, o.body, o.n_body, t.lg);
+  splat_item(g, t.grid, o.rec[(size_t)agent * o.stride + r], agent, slice, o.ego_ids, t.poses, t.stamps, o.body, o.n_body, t.lg);
 }
 __device__ __forceinline__ void overlay_ticket(const GridGeom &g, const OverlayIO &o, const MapTarget &t, int agent, int sub,
                                                int n_sub, int lane) {
@@ -982,11 +982,11 @@ __device__ __forceinline__ void overlay_ticket(const GridGeom &g, const OverlayI
   for (int i = sub * 64 + lane; i < n; i += n_sub * 64) overlay_item(g, o, t, agent, i / g.T, i % g.T);
 }
 __global__ __launch_bounds__(256) void k_splat_neighbours(
-    GridGeom g, void *__restrict__ grid, const SogmTrajRecord *__restrict__ rec, int n_rec,
+    GridGeom g, void *__restrict__ grid, const SogmTrajRecord *__restrict__ rec, int n_rec, int rec_stride,
     const int32_t *__restrict__ ego_ids, const float *__restrict__ poses,
     const double *__restrict__ stamps, const double *__restrict__ body, int n_body, int n_agents, int agent0,
     MarkLog lg, const int *wait_stage, int *wait_err) {
-  const OverlayIO o{.rec = rec, .n_rec = n_rec, .ego_ids = ego_ids, .body = body, .n_body = n_body};
+  const OverlayIO o{.rec = rec, .n_rec = n_rec, .stride = rec_stride, .ego_ids = ego_ids, .body = body, .n_body = n_body};
   const MapTarget tgt{.grid = grid, .lg = lg, .poses = const_cast<float *>(poses), .stamps = const_cast<double *>(stamps)};
   const long long total  = (long long)n_agents * n_rec * g.T;
   const long long stride = (long long)gridDim.x * blockDim.x;  // (one item per lane unless the launch is narrower)
@@ -1332,6 +1332,7 @@ __global__ __launch_bounds__(64) void k_flight_map(GridGeom g, FlightCtl fl, Fli
         OverlayIO ov = d.ov;
         ov.rec       = d.tables + (size_t)((k - fl.lag) & 3) * d.n_total;
         ov.n_rec     = d.n_total;
+        ov.stride    = 0;  // the flight's tables are shared: no per-agent views
         overlay_ticket(g, ov, d.tgt, agent, sub, n_s, lane);
       }
       __threadfence();
@@ -1609,14 +1610,17 @@ static int launch_overlay(sogm_ctx *c, hipStream_t st, const OverlayIO &ov, cons
   if (max_workgroups > 0 && nblk > max_workgroups) nblk = max_workgroups;
   prof_begin(c, SOGM_PROF_SPLAT, st);
   hipLaunchKernelGGL(k_splat_neighbours, dim3((unsigned)nblk), dim3(256), 0, st, c->geom, (void *)c->d_grid, ov.rec, ov.n_rec,
-                     ov.ego_ids, c->d_poses, c->d_stamps, ov.body, ov.n_body, c->n_agents, 0, mark_log(c, c->pool.current()),
+                     ov.stride, ov.ego_ids, c->d_poses, c->d_stamps, ov.body, ov.n_body, c->n_agents, 0, mark_log(c, c->pool.current()),
                      wait_stage, wait_err);
   prof_end(c, SOGM_PROF_SPLAT, st);
   SOGM_HIP_CHECK(hipGetLastError());
   return SOGM_OK;
 }
-static OverlayIO overlay_io(const sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids) {
-  return OverlayIO{.rec = records, .n_rec = n_records, .ego_ids = ego_ids, .body = c->d_body, .n_body = c->n_body};
+// per_agent: `records` is [n_agents][n_records], agent a's own view of the swarm (include/sogm_abi.h "radio links")
+static OverlayIO overlay_io(const sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
+                            bool per_agent = false) {
+  return OverlayIO{.rec = records, .n_rec = n_records, .stride = per_agent ? n_records : 0, .ego_ids = ego_ids,
+                   .body = c->d_body, .n_body = c->n_body};
 }
 
 // updateMap for every agent; with `ov` the neighbour overlay follows in the same call.  `world` (or null): the frame is a
@@ -1672,8 +1676,9 @@ int sogm_update_gt_swarm(sogm_ctx *c, const float *cloud_xyz, const int32_t *clo
   return update_maps(c, (hipStream_t)stream, frame, nullptr, poses, stamps, &ov);
 }
 
-int sogm_update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const double *stamps,
-                      const SogmTrajRecord *records, int n_records, const int32_t *ego_ids, void *stream) {
+// sogm_update_world / _views: `records` is the one table [n_records], or per_agent the agents' views [n_agents][n_records]
+static int update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const double *stamps,
+                        const SogmTrajRecord *records, int n_records, const int32_t *ego_ids, bool per_agent, void *stream) {
   if (!c || !w || !poses || !stamps || !w->cloud_xyz || !w->block_bounds || w->n_points < 0 || w->block_points < 64 ||
       w->block_points > 4096 || w->n_blocks != (w->n_points + w->block_points - 1) / w->block_points || w->n_cyl < 0 ||
       (w->n_cyl > 0 && !w->cylinders) || n_records < 0 || (n_records > 0 && (!records || !ego_ids)))
@@ -1681,8 +1686,16 @@ int sogm_update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const
   if (n_records > 0 && (!c->d_body || c->n_body <= 0)) return SOGM_ERR_STATE;
   // (cb: the context's crop lists, sized for this frame inside the update)
   const MapFrame  frame{.cloud = w->cloud_xyz, .cloud_range = nullptr, .cb = {}, .cyl = w->cylinders, .n_cyl = w->n_cyl};
-  const OverlayIO ov = overlay_io(c, records, n_records, ego_ids);
+  const OverlayIO ov = overlay_io(c, records, n_records, ego_ids, per_agent);
   return update_maps(c, (hipStream_t)stream, frame, w, poses, stamps, n_records > 0 ? &ov : nullptr);
+}
+int sogm_update_world(sogm_ctx *c, const SogmWorld *w, const float *poses, const double *stamps,
+                      const SogmTrajRecord *records, int n_records, const int32_t *ego_ids, void *stream) {
+  return update_world(c, w, poses, stamps, records, n_records, ego_ids, false, stream);
+}
+int sogm_update_world_views(sogm_ctx *c, const SogmWorld *w, const float *poses, const double *stamps,
+                            const SogmTrajRecord *views, int n_records, const int32_t *ego_ids, void *stream) {
+  return update_world(c, w, poses, stamps, views, n_records, ego_ids, true, stream);
 }
 
 int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
@@ -1727,8 +1740,8 @@ int sogm_update_prestamped(sogm_ctx *c, const SogmTrajRecord *records, int n_rec
   return SOGM_OK;
 }
 
-int sogm_project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_records,
-                            const int32_t *ego_ids, void *stream) {
+static int project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
+                              bool per_agent, void *stream) {
   if (!c || n_records < 0 || (n_records > 0 && !records) || !ego_ids) return SOGM_ERR_INVALID_ARG;
   if (!c->updated) return SOGM_ERR_STATE;
   if (!c->d_body || c->n_body <= 0) return SOGM_ERR_STATE;
@@ -1736,7 +1749,15 @@ int sogm_project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_re
   SOGM_HIP_CHECK(hipSetDevice(c->device));
   if (int rc = sogm::join_update(c, (hipStream_t)stream)) return rc;
   if (int rc = sogm::join_exchange(c, (hipStream_t)stream)) return rc;  // records may come from an all-gather in flight
-  return launch_overlay(c, (hipStream_t)stream, overlay_io(c, records, n_records, ego_ids), nullptr, nullptr, 0);
+  return launch_overlay(c, (hipStream_t)stream, overlay_io(c, records, n_records, ego_ids, per_agent), nullptr, nullptr, 0);
+}
+int sogm_project_neighbours(sogm_ctx *c, const SogmTrajRecord *records, int n_records,
+                            const int32_t *ego_ids, void *stream) {
+  return project_neighbours(c, records, n_records, ego_ids, false, stream);
+}
+int sogm_project_neighbours_views(sogm_ctx *c, const SogmTrajRecord *views, int n_records, const int32_t *ego_ids,
+                                  void *stream) {
+  return project_neighbours(c, views, n_records, ego_ids, true, stream);
 }
 
 int sogm_cloud_block_bounds(const float *cloud_xyz, int n_points, int block_points, float *out_bounds, void *stream) {

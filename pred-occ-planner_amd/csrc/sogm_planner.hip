@@ -402,15 +402,25 @@ int sogm_bezier_qp_solve_timed(sogm_planner *p, const double *start_pva, const d
   prof_end(p->map, SOGM_PROF_QP, st);
   return launched("k_qp", e);
 }
-int sogm_safe_after_opt(sogm_planner *p, const double *cpts, const int32_t *npoly,
-                        const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
-                        const double *t_now, int32_t *out_safe, void *stream) {
+static int safe_after_opt(sogm_planner *p, const double *cpts, const int32_t *npoly, const SogmTrajRecord *records,
+                          int n_records, const int32_t *ego_ids, const double *t_now, int32_t *out_safe, bool per_agent,
+                          void *stream) {
   if (!p || !cpts || !npoly || !ego_ids || !t_now || !out_safe || n_records < 0 || (n_records > 0 && !records))
     return SOGM_ERR_INVALID_ARG;
   SOGM_HIP_CHECK(hipSetDevice(p->map->device));
   if (int rc = sogm::join_exchange(p->map, (hipStream_t)stream)) return rc;
   return launched("sogm_safe_after_opt", sogm::launch_deconflict(p->sel_count, cpts, npoly, records, n_records, ego_ids,
-                                                                t_now, out_safe, (hipStream_t)stream, p->sel_first));
+                                                                t_now, out_safe, (hipStream_t)stream, p->sel_first, nullptr,
+                                                                per_agent ? n_records : 0));
+}
+int sogm_safe_after_opt(sogm_planner *p, const double *cpts, const int32_t *npoly,
+                        const SogmTrajRecord *records, int n_records, const int32_t *ego_ids,
+                        const double *t_now, int32_t *out_safe, void *stream) {
+  return safe_after_opt(p, cpts, npoly, records, n_records, ego_ids, t_now, out_safe, false, stream);
+}
+int sogm_safe_after_opt_views(sogm_planner *p, const double *cpts, const int32_t *npoly, const SogmTrajRecord *views,
+                              int n_records, const int32_t *ego_ids, const double *t_now, int32_t *out_safe, void *stream) {
+  return safe_after_opt(p, cpts, npoly, views, n_records, ego_ids, t_now, out_safe, true, stream);
 }
 
 int sogm_planner_select_agents(sogm_planner *p, int first, int count) {
@@ -587,10 +597,18 @@ int sogm_planner_set_flight_fsm(sogm_planner *p, const SogmFlightFsm *fsm) {
 int sogm_planner_set_swarm(sogm_planner *p, const SogmTrajRecord *records, int n_records,
                            const int32_t *ego_ids, const double *t_now) {
   if (!p || n_records < 0 || (records && (!ego_ids || !t_now))) return SOGM_ERR_INVALID_ARG;
-  p->swarm     = records;
-  p->n_swarm   = records ? n_records : 0;
-  p->swarm_ego = ego_ids;
-  p->swarm_now = t_now;
+  p->swarm        = records;
+  p->n_swarm      = records ? n_records : 0;
+  p->swarm_stride = 0;
+  p->swarm_ego    = ego_ids;
+  p->swarm_now    = t_now;
+  return SOGM_OK;
+}
+
+int sogm_planner_set_swarm_views(sogm_planner *p, const SogmTrajRecord *views, int n_records, const int32_t *ego_ids,
+                                 const double *t_now) {
+  if (int rc = sogm_planner_set_swarm(p, views, n_records, ego_ids, t_now)) return rc;
+  p->swarm_stride = p->n_swarm;  // agent a checks against views[a][.]
   return SOGM_OK;
 }
 
@@ -1034,7 +1052,7 @@ static int replan_impl(sogm_planner *p, const double *start_pva, const double *g
     if (p->swarm)
       if (int rc = launched("sogm_replan launch_deconflict",
                             sogm::launch_deconflict(n, p->d_cpts, p->d_npoly, p->swarm, p->n_swarm, p->swarm_ego,
-                                                    p->swarm_now, p->d_safe, st, a0, p->cw.counters)))
+                                                    p->swarm_now, p->d_safe, st, a0, p->cw.counters, p->swarm_stride)))
         return rc;
     SOGM_HIP_CHECK(sogm::launch_pack_records(n, finish_args(p, t_start, drone_ids, out_records, out_ok), st, a0));
     SOGM_HIP_CHECK(hipEventRecord(p->ev_done[g], st));
@@ -1055,7 +1073,9 @@ int sogm_replan(sogm_planner *p, const double *start_pva, const double *goal,
   // other agents' deconfliction still reads the swarm table, and into own_records while out_records is written
   if (p->pub_table && p->swarm) {  // byte ranges, not pointers: a rank's slice INSIDE the all-records buffer overlaps too
     const char *a0 = (const char *)p->pub_table, *a1 = a0 + sizeof(SogmTrajRecord) * (size_t)c->n_agents;
-    const char *b0 = (const char *)p->swarm, *b1 = b0 + sizeof(SogmTrajRecord) * (size_t)p->n_swarm;
+    // (the extent of the one table, or of the agents' views [n_agents][n_swarm])
+    const char *b0 = (const char *)p->swarm;
+    const char *b1 = b0 + sizeof(SogmTrajRecord) * (size_t)p->n_swarm * (size_t)(p->swarm_stride ? c->n_agents : 1);
     if (a0 < b1 && b0 < a1) {
       sogm::set_error_text("sogm_replan: sogm_planner_set_publish's next_table overlaps the table given to sogm_planner_set_swarm");
       return SOGM_ERR_INVALID_ARG;

@@ -103,6 +103,7 @@ struct MapFrame {  // one sensor frame as the kernels read it
 struct OverlayIO {  // the neighbours' records an overlay adds
   const SogmTrajRecord *rec;
   int                   n_rec;
+  int                   stride;  // 0: one table for every agent; n_rec: agent a reads rec[a * stride + r] (its own view)
   const int32_t        *ego_ids;
   const double         *body;
   int                   n_body;
@@ -207,6 +208,7 @@ struct FinishArgs {
   const double         *cpts;
   const SogmTrajRecord *swarm;
   int                   n_swarm;
+  int                   swarm_stride;  // 0: one table for every agent; n_swarm: agent a reads swarm[a * swarm_stride + i]
   const int32_t        *swarm_ego;
   const double         *swarm_now, *t_start;
   const int32_t        *drone_ids;
@@ -258,7 +260,7 @@ hipError_t launch_prestamp_flow(const GridGeom &g, const FlowCtl &fc, const Pres
 // ParticleATC::isSafeAfterOpt for agents [agent0, agent0 + n_agents): out_safe[a] = 1 / 0
 hipError_t launch_deconflict(int n_agents, const double *cpts, const int32_t *npoly, const SogmTrajRecord *rec,
                              int n_rec, const int32_t *ego_ids, const double *t_now, int32_t *out_safe,
-                             hipStream_t st, int agent0, unsigned long long *counters = nullptr);
+                             hipStream_t st, int agent0, unsigned long long *counters = nullptr, int rec_stride = 0);
 // the grouped path's records, ok flags and outcome counts for agents [agent0, agent0 + n_agents) (k_pack_records)
 hipError_t launch_pack_records(int n_agents, const FinishArgs &f, hipStream_t st, int agent0);
 hipError_t launch_corridor(const MapView &m, const SogmPlannerParams &pp, const CorridorWorkspace &ws, int n_agents,
@@ -330,6 +332,7 @@ struct sogm_planner {
   int32_t              *d_safe;
   const SogmTrajRecord *swarm;
   int                   n_swarm;
+  int                   swarm_stride;  // 0: sogm_planner_set_swarm's one table; n_swarm: _set_swarm_views' [A][n_swarm]
   const int32_t        *swarm_ego;
   const double         *swarm_now;
   // publication inside the replan (sogm_planner_set_publish): the host's own-record table and the next swarm table
@@ -420,7 +423,7 @@ inline sogm::FinishArgs finish_args(const sogm_planner *p, const double *t_start
                                     SogmTrajRecord *out, int32_t *out_ok) {
   return sogm::FinishArgs{.corridor_tau = p->pp.corridor_tau, .ret = p->d_ret, .npoly = p->d_npoly,
                           .status = p->d_status, .cpts = p->d_cpts, .swarm = p->swarm, .n_swarm = p->n_swarm,
-                          .swarm_ego = p->swarm_ego, .swarm_now = p->swarm_now, .t_start = t_start,
+                          .swarm_stride = p->swarm_stride, .swarm_ego = p->swarm_ego, .swarm_now = p->swarm_now, .t_start = t_start,
                           .drone_ids = drone_ids, .out = out, .out_ok = out_ok, .out_safe = p->d_safe,
                           .counters = p->cw.counters, .pub_own = p->pub_own, .pub_table = p->pub_table,
                           .due = p->due};

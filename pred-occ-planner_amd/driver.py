@@ -346,6 +346,19 @@ class HipCompute:
     def set_swarm(self, all_records, A_tot, now):
         self.planner.setSwarm(all_records, A_tot, self.ego_ids, now)
 
+    def set_swarm_views(self, views, A_tot, now):
+        """set_swarm with every agent's own table (links.LinkModel.views)"""
+        self.planner.set_swarm_views(views, A_tot, self.ego_ids, now)
+
+    def update_map_views(self, poses, now, views, A_tot, tick=0):
+        """update_map whose closing overlay reads every agent's own table"""
+        d = self.dev
+        if self.use_world:
+            self.map.updateWorldViews(self.world(tick), poses, now, views, A_tot, self.ego_ids)
+        else:
+            self.map.updateMap(d["cloud"], d["cloud_range"], d["cylinders"], d["n_cyl"], poses, now)
+            self.map.addOtherAgentsViews(views, A_tot, self.ego_ids)
+
     def set_publish(self, own, next_table):
         """replan() merges the new records into `own` (latest wins) and writes every agent's current record into
         `next_table` itself (sogm_planner_set_publish) — no merge launch after the replan"""
@@ -412,8 +425,22 @@ class SwarmTick:
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
                  moving_world=None, neighbour_lag=1, audit=False, device_fsm=False, traj_server=None, device_world=None,
-                 world_pool=None, n_rings=0):
+                 world_pool=None, n_rings=0, link=None):
         self.rank, self.world, self.dist = rank, world, dist
+        # link (an _abi.SogmLinkParams, or links.parse_params' text): every agent reads its OWN table of the swarm, what a
+        # radio link with per-message delay, loss and range delivered to it (links.LinkModel; include/sogm_abi.h "radio
+        # links") — on the plain lock-step path of step() and on step_fsm_device().  The audit and the trajectory server
+        # keep reading the true table.  Single process, no fused publication, no pre-stamp, no flights.
+        if link is not None:
+            if world > 1 or (dist is not None and dist.is_initialized()):
+                raise ValueError("SwarmTick(link=...) is single-process: every receiver's links are modelled in one place")
+            if fsm and not device_fsm:
+                raise ValueError("SwarmTick(link=...) with fsm=True needs device_fsm=True")
+            if int(neighbour_lag) != 1:
+                raise ValueError("SwarmTick(link=...) needs neighbour_lag=1: a uniform lag is the link's delay_min = delay_max")
+            if compute is not None and not hasattr(compute, "update_map_views"):
+                raise ValueError("SwarmTick(link=...) needs a compute with per-agent tables")
+            prestamp = False
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
         # points: the reference path the flight's records are held to, bit for bit (single process, no fused publication)
@@ -453,13 +480,20 @@ class SwarmTick:
         # (baseline_fake.cpp:453-460); "now" of the check = the tick's stamp
         self.now = torch.zeros((self.A_loc,), dtype=torch.float64, device=d)
         self.deconflict = deconflict
-        if deconflict:
+        self.links = None
+        if link is not None:
+            from . import links as links_mod
+            prm = links_mod.parse_params(link) if isinstance(link, str) else link
+            self.links = links_mod.LinkModel(self.A_tot, lo, self.A_loc, prm, device=d)
+        if deconflict and self.links is not None:
+            c.set_swarm_views(self.links.views, self.A_tot, self.now)
+        elif deconflict:
             c.set_swarm(self.all, self.A_tot, self.now)
         # publication inside the replan (default; SOGM_PUBLISH=0: the separate sogm_merge_latest launch): a single
         # process alternates between two swarm tables — the replan reads one (overlay, deconfliction) and its
         # finishing kernel fills the other for the next tick
         self.publish = (os.environ.get("SOGM_PUBLISH", "1") != "0" and hasattr(c, "set_publish") and not fsm
-                        and self.neighbour_lag == 1)
+                        and self.neighbour_lag == 1 and self.links is None)
         self._tables = [self.all, torch.zeros_like(self.all)] if self.publish else None
         # pre-stamp (default; SOGM_PRESTAMP=0 or prestamp=False: off): every replan also builds the next tick's map and
         # start states, agent by agent as their records are published; the tick's inputs are double-buffered (the replan
@@ -575,6 +609,16 @@ class SwarmTick:
         if not local:
             self._exchange()
 
+    def _deliver(self):
+        """with link: what tick self.tick's broadcasts and the earlier ones still in the air bring every receiver — the
+        table every agent executes after this tick, sent from the tick's replan start positions (stream-ordered)"""
+        if self.links is not None:
+            self.links.deliver(self.tick, self.own, self.pva[:, 0:3])
+
+    def link_counters(self):
+        """{name: sum over the receivers and the ticks so far} of the link model (synchronises); None without link"""
+        return self.links.totals() if self.links is not None else None
+
     def records_all(self):
         """The swarm's latest records for torch-side readers (waits for an all-gather in flight)."""
         if self.exchange.active:
@@ -636,7 +680,10 @@ class SwarmTick:
         else:
             self.map.updateMap(self.dev["cloud"], self.dev["cloud_range"], self.dev["cylinders"], self.dev["n_cyl"],
                                self.poses, self.now)
-        self.map.addOtherAgents(self.all, self.A_tot, ego)
+        if self.links is not None:
+            self.map.addOtherAgentsViews(self.links.views, self.A_tot, ego)
+        else:
+            self.map.addOtherAgents(self.all, self.A_tot, ego)
         safe = self.map.isTrajSafe(self.own, self.now, COLLI_CHECK_DURATION)
         self.planner.set_due(f.due)
         self.planner.replan(self.pva, self.goals, self.t_start, ego, self.new, self.ok)   # ok = 0 where not due
@@ -648,6 +695,7 @@ class SwarmTick:
                          "pub_new": f.pub == _abi.FSM_PUB_NEW, "pub_hover": f.pub == _abi.FSM_PUB_HOVER,
                          "hover_start": f.hover_start, "t_start": self.t_start, "pos": f.pos_now}
         self._exchange()
+        self._deliver()
         if self.auditor is not None or self.server is not None:
             table = self.own if self.A_loc == self.A_tot and not self.distributed else self.records_all()
             self._audit_tick(table)
@@ -670,7 +718,10 @@ class SwarmTick:
             c.update_prestamped(self.all, self.A_tot)
         else:
             c.tick_inputs(self.own, stamp, self.hover, self.now, self.t_start, self.pva, self.poses)
-            c.update_map(self.poses, self.now, self.all, self.A_tot, self.tick)
+            if self.links is not None:
+                c.update_map_views(self.poses, self.now, self.links.views, self.A_tot, self.tick)
+            else:
+                c.update_map(self.poses, self.now, self.all, self.A_tot, self.tick)
         if self.publish:
             local = not self.exchange.active and not self.distributed
             nxt = self._tables[(self.tick + 1) & 1] if local else None
@@ -698,6 +749,7 @@ class SwarmTick:
         else:
             c.replan(self.pva, self.goals, self.t_start, self.new, self.ok)
             self._publish()
+            self._deliver()
         if (self.auditor is not None or self.server is not None) and self.neighbour_lag == 1:
             self._audit_tick(self.records_all())
             self._serve_tick(self.records_all())
@@ -718,6 +770,8 @@ class SwarmTick:
         "hover_start" — step_fsm_device's without "t_start" and "pos", which the head of a flight's tick keeps in the
         planner's own per-agent arrays and SogmFlightFsm does not log."""
         c = self.compute
+        if self.links is not None:
+            raise ValueError("fly() with link: a flight reads its own ring of tables; fly step() ticks instead")
         assert getattr(c, "use_world", False), "fly() needs world frames (moving_world=True / False)"
         # the closed loop flies with the machines on the device only (sogm_planner_set_flight_fsm); the torch machines of
         # fsm=True, device_fsm=False have no flight

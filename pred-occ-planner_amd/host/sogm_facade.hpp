@@ -200,6 +200,11 @@ class RiskMap {
                    int n_records = 0, const int32_t *ego_ids = nullptr, hipStream_t st = nullptr) {
     check(sogm_update_world(ctx_, &frame, poses, stamps, records, n_records, ego_ids, st), "sogm_update_world");
   }
+  // updateWorld whose closing overlay reads every agent's OWN table: dev views [n_agents][n_records] (Links::views())
+  void updateWorldViews(const SogmWorld &frame, const float *poses, const double *stamps, const SogmTrajRecord *views,
+                        int n_records, const int32_t *ego_ids, hipStream_t st = nullptr) {
+    check(sogm_update_world_views(ctx_, &frame, poses, stamps, views, n_records, ego_ids, st), "sogm_update_world_views");
+  }
   // The update of a tick whose map the previous replan pre-stamped (Planner::setPrestamp): grid swap + overlay
   bool prestampPending() const { return sogm_prestamp_pending(ctx_) != 0; }
   void prestampJoin(void *stream = nullptr) { check(sogm_prestamp_join(ctx_, stream), "sogm_prestamp_join"); }
@@ -228,6 +233,10 @@ class RiskMap {
   // RiskBase::addOtherAgents
   void addOtherAgents(const SogmTrajRecord *records, int n, const int32_t *ego_ids, hipStream_t st = nullptr) {
     check(sogm_project_neighbours(ctx_, records, n, ego_ids, st), "sogm_project_neighbours");
+  }
+  // addOtherAgents from every agent's OWN ParticleATC store: dev views [n_agents][n] (Links::views())
+  void addOtherAgentsViews(const SogmTrajRecord *views, int n, const int32_t *ego_ids, hipStream_t st = nullptr) {
+    check(sogm_project_neighbours_views(ctx_, views, n, ego_ids, st), "sogm_project_neighbours_views");
   }
   // int getClearOcccupancy(const Vector3d& pos, double dt) const  -> 0 free / 1 occupied / -1 out
   int getClearOcccupancy(int agent, const Vec3 &pos, double dt) {
@@ -500,6 +509,11 @@ class Planner {
   void setPrestamp(const SogmPrestamp *next_tick) {
     check(sogm_planner_set_prestamp(p_, next_tick), "sogm_planner_set_prestamp");
   }
+  // replan() ends with isSafeAfterOpt of every agent against its OWN table: dev views [n_agents][n_records]
+  // (Links::views()), ego_ids / t_now dev [n_agents]; read by later replan() calls (sogm_planner_set_swarm_views)
+  void setSwarmViews(const SogmTrajRecord *views, int n_records, const int32_t *ego_ids, const double *t_now) {
+    check(sogm_planner_set_swarm_views(p_, views, n_records, ego_ids, t_now), "sogm_planner_set_swarm_views");
+  }
   // The reference plans only in NEW_PLAN and REPLAN (plan_manager.cpp:110-135,164-175): later replan() calls plan only
   // the agents with due[a] != 0 (dev int32 [n_agents], e.g. Fsm::due()); nullptr = every agent (sogm_planner_set_due)
   void setDue(const int32_t *due_dev_or_null) { check(sogm_planner_set_due(p_, due_dev_or_null), "sogm_planner_set_due"); }
@@ -728,6 +742,63 @@ class TrajServer {
   DevBuf<SogmTrajServerState>  state_;
   DevBuf<SogmTrajPoint>        queue_;
   DevBuf<SogmPositionCommand>  cmd_;
+};
+
+// Radio links (sogm_abi.h "radio links"): owns the ring of sent tables, the views, the held ticks and the counters of the
+// receivers [agent0, agent0 + n_local) of an n_total swarm on the device.  deliver() is one tick on the caller's stream (no
+// synchronisation), ticks consecutive from the first; views() is what RiskMap::addOtherAgentsViews / updateWorldViews and
+// Planner::setSwarmViews take.
+class Links {
+ public:
+  Links(const SogmLinkParams &prm, int n_total, int agent0, int n_local, void *stream = nullptr)
+      : prm_(prm), n_total_(n_total), agent0_(agent0), n_local_(n_local) {
+    check_abi();
+    const size_t slots = (size_t)(prm.delay_max >= 0 && prm.delay_max <= SOGM_LINK_MAX_DELAY ? prm.delay_max : 0) + 1;
+    const size_t nt = (size_t)(n_total > 0 ? n_total : 1), nl = (size_t)(n_local > 0 ? n_local : 1);
+    ring_table_.resize(slots * nt);
+    ring_pos_.resize(slots * nt * 3);
+    views_.resize(nl * nt);
+    held_.resize(nl * nt);
+    counters_.resize(nl * SOGM_LINK_COUNTERS);
+    buf_ = SogmLinkBuffers{ring_table_.data(), ring_pos_.data(), views_.data(), held_.data(), counters_.data()};
+    check(sogm_link_init(&prm_, n_total, n_local, &buf_, stream), "sogm_link_init");
+  }
+  static SogmLinkParams defaultParams() {
+    SogmLinkParams p;
+    check(sogm_link_default_params(&p), "sogm_link_default_params");
+    return p;
+  }
+  // dev table [n_total] (what every agent executes after `tick`), dev pos [n_total][3] or null (needed with a range)
+  const SogmTrajRecord *deliver(int tick, const SogmTrajRecord *table, const double *pos, void *stream = nullptr) {
+    if (next_ >= 0 && tick != next_) throw std::logic_error("sogm_host::Links::deliver: ticks are consecutive");
+    if (next_ < 0) tick0_ = tick;
+    check(sogm_link_deliver(&prm_, tick, tick0_, table, pos, n_total_, agent0_, n_local_, &buf_, stream), "sogm_link_deliver");
+    next_ = tick + 1;
+    return views_.data();
+  }
+  const SogmTrajRecord *views() { return views_.data(); }
+  // synchronous read-backs: counters [n_local][SOGM_LINK_COUNTERS], held ticks [n_local][n_total]
+  std::vector<int64_t> counters() {
+    std::vector<int64_t> out((size_t)n_local_ * SOGM_LINK_COUNTERS);
+    (void)hipDeviceSynchronize();
+    counters_.get(out.data(), out.size());
+    return out;
+  }
+  std::vector<int32_t> heldTicks() {
+    std::vector<int32_t> out((size_t)n_local_ * (size_t)n_total_);
+    (void)hipDeviceSynchronize();
+    held_.get(out.data(), out.size());
+    return out;
+  }
+
+ private:
+  SogmLinkParams         prm_;
+  int                    n_total_, agent0_, n_local_, tick0_ = 0, next_ = -1;
+  DevBuf<SogmTrajRecord> ring_table_, views_;
+  DevBuf<double>         ring_pos_;
+  DevBuf<int32_t>        held_;
+  DevBuf<int64_t>        counters_;
+  SogmLinkBuffers        buf_{};
 };
 
 }  // namespace sogm_host

@@ -248,6 +248,22 @@ class SogmPlanner:
             check(lib().sogm_planner_set_swarm(self._p, records.data_ptr(), n_records, ego_ids.data_ptr(),
                                                t_now.data_ptr()), "sogm_planner_set_swarm")
 
+    def set_swarm_views(self, views, n_records, ego_ids, t_now):
+        """setSwarm with every agent's OWN table: views uint8 [A, n_records, 2064] (links.LinkModel.views), agent a is
+        checked against views[a] (sogm_planner_set_swarm_views).  Kept alive here; setSwarm switches back."""
+        assert views.shape[0] == self.A and views.shape[1] == n_records, views.shape
+        self._swarm = (views, ego_ids, t_now)
+        check(lib().sogm_planner_set_swarm_views(self._p, views.data_ptr(), n_records, ego_ids.data_ptr(),
+                                                 t_now.data_ptr()), "sogm_planner_set_swarm_views")
+
+    def isSafeAfterOptViews(self, cpts, npoly, views, n_records, ego_ids, t_now):
+        """isSafeAfterOpt of every agent against its own table views[a] (sogm_safe_after_opt_views)"""
+        safe = torch.empty((self.A,), dtype=torch.int32, device=cpts.device)
+        check(lib().sogm_safe_after_opt_views(self._p, cpts.data_ptr(), npoly.data_ptr(), views.data_ptr(), n_records,
+                                              ego_ids.data_ptr(), t_now.data_ptr(), safe.data_ptr(), _stream()),
+              "sogm_safe_after_opt_views")
+        return safe
+
     def set_due(self, due=None):
         """Later replan() calls plan only the agents with due[a] != 0 (device int32 [A], read by those calls and kept
         alive here; sogm_planner_set_due); the others end like a failed search — ok 0, an empty record — without

@@ -287,6 +287,20 @@ class SogmMap:
                                             ego_ids.data_ptr(), _stream()),
               "sogm_project_neighbours")
 
+    def addOtherAgentsViews(self, views, n_records, ego_ids):
+        """addOtherAgents with every agent's OWN table: views uint8 [n_agents, n_records, 2064] (links.LinkModel.views);
+        agent a's map gets the records of views[a] (sogm_project_neighbours_views)."""
+        check(lib().sogm_project_neighbours_views(self._ctx, views.data_ptr(), n_records, ego_ids.data_ptr(), _stream()),
+              "sogm_project_neighbours_views")
+
+    def updateWorldViews(self, world, poses, stamps, views, n_records, ego_ids):
+        """updateWorld whose closing overlay reads every agent's OWN table views[a] (sogm_update_world_views)"""
+        self._poses, self._stamps, self._world = poses, stamps, world
+        check(lib().sogm_update_world_views(self._ctx, C.byref(world.c), poses.data_ptr(), stamps.data_ptr(),
+                                            views.data_ptr() if n_records else None, n_records,
+                                            ego_ids.data_ptr() if ego_ids is not None else None, _stream()),
+              "sogm_update_world_views")
+
     def futureRiskCallback(self, grid_vt, poses, stamps):
         check(lib().sogm_set_future_risk(self._ctx, grid_vt.data_ptr(), poses.data_ptr(),
                                          stamps.data_ptr(), _stream()), "sogm_set_future_risk")

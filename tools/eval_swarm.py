@@ -2,6 +2,11 @@
 minimum separation and gap) and its cost.
 
     python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight|flight_fsm [rings] [--frozen] [--events N]
+                               [--link loss=P,delay=A..B,range=R,seed=N[,newest]]
+
+--link (lockstep only): every agent reads its own table of the swarm, what radio links with that loss, delay (whole ticks),
+range (metres) and seed delivered to it (links.LinkModel; include/sogm_abi.h "radio links"); the audit still judges the true
+tables.  The line then has a `link` block: the parameters and the link model's counters summed over receivers and ticks.
 
 rings (optional, default 0): that many ring obstacles in the scene (scene.make_scene(n_rings=...)), audited as rings; the
 report then also has ring_agents / ring_samples / min_ring_gap, counted from the event list and the per-agent minima.
@@ -27,7 +32,7 @@ def run(driver, args, audit):
     flight = args.mode in ("flight", "flight_fsm")
     sw = driver.SwarmTick(args.grid, args.agents, moving_world=not args.frozen, prestamp=False if flight else None,
                           fsm=args.mode in ("fsm", "flight_fsm"), device_fsm=args.mode == "flight_fsm", audit=audit,
-                          n_rings=args.rings)
+                          n_rings=args.rings, link=args.link)
     sw.compute.prepare(0, args.ticks)
     audit_ms = []
     if audit:   # time every audit call with events of its own on the same stream
@@ -67,6 +72,8 @@ def run(driver, args, audit):
                    ring_events_complete=not rep["events_truncated"],
                    min_ring_gap_where_nearest=float(acc["min_gap"][near].min()) if near.any() else None)
     a_ms = sum(e0.elapsed_time(e1) for e0, e1 in audit_ms) / args.ticks if audit else None
+    if audit and args.link:
+        rep["link"] = dict(spec=args.link, **sw.link_counters())
     sw.close()
     return ms, rep, a_ms
 
@@ -80,7 +87,10 @@ def main():
     ap.add_argument("rings", type=int, nargs="?", default=0, help="ring obstacles in the scene (default 0)")
     ap.add_argument("--frozen", action="store_true", help="a frozen world (moving_world=False)")
     ap.add_argument("--events", type=int, default=20, help="events printed (the report counts all)")
+    ap.add_argument("--link", default=None, help="loss=P,delay=A..B,range=R,seed=N[,newest] (lockstep only)")
     args = ap.parse_args()
+    if args.link and args.mode != "lockstep":
+        ap.error("--link flies the lock-step tick only")
     driver = importlib.import_module("pred-occ-planner_amd.driver")
     run(driver, argparse.Namespace(**dict(vars(args), ticks=min(args.ticks, 5))), False)   # warm-up
     ms_off, _, _ = run(driver, args, False)
