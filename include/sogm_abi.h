@@ -1876,6 +1876,104 @@ int sogm_planner_set_swarm_views(sogm_planner *p, const SogmTrajRecord *views, i
                                  const double *t_now);
 
 /* ------------------------------------------------------------------------------------------ */
+/* message noise: what a sender broadcasts against what it flies.  The reference's authors run   */
+/*   eval_helper/traj_noise_maker between /broadcast_traj and /noisy_broadcast_traj               */
+/*   (plan_manager/launch/sim_fkpcp_8_case_{1,2}.launch:169-178: noise/seed, noise/loc/{x,y,z},   */
+/*   noise/time_sync, noise/tracking) and point the planner at the noisy topic                    */
+/*   (launch/simulator/noisy_drone_fake_perception.xml:39).  eval_helper is an absent submodule:  */
+/*   only the parameters are known, so the rule is the build's OWN definition, held by two        */
+/*   independent implementations (csrc/sogm_trajnoise.hpp; tests/traj_noise_reference.py), bit    */
+/*   for bit.  Only traj_noise_maker's side: the per-drone noisy pose and odometry of noise_maker */
+/*   (noisy_drone_fake_perception.xml:100-108) stay out of scope.                                 */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * mix and N(h) are "sensor noise"'s noise_mix and noise_normal: N is the twelve-piece Irwin-Hall normal, a multiple of
+ * 2^-16 with |N| <= 6.  All keys are uint64 and wrap.  Every fp64 expression is one IEEE operation, with no contraction.
+ *
+ *   key(tag, x, j) = mix( mix( mix( mix(seed) ^ tag ) ^ x ) ^ j ).  Component c draws N(key + 16*c).
+ *   Localisation bias of sender j at send tick m: b[c] = sigma_loc[c] * N(key(1, e, j) + 16c), with
+ *     e = loc_hold > 0 ? m / loc_hold : 0.
+ *   Clock offset of sender j, constant over the run: tau = sigma_time * N(key(2, 0, j)).
+ *   Tracking error of message (m, j): e[c] = sigma_track * N(key(3, m, j) + 16c).
+ *   shift[c] = b[c] + e[c].
+ *   Row j with n_pieces <= 0 is not a message.  It is copied unchanged and its out_shift is four zeros.
+ *   Otherwise every coordinate c of the control points k < 5 * min(n_pieces, SOGM_MAX_PIECES) becomes cpts + shift[c], one
+ *     add.  It is copied bit for bit when shift[c] == 0.0, so a -0.0 survives zero parameters.
+ *   Control points beyond those, drone_id, n_pieces and duration[] are copied.
+ *   time_start becomes time_start + tau, and is copied when tau == 0.0.
+ *   The same noisy message reaches every receiver, since one node republishes it in the reference.
+ *   A receiver's own row in its view is therefore noisy too.  That is harmless: the overlay and both forms of
+ *     isSafeAfterOpt skip it by drone_id.
+ * Known answers, seed 0x5067:
+ *   key(1, 0, 0) = 0x4ACD8EB1A9CFDCC6   N at c = 0, 1, 2: 0x1.469p-2, -0x1.c25p-4, -0x1.a0b6p-1
+ *   key(2, 0, 3) = 0xF86E1BF400FF8055   N = -0x1.1598p-1
+ *   key(3, 7, 4) = 0x0E12DE2E62B1FC89   N at c = 0, 1, 2: 0x1.d6dep-1, -0x1.34dep+0, 0x1.8a64p-1
+ *
+ * Context-free, stream-ordered, no allocation, no host synchronisation, like sogm_link_deliver.  `tick` is the send tick m
+ * of every row; `out` may be `table` itself (in place) and must not overlap it otherwise.  out_shift (or NULL) receives
+ * every row's shift x, y, z and tau.  SOGM_ERR_INVALID_ARG (checked before a device is looked for; sogm_last_error() names
+ * the rule): a null prm, table or out; a sigma that is negative or not finite; loc_hold < 0; tick < 0; n_total < 1; a record
+ * buffer that is not 16-byte aligned.  SOGM_ERR_NO_DEVICE without a GPU.
+ */
+typedef struct SogmTrajNoise {
+  uint64_t seed;
+  double   sigma_loc[3];   /* metres, per axis: the sender's localisation bias */
+  double   sigma_time;     /* seconds: the sender's clock offset */
+  double   sigma_track;    /* metres, all three axes: tracking error, new with every message */
+  int32_t  loc_hold;       /* ticks a localisation bias lasts; 0: the whole run */
+  int32_t  reserved_;
+} SogmTrajNoise;           /* 56 bytes */
+
+int sogm_traj_noise_default_params(SogmTrajNoise *out);   /* all zero: out == table, byte for byte */
+int sogm_traj_noise(const SogmTrajNoise *prm, int tick, const SogmTrajRecord *table /* dev [n_total] */, int n_total,
+                    SogmTrajRecord *out /* dev [n_total]; may be table */,
+                    double *out_shift /* dev [n_total][4] = shift x, y, z, tau; or NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* belief audit: what each receiver believes about its neighbours' trajectories (its view,       */
+/*   SogmLinkBuffers.views) against what the senders intend (the table they execute).  Like the  */
+/*   link model and the message noise it is the build's own definition, held by                  */
+/*   csrc/sogm_belief.hpp and tests/belief_audit_reference.py, count for count.                  */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * For receiver row a = agent0 + a_local and sender row j != a, with T = truth[j] and B = views[a_local][j]:
+ *   Both rows empty (n_pieces <= 0): nothing is counted.
+ *   T has a trajectory and B has none: unheard (+1).   B has one and T has none: phantom (+1).
+ *   Otherwise the pair is compared.  For s = 0 .. n_samples - 1:
+ *     t = t_now[a_local] + (double)s * dt_sample.
+ *     pT and pB are the positions of T and B at t: sogm_traj_eval's arithmetic (Bezier::getPos), t clamped to the
+ *       record's span [time_start, time_start + total]; a record's n_pieces above SOGM_MAX_PIECES counts as
+ *       SOGM_MAX_PIECES.
+ *     d2 = (dx*dx + dy*dy) + dz*dz.  There is no square root: bins compare d2 <= edges[i] * edges[i].
+ *     The sample goes to the first bin that holds it, else to bin 5.  A NaN goes to bin 5.
+ *     q = min((int64)floor(d2 * 1e6 + 0.5), 2^40), the squared error in mm^2, clamped.  It is 2^40 for a NaN.
+ * counters[a_local][12] int64, the caller zeroes them once and every call adds (integer adds and maxima: the same bits from
+ * run to run):
+ *   0 compared pairs   1 unheard   2 phantom   3 samples   4 .. 9 the six bins   10 sum of q   11 max q (an integer max)
+ * out_pair_q[a_local][j] (or NULL) is the pair's largest q of this call, -1 when the pair is not compared or j == a.
+ * Nothing is written to truth or views.
+ *
+ * Context-free, stream-ordered, no allocation, no host synchronisation.  SOGM_ERR_INVALID_ARG (checked first): a null prm,
+ * truth, views, t_now or counters; n_samples outside 1 .. SOGM_BELIEF_MAX_SAMPLES; dt_sample not positive or not finite;
+ * edges not strictly ascending, not positive or not finite; n_total < 1, agent0 < 0, n_local outside 1 .. n_total - agent0;
+ * a record buffer that is not 16-byte aligned; n_local > 65535.  SOGM_ERR_NO_DEVICE without a GPU.
+ */
+#define SOGM_BELIEF_COUNTERS    12
+#define SOGM_BELIEF_MAX_SAMPLES 16
+typedef struct SogmBeliefParams {
+  double  dt_sample;     /* seconds between samples (> 0) */
+  double  edges[5];      /* metres, strictly ascending, > 0; default 0.05 0.1 0.2 0.5 1.0 */
+  int32_t n_samples;     /* 1 .. 16; default 8, dt_sample 0.2 */
+  int32_t reserved_;
+} SogmBeliefParams;      /* 56 bytes */
+
+int sogm_belief_default_params(SogmBeliefParams *out);
+int sogm_belief_audit(const SogmBeliefParams *prm, const SogmTrajRecord *truth /* dev [n_total]: the table the agents execute */,
+                      const SogmTrajRecord *views /* dev [n_local][n_total] */, const double *t_now /* dev [n_local] */,
+                      int n_total, int agent0, int n_local, int64_t *counters /* dev [n_local][12] */,
+                      int64_t *out_pair_q /* dev [n_local][n_total] or NULL */, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* trajectory exchange: the /broadcast_traj topic as ONE RCCL all-gather per replan tick          */
 /*   (plan_manager/src/plan_manager.cpp:364-399 publish, traj_coordinator/src/particles.cpp:131-191 receive)  */
 /* ------------------------------------------------------------------------------------------ */

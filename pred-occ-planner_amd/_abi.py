@@ -88,6 +88,15 @@ class SogmLinkParams(C.Structure):
                 ("delay_max", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class SogmTrajNoise(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("sigma_loc", C.c_double * 3), ("sigma_time", C.c_double), ("sigma_track", C.c_double),
+                ("loc_hold", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SogmBeliefParams(C.Structure):
+    _fields_ = [("dt_sample", C.c_double), ("edges", C.c_double * 5), ("n_samples", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class SogmLinkBuffers(C.Structure):
     _fields_ = [("ring_table", C.c_void_p), ("ring_pos", C.c_void_p), ("views", C.c_void_p), ("held_tick", C.c_void_p),
                 ("counters", C.c_void_p)]
@@ -293,6 +302,12 @@ LABEL_SOURCES_BYTES = C.sizeof(SogmLabelSources)  # 32
 SOGM_LINK_MAX_DELAY, SOGM_LINK_NEWEST_WINS, SOGM_LINK_COUNTERS = 7, 1, 8
 LINK_PARAMS_BYTES = C.sizeof(SogmLinkParams)  # 40
 LINK_COUNTER_NAMES = ("sent", "out_of_range", "lost", "arrivals", "applied", "stale", "age_sum", "unheard")
+# message noise and belief audit (include/sogm_abi.h "message noise", "belief audit")
+TRAJ_NOISE_BYTES = C.sizeof(SogmTrajNoise)  # 56
+SOGM_BELIEF_COUNTERS, SOGM_BELIEF_MAX_SAMPLES = 12, 16
+BELIEF_PARAMS_BYTES = C.sizeof(SogmBeliefParams)  # 56
+BELIEF_COUNTER_NAMES = ("compared", "unheard", "phantom", "samples", "bin0", "bin1", "bin2", "bin3", "bin4", "bin5", "sum_q",
+                        "max_q")
 
 
 class SogmTrajServerState(C.Structure):
@@ -418,6 +433,10 @@ PROTOTYPES = {
     "sogm_link_default_params": (_i, [C.POINTER(SogmLinkParams)]),
     "sogm_link_init": (_i, [C.POINTER(SogmLinkParams), _i, _i, C.POINTER(SogmLinkBuffers), _vp]),
     "sogm_link_deliver": (_i, [C.POINTER(SogmLinkParams), _i, _i, _vp, _vp, _i, _i, _i, C.POINTER(SogmLinkBuffers), _vp]),
+    "sogm_traj_noise_default_params": (_i, [C.POINTER(SogmTrajNoise)]),
+    "sogm_traj_noise": (_i, [C.POINTER(SogmTrajNoise), _i, _vp, _i, _vp, _vp, _vp]),
+    "sogm_belief_default_params": (_i, [C.POINTER(SogmBeliefParams)]),
+    "sogm_belief_audit": (_i, [C.POINTER(SogmBeliefParams), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sogm_project_neighbours_views": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sogm_update_world_views": (_i, [_vp, C.POINTER(SogmWorld), _vp, _vp, _vp, _i, _vp, _vp]),
     "sogm_safe_after_opt_views": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

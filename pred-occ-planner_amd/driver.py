@@ -425,21 +425,30 @@ class SwarmTick:
                  spec=None, scene=None, dist=None, overlap_clear=True, deconflict=True, fsm=False,
                  double_buffer=None, grids=None, compute=None, exchange=None, prestamp=None, tuning=None,
                  moving_world=None, neighbour_lag=1, audit=False, device_fsm=False, traj_server=None, device_world=None,
-                 world_pool=None, n_rings=0, link=None):
+                 world_pool=None, n_rings=0, link=None, msg_noise=None, belief=False):
         self.rank, self.world, self.dist = rank, world, dist
+        # msg_noise (an _abi.SogmTrajNoise, or links.parse_noise's text): what every sender broadcasts is its executed record
+        # with a localisation bias, a clock offset and a tracking error on it (include/sogm_abi.h "message noise"); the table
+        # every agent executes, the audit and the trajectory server stay the true one.  belief=True: after each delivery every
+        # receiver's view is scored against that true table at the tick's stamp ("belief audit"; belief_report()).  Both ride
+        # on the link model and keep its restrictions; without link they fly perfect links.
+        asked = "link" if link is not None else "msg_noise" if msg_noise is not None else "belief"   # named in the refusals
+        if (msg_noise is not None or belief) and link is None:
+            from . import links as links_mod
+            link = links_mod.make_params()
         # link (an _abi.SogmLinkParams, or links.parse_params' text): every agent reads its OWN table of the swarm, what a
         # radio link with per-message delay, loss and range delivered to it (links.LinkModel; include/sogm_abi.h "radio
         # links") — on the plain lock-step path of step() and on step_fsm_device().  The audit and the trajectory server
         # keep reading the true table.  Single process, no fused publication, no pre-stamp, no flights.
         if link is not None:
             if world > 1 or (dist is not None and dist.is_initialized()):
-                raise ValueError("SwarmTick(link=...) is single-process: every receiver's links are modelled in one place")
+                raise ValueError(f"SwarmTick({asked}=...) is single-process: every receiver's links are modelled in one place")
             if fsm and not device_fsm:
-                raise ValueError("SwarmTick(link=...) with fsm=True needs device_fsm=True")
+                raise ValueError(f"SwarmTick({asked}=...) with fsm=True needs device_fsm=True")
             if int(neighbour_lag) != 1:
-                raise ValueError("SwarmTick(link=...) needs neighbour_lag=1: a uniform lag is the link's delay_min = delay_max")
+                raise ValueError(f"SwarmTick({asked}=...) needs neighbour_lag=1: a uniform lag is the link's delay_min = delay_max")
             if compute is not None and not hasattr(compute, "update_map_views"):
-                raise ValueError("SwarmTick(link=...) needs a compute with per-agent tables")
+                raise ValueError(f"SwarmTick({asked}=...) needs a compute with per-agent tables")
             prestamp = False
         # neighbour_lag = 2: the overlay and isSafeAfterOpt of tick k read table ver(k - 2) instead of ver(k - 1) — the
         # staleness rule of sogm_flight_run, flown here lock-step (one tick after the other) through the per-tick entry
@@ -480,11 +489,13 @@ class SwarmTick:
         # (baseline_fake.cpp:453-460); "now" of the check = the tick's stamp
         self.now = torch.zeros((self.A_loc,), dtype=torch.float64, device=d)
         self.deconflict = deconflict
-        self.links = None
+        self.links, self.msg_noise, self.belief = None, None, bool(belief)
         if link is not None:
             from . import links as links_mod
             prm = links_mod.parse_params(link) if isinstance(link, str) else link
             self.links = links_mod.LinkModel(self.A_tot, lo, self.A_loc, prm, device=d)
+            if msg_noise is not None:
+                self.msg_noise = links_mod.parse_noise(msg_noise) if isinstance(msg_noise, str) else msg_noise
         if deconflict and self.links is not None:
             c.set_swarm_views(self.links.views, self.A_tot, self.now)
         elif deconflict:
@@ -613,7 +624,18 @@ class SwarmTick:
         """with link: what tick self.tick's broadcasts and the earlier ones still in the air bring every receiver — the
         table every agent executes after this tick, sent from the tick's replan start positions (stream-ordered)"""
         if self.links is not None:
-            self.links.deliver(self.tick, self.own, self.pva[:, 0:3])
+            self.links.deliver(self.tick, self.own, self.pva[:, 0:3], noise=self.msg_noise)
+            if self.belief:
+                self.links.audit_belief(self.own, self.now)
+
+    def belief_report(self):
+        """{name: total over the receivers and the ticks so far} of the belief audit, max_q as a maximum, plus rms_m, the
+        root mean square position error of the compared samples in metres (synchronises); None without belief=True"""
+        if self.links is None or not self.belief:
+            return None
+        out = self.links.belief()
+        out["rms_m"] = (out["sum_q"] / out["samples"]) ** 0.5 / 1000.0 if out["samples"] else 0.0
+        return out
 
     def link_counters(self):
         """{name: sum over the receivers and the ticks so far} of the link model (synchronises); None without link"""
@@ -771,7 +793,7 @@ class SwarmTick:
         planner's own per-agent arrays and SogmFlightFsm does not log."""
         c = self.compute
         if self.links is not None:
-            raise ValueError("fly() with link: a flight reads its own ring of tables; fly step() ticks instead")
+            raise ValueError("fly() with link, msg_noise or belief: a flight reads its own ring of tables; fly step() ticks instead")
         assert getattr(c, "use_world", False), "fly() needs world frames (moving_world=True / False)"
         # the closed loop flies with the machines on the device only (sogm_planner_set_flight_fsm); the torch machines of
         # fsm=True, device_fsm=False have no flight

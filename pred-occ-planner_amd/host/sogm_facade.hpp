@@ -761,7 +761,9 @@ class Links {
     held_.resize(nl * nt);
     counters_.resize(nl * SOGM_LINK_COUNTERS);
     buf_ = SogmLinkBuffers{ring_table_.data(), ring_pos_.data(), views_.data(), held_.data(), counters_.data()};
+    belief_.resize(beliefSize());
     check(sogm_link_init(&prm_, n_total, n_local, &buf_, stream), "sogm_link_init");
+    (void)hipMemsetAsync(belief_.data(), 0, beliefSize() * sizeof(int64_t), (hipStream_t)stream);
   }
   static SogmLinkParams defaultParams() {
     SogmLinkParams p;
@@ -772,11 +774,51 @@ class Links {
   const SogmTrajRecord *deliver(int tick, const SogmTrajRecord *table, const double *pos, void *stream = nullptr) {
     if (next_ >= 0 && tick != next_) throw std::logic_error("sogm_host::Links::deliver: ticks are consecutive");
     if (next_ < 0) tick0_ = tick;
+    if (has_noise_) {
+      check(sogm_traj_noise(&noise_, tick, table, n_total_, sent_.data(), sent_shift_.data(), stream), "sogm_traj_noise");
+      table = sent_.data();
+    }
     check(sogm_link_deliver(&prm_, tick, tick0_, table, pos, n_total_, agent0_, n_local_, &buf_, stream), "sogm_link_deliver");
     next_ = tick + 1;
     return views_.data();
   }
   const SogmTrajRecord *views() { return views_.data(); }
+  // Message noise (sogm_abi.h "message noise"): from now on deliver() sends every table through sogm_traj_noise into a
+  // buffer of this object's (sent(), its shifts in sentShift()) and the links carry that; the caller's table is not
+  // touched and the positions stay the true ones.  All-zero parameters send the table as it is.  setNoise allocates the
+  // buffer (call it before the run, not between two ticks in flight).
+  static SogmTrajNoise defaultNoise() {
+    SogmTrajNoise p;
+    check(sogm_traj_noise_default_params(&p), "sogm_traj_noise_default_params");
+    return p;
+  }
+  void setNoise(const SogmTrajNoise &noise) {
+    noise_     = noise;
+    has_noise_ = true;
+    sent_.resize((size_t)(n_total_ > 0 ? n_total_ : 1));
+    sent_shift_.resize((size_t)(n_total_ > 0 ? n_total_ : 1) * 4);
+  }
+  const SogmTrajRecord *sent() { return sent_.data(); }
+  const double         *sentShift() { return sent_shift_.data(); }
+  // Belief audit (sogm_abi.h "belief audit"): scores views() against dev truth [n_total], the table the senders execute,
+  // at the receivers' times dev t_now [n_local]; every call adds to belief() (the counters were allocated and zeroed by the
+  // constructor: stream-ordered from the first call, no synchronisation).
+  static SogmBeliefParams defaultBeliefParams() {
+    SogmBeliefParams p;
+    check(sogm_belief_default_params(&p), "sogm_belief_default_params");
+    return p;
+  }
+  void auditBelief(const SogmBeliefParams &prm, const SogmTrajRecord *truth, const double *t_now, void *stream = nullptr) {
+    check(sogm_belief_audit(&prm, truth, views_.data(), t_now, n_total_, agent0_, n_local_, belief_.data(), nullptr, stream),
+          "sogm_belief_audit");
+  }
+  // synchronous read-back: [n_local][SOGM_BELIEF_COUNTERS] (all zero before the first auditBelief)
+  std::vector<int64_t> belief() {
+    std::vector<int64_t> out(beliefSize());
+    (void)hipDeviceSynchronize();
+    belief_.get(out.data(), out.size());
+    return out;
+  }
   // synchronous read-backs: counters [n_local][SOGM_LINK_COUNTERS], held ticks [n_local][n_total]
   std::vector<int64_t> counters() {
     std::vector<int64_t> out((size_t)n_local_ * SOGM_LINK_COUNTERS);
@@ -799,6 +841,12 @@ class Links {
   DevBuf<int32_t>        held_;
   DevBuf<int64_t>        counters_;
   SogmLinkBuffers        buf_{};
+  size_t                 beliefSize() const { return (size_t)(n_local_ > 0 ? n_local_ : 1) * SOGM_BELIEF_COUNTERS; }
+  SogmTrajNoise          noise_{};
+  bool                   has_noise_ = false;
+  DevBuf<SogmTrajRecord> sent_;
+  DevBuf<double>         sent_shift_;
+  DevBuf<int64_t>        belief_;
 };
 
 }  // namespace sogm_host

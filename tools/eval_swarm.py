@@ -3,10 +3,16 @@ minimum separation and gap) and its cost.
 
     python tools/eval_swarm.py cfg2 128 300 lockstep|fsm|flight|flight_fsm [rings] [--frozen] [--events N]
                                [--link loss=P,delay=A..B,range=R,seed=N[,newest]]
+                               [--msg-noise loc=S|X/Y/Z,time=S,track=S,hold=N,seed=N] [--belief]
 
 --link (lockstep only): every agent reads its own table of the swarm, what radio links with that loss, delay (whole ticks),
 range (metres) and seed delivered to it (links.LinkModel; include/sogm_abi.h "radio links"); the audit still judges the true
 tables.  The line then has a `link` block: the parameters and the link model's counters summed over receivers and ticks.
+
+--msg-noise (lockstep only): what every sender broadcasts carries a localisation bias, a clock offset and a tracking error
+(links.parse_noise; include/sogm_abi.h "message noise"); --belief scores every receiver's view against the table the senders
+execute after each delivery ("belief audit").  Without --link both fly perfect links.  The line then has a `msg_noise` block
+with the spec and a `belief` block: the twelve totals and rms_m = sqrt(sum_q / samples) / 1000.
 
 rings (optional, default 0): that many ring obstacles in the scene (scene.make_scene(n_rings=...)), audited as rings; the
 report then also has ring_agents / ring_samples / min_ring_gap, counted from the event list and the per-agent minima.
@@ -30,9 +36,14 @@ sys.path.insert(0, ROOT)
 def run(driver, args, audit):
     import torch
     flight = args.mode in ("flight", "flight_fsm")
+    extra = {}
+    if args.msg_noise is not None:
+        extra["msg_noise"] = args.msg_noise
+    if args.belief:
+        extra["belief"] = True
     sw = driver.SwarmTick(args.grid, args.agents, moving_world=not args.frozen, prestamp=False if flight else None,
                           fsm=args.mode in ("fsm", "flight_fsm"), device_fsm=args.mode == "flight_fsm", audit=audit,
-                          n_rings=args.rings, link=args.link)
+                          n_rings=args.rings, link=args.link, **extra)
     sw.compute.prepare(0, args.ticks)
     audit_ms = []
     if audit:   # time every audit call with events of its own on the same stream
@@ -74,6 +85,10 @@ def run(driver, args, audit):
     a_ms = sum(e0.elapsed_time(e1) for e0, e1 in audit_ms) / args.ticks if audit else None
     if audit and args.link:
         rep["link"] = dict(spec=args.link, **sw.link_counters())
+    if audit and args.msg_noise is not None:
+        rep["msg_noise"] = dict(spec=args.msg_noise)
+    if audit and args.belief:
+        rep["belief"] = sw.belief_report()
     sw.close()
     return ms, rep, a_ms
 
@@ -88,9 +103,11 @@ def main():
     ap.add_argument("--frozen", action="store_true", help="a frozen world (moving_world=False)")
     ap.add_argument("--events", type=int, default=20, help="events printed (the report counts all)")
     ap.add_argument("--link", default=None, help="loss=P,delay=A..B,range=R,seed=N[,newest] (lockstep only)")
+    ap.add_argument("--msg-noise", default=None, help="loc=S|X/Y/Z,time=S,track=S,hold=N,seed=N (lockstep only)")
+    ap.add_argument("--belief", action="store_true", help="score every receiver's view against the true table (lockstep only)")
     args = ap.parse_args()
-    if args.link and args.mode != "lockstep":
-        ap.error("--link flies the lock-step tick only")
+    if (args.link or args.msg_noise is not None or args.belief) and args.mode != "lockstep":
+        ap.error("--link, --msg-noise and --belief fly the lock-step tick only")
     driver = importlib.import_module("pred-occ-planner_amd.driver")
     run(driver, argparse.Namespace(**dict(vars(args), ticks=min(args.ticks, 5))), False)   # warm-up
     ms_off, _, _ = run(driver, args, False)
